@@ -3,9 +3,21 @@
 
 A "step" is one relaxation iteration (one pass over all N x N ordered pairs, plus the
 convergence check the reference runs every `convergence_check_freq`=3 iterations).  The job is ONE embedding
-relaxed to the controller's own stop; it is timed in slices of exactly --steps iterations after --warmup untimed
-ones (a throw-away run), every slice between two device synchronisations, and `value` = steps / mean slice: the
-job's average rate, whatever --steps and --warmup are (the schedule's cost per iteration is not uniform: run_single).
+relaxed to the controller's own stop; exactly --steps iterations of it are timed after --warmup untimed ones (a
+throw-away run), in slices between device synchronisations, and `value` = steps / their summed time.  With --steps
+at least the job's length that is the run's first --steps iterations; with fewer, each phase of the job's schedule
+gets its share of the steps to within one iteration (timed_slices), so `value` is the job's average rate up to that
+rounding (config 3, measured: within 2 % of the --full rotation median at 20, 50, 100 and 200 steps; at 10-20 steps
+the unfolding phase's share is 0.4 of an iteration, whose rounding alone is worth about 5 %).  `ms_per_step` is the
+milliseconds of one timed step.
+Exact --steps and --full apply to the one-GPU path; the row-sharded path (N > 1, --mode, --devices) keeps its K-step
+slices and reports everything on every run.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what the headline does not need
+(N = 1): the job timed in rotations of K-iteration slices, the profiled pass behind `roofline`, the job in one
+piece, the MAE gates against the oracle, the f64 job and the CPU baseline.  `--dump-outputs DIR` writes what the
+timed run returned (positions, check trace, result scalars) to DIR/*.npy; the inputs are seeded, so two builds
+can be compared output for output.
 
   N = 1 : BASELINE.json config 3 -- synthetic N=10 000, 70 % missing, ndim=5, k0=5,
           cooling=0.01, c_repulsion=0.01 -- one embedding on one GPU, targets resident in HBM.
@@ -19,11 +31,11 @@ job's average rate, whatever --steps and --warmup are (the schedule's cost per i
           the field `replicas` (`--mode sharded` / `--mode replicas` run only one of the two).  `--gpus 1 --mode
           sharded` runs the same code at world size 1: the base of the strong-scaling curve.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (slab_stage_pipe_kernel):
+Prints ONE JSON line (rank 0).  `roofline` (--full) prices the dominant kernel (slab_stage_pipe_kernel):
 algorithmic bytes per launch = (4*rows*N + 8*N*ndim + 4*N) / stages, divided by its mean
 duration from HIP events recorded on the session stream around every launch in a separate
-profiled pass.  `cpu_baseline` times the CPU oracle (reference schedule, 1 core) on a bounded
-sample of the same workload (N=1 only); `precision_f64` is the same job in the reference's arithmetic width.
+profiled pass.  `cpu_baseline` (--full) times the CPU oracle (reference schedule, 1 core) on a bounded
+sample of the same workload (N=1 only); `precision_f64` (--full) is the same job in the reference's arithmetic width.
 """
 import argparse
 import json
@@ -44,21 +56,28 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (N = 1: rotations, roofline, "
+                         "whole run, MAE gates, f64 job, CPU baseline)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default="",
+                    help="write what the timed run returned to DIR/<name>.npy (one-GPU path)")
     ap.add_argument("--min-timed", dest="min_timed", type=float, default=0.25,
-                    help="repeat the rotation of K-step slices over the job until this many seconds have been timed")
+                    help="--full: repeat the rotation of K-step slices over the job until this many seconds have "
+                         "been timed")
     ap.add_argument("--devices", type=str, default="",
                     help="--mode sharded in ONE process: comma-separated HIP ordinals of the row blocks, e.g. "
                          "0,1,2,3,4,5,6,7 (an ordinal may repeat: several row blocks on one GPU)")
     ap.add_argument("--points", dest="n", type=int, default=0, help="override the number of points (testing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-iters", type=int, default=3)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-iters", type=int, default=3, help="--full: iterations of the CPU baseline")
     ap.add_argument("--stages", type=int, default=0, help="fixed slab stages (0 = adaptive)")
     ap.add_argument("--mode", choices=["auto", "replicas", "sharded"], default="auto",
                     help="auto: one GPU -> config 3 on that GPU; more than one -> ONE row-sharded config-4 embedding "
                          "(strong scaling: the line's value) followed by independent config-3 embeddings per GPU "
                          "(weak scaling: the line's `replicas` field); replicas / sharded: only that one")
     ap.add_argument("--precision-f64", dest="f64", action="store_true", default=True,
-                    help="also time the same job in f64 (the reference's arithmetic width); --no-precision-f64 skips it")
+                    help="--full: also time the same job in f64 (the reference's arithmetic width); --no-precision-f64 "
+                         "skips it")
     ap.add_argument("--no-precision-f64", dest="f64", action="store_false")
     return ap.parse_args()
 
@@ -73,6 +92,63 @@ def workload_single(n):
     return call, time.time() - t0
 
 
+def job_phases(n_job, k0, cooling, ndim, fixed_stages):
+    """[first, end) of each run of iterations with the same number of slab stages in the job's n_job iterations: the
+    session's own schedule, slab_stages_at(iteration, k) with k = k0 (1 - cooling)^iteration (16 stages while the
+    layout unfolds, two while k > 3, then one: DESIGN.md section 2b)."""
+    from topolow_amd import _native
+    k, firsts, prev = k0, [], None
+    for it in range(n_job):
+        st = fixed_stages if fixed_stages > 0 else _native.slab_stages_at(it, k, ndim)
+        if st != prev:
+            firsts.append(it)
+            prev = st
+        k *= 1.0 - cooling
+    return list(zip(firsts, firsts[1:] + [n_job]))
+
+
+def timed_slices(K, phases):
+    """(start, length) of the timed slices: K iterations of the run's first max(K, job) iterations.
+
+    K >= job: one slice, the run's first K iterations -- the job from its start and, the controller being unable to
+    stop the run, as many further iterations as K asks for.  K < job: K iterations cannot hold the whole job, whose
+    cost per iteration differs between its phases (job_phases) but not within one, so every phase gets its share of
+    K (largest remainders: within one iteration of K x phase length / job length).  A phase's iterations sit at its
+    end or its start, alternately, so that the slices of neighbouring phases meet at the boundary and are timed as
+    one."""
+    n_job = phases[-1][1]
+    if K >= n_job:
+        return [(0, K)]
+    share = [K * (b - a) / n_job for a, b in phases]
+    count = [int(x) for x in share]
+    for p in sorted(range(len(phases)), key=lambda p: count[p] - share[p])[:K - sum(count)]:
+        count[p] += 1
+    out = []
+    for p, ((a, b), c) in enumerate(zip(phases, count)):
+        if c == 0:
+            continue
+        start = b - c if p % 2 == 0 else a
+        if out and out[-1][0] + out[-1][1] == start:
+            out[-1] = (out[-1][0], out[-1][1] + c)
+        else:
+            out.append((start, c))
+    return out
+
+
+def dump_outputs(dirname, res, trace):
+    """What a caller of the timed path receives from its last run (Session.finish, Session.check_trace), as .npy."""
+    os.makedirs(dirname, exist_ok=True)
+    pos = np.ascontiguousarray(res.positions, dtype=np.float64)
+    if pos.nbytes > 48 << 20:                # a fixed, seeded sample of the rows keeps the files under 64 MB
+        rows = np.sort(np.random.default_rng(0).choice(pos.shape[0], (48 << 20) // pos[0].nbytes, replace=False))
+        np.save(os.path.join(dirname, "positions_rows.npy"), rows.astype(np.float64))
+        pos = pos[rows]
+    np.save(os.path.join(dirname, "positions.npy"), pos)
+    np.save(os.path.join(dirname, "check_trace.npy"), np.asarray(trace, dtype=np.float64))
+    np.save(os.path.join(dirname, "result.npy"), np.array([float(res.converged), float(res.iterations),
+                                                           res.final_mae, res.final_k], dtype=np.float64))
+
+
 def run_single(args):
     import torch
     from topolow_amd import _native
@@ -80,6 +156,7 @@ def run_single(args):
     n = args.n or 10000
     ndim = 5
     K, W = args.steps, args.warmup
+    assert K >= 1 and W >= 0, (K, W)
     k0, cool, c_rep = 5.0, 0.01, 0.01
     call, gen_s = workload_single(n)
 
@@ -96,25 +173,123 @@ def run_single(args):
         # the window is large enough that it never stops the run
         s.begin(total, k0, cool, c_rep, 1e-4, 10 ** 9, 3, 2024, args.stages)
 
+    def advance(m):
+        done = 0
+        while done < m:
+            got = s.enqueue(m - done)
+            if got == 0:
+                break
+            done += got
+        return done
+
     # ---- the job: one embedding relaxed to the controller's own stop (the reference's use) ----
-    for _warm in (True, False):      # the first run loads the code objects; the second is the one timed
+    def job():
         s.set_positions(call.initial_positions)
         s.begin(1000, k0, cool, c_rep, 1e-4, 5, 3, 2024, args.stages)
         torch.cuda.synchronize()
         t = time.perf_counter()
         s.run()
-        iters_run, _st, _m = s.sync()
+        iters, _st, _m = s.sync()
         torch.cuda.synchronize()
-        whole = time.perf_counter() - t
-        q = s.finish()
-    n_job = int(iters_run)
+        return int(iters), time.perf_counter() - t, s.finish()
 
-    # ---- timed region: the job in slices of EXACTLY K iterations.  The schedule's cost per iteration is not
-    # uniform (16 stages per iteration while the layout unfolds, two while k > 3, then one: DESIGN.md section
-    # 2b), so K iterations from one place would price that place, not the job; every iteration of the job is
-    # therefore timed exactly once per rotation, K at a time, each slice bracketed by device synchronisations,
-    # and value = K / mean slice.  The W warm-up iterations are spent before the job starts.  (Throughput run: the controller checks and
-    # snapshots every 3 iterations as always, but cannot stop the run.)
+    n_job = job()[0]                 # untimed: loads the code objects and fixes the job's length
+    if args.full:                    # the job again, timed in one piece (whole_run)
+        iters_run, whole, q = job()
+
+    # ---- timed region: EXACTLY K iterations (timed_slices says which), each slice bracketed by device
+    # synchronisations, value = K / their summed time.  The W warm-up iterations (clocks, caches) are a throw-away
+    # run before the timed one; iterations between two slices run untimed.  (Throughput run: the controller checks
+    # and snapshots every 3 iterations as always, but cannot stop the run.)
+    slices = timed_slices(K, job_phases(n_job, k0, cool, ndim, args.stages))
+    total = max(K, n_job)
+    if W > 0:
+        fresh(W)
+        advance(W)
+        s.sync()
+    fresh(total)
+    at, times = 0, []
+    for start, ln in slices:
+        if start > at:
+            got = advance(start - at)
+            assert got == start - at, (got, start - at)
+            s.wait()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        done = advance(ln)
+        # a slice ends when its launches have completed; a convergence check that is waiting to ride on the next
+        # iteration's sweep stays pending across the slice boundary, exactly as in the uninterrupted job (forcing
+        # it would add a separate error pass the job never runs).  The flush at the run's end is timed when K >= job
+        # (the run's own end, as in the rotations); after a sample of the job it is not (the job pays it once in
+        # job_iterations, a sample of K would otherwise pay it once in K)
+        stopped = False
+        if K >= n_job:
+            _iters, stopped, _mae = s.sync()
+        else:
+            s.wait()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t)
+        assert done == ln and not stopped, (done, stopped)
+        at = start + ln
+    if K < n_job:                                # the rest of the job and its flush, untimed: final_mae and the dump
+        got = advance(total - at)
+        assert got == total - at, (got, total - at)
+        s.sync()
+    elapsed = float(sum(times))                  # seconds of the K timed iterations
+    trace = s.check_trace()
+    res = s.finish()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, trace)
+
+    out = {
+        "metric": "relaxation iterations/sec (NxN pairs)",
+        "value": K / elapsed,
+        "unit": "iterations/s",
+        "n_gpus": 1,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": 1e3 * elapsed / K,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"config 3: synthetic N={n}, 70% missing, ndim=5, k0=5, cooling=0.01, "
+                               "c_repulsion=0.01, check every 3 iterations",
+                   "n_points": n, "ndim": ndim, "schedule": "slab",
+                   "edges": int(call.edge_i.size), "mae_pass": "dense" if s.uses_dense_mae else "edges"},
+        "timing": {"job_iterations": n_job, "timed_steps": K, "timed_seconds": elapsed,
+                   "slices": [[int(a), int(b)] for a, b in slices],
+                   "note": "K timed iterations after W untimed ones of a throw-away run: for K >= job_iterations the "
+                           "run's first K iterations (the job, then one-stage iterations past the controller's stop), "
+                           "for fewer each phase of the job (16-, 2-, 1-stage iterations) in proportion, to within one "
+                           "iteration (slices = [first iteration, length]); each slice between two device "
+                           "synchronisations; value = K / their summed time.  A convergence check that is waiting to "
+                           "ride on the next iteration's sweep stays pending across a slice boundary, as in the "
+                           "uninterrupted job.  final_mae and --dump-outputs: the run of max(K, job_iterations) "
+                           "iterations the slices were taken from"},
+        "final_mae": res.final_mae,
+        "final_mae_iteration": res.iterations,
+        "setup_seconds": {"generate": gen_s, "upload_encode": upload_s},
+        "dtype_note": ("the reference computes in f64 (src/optimization.cpp:134,207-281); value is the fp32 slab path, "
+                       "whose parity band is the header's statement (include/topolow_relax.h); the same job in f64: "
+                       "precision_f64 (--full)"),
+    }
+    if args.full:
+        full_report(args, out, s, call, n, ndim, K, W, fresh, n_job, iters_run, whole, q)
+    s.close()
+    print(json.dumps(out))
+
+
+def full_report(args, out, s, call, n, ndim, K, W, fresh, n_job, iters_run, whole, q):
+    """--full: everything the headline does not need -- the job timed in rotations of K-iteration slices, the
+    profiled pass behind `roofline`, the job in one piece, the MAE gates, the f64 job and the CPU baseline."""
+    import torch
+    from topolow_amd import _native
+    k0, cool, c_rep = 5.0, 0.01, 0.01
+
+    # ---- the job in slices of EXACTLY K iterations, every iteration of the job timed once per rotation, K at a
+    # time, each slice bracketed by device synchronisations; rotations until --min-timed seconds (at least 3) ----
     P = max(1, -(-n_job // K))
 
     def rotation():
@@ -135,10 +310,6 @@ def run_single(args):
                 if got == 0:
                     break
                 done += got
-            # a slice ends when its launches have completed; a convergence check that is waiting to ride on the next
-            # iteration's sweep stays pending across the slice boundary, exactly as in the uninterrupted job (forcing
-            # it would add a separate error pass the job never runs); the LAST slice flushes it, so every check of
-            # the job is inside a timed slice
             stopped = False
             if _p + 1 < P:
                 s.wait()
@@ -152,10 +323,18 @@ def run_single(args):
     rotations = []
     while (sum(map(sum, rotations)) < args.min_timed or len(rotations) < 3) and len(rotations) < 100:
         rotations.append(rotation())
-    res = s.finish()
+    s.finish()
     rates = [K / float(np.mean(r)) for r in rotations]          # one job-average estimate per rotation
-    elapsed = K / float(np.median(rates))                        # seconds per K steps at the median estimate
     slice_rates = K / np.mean(np.array(rotations), axis=0)       # per slice position, mean over rotations
+    out["timing"].update({
+        "slices_per_rotation": P, "rotations": len(rotations), "rotation_seconds": float(sum(map(sum, rotations))),
+        "iterations_per_s": {"min": min(rates), "median": float(np.median(rates)), "max": max(rates)},
+        "iterations_per_s_by_slice": [round(float(x), 1) for x in slice_rates],
+        "rotation_note": "the job (one embedding to the controller's own stop: job_iterations) timed in slices of "
+                         "exactly K iterations, each between two device synchronisations, after W untimed iterations "
+                         "of a throw-away run; a rotation times every slice once; iterations_per_s = K / mean slice "
+                         "per rotation.  by_slice shows the schedule: the first slices hold the 16- and 2-stage "
+                         "iterations"})
 
     # ---- profiled pass over the same iterations: HIP events around every stage launch on the session stream ----
     fresh(P * K)
@@ -239,52 +418,20 @@ def run_single(args):
     achieved = dominant["achieved"]
     avg_launch_s = dominant["avg_launch_us"] * 1e-6
     bytes_per_launch = dominant["algorithmic_bytes_per_launch"]
-
-    out = {
-        "metric": "relaxation iterations/sec (NxN pairs)",
-        "value": K / elapsed,
-        "unit": "iterations/s",
-        "n_gpus": 1,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": 1e3 * elapsed / K,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"config 3: synthetic N={n}, 70% missing, ndim=5, k0=5, cooling=0.01, "
-                               "c_repulsion=0.01, check every 3 iterations",
-                   "n_points": n, "ndim": ndim, "schedule": "slab", "stages_per_iteration": stages_per_iter,
-                   "edges": int(call.edge_i.size), "mae_pass": "dense" if s.uses_dense_mae else "edges"},
-        "timing": {"job_iterations": n_job, "slices_per_rotation": P, "rotations": len(rotations),
-                   "timed_seconds": float(sum(map(sum, rotations))),
-                   "iterations_per_s": {"min": min(rates), "median": float(np.median(rates)), "max": max(rates)},
-                   "iterations_per_s_by_slice": [round(float(x), 1) for x in slice_rates],
-                   "note": "the job (one embedding to the controller's own stop: job_iterations) is timed in slices "
-                           "of exactly K iterations, each between two device synchronisations, after W untimed "
-                           "iterations of a throw-away run; a rotation times every slice once; value = K / mean slice, median "
-                           "over rotations -- the job's average rate whatever K and W are.  by_slice shows the "
-                           "schedule: the first slices hold the 16- and 2-stage iterations.  A convergence check that "
-                           "is waiting to ride on the next iteration's sweep stays pending across a slice boundary, as "
-                           "in the uninterrupted job; the last slice flushes it, so every check lies inside a timed slice"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
-                     "traffic_refers_to": {"launch": "one one-stage iteration of the dominant kind",
-                                           "algorithmic_bytes": bytes_iter,
-                                           "ratio": (traffic / bytes_iter) if traffic else None,
-                                           "physical_GBps": (traffic / avg_launch_s / 1e9) if traffic else None},
-                     "kernel": dominant["kernel"], "avg_launch_us": avg_launch_s * 1e6,
-                     "launches": dominant["launches"], "algorithmic_bytes_per_launch": bytes_per_launch,
-                     "dominant_note": dominant["note"], "by_kind": parts, "job": job,
-                     "timing": "HIP events on the session stream around every sweep (a symmetric sweep and its apply "
-                               "as one), in a separate pass over the same iterations (inside the timed slices the "
-                               "events themselves would cost throughput); rocprofv3 kernel-trace means: profiles/",
-                     "check_us": (check_ms * 1e3 / checks) if checks else None},
-        "final_mae": res.final_mae,
-        "final_mae_iteration": res.iterations,
-        "setup_seconds": {"generate": gen_s, "upload_encode": upload_s},
-    }
+    out["config"]["stages_per_iteration"] = stages_per_iter
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
+                       "traffic_refers_to": {"launch": "one one-stage iteration of the dominant kind",
+                                             "algorithmic_bytes": bytes_iter,
+                                             "ratio": (traffic / bytes_iter) if traffic else None,
+                                             "physical_GBps": (traffic / avg_launch_s / 1e9) if traffic else None},
+                       "kernel": dominant["kernel"], "avg_launch_us": avg_launch_s * 1e6,
+                       "launches": dominant["launches"], "algorithmic_bytes_per_launch": bytes_per_launch,
+                       "dominant_note": dominant["note"], "by_kind": parts, "job": job,
+                       "timing": "HIP events on the session stream around every sweep (a symmetric sweep and its apply "
+                                 "as one), in a separate pass over the same iterations (inside the timed slices the "
+                                 "events themselves would cost throughput); rocprofv3 kernel-trace means: profiles/",
+                       "check_us": (check_ms * 1e3 / checks) if checks else None}
 
     # the job itself, timed in one piece (measured first, above)
     out["whole_run"] = {"iterations_run": int(iters_run), "seconds": whole, "iterations_per_s": iters_run / whole,
@@ -303,9 +450,6 @@ def run_single(args):
                             "band": 0.04}
         assert q.converged and abs(q.final_mae / ref - 1.0) <= 0.04, out["mae_check"]
 
-    out["dtype_note"] = ("the reference computes in f64 (src/optimization.cpp:134,207-281); value is the fp32 slab path, "
-                         "whose parity band is the header's statement (include/topolow_relax.h); the same job in f64: "
-                         "precision_f64")
     if args.f64:
         # the same job, same schedule and labels, in the reference's arithmetic width (f64 instance of the stage
         # kernel; the symmetric sweep is fp32 only): rate of the whole run to the controller's own stop
@@ -369,8 +513,6 @@ def run_single(args):
         assert abs(g.final_mae - sm / cnt) <= 2e-5 * (sm / cnt), out["mae_check_early"]
         assert abs(g.final_mae / ref.final_mae - 1.0) <= 0.25, out["mae_check_early"]
         out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-    s.close()
-    print(json.dumps(out))
 
 
 def launch_ranks(args):
@@ -397,6 +539,7 @@ def main():
     if args.gpus > 1 and world == 1 and not args.devices:
         launch_ranks(args)
     if args.gpus > 1 or world > 1 or args.mode == "sharded" or args.devices:
+        assert not args.dump_outputs, "--dump-outputs: the one-GPU path only"
         from topolow_amd import sharded
         sharded.bench_main(args)
     else:

@@ -1,19 +1,22 @@
 """bench.py's contract on a small instance of its workload (run with -m gpu): one JSON line with the fields the
-driver reads, `value` = the job's average rate whatever --steps / --warmup are."""
+driver reads, `value` = the job's average rate whatever --steps / --warmup are, exactly --steps timed iterations;
+a plain run only times, --full adds the rest."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*extra):
+def run_bench(*extra, full=True):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--points", "2048", "--no-cpu-baseline",
-                        "--min-timed", "0.05", *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--min-timed", "0.05", *(("--full",) if full else ()), *extra], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -29,6 +32,11 @@ def test_bench_line_and_job_average():
         assert d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None
         assert d["value"] > 0 and abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-6 * 1e3
         t = d["timing"]
+        # exactly K timed iterations, in order, inside the run's first max(K, job) iterations
+        assert t["timed_steps"] == k and sum(ln for _s, ln in t["slices"]) == k
+        ends = [a + ln for a, ln in t["slices"]]
+        assert all(e <= a for e, (a, _l) in zip(ends, t["slices"][1:])) and ends[-1] <= max(k, t["job_iterations"])
+        assert abs(d["ms_per_step"] - 1e3 * t["timed_seconds"] / k) < 1e-9 * d["ms_per_step"]
         assert t["slices_per_rotation"] == -(-t["job_iterations"] // k) and t["rotations"] >= 3
         assert len(t["iterations_per_s_by_slice"]) == t["slices_per_rotation"]
         r = d["roofline"]
@@ -42,6 +50,46 @@ def test_bench_line_and_job_average():
     # config 3's size the same comparison is within 2 %: DESIGN.md section 6)
     assert abs(a["value"] / b["value"] - 1.0) < 0.35, (a["value"], b["value"])
     assert abs(a["value"] / a["whole_run"]["iterations_per_s"] - 1.0) < 0.35
+
+
+def test_plain_run_times_only_and_dumps_its_outputs(tmp_path):
+    """A plain run carries the headline and nothing that needs runs of its own; --dump-outputs writes what the timed
+    run returned, the same arrays from run to run (seeded inputs, fixed-order sums, a run the controller cannot stop)."""
+    runs = []
+    for tag in ("a", "b"):
+        d = run_bench("--steps", "150", "--warmup", "5", "--dump-outputs", str(tmp_path / tag), full=False)
+        assert d["steps"] == 150 and d["warmup"] == 5 and d["timing"]["timed_steps"] == 150
+        assert d["value"] > 0 and abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-6 * 1e3
+        assert d["dtype"] == "f32" and d["higher_is_better"] is True and d["unit"] == "iterations/s"
+        for key in ("roofline", "whole_run", "precision_f64", "cpu_baseline", "mae_check"):
+            assert key not in d, key
+        assert "rotations" not in d["timing"]
+        runs.append({f: np.load(tmp_path / tag / f) for f in ("positions.npy", "check_trace.npy", "result.npy")})
+    a, b = runs
+    assert a["positions.npy"].shape == (2048, 5) and a["positions.npy"].dtype == np.float64
+    assert np.isfinite(a["positions.npy"]).all() and a["result.npy"].shape == (4,)
+    total = sum(v.nbytes for v in a.values())
+    assert total <= 64 << 20
+    for f in a:
+        scale = max(1.0, float(np.abs(a[f]).max()))
+        assert a[f].shape == b[f].shape and np.allclose(a[f], b[f], rtol=0, atol=1e-6 * scale), f
+
+
+@pytest.mark.parametrize("k", [20, 50, 100, 200])
+def test_fewer_steps_than_the_job_still_price_the_job(k):
+    """Config 3 at its own size (a 396-iteration job: 8 sixteen-stage, 43 two-stage, 345 one-stage iterations).  With
+    K below the job's length the K timed iterations hold every phase in proportion, so the headline agrees with the
+    rotation median of the same process, which times every iteration of the job in K-iteration slices.  At K = 20 the
+    unfolding phase's share is 0.4 of an iteration, and its rounding is worth about 5 %."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(k), "--warmup", "5", "--full",
+                        "--no-cpu-baseline", "--no-precision-f64"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    t = d["timing"]
+    assert t["job_iterations"] > k and t["timed_steps"] == k and sum(ln for _s, ln in t["slices"]) == k
+    assert t["slices"][0][0] < 8 or k < 50               # from 50 steps up the sample holds an unfolding iteration
+    band = 0.08 if k < 50 else 0.04                      # measured: 0.980-0.997 of the median
+    assert abs(d["value"] / t["iterations_per_s"]["median"] - 1) <= band, (k, d["value"], t["iterations_per_s"])
 
 
 def run_bench_env(env_extra, *args):

@@ -1,6 +1,6 @@
 """topolow_amd.rda: the .rda (RDX3/RDX2 XDR) reader.  The streams are built here, byte by byte, after
-R's serialisation format (R Internals, section 'Serialization Formats'); when the reference checkout
-is present its bundled data sets are parsed as well (data only, nothing executed)."""
+R's serialisation format (R Internals, section 'Serialization Formats'); the reference package's bundled
+data sets, stored under tests/golden/reference_data/, are parsed as well (data only, nothing executed)."""
 import bz2
 import gzip
 import lzma
@@ -130,17 +130,17 @@ def test_refuses_what_it_cannot_parse(tmp_path):
         rda.read_rda(str(p))
 
 
-REF_DATA = "/root/reference/data"
+# the reference package's data/h3n2_data.rda and data/hiv_titers.rda as shipped, and data-raw/Smith2004-data.csv gzipped
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference checkout not present")
 def test_reference_data_sets_parse_and_feed_the_pipeline():
     """h3n2_data = 3 542 rows (the same table as data-raw/Smith2004-data.csv),
     hiv_titers = 178 912 rows of Antibody / Virus / IC50 with censored values such as ">150"."""
     import csv
     h3 = rda.read_rda(os.path.join(REF_DATA, "h3n2_data.rda"))["h3n2_data"]
     assert len(h3) == 3542 and h3.names[:3] == ["virusStrain", "serumStrain", "titer"]
-    raw = list(csv.DictReader(open("/root/reference/data-raw/Smith2004-data.csv", encoding="utf-8-sig")))
+    raw = list(csv.DictReader(gzip.open(os.path.join(REF_DATA, "Smith2004-data.csv.gz"), "rt", encoding="utf-8-sig")))
     rows = h3.rows()
     assert [r["titer"] for r in rows] == [r["titer"] for r in raw]
     assert [r["virusStrain"] for r in rows] == [r["virusStrain"] for r in raw]

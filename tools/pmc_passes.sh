@@ -5,7 +5,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 P=$1
-run() { rocprofv3 --pmc $2 --output-format csv -d $P_$1 -- python3 bench.py --steps 9 --warmup 3 --no-cpu-baseline > $P_$1.log 2>&1; }
+run() { rocprofv3 --pmc $2 --output-format csv -d $P_$1 -- python3 bench.py --full --steps 9 --warmup 3 --no-cpu-baseline > $P_$1.log 2>&1; }
 P_=${P}_
 run a "SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_ANY"
 run b "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_WAIT_INST_LDS SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_INST_LEVEL_LDS"
