@@ -85,7 +85,7 @@ for k, v in summary.items():
         v["hbm_traffic_bytes_per_launch"] = v["hbm_read_bytes_per_launch"] + v["hbm_write_bytes_per_launch"]
 # one symmetric one-stage iteration = its sweep (plain instance) + its apply: the entry bench.py's roofline.traffic reads
 sw = [k for k in summary if "symm_sweep_kernel<5, false, false>" in k and "[whole-triangle sweeps]" in k]
-ap = [k for k in summary if "symm_apply_kernel<5>" in k]
+ap = [k for k in summary if "symm_apply_kernel<5, float>" in k]
 if sw and ap and "hbm_traffic_bytes_per_launch" in summary[sw[0]] and "hbm_traffic_bytes_per_launch" in summary[ap[0]]:
     a, b = summary[sw[0]], summary[ap[0]]
     both = {}

@@ -104,15 +104,15 @@ int main(int argc, char** argv) {
   const std::vector<SymRun> runs = plan.runs();
   CK(hipMalloc(&d_wf, runs.size() * sizeof(SymRun))); CK(hipMemcpy(d_wf, runs.data(), runs.size() * sizeof(SymRun), hipMemcpyHostToDevice));
 
-  hipLaunchKernelGGL(symm_records_kernel<DIM>, dim3((npad + 255) / 256), dim3(256), 0, 0, d_pos, d_g, d_rec, n, npad, k, c_rep);
-  hipLaunchKernelGGL(symm_records_kernel<DIM>, dim3((npad + 255) / 256), dim3(256), 0, 0, d_pos, d_g, d_rec2, n, npad, k, c_rep);
+  hipLaunchKernelGGL((symm_records_kernel<DIM, float>), dim3((npad + 255) / 256), dim3(256), 0, 0, d_pos, d_g, d_rec, n, npad, k, c_rep);
+  hipLaunchKernelGGL((symm_records_kernel<DIM, float>), dim3((npad + 255) / 256), dim3(256), 0, 0, d_pos, d_g, d_rec2, n, npad, k, c_rep);
   CK(hipDeviceSynchronize()); printf("records done\n");
   hipLaunchKernelGGL(ref_kernel<DIM>, dim3((n + 63) / 64), dim3(64), 0, 0, d_enc, ld, d_pos, d_g, n, k, c_rep, d_ref, d_err);
   CK(hipDeviceSynchronize()); printf("ref done\n");
   hipLaunchKernelGGL((symm_sweep_kernel<DIM, false, true>), dim3(grid), dim3(64 * kSymWaves), 0, 0, d_tenc, d_rec, d_units,
                      d_wf, d_rowp, d_colp, npad, (const RunState*)nullptr, d_psum, d_pcnt, 0ull, 0);
   CK(hipDeviceSynchronize()); printf("sweep done\n");
-  hipLaunchKernelGGL(symm_apply_kernel<DIM>, dim3(TC), dim3(32 * kSymApplyParts), 0, 0, d_rec, d_rec2, d_out, d_g, d_rowp, d_colp, d_ru, n, npad,
+  hipLaunchKernelGGL((symm_apply_kernel<DIM, float>), dim3(TC), dim3(32 * kSymApplyParts), 0, 0, d_rec, d_rec2, d_out, d_g, d_rowp, d_colp, d_ru, n, npad,
                      k * 0.99, c_rep, 1, (RunState*)nullptr);
   CK(hipDeviceSynchronize()); printf("apply done\n");
   std::vector<float> out(pos.size()), ref(pos.size());
@@ -144,7 +144,7 @@ int main(int argc, char** argv) {
                        d_units, d_wf, d_rowp, d_colp, npad, (const RunState*)nullptr, d_psum, d_pcnt, 0ull, 0);
   };
   auto apply = [&]() {
-    hipLaunchKernelGGL(symm_apply_kernel<DIM>, dim3(TC), dim3(32 * kSymApplyParts), 0, 0, d_rec, d_rec2, d_out, d_g, d_rowp, d_colp, d_ru, n, npad,
+    hipLaunchKernelGGL((symm_apply_kernel<DIM, float>), dim3(TC), dim3(32 * kSymApplyParts), 0, 0, d_rec, d_rec2, d_out, d_g, d_rowp, d_colp, d_ru, n, npad,
                        k * 0.99, c_rep, 1, (RunState*)nullptr);
   };
   time([&]() { sweep(std::false_type{}); }, "sweep");

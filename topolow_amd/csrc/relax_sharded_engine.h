@@ -173,17 +173,19 @@ inline void sharded_worker(ShardedRun& R, int r) {
     if (pend && !fuse_now) { if (!separate_check(pend_buf, pend_iter1, pend_k)) return; pend = false; }
     const int tab = (int)(n_check & 1) * R.P;   // the table of the check this sweep carries, if any
     if (fuse_now) ++n_check;
+    // ONE block = the whole matrix: its iterations take the forms of the session's own loop (sym_form)
+    const SymForm form = R.P == 1 ? sym_form(lead, geo.n_stages) : SymForm::kRowOwner;
     if (R.pair_sharded && geo.n_stages == 1) {
       // every session sweeps its segment of the tile list and folds its partials into the owners' inboxes; barrier;
       // the owners move their points and store them into every session's next buffer; barrier
       const int nxt = (cur + 1) % 3;
       for (int b : G.blocks) {
         topolow_session* s = R.ss[b];
-        TL_DISPATCH_DIM(s->dim, sym_sharded_sweep, s, s->pos[cur].p, iter, k, fuse_now);
+        TL_DISPATCH_SYM(s->dim, sym_sharded_sweep, s, s->pos[cur].p, iter, k, fuse_now);
         if (fuse_now) {
           ProfScope prof(s, &s->prof_check);
           hipLaunchKernelGGL(reduce_push_kernel, dim3(1), dim3(1024), 0, s->stream, s->part_sum.p, s->part_cnt.p,
-                             s->sym.n_units, s->rsum_tab.p, s->rcnt_tab.p, s->n_ranks, tab + s->rank, s->state.p);
+                             s->sym.plan.n_units, s->rsum_tab.p, s->rcnt_tab.p, s->n_ranks, tab + s->rank, s->state.p);
           HIP_TRY(hipGetLastError());
         }
       }
@@ -198,21 +200,18 @@ inline void sharded_worker(ShardedRun& R, int r) {
       }
       for (int b : G.blocks) {
         topolow_session* s = R.ss[b];
-        TL_DISPATCH_DIM(s->dim, sym_sharded_apply, s, s->pos[cur].p, s->pos[nxt].p, s->push_tab[nxt].p, iter);
+        TL_DISPATCH_SYM(s->dim, sym_owner_apply, s, s->pos[cur].p, s->pos[nxt].p, s->row_begin, s->row_end, s->push_tab[nxt].p,
+                        s->n_push, iter);
       }
       if (!exchange()) return;
       cur = nxt;
-    } else if (R.P == 1 && lead->sym.two_stage && sym_rr_stages_ok(geo.n_stages) && sym_eligible(lead) && sym_available(lead) &&
-               sym_rr_available(lead, geo.n_stages)) {
-      // ONE block = the whole matrix: a 2-, 4- or 8-stage iteration as symmetric sweeps over the tiles of one stage each,
-      // as in the session's own loop
+    } else if (form == SymForm::kStages) {   // a 2-, 4- or 8-stage iteration as symmetric sweeps over the tiles of one stage each
       const int S = geo.n_stages;
       int order[8];
       sym_rr_order(lead->seed, iter, S, order);
       for (int t = 0; t < S; ++t) {
-        const bool last = t == S - 1;
-        TL_DISPATCH_DIM(lead->dim, sym_rr_stage, lead, lead->pos[cur].p, lead->pos[(cur + 1) % 3].p, iter, k,
-                        last ? k * (1.0 - R.cooling) : k, S, order[t], last ? iter + 1 : iter);
+        TL_DISPATCH_SYM(lead->dim, sym_iteration, lead, lead->pos[cur].p, lead->pos[(cur + 1) % 3].p, iter, k, false, S,
+                        order[t], t == S - 1);
         if (!exchange()) return;
         cur = (cur + 1) % 3;
       }
@@ -222,11 +221,9 @@ inline void sharded_worker(ShardedRun& R, int r) {
       for (int b : G.blocks) {
         topolow_session* s = R.ss[b];
         int stage_blocks = (s->rows() + CfgProd::ROWS - 1) / CfgProd::ROWS;
-        if (R.P == 1 && geo.n_stages == 1 && sym_eligible(s) && sym_available(s)) {
-          // ONE block = the whole matrix: a one-stage iteration may run as the symmetric sweep (relax_symm.h), as in
-          // the session's own loop; its error partials are one per (unit)
-          TL_DISPATCH_DIM(s->dim, sym_iteration, s, s->pos[cur].p, s->pos[(cur + 1) % 3].p, iter, k, fuse_now);
-          stage_blocks = s->sym.n_units;
+        if (form == SymForm::kSweep) {   // (relax_symm.h) its error partials are one per unit
+          TL_DISPATCH_SYM(s->dim, sym_iteration, s, s->pos[cur].p, s->pos[(cur + 1) % 3].p, iter, k, fuse_now);
+          stage_blocks = s->sym.plan.n_units;
         } else {
           TL_DISPATCH_DIM(s->dim, launch_stage, s, s->pos[cur].p, s->pos[(cur + 1) % 3].p, s->state.p, rg, iter + 1, k,
                           s->push_tab[(cur + 1) % 3].p, s->n_push, fuse_now);

@@ -539,6 +539,16 @@ __global__ __launch_bounds__(64 * kSymWaves, TOPOLOW_SYM_MINW) void symm_sweep_k
 #endif
 }
 
+// What the apply and records kernels do differently per type: record width, the record's constants (each type keeps
+// its own expression), the phantom record and (f64) the lane exchange.  (f64: relax_symm64.h.)
+template <int DIM, typename real> struct SymReal;
+template <int DIM> struct SymReal<DIM, float> {
+  static constexpr int W = SymRec<DIM>::W;
+  __device__ static float ks(double k, float g) { return (float)(2.0 * k) / (4.0f * g + (float)k); }
+  __device__ static float cg(double c_rep, float g) { return (float)(0.5 * c_rep) / g; }
+  __device__ static float far(int) { return kFarF32; }
+};
+
 // Sums the partials of one column block's 32 points in a fixed order and moves the points:
 //   p_i(new) = p_i - (row sums of i's units) + (column sums of the tile-rows above i's)
 // (relax_kernels.h: p_i(new) = p_i - sum over ALL c of (p_c - p_i) coef_i; for c in a tile-row above, the stored
@@ -549,21 +559,22 @@ __global__ __launch_bounds__(64 * kSymWaves, TOPOLOW_SYM_MINW) void symm_sweep_k
 #define TL_APPLY_PARTS 16
 #endif
 constexpr int kSymApplyParts = TL_APPLY_PARTS;   // threads of the apply kernel: 16 parts x 32 points (a column block); a wave = 2 parts
-template <int DIM>
+template <int DIM, typename real>
 __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
-    const float* __restrict__ rec, float* __restrict__ rec_next, float* __restrict__ pos_out, const float* __restrict__ gplus,
-    const float* __restrict__ rowpart, const float* __restrict__ colpart, const int2* __restrict__ row_units, int n,
+    const real* __restrict__ rec, real* __restrict__ rec_next, real* __restrict__ pos_out, const float* __restrict__ gplus,
+    const real* __restrict__ rowpart, const real* __restrict__ colpart, const int2* __restrict__ row_units, int n,
     int npad, double k_next, double c_rep, int iter1, RunState* st, int rr_stages = 0, int rr_stage = 0) {
   if (st != nullptr && st->stopped) return;
-  constexpr int W = SymRec<DIM>::W;
+  using T = SymReal<DIM, real>;
+  constexpr int W = T::W;
   constexpr int kWavesA = kSymApplyParts / 2;
-  __shared__ float red[kWavesA][kSymCols][DIM];
+  __shared__ real red[kWavesA][kSymCols][DIM];
   const int R = blockIdx.x >> 1;                   // the tile-row of this column block's points
   const int part = threadIdx.x >> 5, pt = threadIdx.x & 31;
   const int i = blockIdx.x * kSymCols + pt;
-  float acc[DIM];
+  real acc[DIM];
 #pragma unroll
-  for (int d = 0; d < DIM; ++d) acc[d] = 0.0f;
+  for (int d = 0; d < DIM; ++d) acc[d] = 0;
   // column sums of the tile-rows above (added), this thread's share: R' = part, part + 16, ... (independent loads: all
   // of a thread's strips are in flight together).  rr_stages > 0: the sweep was ONE STAGE of a multi-stage iteration
   // (sym_rr_*: the tiles that pair this point's slab with its partner slab of the stage): only those tile-rows' sums are
@@ -571,20 +582,23 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
   int rp0 = 0, rp1 = R;
   if (rr_stages > 0) sym_rr_above(npad / kSymRows, rr_stages, rr_stage, R, rp0, rp1);
   for (int Rp = rp0 + part; Rp < rp1; Rp += kSymApplyParts) {
-    const float* src = colpart + ((size_t)Rp * npad + i) * DIM;
+    const real* src = colpart + ((size_t)Rp * npad + i) * DIM;
 #pragma unroll
     for (int d = 0; d < DIM; ++d) acc[d] += src[d];
   }
   const int2 ru = row_units[R];
   const int row_in_tile = i - R * kSymRows;
   for (int q = part; q < ru.y; q += kSymApplyParts) {
-    const float* src = rowpart + ((size_t)(ru.x + q) * kSymRows + row_in_tile) * DIM;
+    const real* src = rowpart + ((size_t)(ru.x + q) * kSymRows + row_in_tile) * DIM;
 #pragma unroll
     for (int d = 0; d < DIM; ++d) acc[d] -= src[d];
   }
   // fixed order: the two parts of a wave (lanes l, l + 32), then the waves, then onto the point
 #pragma unroll
-  for (int d = 0; d < DIM; ++d) acc[d] += __shfl_xor(acc[d], 32, 64);
+  for (int d = 0; d < DIM; ++d) {   // (each type keeps its own spelling of the exchange: a wrapped fp32 shuffle allocates differently)
+    if constexpr (std::is_same<real, float>::value) acc[d] += __shfl_xor(acc[d], 32, 64);
+    else acc[d] += T::lane_xor(acc[d], 32);
+  }
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 32) == 0) {
 #pragma unroll
@@ -593,10 +607,10 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
   __syncthreads();
   if (part == 0 && i < n) {
     bool finite = true;
-    float out[DIM];
+    real out[DIM];
 #pragma unroll
     for (int d = 0; d < DIM; ++d) {
-      float t = red[0][pt][d];
+      real t = red[0][pt][d];
 #pragma unroll
       for (int p = 1; p < kWavesA; ++p) t += red[p][pt][d];
       out[d] = rec[(size_t)i * W + d] + t;
@@ -604,36 +618,37 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
       pos_out[(size_t)i * DIM + d] = out[d];
       rec_next[(size_t)i * W + d] = out[d];
     }
-    const float g = gplus[i];
-    rec_next[(size_t)i * W + DIM] = (float)(2.0 * k_next) / (4.0f * g + (float)k_next);
-    rec_next[(size_t)i * W + DIM + 1] = (float)(0.5 * c_rep) / g;
+    const real g = (real)gplus[i];
+    rec_next[(size_t)i * W + DIM] = T::ks(k_next, g);
+    rec_next[(size_t)i * W + DIM + 1] = T::cg(c_rep, g);
     if (!finite && st != nullptr) atomicMin(&st->first_nonfinite, iter1);
   }
 }
 
 // Records of iteration `k` from plain positions (the first symmetric iteration after multi-stage ones, and the
 // phantom records [n, npad)).
-template <int DIM>
-__global__ __launch_bounds__(256) void symm_records_kernel(const float* __restrict__ pos, const float* __restrict__ gplus,
-                                                          float* __restrict__ rec, int n, int npad, double k, double c_rep) {
-  constexpr int W = SymRec<DIM>::W;
+template <int DIM, typename real>
+__global__ __launch_bounds__(256) void symm_records_kernel(const real* __restrict__ pos, const float* __restrict__ gplus,
+                                                          real* __restrict__ rec, int n, int npad, double k, double c_rep) {
+  using T = SymReal<DIM, real>;
+  constexpr int W = T::W;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= npad) return;
-  float* r = rec + (size_t)i * W;
+  real* r = rec + (size_t)i * W;
   if (i < n) {
 #pragma unroll
     for (int d = 0; d < DIM; ++d) r[d] = pos[(size_t)i * DIM + d];
-    const float g = gplus[i];
-    r[DIM] = (float)(2.0 * k) / (4.0f * g + (float)k);
-    r[DIM + 1] = (float)(0.5 * c_rep) / g;
+    const real g = (real)gplus[i];
+    r[DIM] = T::ks(k, g);
+    r[DIM + 1] = T::cg(c_rep, g);
   } else {
 #pragma unroll
-    for (int d = 0; d < DIM; ++d) r[d] = kFarF32;
-    r[DIM] = 0.0f;
-    r[DIM + 1] = 0.0f;
+    for (int d = 0; d < DIM; ++d) r[d] = T::far(d);
+    r[DIM] = 0;
+    r[DIM + 1] = 0;
   }
 #pragma unroll
-  for (int d = DIM + 2; d < W; ++d) r[d] = 0.0f;
+  for (int d = DIM + 2; d < W; ++d) r[d] = 0;
 }
 
 // The tile-major copy of tiles [t_first, t_first + gridDim.x) of the upper triangle from the row-major encoded matrix,

@@ -30,6 +30,15 @@ template <int DIM> struct SymRec64 { static constexpr int W = (DIM + 2 + 1) & ~1
 
 __device__ __forceinline__ double sym64_xor(double v, int mask) { return __shfl_xor(v, mask, 64); }
 
+// The apply and records kernels in f64 (relax_symm.h: symm_apply_kernel<DIM, double>, symm_records_kernel<DIM, double>).
+template <int DIM> struct SymReal<DIM, double> {
+  static constexpr int W = SymRec64<DIM>::W;
+  __device__ static double ks(double k, double g) { return 2.0 * k / (4.0 * g + k); }
+  __device__ static double cg(double c_rep, double g) { return 0.5 * c_rep / g; }
+  __device__ static double far(int d) { return d == 0 ? kFarF64 : 0.0; }
+  __device__ static double lane_xor(double v, int mask) { return sym64_xor(v, mask); }
+};
+
 // one row x one column: both halves of the pair.  base = (t - r) / (r + 0.01) for a spring, 1 / (r + 0.01)^3 otherwise;
 // every endpoint multiplies it with its own constant of that kind.
 template <int DIM, bool THR, bool ERR>
@@ -297,89 +306,6 @@ __global__ __launch_bounds__(64 * kSymWaves, ((DIM <= 3 || (DIM == 4 && !(ANYTHR
       }
     }
   }
-}
-
-// As symm_apply_kernel, in f64: p_i(new) = p_i - (row sums of i's units) + (column sums of the tile-rows above i's),
-// summed in a fixed order; writes the positions and the records of the next iteration.
-template <int DIM>
-__global__ __launch_bounds__(32 * kSymApplyParts) void symm64_apply_kernel(
-    const double* __restrict__ rec, double* __restrict__ rec_next, double* __restrict__ pos_out, const float* __restrict__ gplus,
-    const double* __restrict__ rowpart, const double* __restrict__ colpart, const int2* __restrict__ row_units, int n,
-    int npad, double k_next, double c_rep, int iter1, RunState* st, int rr_stages = 0, int rr_stage = 0) {
-  if (st != nullptr && st->stopped) return;
-  constexpr int W = SymRec64<DIM>::W;
-  constexpr int kWavesA = kSymApplyParts / 2;
-  __shared__ double red[kWavesA][kSymCols][DIM];
-  const int R = blockIdx.x >> 1;
-  const int part = threadIdx.x >> 5, pt = threadIdx.x & 31;
-  const int i = blockIdx.x * kSymCols + pt;
-  double acc[DIM];
-#pragma unroll
-  for (int d = 0; d < DIM; ++d) acc[d] = 0.0;
-  int rp0 = 0, rp1 = R;           // (rr_stages, rr_stage: as symm_apply_kernel)
-  if (rr_stages > 0) sym_rr_above(npad / kSymRows, rr_stages, rr_stage, R, rp0, rp1);
-  for (int Rp = rp0 + part; Rp < rp1; Rp += kSymApplyParts) {
-    const double* src = colpart + ((size_t)Rp * npad + i) * DIM;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) acc[d] += src[d];
-  }
-  const int2 ru = row_units[R];
-  const int row_in_tile = i - R * kSymRows;
-  for (int q = part; q < ru.y; q += kSymApplyParts) {
-    const double* src = rowpart + ((size_t)(ru.x + q) * kSymRows + row_in_tile) * DIM;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) acc[d] -= src[d];
-  }
-#pragma unroll
-  for (int d = 0; d < DIM; ++d) acc[d] += sym64_xor(acc[d], 32);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 32) == 0) {
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) red[wave][pt][d] = acc[d];
-  }
-  __syncthreads();
-  if (part == 0 && i < n) {
-    bool finite = true;
-    double out[DIM];
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-      double t = red[0][pt][d];
-#pragma unroll
-      for (int p = 1; p < kWavesA; ++p) t += red[p][pt][d];
-      out[d] = rec[(size_t)i * W + d] + t;
-      finite = finite && isfinite(out[d]);
-      pos_out[(size_t)i * DIM + d] = out[d];
-      rec_next[(size_t)i * W + d] = out[d];
-    }
-    const double g = (double)gplus[i];
-    rec_next[(size_t)i * W + DIM] = 2.0 * k_next / (4.0 * g + k_next);
-    rec_next[(size_t)i * W + DIM + 1] = 0.5 * c_rep / g;
-    if (!finite && st != nullptr) atomicMin(&st->first_nonfinite, iter1);
-  }
-}
-
-// Records of iteration `k` from plain positions, and the phantom records [n, npad).
-template <int DIM>
-__global__ __launch_bounds__(256) void symm64_records_kernel(const double* __restrict__ pos, const float* __restrict__ gplus,
-                                                            double* __restrict__ rec, int n, int npad, double k, double c_rep) {
-  constexpr int W = SymRec64<DIM>::W;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npad) return;
-  double* r = rec + (size_t)i * W;
-  if (i < n) {
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) r[d] = pos[(size_t)i * DIM + d];
-    const double g = (double)gplus[i];
-    r[DIM] = 2.0 * k / (4.0 * g + k);
-    r[DIM + 1] = 0.5 * c_rep / g;
-  } else {
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) r[d] = d == 0 ? kFarF64 : 0.0;
-    r[DIM] = 0.0;
-    r[DIM + 1] = 0.0;
-  }
-#pragma unroll
-  for (int d = DIM + 2; d < W; ++d) r[d] = 0.0;
 }
 
 }  // namespace topolow

@@ -268,34 +268,45 @@ struct topolow_session {
   DevBuf<double*> rsum_tab;            // every block's rank_sum / rank_cnt (self included)
   DevBuf<unsigned long long*> rcnt_tab;
   int n_ranks = 0, rank = 0;
-  // Symmetric sweep (relax_symm.h): one-stage iterations of a whole-matrix fp32 session.
+  // Symmetric sweep (relax_symm.h, relax_symm64.h): one-stage iterations of a whole-matrix session.
   struct SymState {
     bool allowed = false;          // TOPOLOW_SYMMETRIC=1 (session creation)
     int min_n = 0;                 // size gate (TOPOLOW_SYMMETRIC_MIN_N at session creation; default kSymMinPoints)
     bool ready = false;            // plan + tile-major copy built for the current block
-    int npad = 0, tiles = 0, grid = 0, n_units = 0;   // npad = roundup(n, 64): whole 64-row tiles
+    int npad = 0, tiles = 0, grid = 0;   // npad = roundup(n, 64): whole 64-row tiles
     DevBuf<uint32_t> tenc;
-    DevBuf<float> rec[2];
+    // records, row and column partials in the session's precision (SymRec<DIM> floats or SymRec64<DIM> doubles)
+    DevBuf<unsigned char> rec[2], rowpart, colpart;
     int rec_cur = 0, rec_iter = -1;   // rec[rec_cur] holds the records of iteration rec_iter
-    DevBuf<float> rowpart, colpart;
-    DevBuf<double> rec64[2], rowpart64, colpart64;   // f64 sessions (relax_symm64.h)
-    DevBuf<float> tdelta;          // ... exact target - decoded word per cell of tenc: the fused check's MAE is exact
+    DevBuf<float> tdelta;          // f64: exact target - decoded word per cell of tenc: the fused check's MAE is exact
     bool delta_ready = false;
-    // multi-stage iterations (2, 4, 8 stages) as symmetric sweeps over the tiles of one stage each (relax_symm.h:
-    // sym_rr_*; sym_rr_stage below): rr[log2 S] holds the S plans, built when an iteration first needs them
-    struct StagePlan {
+    // A sweep plan on the device (relax_symm.h: SymPlan): units, every wave's run of them, per tile-row its units.
+    struct Plan {
       DevBuf<SymUnit> units;
       DevBuf<SymRun> runs;
       DevBuf<int2> row_units;
       int n_units = 0;
+      void load(const SymPlan& hp) {
+        const std::vector<SymRun> hr = hp.runs();
+        n_units = (int)hp.units.size();
+        units.alloc(std::max<size_t>(hp.units.size(), 1));
+        runs.alloc(hr.size());
+        row_units.alloc(std::max<size_t>(hp.row_units.size(), 1));
+        if (!hp.units.empty())
+          HIP_TRY(hipMemcpy(units.p, hp.units.data(), hp.units.size() * sizeof(SymUnit), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(runs.p, hr.data(), hr.size() * sizeof(SymRun), hipMemcpyHostToDevice));
+        if (!hp.row_units.empty())
+          HIP_TRY(hipMemcpy(row_units.p, hp.row_units.data(), hp.row_units.size() * sizeof(int2), hipMemcpyHostToDevice));
+      }
+      void release() { units.release(); runs.release(); row_units.release(); n_units = 0; }
     };
-    std::vector<StagePlan> rr[4];
+    Plan plan;                     // the whole triangle, or this session's segment
+    // multi-stage iterations (2, 4, 8 stages) as symmetric sweeps over the tiles of one stage each (relax_symm.h:
+    // sym_rr_*): rr[log2 S] holds the S plans, built when an iteration first needs them
+    std::vector<Plan> rr[4];
     bool whole = false;            // the buffers describe the whole triangle (not a segment): stage plans may be cut from it
     bool two_stage = true;         // TOPOLOW_SYMMETRIC_TWO_STAGE=0: multi-stage iterations stay on the row-owner kernel
     int rr_min_tiles = 5;          // tiles per resident wave a stage must have (TOPOLOW_SYMMETRIC_STAGE_MIN_TILES; tests: 0)
-    DevBuf<SymUnit> units;
-    DevBuf<SymRun> wave_first;     // per wave of the grid: its run of units (relax_symm.h: SymPlan::runs)
-    DevBuf<int2> row_units;
     DevBuf<const uint32_t*> src_tab;   // the row blocks the tile-major copy is gathered from (one: the session's own)
     DevBuf<int> src_row0;
     // the sweep sharded over the row-block sessions of a run (relax_sharded_engine.h): this session's segment
@@ -310,6 +321,16 @@ struct topolow_session {
     DevBuf<float*> inbox_tab;      // every session's inbox (self included)
     DevBuf<int> own0;              // first row of every session, then n
     std::vector<const void*> seg_peers;   // the sessions the segment was built with (their encoded blocks)
+
+    // Frees every sweep buffer (a build that failed: the session keeps the row-owner sweep).  The callers set the flags.
+    void release() {
+      tenc.release(); rec[0].release(); rec[1].release(); rowpart.release(); colpart.release();
+      tdelta.release(); delta_ready = false;
+      plan.release();
+      for (auto& v : rr) v.clear();
+      src_tab.release(); src_row0.release();
+      inbox.release(); inbox_tab.release(); own0.release();
+    }
   } sym;
   int fused_parts = 0;             // partial sums the last ERR launch wrote (stage kernel: workgroups; sweep: units)
   // profiling (roofline accounting)
@@ -728,19 +749,54 @@ void launch_tilegs_finite(topolow_session* s, const void* pos, int iter1) {
   HIP_TRY(hipGetLastError());
 }
 
-// ---- symmetric sweep (relax_symm.h) ----------------------------------------------------------
-// Which sessions take it: the whole matrix on one GPU (no row block, nothing to push), fp32 slab schedule, ndim
+// ---- symmetric sweep (relax_symm.h, relax_symm64.h) --------------------------------------------------------
+// Which sessions take it: the whole matrix on one GPU (no row block, nothing to push), fp32 or f64 slab schedule, ndim
 // 2..6 (the register-tiled kernel keeps eight rows' coordinates, constants and sums in VGPRs: 20 x ndim + 16 of
 // them), at least kSymMinPoints points.  Row-sharded runs shard it over their sessions (sym_sharded_*, below).
-// Everything else -- and every multi-stage iteration -- stays on the row-owner stage kernel.
-template <int DIM> constexpr bool kSymDim = DIM >= 2 && DIM <= 6;
+// Everything else stays on the row-owner stage kernel.
 constexpr int kSymMinPoints = 7168;   // below ~7000 points a resident wave gets fewer than 8 tiles and the row-owner sweep is faster (tests/study/symm_crossover.py)
 
+// The sweep's host functions exist for ndim 2..6 only, the dims its kernels are instantiated for.
+#define TL_DISPATCH_SYM(dim, FN, ...)                                                 \
+  switch (dim) {                                                                      \
+    case 2: FN<2>(__VA_ARGS__); break;                                                \
+    case 3: FN<3>(__VA_ARGS__); break;                                                \
+    case 4: FN<4>(__VA_ARGS__); break;                                                \
+    case 5: FN<5>(__VA_ARGS__); break;                                                \
+    case 6: FN<6>(__VA_ARGS__); break;                                                \
+    default: throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim"};        \
+  }
+
+using SymPlanDev = topolow_session::SymState::Plan;
+
+// The shape every form of the sweep needs; the eligibility of each form adds its own terms.
+bool sym_shape_ok(const topolow_session* s) {
+  return s->sym.allowed && s->schedule == TOPOLOW_SCHEDULE_SLAB && s->dim >= 2 && s->dim <= 6 && s->dim == s->udim &&
+         s->n >= s->sym.min_n;
+}
+
 bool sym_eligible(const topolow_session* s) {
-  return s->sym.allowed && s->schedule == TOPOLOW_SCHEDULE_SLAB &&
-         (s->precision == TOPOLOW_PRECISION_F32 || s->precision == TOPOLOW_PRECISION_F64) &&
-         s->row_begin == 0 && s->row_end == s->n && s->n_push == 0 && s->dim >= 2 && s->dim <= 6 && s->n >= s->sym.min_n &&
-         s->dim == s->udim;
+  return sym_shape_ok(s) && (s->precision == TOPOLOW_PRECISION_F32 || s->precision == TOPOLOW_PRECISION_F64) &&
+         s->row_begin == 0 && s->row_end == s->n && s->n_push == 0;
+}
+
+// f(real{}) in the session's precision.
+template <typename F>
+void sym_real(const topolow_session* s, F&& f) {
+  if (s->precision == TOPOLOW_PRECISION_F64) f(double{}); else f(float{});
+}
+
+// f(kernel) with the sweep instance for (real, thresholds, err): the one list of instances, for the launches and the
+// occupancy probe alike.
+template <int DIM, typename real, typename F>
+void sym_sweep_instance(bool thr, bool err, F&& f) {
+  if constexpr (std::is_same<real, double>::value) {
+    if (thr) { if (err) f(&symm64_sweep_kernel<DIM, true, true>); else f(&symm64_sweep_kernel<DIM, true, false>); }
+    else { if (err) f(&symm64_sweep_kernel<DIM, false, true>); else f(&symm64_sweep_kernel<DIM, false, false>); }
+  } else {
+    if (thr) { if (err) f(&symm_sweep_kernel<DIM, true, true>); else f(&symm_sweep_kernel<DIM, true, false>); }
+    else { if (err) f(&symm_sweep_kernel<DIM, false, true>); else f(&symm_sweep_kernel<DIM, false, false>); }
+  }
 }
 
 // Builds the plan, the tile-major copy and the partial buffers of tiles [t0, t1) of the upper triangle (t1 < 0: all of
@@ -748,90 +804,65 @@ bool sym_eligible(const topolow_session* s) {
 template <int DIM>
 void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, const std::vector<int>& row0, bool any_thr,
                long long t0, long long t1) {
-  if constexpr (!kSymDim<DIM>) {
-    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim"};
-  } else {
-    auto& y = s->sym;
-    y.npad = (s->n + kSymRows - 1) & ~(kSymRows - 1);
-    const int TR = y.npad / kSymRows, TC = y.npad / kSymCols;
-    if (t1 < 0) t1 = (long long)TR * (TR + 1);
-    y.tiles = (int)(t1 - t0);
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-    int occ = 1 << 30;   // the session's two instances (plain, ERR) share one plan: the smaller occupancy decides the grid
-    auto probe = [&](auto kern) {
-      int per_cu = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * kSymWaves, 0));
-      occ = std::min(occ, std::max(1, per_cu));
-    };
-    const bool f64 = s->precision == TOPOLOW_PRECISION_F64;
-    if (f64) {
-      if (any_thr) { probe(&symm64_sweep_kernel<DIM, true, false>); probe(&symm64_sweep_kernel<DIM, true, true>); }
-      else { probe(&symm64_sweep_kernel<DIM, false, false>); probe(&symm64_sweep_kernel<DIM, false, true>); }
-    } else if (any_thr) {
-      probe(&symm_sweep_kernel<DIM, true, false>);
-      probe(&symm_sweep_kernel<DIM, true, true>);
-    } else {
-      probe(&symm_sweep_kernel<DIM, false, false>);
-      probe(&symm_sweep_kernel<DIM, false, true>);
+  auto& y = s->sym;
+  y.npad = (s->n + kSymRows - 1) & ~(kSymRows - 1);
+  const int TR = y.npad / kSymRows, TC = y.npad / kSymCols;
+  if (t1 < 0) t1 = (long long)TR * (TR + 1);
+  y.tiles = (int)(t1 - t0);
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, s->device));
+  int occ = 1 << 30;   // the session's two instances (plain, ERR) share one plan: the smaller occupancy decides the grid
+  auto probe = [&](auto kern) {
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * kSymWaves, 0));
+    occ = std::min(occ, std::max(1, per_cu));
+  };
+  const bool f64 = s->precision == TOPOLOW_PRECISION_F64;
+  sym_real(s, [&](auto r) {
+    sym_sweep_instance<DIM, decltype(r)>(any_thr, false, probe);
+    sym_sweep_instance<DIM, decltype(r)>(any_thr, true, probe);
+  });
+  y.grid = occ * prop.multiProcessorCount;
+  y.plan.load(relax_symm_plan(y.npad, y.grid * kSymWaves, t0, t1, &y.seg_first, &y.seg_last));
+  y.whole = t0 == 0 && (long long)y.tiles == (long long)TR * (TR + 1);
+  for (auto& v : y.rr) v.clear();
+  // a stage plan has at most one unit per wave and one more per tile-row and interval end
+  const int max_units = std::max(y.plan.n_units, y.grid * kSymWaves + 2 * TR + 8);
+  y.src_tab.alloc(src.size());
+  y.src_row0.alloc(row0.size());
+  HIP_TRY(hipMemcpy(y.src_tab.p, src.data(), src.size() * sizeof(const uint32_t*), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(y.src_row0.p, row0.data(), row0.size() * sizeof(int), hipMemcpyHostToDevice));
+  y.tenc.alloc((size_t)std::max(y.tiles, 1) * kSymTileWords);
+  if (y.tiles > 0)
+    hipLaunchKernelGGL(symm_tiles_kernel, dim3(y.tiles), dim3(256), 0, s->stream, y.src_tab.p, y.src_row0.p, (int)src.size(),
+                       s->ld, y.tenc.p, TC, t0);
+  HIP_TRY(hipGetLastError());
+  const int seg_rows = y.seg_last >= y.seg_first ? y.seg_last - y.seg_first + 1 : 1;
+  const size_t rs = s->real_size();
+  for (auto& r : y.rec) r.alloc((size_t)y.npad * (f64 ? SymRec64<DIM>::W : SymRec<DIM>::W) * rs);
+  y.rowpart.alloc((size_t)std::max(max_units, 1) * kSymRows * DIM * rs);
+  y.colpart.alloc((size_t)seg_rows * y.npad * DIM * rs);
+  // (a segment's first and last tile-row are partial: the columns its tiles never reach must read as zero)
+  HIP_TRY(hipMemsetAsync(y.colpart.p, 0, (size_t)seg_rows * y.npad * DIM * rs, s->stream));
+  if (f64) {
+    // the fused check needs the edge list to BE the block's measured cells and to be on the device in f64
+    y.delta_ready = false;
+    if (s->list_is_block && !s->dense_mae && s->n_edges > 0 && y.whole) {
+      y.tdelta.alloc((size_t)y.tiles * kSymTileWords);
+      HIP_TRY(hipMemsetAsync(y.tdelta.p, 0, (size_t)y.tiles * kSymTileWords * sizeof(float), s->stream));
+      hipLaunchKernelGGL(symm64_delta_kernel, dim3(2048), dim3(256), 0, s->stream, s->ei.p, s->ej.p, (const double*)s->et.p,
+                         s->ec.p, (long long)s->n_edges, y.tdelta.p, TC, s->n);
+      HIP_TRY(hipGetLastError());
+      y.delta_ready = true;
     }
-    y.grid = occ * prop.multiProcessorCount;
-    const SymPlan plan = relax_symm_plan(y.npad, y.grid * kSymWaves, t0, t1, &y.seg_first, &y.seg_last);
-    y.n_units = (int)plan.units.size();
-    y.units.alloc(std::max<size_t>(plan.units.size(), 1));
-    const std::vector<SymRun> runs = plan.runs();
-    y.wave_first.alloc(runs.size());
-    y.row_units.alloc(std::max<size_t>(plan.row_units.size(), 1));
-    if (!plan.units.empty())
-      HIP_TRY(hipMemcpy(y.units.p, plan.units.data(), plan.units.size() * sizeof(SymUnit), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(y.wave_first.p, runs.data(), runs.size() * sizeof(SymRun), hipMemcpyHostToDevice));
-    if (!plan.row_units.empty())
-      HIP_TRY(hipMemcpy(y.row_units.p, plan.row_units.data(), plan.row_units.size() * sizeof(int2), hipMemcpyHostToDevice));
-    y.whole = t0 == 0 && (long long)y.tiles == (long long)TR * (TR + 1);
-    for (auto& v : y.rr) v.clear();
-    // a stage plan has at most one unit per wave and one more per tile-row and interval end
-    const int max_units = std::max(y.n_units, y.grid * kSymWaves + 2 * TR + 8);
-    y.src_tab.alloc(src.size());
-    y.src_row0.alloc(row0.size());
-    HIP_TRY(hipMemcpy(y.src_tab.p, src.data(), src.size() * sizeof(const uint32_t*), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(y.src_row0.p, row0.data(), row0.size() * sizeof(int), hipMemcpyHostToDevice));
-    y.tenc.alloc((size_t)std::max(y.tiles, 1) * kSymTileWords);
-    if (y.tiles > 0)
-      hipLaunchKernelGGL(symm_tiles_kernel, dim3(y.tiles), dim3(256), 0, s->stream, y.src_tab.p, y.src_row0.p, (int)src.size(),
-                         s->ld, y.tenc.p, TC, t0);
-    HIP_TRY(hipGetLastError());
-    const int seg_rows = y.seg_last >= y.seg_first ? y.seg_last - y.seg_first + 1 : 1;
-    if (f64) {
-      for (auto& r : y.rec64) r.alloc((size_t)y.npad * SymRec64<DIM>::W);
-      y.rowpart64.alloc((size_t)std::max(max_units, 1) * kSymRows * DIM);
-      y.colpart64.alloc((size_t)seg_rows * y.npad * DIM);
-      HIP_TRY(hipMemsetAsync(y.colpart64.p, 0, (size_t)seg_rows * y.npad * DIM * sizeof(double), s->stream));
-      // the fused check needs the edge list to BE the block's measured cells and to be on the device in f64
-      y.delta_ready = false;
-      if (s->list_is_block && !s->dense_mae && s->n_edges > 0 && t0 == 0 && (long long)y.tiles == (long long)TR * (TR + 1)) {
-        y.tdelta.alloc((size_t)y.tiles * kSymTileWords);
-        HIP_TRY(hipMemsetAsync(y.tdelta.p, 0, (size_t)y.tiles * kSymTileWords * sizeof(float), s->stream));
-        hipLaunchKernelGGL(symm64_delta_kernel, dim3(2048), dim3(256), 0, s->stream, s->ei.p, s->ej.p, (const double*)s->et.p,
-                           s->ec.p, (long long)s->n_edges, y.tdelta.p, TC, s->n);
-        HIP_TRY(hipGetLastError());
-        y.delta_ready = true;
-      }
-    } else {
-      constexpr int W = SymRec<DIM>::W;
-      for (auto& r : y.rec) r.alloc((size_t)y.npad * W);
-      y.rowpart.alloc((size_t)std::max(max_units, 1) * kSymRows * DIM);
-      y.colpart.alloc((size_t)seg_rows * y.npad * DIM);
-      // (a segment's first and last tile-row are partial: the columns its tiles never reach must read as zero)
-      HIP_TRY(hipMemsetAsync(y.colpart.p, 0, (size_t)seg_rows * y.npad * DIM * sizeof(float), s->stream));
-    }
-    if ((size_t)y.n_units > s->part_sum.n) {   // error partials: one per unit
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      HIP_TRY(hipStreamSynchronize(s->check_stream));
-      s->part_sum.alloc(y.n_units);
-      s->part_cnt.alloc(y.n_units);
-    }
-    y.rec_iter = -1;
   }
+  if ((size_t)y.plan.n_units > s->part_sum.n) {   // error partials: one per unit
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipStreamSynchronize(s->check_stream));
+    s->part_sum.alloc(y.plan.n_units);
+    s->part_cnt.alloc(y.plan.n_units);
+  }
+  y.rec_iter = -1;
 }
 
 template <int DIM>
@@ -846,89 +877,62 @@ void sym_prepare(topolow_session* s) {
 bool sym_available(topolow_session* s) {
   if (s->sym.ready) return true;
   try {
-    TL_DISPATCH_DIM(s->dim, sym_prepare, s);
+    TL_DISPATCH_SYM(s->dim, sym_prepare, s);
   } catch (const HipError&) {
     (void)hipGetLastError();
-    auto& y = s->sym;
-    y.tenc.release(); y.rec[0].release(); y.rec[1].release(); y.rowpart.release(); y.colpart.release();
-    y.rec64[0].release(); y.rec64[1].release(); y.rowpart64.release(); y.colpart64.release(); y.tdelta.release();
-    y.delta_ready = false;
-    y.units.release(); y.wave_first.release(); y.row_units.release();
-    y.ready = false;
-    y.allowed = false;
+    s->sym.release();
+    s->sym.ready = false;
+    s->sym.allowed = false;
   }
   return s->sym.ready;
 }
 
-// One one-stage iteration: records of this iteration (built from `pin` unless the previous iteration's apply left
-// them), sweep, apply into `pout` (and the next iteration's records).  err: the sweep also reduces the pending
-// check's MAE (positions read = that check's positions).
+// ---- launches: records, sweep, apply ----
+// The records of iteration `k` from plain positions (all npad of them: the phantom ones too).
 template <int DIM>
-void sym_iteration(topolow_session* s, const void* pin, void* pout, int iter, double k, bool err) {
-  if constexpr (!kSymDim<DIM>) {
-    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim"};
-  } else {
-    auto& y = s->sym;
-    ProfScope prof(s, err ? &s->prof_sym_err : &s->prof_sym);
-    const int TC = y.npad / kSymCols;
-    if (s->precision == TOPOLOW_PRECISION_F64) {   // relax_symm64.h: same plan, tiles and partial layout, everything else in f64
-      if (err && !y.delta_ready) throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep (f64): no delta tiles for a fused check"};
-      if (y.rec_iter != iter) {
-        for (int b = 0; b < 2; ++b)
-          hipLaunchKernelGGL(symm64_records_kernel<DIM>, dim3((y.npad + 255) / 256), dim3(256), 0, s->stream, (const double*)pin,
-                             s->gplus.p, y.rec64[b].p, s->n, y.npad, k, s->c_rep);
-        y.rec_cur = 0;
-      }
-      const double* rec = y.rec64[y.rec_cur].p;
-      double* rec_next = y.rec64[y.rec_cur ^ 1].p;
-      auto sweep64 = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, rec, y.units.p, y.wave_first.p,
-                           y.rowpart64.p, y.colpart64.p, y.npad, s->state.p, 0, y.tdelta.p, s->part_sum.p, s->part_cnt.p,
-                           s->block_cells);
-      };
-      if (s->any_threshold) {
-        if (err) sweep64(&symm64_sweep_kernel<DIM, true, true>); else sweep64(&symm64_sweep_kernel<DIM, true, false>);
-      } else {
-        if (err) sweep64(&symm64_sweep_kernel<DIM, false, true>); else sweep64(&symm64_sweep_kernel<DIM, false, false>);
-      }
-      hipLaunchKernelGGL(symm64_apply_kernel<DIM>, dim3(TC), dim3(32 * kSymApplyParts), 0, s->stream, rec, rec_next, (double*)pout,
-                         s->gplus.p, y.rowpart64.p, y.colpart64.p, y.row_units.p, s->n, y.npad, k * (1.0 - s->cooling), s->c_rep,
-                         iter + 1, s->state.p);
-      HIP_TRY(hipGetLastError());
-      y.rec_cur ^= 1;
-      y.rec_iter = iter + 1;
-      if (err) s->fused_parts = y.n_units;
-      s->stage_launches += 1;
-      return;
-    }
-    if (y.rec_iter != iter) {
-      for (int b = 0; b < 2; ++b)   // both buffers need the phantom records; the second one's points are overwritten by the apply
-        hipLaunchKernelGGL(symm_records_kernel<DIM>, dim3((y.npad + 255) / 256), dim3(256), 0, s->stream, (const float*)pin,
-                           s->gplus.p, y.rec[b].p, s->n, y.npad, k, s->c_rep);
-      y.rec_cur = 0;
-    }
-    const float* rec = y.rec[y.rec_cur].p;
-    float* rec_next = y.rec[y.rec_cur ^ 1].p;
-    auto sweep = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, rec, y.units.p, y.wave_first.p,
-                         y.rowpart.p, y.colpart.p, y.npad, s->state.p, s->part_sum.p, s->part_cnt.p,
-                         s->block_cells, 0);
-    };
-    if (s->any_threshold) {
-      if (err) sweep(&symm_sweep_kernel<DIM, true, true>); else sweep(&symm_sweep_kernel<DIM, true, false>);
-    } else {
-      if (err) sweep(&symm_sweep_kernel<DIM, false, true>); else sweep(&symm_sweep_kernel<DIM, false, false>);
-    }
-    const double k_next = k * (1.0 - s->cooling);
-    hipLaunchKernelGGL(symm_apply_kernel<DIM>, dim3(TC), dim3(32 * kSymApplyParts), 0, s->stream, rec, rec_next, (float*)pout,
-                       s->gplus.p, y.rowpart.p, y.colpart.p, y.row_units.p, s->n, y.npad, k_next, s->c_rep, iter + 1,
-                       s->state.p);
-    HIP_TRY(hipGetLastError());
-    y.rec_cur ^= 1;
-    y.rec_iter = iter + 1;
-    if (err) s->fused_parts = y.n_units;
-    s->stage_launches += 1;
-  }
+void sym_records(topolow_session* s, const void* pin, void* rec, double k) {
+  sym_real(s, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((symm_records_kernel<DIM, real>), dim3((s->sym.npad + 255) / 256), dim3(256), 0, s->stream,
+                       (const real*)pin, s->gplus.p, (real*)rec, s->n, s->sym.npad, k, s->c_rep);
+  });
+}
+
+// The sweep of `plan` over the records `rec` into the partials.  err: it also reduces the pending check's MAE into
+// part_sum / part_cnt (one partial per unit); block_cells: the count of a threshold-free block (0: none reduced);
+// col_row0: the first tile-row of the column partials (a segment's; 0 for the whole triangle).
+template <int DIM>
+void sym_sweep(topolow_session* s, const SymPlanDev& plan, const void* rec, bool thr, bool err,
+               unsigned long long block_cells, int col_row0) {
+  auto& y = s->sym;
+  sym_real(s, [&](auto r) {
+    using real = decltype(r);
+    sym_sweep_instance<DIM, real>(thr, err, [&](auto kern) {
+      if constexpr (std::is_same<real, double>::value)
+        hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, (const double*)rec,
+                           plan.units.p, plan.runs.p, (double*)y.rowpart.p, (double*)y.colpart.p, y.npad, s->state.p,
+                           col_row0, y.tdelta.p, s->part_sum.p, s->part_cnt.p, block_cells);
+      else
+        hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, (const float*)rec,
+                           plan.units.p, plan.runs.p, (float*)y.rowpart.p, (float*)y.colpart.p, y.npad, s->state.p,
+                           s->part_sum.p, s->part_cnt.p, block_cells, col_row0);
+    });
+  });
+}
+
+// The apply of the whole triangle (rr_stages = 0) or of stage rr_stage of an rr_stages-stage iteration: positions into
+// `pout`, the records of k_next into `rec_next`.
+template <int DIM>
+void sym_apply(topolow_session* s, const SymPlanDev& plan, const void* rec, void* rec_next, void* pout, double k_next,
+               int iter, int rr_stages, int rr_stage) {
+  auto& y = s->sym;
+  sym_real(s, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((symm_apply_kernel<DIM, real>), dim3(y.npad / kSymCols), dim3(32 * kSymApplyParts), 0, s->stream,
+                       (const real*)rec, (real*)rec_next, (real*)pout, s->gplus.p, (const real*)y.rowpart.p,
+                       (const real*)y.colpart.p, plan.row_units.p, s->n, y.npad, k_next, s->c_rep, iter + 1, s->state.p,
+                       rr_stages, rr_stage);
+  });
 }
 
 // Multi-stage iterations on the symmetric sweep (relax_symm.h: sym_rr_*).  The row-owner form of an S-stage iteration gives
@@ -938,6 +942,7 @@ void sym_iteration(topolow_session* s, const void* pin, void* pout, int iter, do
 // the reference (src/optimization.cpp:245-281), and every pair is evaluated once per iteration instead of twice.  The
 // order of the stages is drawn per iteration.  S = 2, 4, 8; sixteen stages (the unfolding phase, k > 24) stay row-owner.
 bool sym_rr_stages_ok(int S) { return S == 2 || S == 4 || S == 8; }
+int sym_rr_log2(int S) { return S == 2 ? 1 : (S == 4 ? 2 : 3); }
 
 bool sym_rr_available(topolow_session* s, int S) {
   auto& y = s->sym;
@@ -949,81 +954,82 @@ bool sym_rr_available(topolow_session* s, int S) {
   // a run with k0 = 6 26.1 against 27.6 ms on the row-owner stages; four stages, 3 tiles: +25 us per iteration; eight
   // stages, 1.5 tiles: 16.0 against 13.0 ms per run with k0 = 20)
   if ((long long)TR * (TR + 1) / S < (long long)y.rr_min_tiles * y.grid * kSymWaves) return false;
-  int lg = S == 2 ? 1 : (S == 4 ? 2 : 3);
+  const int lg = sym_rr_log2(S);
   if (!y.rr[lg].empty()) return true;
-  std::vector<topolow_session::SymState::StagePlan> plans(S);
+  std::vector<SymPlanDev> plans(S);
   for (int st = 0; st < S; ++st) {
     const SymPlan hp = relax_symm_plan_rows(y.npad, y.grid * kSymWaves, [&](int R, int& j0, int& j1) { sym_rr_row(TR, S, st, R, j0, j1); });
-    auto& h = plans[st];
-    h.n_units = (int)hp.units.size();
-    if ((size_t)h.n_units * kSymRows * s->dim > std::max(y.rowpart.n, y.rowpart64.n)) return false;   // (never: sym_build sizes for it)
-    const std::vector<SymRun> hr = hp.runs();
-    h.units.alloc(std::max<size_t>(hp.units.size(), 1));
-    h.runs.alloc(hr.size());
-    h.row_units.alloc(hp.row_units.size());
-    if (!hp.units.empty())
-      HIP_TRY(hipMemcpy(h.units.p, hp.units.data(), hp.units.size() * sizeof(SymUnit), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h.runs.p, hr.data(), hr.size() * sizeof(SymRun), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h.row_units.p, hp.row_units.data(), hp.row_units.size() * sizeof(int2), hipMemcpyHostToDevice));
+    if (hp.units.size() * kSymRows * s->dim * s->real_size() > y.rowpart.n) return false;   // (never: sym_build sizes for it)
+    plans[st].load(hp);
   }
   y.rr[lg] = std::move(plans);
   return true;
 }
 
-// Stage st of S of iteration iter.  k_records: the spring constant of the records the apply kernel leaves (this
-// iteration's until its last stage, then the next one's).
+// One symmetric sweep + apply from `pin` into `pout`: a whole one-stage iteration (S = 0), or stage st of an S-stage
+// iteration (the tiles of rr[log2 S][st]).  The records of this iteration are built from `pin` unless the previous apply
+// left them; the apply leaves the next sweep's: this iteration's, or after the iteration's last sweep (`last`) the next
+// one's.  err: the sweep also reduces the pending check's MAE (positions read = that check's positions).
 template <int DIM>
-void sym_rr_stage(topolow_session* s, const void* pin, void* pout, int iter, double k, double k_records, int S, int st,
-                  int rec_iter_after) {
-  if constexpr (!kSymDim<DIM>) {
-    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim"};
-  } else {
-    auto& y = s->sym;
-    auto& h = y.rr[S == 2 ? 1 : (S == 4 ? 2 : 3)][st];
-    ProfScope prof(s, &s->prof_stage);
-    const int TC = y.npad / kSymCols;
-    const bool f64 = s->precision == TOPOLOW_PRECISION_F64;
-    if (y.rec_iter != iter) {
-      for (int b = 0; b < 2; ++b) {
-        if (f64)
-          hipLaunchKernelGGL(symm64_records_kernel<DIM>, dim3((y.npad + 255) / 256), dim3(256), 0, s->stream, (const double*)pin,
-                             s->gplus.p, y.rec64[b].p, s->n, y.npad, k, s->c_rep);
-        else
-          hipLaunchKernelGGL(symm_records_kernel<DIM>, dim3((y.npad + 255) / 256), dim3(256), 0, s->stream, (const float*)pin,
-                             s->gplus.p, y.rec[b].p, s->n, y.npad, k, s->c_rep);
-      }
-      y.rec_cur = 0;
-    }
-    if (f64) {
-      const double* rec = y.rec64[y.rec_cur].p;
-      auto sweep = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, rec, h.units.p, h.runs.p,
-                           y.rowpart64.p, y.colpart64.p, y.npad, s->state.p, 0, (const float*)nullptr, s->part_sum.p,
-                           s->part_cnt.p, 0ull);
-      };
-      if (s->any_threshold) sweep(&symm64_sweep_kernel<DIM, true, false>); else sweep(&symm64_sweep_kernel<DIM, false, false>);
-      hipLaunchKernelGGL(symm64_apply_kernel<DIM>, dim3(TC), dim3(32 * kSymApplyParts), 0, s->stream, rec, y.rec64[y.rec_cur ^ 1].p,
-                         (double*)pout, s->gplus.p, y.rowpart64.p, y.colpart64.p, h.row_units.p, s->n, y.npad, k_records, s->c_rep,
-                         iter + 1, s->state.p, S, st);
-    } else {
-      const float* rec = y.rec[y.rec_cur].p;
-      auto sweep = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, rec, h.units.p, h.runs.p,
-                           y.rowpart.p, y.colpart.p, y.npad, s->state.p, s->part_sum.p, s->part_cnt.p, 0ull, 0);
-      };
-      if (s->any_threshold) sweep(&symm_sweep_kernel<DIM, true, false>); else sweep(&symm_sweep_kernel<DIM, false, false>);
-      hipLaunchKernelGGL(symm_apply_kernel<DIM>, dim3(TC), dim3(32 * kSymApplyParts), 0, s->stream, rec, y.rec[y.rec_cur ^ 1].p,
-                         (float*)pout, s->gplus.p, y.rowpart.p, y.colpart.p, h.row_units.p, s->n, y.npad, k_records, s->c_rep,
-                         iter + 1, s->state.p, S, st);
-    }
-    HIP_TRY(hipGetLastError());
-    y.rec_cur ^= 1;
-    y.rec_iter = rec_iter_after;
-    s->stage_launches += 1;
+void sym_iteration(topolow_session* s, const void* pin, void* pout, int iter, double k, bool err, int S = 0, int st = 0,
+                   bool last = true) {
+  auto& y = s->sym;
+  const SymPlanDev& plan = S == 0 ? y.plan : y.rr[sym_rr_log2(S)][st];
+  ProfScope prof(s, S > 0 ? &s->prof_stage : err ? &s->prof_sym_err : &s->prof_sym);
+  if (err && s->precision == TOPOLOW_PRECISION_F64 && !y.delta_ready)
+    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep (f64): no delta tiles for a fused check"};
+  if (y.rec_iter != iter) {
+    for (int b = 0; b < 2; ++b)   // both buffers need the phantom records; the second one's points are overwritten by the apply
+      sym_records<DIM>(s, pin, y.rec[b].p, k);
+    y.rec_cur = 0;
   }
+  sym_sweep<DIM>(s, plan, y.rec[y.rec_cur].p, s->any_threshold, err, S == 0 ? s->block_cells : 0ull, 0);
+  sym_apply<DIM>(s, plan, y.rec[y.rec_cur].p, y.rec[y.rec_cur ^ 1].p, pout, last ? k * (1.0 - s->cooling) : k, iter, S, st);
+  HIP_TRY(hipGetLastError());
+  y.rec_cur ^= 1;
+  y.rec_iter = last ? iter + 1 : iter;
+  if (err) s->fused_parts = plan.n_units;
+  s->stage_launches += 1;
+}
+
+// How an iteration of n_stages stages runs on a whole-matrix session: one symmetric sweep (one stage), S sweeps over the
+// tiles of one stage each (S = 2, 4, 8), or the row-owner stage kernel.  Builds the sweep on first use.
+enum class SymForm { kRowOwner, kSweep, kStages };
+SymForm sym_form(topolow_session* s, int n_stages) {
+  if (n_stages == 1) return sym_eligible(s) && sym_available(s) ? SymForm::kSweep : SymForm::kRowOwner;
+  return s->sym.two_stage && sym_rr_stages_ok(n_stages) && sym_eligible(s) && sym_available(s) &&
+                 sym_rr_available(s, n_stages)
+             ? SymForm::kStages
+             : SymForm::kRowOwner;
+}
+
+// Whether a check may be fused into an iteration of n_stages stages: the iteration's one sweep reduces the MAE of the
+// positions it reads.  The row-owner ERR instance pairs rows two by two (an odd block keeps the separate pass), the
+// symmetric sweep's has no such rule; f64 fuses into the symmetric sweep only, exact through its delta tiles (asked
+// first: an f64 session builds its sweep at its first check).
+bool check_fusable(topolow_session* s, int n_stages) {
+  if (s->precision == TOPOLOW_PRECISION_F64)
+    return sym_form(s, 1) == SymForm::kSweep && s->sym.delta_ready && n_stages == 1;
+  return n_stages == 1 && (s->rows() % 2 == 0 || sym_form(s, 1) == SymForm::kSweep);
 }
 
 // ---- the symmetric sweep sharded over the row-block sessions of one run (relax_symm.h, relax_sharded_engine.h) ----
+// Segment b of P of the sweep over n points: tiles [t0, t1), equal runs of the tile-row-major list of the upper
+// triangle (`total` tiles); tile-rows [r_first, r_last] hold its tiles (-1: none).
+struct SymSegment {
+  long long total, t0, t1;
+  int r_first = -1, r_last = -1;
+};
+SymSegment sym_segment(int n, int b, int P) {
+  SymSegment g;
+  const int npad = (n + kSymRows - 1) & ~(kSymRows - 1), TR = npad / kSymRows;
+  g.total = (long long)TR * (TR + 1);
+  g.t0 = g.total * b / P;
+  g.t1 = g.total * (b + 1) / P;
+  (void)relax_symm_plan(npad, 1, g.t0, g.t1, &g.r_first, &g.r_last);
+  return g;
+}
+
 bool sym_sharded_eligible(const std::vector<topolow_session*>& ss) {
   const char* e = getenv("TOPOLOW_SHARD_SYMMETRIC");
   if (e != nullptr && e[0] == '0') return false;       // row-owner sweeps only
@@ -1033,10 +1039,21 @@ bool sym_sharded_eligible(const std::vector<topolow_session*>& ss) {
   const long long TR = ((a->n + kSymRows - 1) & ~(kSymRows - 1)) / kSymRows;
   if (TR * (TR + 1) < 8ll * P) return false;
   for (const topolow_session* s : ss)
-    if (!(s->sym.allowed && s->schedule == TOPOLOW_SCHEDULE_SLAB && s->precision == TOPOLOW_PRECISION_F32 && s->dim >= 2 &&
-          s->dim <= 6 && s->dim == s->udim && s->n >= s->sym.min_n && s->rows() > 0 && s->fuse_checks == a->fuse_checks))
+    if (!(sym_shape_ok(s) && s->precision == TOPOLOW_PRECISION_F32 && s->rows() > 0 && s->fuse_checks == a->fuse_checks))
       return false;
   return true;
+}
+
+// A segment's inbox: `slots` zeroed slots of npad x DIM floats for every session's folded partials of this session's
+// points, and own0: the first row of every owner, then n.  (The table of the inboxes the segment's own partials go to,
+// inbox_tab, needs every owner's inbox: the callers set it.)
+template <int DIM>
+void sym_inbox(topolow_session* s, int slots, const std::vector<int>& own0) {
+  auto& y = s->sym;
+  y.inbox.alloc((size_t)slots * y.npad * DIM);
+  HIP_TRY(hipMemsetAsync(y.inbox.p, 0, (size_t)slots * y.npad * DIM * sizeof(float), s->stream));
+  y.own0.alloc(own0.size());
+  HIP_TRY(hipMemcpy(y.own0.p, own0.data(), own0.size() * sizeof(int), hipMemcpyHostToDevice));
 }
 
 // Session b's segment: tiles [total b / P, total (b + 1) / P) of the tile-row-major list, gathered from every session's
@@ -1059,19 +1076,15 @@ void sym_sharded_build(std::vector<topolow_session*>& ss, int b) {
   auto& y = s->sym;
   if (y.seg_ready && !y.seg_caller && y.seg_peers == peers && y.seg_thr == any_thr) { y.seg_slot = s->rank; return; }
   HIP_TRY(hipSetDevice(s->device));
-  const long long npad = (s->n + kSymRows - 1) & ~(kSymRows - 1);
-  const long long TR = npad / kSymRows, total = TR * (TR + 1);
-  sym_build<DIM>(s, src, row0, any_thr, total * b / P, total * (b + 1) / P);
+  const SymSegment g = sym_segment(s->n, b, P);
+  sym_build<DIM>(s, src, row0, any_thr, g.t0, g.t1);
   if (y.seg_first < 0) { y.seg_first = 0; y.seg_last = -1; }
   y.ready = false;            // the buffers now describe a segment, not the session's own whole-matrix plan
   y.seg_thr = any_thr;
   y.seg_slots = P;
   y.seg_slot = s->rank;
   y.seg_caller = false;
-  y.inbox.alloc((size_t)P * y.npad * DIM);
-  HIP_TRY(hipMemsetAsync(y.inbox.p, 0, (size_t)P * y.npad * DIM * sizeof(float), s->stream));
-  y.own0.alloc(row0.size());
-  HIP_TRY(hipMemcpy(y.own0.p, row0.data(), row0.size() * sizeof(int), hipMemcpyHostToDevice));
+  sym_inbox<DIM>(s, P, row0);
   HIP_TRY(hipStreamSynchronize(s->stream));
   y.seg_peers = peers;
 }
@@ -1082,7 +1095,7 @@ void sym_sharded_prepare(std::vector<topolow_session*>& ss) {
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());
   }
-  for (int b = 0; b < P; ++b) TL_DISPATCH_DIM(ss[b]->dim, sym_sharded_build, ss, b);
+  for (int b = 0; b < P; ++b) TL_DISPATCH_SYM(ss[b]->dim, sym_sharded_build, ss, b);
   for (int b = 0; b < P; ++b) {
     topolow_session* s = ss[b];
     HIP_TRY(hipSetDevice(s->device));
@@ -1105,49 +1118,29 @@ void sym_sharded_prepare(std::vector<topolow_session*>& ss) {
 // the pending check's MAE (one partial per unit: s->fused_parts).
 template <int DIM>
 void sym_sharded_sweep(topolow_session* s, const void* pin, int iter, double k, bool err) {
-  if constexpr (!kSymDim<DIM>) {
-    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim"};
-  } else {
-    auto& y = s->sym;
-    ProfScope prof(s, err ? &s->prof_sym_err : &s->prof_sym);
-    const int TC = y.npad / kSymCols;
-    hipLaunchKernelGGL(symm_records_kernel<DIM>, dim3((y.npad + 255) / 256), dim3(256), 0, s->stream, (const float*)pin,
-                       s->gplus.p, y.rec[0].p, s->n, y.npad, k, s->c_rep);
-    auto sweep = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, y.rec[0].p, y.units.p,
-                         y.wave_first.p, y.rowpart.p, y.colpart.p, y.npad, s->state.p, s->part_sum.p, s->part_cnt.p,
-                         s->block_cells, y.seg_first);
-    };
-    if (y.tiles > 0) {
-      if (y.seg_thr) {
-        if (err) sweep(&symm_sweep_kernel<DIM, true, true>); else sweep(&symm_sweep_kernel<DIM, true, false>);
-      } else {
-        if (err) sweep(&symm_sweep_kernel<DIM, false, true>); else sweep(&symm_sweep_kernel<DIM, false, false>);
-      }
-    }
-    hipLaunchKernelGGL(symm_partial_kernel<DIM>, dim3(TC), dim3(32 * 32), 0, s->stream, y.rowpart.p, y.colpart.p,
-                       y.row_units.p, y.seg_first, y.seg_last, s->n, y.npad, y.inbox_tab.p, y.own0.p, y.seg_slots, y.seg_slot,
-                       s->state.p);
-    HIP_TRY(hipGetLastError());
-    if (err) s->fused_parts = y.n_units;
-    (void)iter;
-    s->stage_launches += 1;
-  }
+  auto& y = s->sym;
+  ProfScope prof(s, err ? &s->prof_sym_err : &s->prof_sym);
+  sym_records<DIM>(s, pin, y.rec[0].p, k);
+  if (y.tiles > 0) sym_sweep<DIM>(s, y.plan, y.rec[0].p, y.seg_thr, err, s->block_cells, y.seg_first);
+  hipLaunchKernelGGL(symm_partial_kernel<DIM>, dim3(y.npad / kSymCols), dim3(32 * 32), 0, s->stream, (const float*)y.rowpart.p,
+                     (const float*)y.colpart.p, y.plan.row_units.p, y.seg_first, y.seg_last, s->n, y.npad, y.inbox_tab.p,
+                     y.own0.p, y.seg_slots, y.seg_slot, s->state.p);
+  HIP_TRY(hipGetLastError());
+  if (err) s->fused_parts = y.plan.n_units;
+  (void)iter;
+  s->stage_launches += 1;
 }
 
-// Second half, behind the run's barrier: the session's own points move by the sum of the inbox's slots; `push`: the
-// other sessions' copies of the output buffer.
+// Second half, behind the run's barrier (or the caller's sum over the processes): the points [row_begin, row_end) move
+// by the sum of the inbox's slots; `push`: the other sessions' copies of the output buffer (n_push of them).
 template <int DIM>
-void sym_sharded_apply(topolow_session* s, const void* pin, void* pout, const void* push, int iter) {
-  if constexpr (!kSymDim<DIM>) {
-    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim"};
-  } else {
-    auto& y = s->sym;
-    hipLaunchKernelGGL(symm_owner_apply_kernel<DIM>, dim3((s->rows() + 255) / 256), dim3(256), 0, s->stream, (const float*)pin,
-                       (float*)pout, y.inbox.p, y.seg_slots, y.npad, s->row_begin, s->row_end, (float* const*)push, s->n_push,
-                       iter + 1, s->state.p);
-    HIP_TRY(hipGetLastError());
-  }
+void sym_owner_apply(topolow_session* s, const void* pin, void* pout, int row_begin, int row_end, const void* push,
+                     int n_push, int iter) {
+  auto& y = s->sym;
+  hipLaunchKernelGGL(symm_owner_apply_kernel<DIM>, dim3((row_end - row_begin + 255) / 256), dim3(256), 0, s->stream,
+                     (const float*)pin, (float*)pout, y.inbox.p, y.seg_slots, y.npad, row_begin, row_end,
+                     (float* const*)push, n_push, iter + 1, s->state.p);
+  HIP_TRY(hipGetLastError());
 }
 
 // ---- the same sweep sharded over caller-driven sessions (one process per GPU: topolow_session_symm_segment_*) ----
@@ -1158,14 +1151,11 @@ template <int DIM>
 void sym_segment_build(topolow_session* s, int segment, int P, const uint32_t* d_rows, int row_first, int n_rows,
                        bool any_thr) {
   auto& y = s->sym;
-  const long long npad = (s->n + kSymRows - 1) & ~(kSymRows - 1);
-  const long long TR = npad / kSymRows, total = TR * (TR + 1);
-  const long long t0 = total * segment / P, t1 = total * (segment + 1) / P;
-  int rf = -1, rl = -1;
-  (void)relax_symm_plan((int)npad, 1, t0, t1, &rf, &rl);
-  if (rf >= 0 && (row_first > rf * kSymRows || row_first + n_rows < std::min<long long>(s->n, (long long)(rl + 1) * kSymRows)))
+  const SymSegment g = sym_segment(s->n, segment, P);
+  if (g.r_first >= 0 && (row_first > g.r_first * kSymRows ||
+                         row_first + n_rows < std::min<long long>(s->n, (long long)(g.r_last + 1) * kSymRows)))
     throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, "symm_segment_build: d_rows does not hold the rows of the segment's tiles"};
-  sym_build<DIM>(s, {d_rows}, {row_first, row_first + n_rows}, any_thr, t0, t1);
+  sym_build<DIM>(s, {d_rows}, {row_first, row_first + n_rows}, any_thr, g.t0, g.t1);
   if (y.seg_first < 0) { y.seg_first = 0; y.seg_last = -1; }
   y.ready = false;            // the buffers now describe a segment, not the session's own whole-matrix plan
   y.seg_thr = any_thr;
@@ -1173,28 +1163,12 @@ void sym_segment_build(topolow_session* s, int segment, int P, const uint32_t* d
   y.seg_slot = 0;
   y.seg_caller = true;
   y.seg_peers.clear();
-  y.inbox.alloc((size_t)y.npad * DIM);
-  HIP_TRY(hipMemsetAsync(y.inbox.p, 0, (size_t)y.npad * DIM * sizeof(float), s->stream));
-  const int own[2] = {0, s->n};
-  y.own0.alloc(2);
-  HIP_TRY(hipMemcpy(y.own0.p, own, sizeof own, hipMemcpyHostToDevice));
+  sym_inbox<DIM>(s, 1, {0, s->n});
   float* tab[1] = {y.inbox.p};
   y.inbox_tab.alloc(1);
   HIP_TRY(hipMemcpy(y.inbox_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
   HIP_TRY(hipStreamSynchronize(s->stream));     // the tile-major copy is complete: the caller may free d_rows
   y.seg_ready = true;
-}
-
-template <int DIM>
-void sym_segment_apply(topolow_session* s, const void* pin, void* pout, int iter) {
-  if constexpr (!kSymDim<DIM>) {
-    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim"};
-  } else {
-    auto& y = s->sym;
-    hipLaunchKernelGGL(symm_owner_apply_kernel<DIM>, dim3((s->n + 255) / 256), dim3(256), 0, s->stream, (const float*)pin,
-                       (float*)pout, y.inbox.p, 1, y.npad, 0, s->n, (float* const*)nullptr, 0, iter + 1, s->state.p);
-    HIP_TRY(hipGetLastError());
-  }
 }
 
 // One convergence check of the session's own loop.  error_pass = true: the separate pass over the block (or
@@ -1706,29 +1680,23 @@ int topolow_session_enqueue(topolow_session* s, int32_t max_iters, int32_t* enqu
       } else {
         const int stages = s->fixed_stages > 0 ? s->fixed_stages : slab_stages_at(iter, s->k_host, s->dim);
         const SlabGeom g = slab_geom(s->n, stages);
-        const bool sym = g.n_stages == 1 && sym_eligible(s) && sym_available(s);
-        // (the row-owner ERR instance pairs rows two by two: an odd block keeps the separate pass; the symmetric
-        //  sweep's ERR instance has no such rule)
-        const bool fuse_now = s->pcheck.active && g.n_stages == 1 &&
-                              (s->precision == TOPOLOW_PRECISION_F64 ? (sym && s->sym.delta_ready) : (sym || s->rows() % 2 == 0));
+        const bool fuse_now = s->pcheck.active && check_fusable(s, g.n_stages);
         if (s->pcheck.active && !fuse_now) flush_pending_check(s);
-        const bool symrr = s->sym.two_stage && sym_rr_stages_ok(g.n_stages) && sym_eligible(s) && sym_available(s) &&
-                           sym_rr_available(s, g.n_stages);
-        if (sym) {   // one sweep over the upper triangle moves both ends of every pair
+        const SymForm form = sym_form(s, g.n_stages);
+        if (form == SymForm::kSweep) {   // one sweep over the upper triangle moves both ends of every pair
           int out = 0;
           while (out == s->cur || out == s->held) ++out;
-          TL_DISPATCH_DIM(s->dim, sym_iteration, s, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host, fuse_now);
+          TL_DISPATCH_SYM(s->dim, sym_iteration, s, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host, fuse_now);
           s->cur = out;
-        } else if (symrr) {   // S symmetric sweeps over the tiles of one stage each, in random order
+        } else if (form == SymForm::kStages) {   // S symmetric sweeps over the tiles of one stage each, in random order
           const int S = g.n_stages;
           int order[8];
           sym_rr_order(s->seed, iter, S, order);
           for (int t = 0; t < S; ++t) {
             int out = 0;
             while (out == s->cur || out == s->held) ++out;
-            const bool last = t == S - 1;
-            TL_DISPATCH_DIM(s->dim, sym_rr_stage, s, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host,
-                            last ? s->k_host * (1.0 - s->cooling) : s->k_host, S, order[t], last ? iter + 1 : iter);
+            TL_DISPATCH_SYM(s->dim, sym_iteration, s, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host, false, S, order[t],
+                            t == S - 1);
             s->cur = out;
           }
         } else
@@ -1762,12 +1730,12 @@ int topolow_session_enqueue(topolow_session* s, int32_t max_iters, int32_t* enqu
         s->held = pc.beside ? s->cur : -1;
         // one stage next iteration: its kernel reduces this check's MAE (the positions it reads ARE this
         // check's positions) and the separate pass over the block is dropped
-        // (fp32: the row-owner ERR instance or the symmetric sweep's; f64: the symmetric sweep's, exact through its delta tiles)
+        // (fp32: the row-owner ERR instance or the symmetric sweep's, when the MAE comes from the block; f64: the
+        //  symmetric sweep's, exact through its delta tiles)
         const bool fuse = s->fuse_checks && s->schedule == TOPOLOW_SCHEDULE_SLAB && iter + 1 < s->n_iter &&
-                          ((s->dense_mae && s->precision == TOPOLOW_PRECISION_F32 && (s->rows() % 2 == 0 || sym_eligible(s))) ||
-                           (s->precision == TOPOLOW_PRECISION_F64 && sym_eligible(s) && sym_available(s) && s->sym.delta_ready)) &&
-                          slab_geom(s->n, s->fixed_stages > 0 ? s->fixed_stages
-                                                              : slab_stages_at(iter + 1, s->k_host, s->dim)).n_stages == 1;
+                          (s->dense_mae || s->precision == TOPOLOW_PRECISION_F64) &&
+                          check_fusable(s, slab_geom(s->n, s->fixed_stages > 0 ? s->fixed_stages
+                                                                               : slab_stages_at(iter + 1, s->k_host, s->dim)).n_stages);
         if (fuse) s->pcheck = pc;
         else launch_check(s, pc, /*error_pass=*/true);
       }
@@ -2056,20 +2024,15 @@ int32_t topolow_symm_stage_order(uint64_t seed, int32_t iter, int32_t stages, in
 int32_t topolow_symm_segment_rows(int32_t n, int32_t segment, int32_t n_segments, int32_t* row_first,
                                   int32_t* row_end) {
   if (n < 2 || n_segments < 1 || segment < 0 || segment >= n_segments) return 0;
-  const long long npad = ((long long)n + kSymRows - 1) & ~(long long)(kSymRows - 1);
-  const long long TR = npad / kSymRows, total = TR * (TR + 1);
-  if (total < 8ll * n_segments) return 0;
-  int rf = -1, rl = -1;
-  (void)relax_symm_plan((int)npad, 1, total * segment / n_segments, total * (segment + 1) / n_segments, &rf, &rl);
-  if (rf < 0) return 0;
-  if (row_first) *row_first = rf * kSymRows;
-  if (row_end) *row_end = (int32_t)std::min<long long>(n, (long long)(rl + 1) * kSymRows);
+  const SymSegment g = sym_segment(n, segment, n_segments);
+  if (g.total < 8ll * n_segments || g.r_first < 0) return 0;
+  if (row_first) *row_first = g.r_first * kSymRows;
+  if (row_end) *row_end = (int32_t)std::min<long long>(n, (long long)(g.r_last + 1) * kSymRows);
   return 1;
 }
 
 int32_t topolow_session_symm_segment_eligible(const topolow_session* s, int32_t n_segments) {
-  return s && s->sym.allowed && s->schedule == TOPOLOW_SCHEDULE_SLAB && s->precision == TOPOLOW_PRECISION_F32 &&
-                 s->dim >= 2 && s->dim <= 6 && s->dim == s->udim && s->n >= s->sym.min_n && s->gplus.p != nullptr &&
+  return s && sym_shape_ok(s) && s->precision == TOPOLOW_PRECISION_F32 && s->gplus.p != nullptr &&
                  topolow_symm_segment_rows(s->n, 0, n_segments, nullptr, nullptr)
              ? 1 : 0;
 }
@@ -2092,13 +2055,12 @@ int topolow_session_symm_segment_build(topolow_session* s, int32_t segment, int3
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
     try {
-      TL_DISPATCH_DIM(s->dim, sym_segment_build, s, segment, n_segments, (const uint32_t*)d_rows, row_first, n_rows,
+      TL_DISPATCH_SYM(s->dim, sym_segment_build, s, segment, n_segments, (const uint32_t*)d_rows, row_first, n_rows,
                       any_threshold != 0);
     } catch (const HipError&) {      // e.g. the device cannot hold the extra buffers: the session keeps its row-owner sweep
-      auto& y = s->sym;
-      y.tenc.release(); y.rowpart.release(); y.colpart.release(); y.inbox.release();
-      y.seg_ready = false;
-      y.seg_caller = false;
+      s->sym.release();
+      s->sym.seg_ready = false;
+      s->sym.seg_caller = false;
       throw;
     }
   });
@@ -2113,10 +2075,10 @@ int topolow_session_symm_segment_sweep(topolow_session* s, const void* d_pos_in,
   }
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
-    TL_DISPATCH_DIM(s->dim, sym_sharded_sweep, s, d_pos_in, iter, k, d_out2 != nullptr);
+    TL_DISPATCH_SYM(s->dim, sym_sharded_sweep, s, d_pos_in, iter, k, d_out2 != nullptr);
     if (d_out2 != nullptr) {
       hipLaunchKernelGGL(reduce_total_kernel, dim3(1), dim3(1024), 0, s->stream, s->part_sum.p, s->part_cnt.p,
-                         s->sym.tiles > 0 ? s->sym.n_units : 0, d_out2, s->state.p);
+                         s->sym.tiles > 0 ? s->sym.plan.n_units : 0, d_out2, s->state.p);
       HIP_TRY(hipGetLastError());
     }
     s->iters_enqueued = std::max(s->iters_enqueued, iter + 1);
@@ -2129,7 +2091,7 @@ int topolow_session_symm_segment_apply(topolow_session* s, const void* d_pos_in,
     return TOPOLOW_ERR_BAD_ARGUMENT;
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
-    TL_DISPATCH_DIM(s->dim, sym_segment_apply, s, d_pos_in, d_pos_out, iter);
+    TL_DISPATCH_SYM(s->dim, sym_owner_apply, s, d_pos_in, d_pos_out, 0, s->n, nullptr, 0, iter);
   });
 }
 
@@ -2471,10 +2433,9 @@ int topolow_sessions_run_sharded(topolow_session** sessions, int32_t count, cons
       } catch (const HipError&) {
         (void)hipGetLastError();
         for (topolow_session* s : R.ss) {
-          auto& y = s->sym;
-          y.tenc.release(); y.rec[0].release(); y.rec[1].release(); y.rowpart.release(); y.colpart.release();
-          y.units.release(); y.wave_first.release(); y.row_units.release(); y.inbox.release();
-          y.ready = false; y.seg_ready = false;
+          s->sym.release();
+          s->sym.ready = false;
+          s->sym.seg_ready = false;
         }
         R.pair_sharded = false;
       }
