@@ -690,6 +690,11 @@ def slab_plan(n: int, slab_stages: int, seed: int, it: int) -> np.ndarray:
     return buf[:ns].copy()
 
 
+def slab_stage_count(n: int, slab_stages: int) -> int:
+    """Stages of an iteration of n points that asks for slab_stages: its slab geometry's count, without the plan."""
+    return int(load().topolow_slab_plan(int(n), int(slab_stages), 0, 0, None, 0))
+
+
 def slab_stages_for_k(k: float, ndim: int = 5) -> int:
     return int(load().topolow_slab_stages_for_k(float(k), int(ndim)))
 

@@ -65,10 +65,6 @@ struct ShardedGroup {
 struct ShardedRun {
   std::vector<topolow_session*> ss;
   std::vector<ShardedGroup> groups;
-  int P = 0;
-  int n_iter = 0, check_freq = 3;
-  double k0 = 0, cooling = 0;
-  int fixed_stages = 0;
   std::vector<std::array<hipEvent_t, 2>> ev;      // per group
   ShardedAbortableBarrier* bar = nullptr;
   std::atomic<int> flag[2];      // published by group 0's thread before barrier g (slot g & 1): bit 0 stop, bit 1 interrupt
@@ -109,8 +105,10 @@ inline void sharded_worker(ShardedRun& R, int r) {
     ++g;
     return true;
   };
+  // The run's parameters are every session's (topolow_session_begin); the schedule is the lead block's.
+  const int P = (int)R.ss.size();
   int cur = 0;
-  double k = R.k0;
+  double k = lead->k0;
   int iter = 0;
   // Position buffers rotate through three: a stage reads `cur` and writes (own rows, and the other blocks' copies)
   // the next one, so the buffer a check measured is not written for two more stages.
@@ -119,9 +117,7 @@ inline void sharded_worker(ShardedRun& R, int r) {
   // block and no barrier of its own.  Its controller runs behind that barrier and snapshots the buffer the sweep
   // READ; other blocks may already be writing their next stage -- into the third buffer.  Decided from the
   // schedule alone, hence identically in every thread.
-  bool pend = false;
-  int pend_iter1 = 0, pend_buf = 0;
-  double pend_k = 0.0;
+  PendingCheck pend;
   // Rank tables alternate between successive checks: with fused checks a block may already be pushing the NEXT
   // check's (sum, count) -- it rides on the sweep that follows the barrier -- while another block's controller
   // still reads this check's table behind the same barrier.  Two tables are enough: the push of check q + 2 is
@@ -138,26 +134,34 @@ inline void sharded_worker(ShardedRun& R, int r) {
   bool fusable_pair = R.pair_sharded;
   for (topolow_session* s : R.ss)
     fusable_pair = fusable_pair && s->fuse_checks && s->dense_mae && s->precision == TOPOLOW_PRECISION_F32;
-  auto separate_check = [&](int buf, int iter1, double k_after) -> bool {
-    const int tab = (int)(n_check & 1) * R.P;
+  // a check's `parts` partials -> this block's slot of every rank table `tab` (inside the caller's check ProfScope)
+  auto push_partials = [&](topolow_session* s, int parts, int tab) {
+    hipLaunchKernelGGL(reduce_push_kernel, dim3(1), dim3(1024), 0, s->stream, s->part_sum.p, s->part_cnt.p, parts,
+                       s->rsum_tab.p, s->rcnt_tab.p, s->n_ranks, tab + s->rank, s->state.p);
+    HIP_TRY(hipGetLastError());
+  };
+  // behind the barrier: every block's controller on rank table `tab`, for check pc
+  auto controllers = [&](const PendingCheck& pc, int tab) {
+    for (int b : G.blocks) {
+      topolow_session* s = R.ss[b];
+      ProfScope prof(s, &s->prof_check);
+      launch_controller(s, s->pos[pc.buf].p, pc.iter1, pc.k_after, s->rank_sum.p + tab, s->rank_cnt.p + tab, s->n_ranks);
+    }
+  };
+  auto separate_check = [&](const PendingCheck& pc) -> bool {
+    const int tab = (int)(n_check & 1) * P;
     ++n_check;
     for (int b : G.blocks) {
       topolow_session* s = R.ss[b];
       ProfScope prof(s, &s->prof_check);
-      TL_DISPATCH_DIM(s->dim, launch_edge_error, s, s->pos[buf].p, s->state.p);
-      hipLaunchKernelGGL(reduce_push_kernel, dim3(1), dim3(1024), 0, s->stream, s->part_sum.p, s->part_cnt.p,
-                         error_parts(s), s->rsum_tab.p, s->rcnt_tab.p, s->n_ranks, tab + s->rank, s->state.p);
-      HIP_TRY(hipGetLastError());
+      TL_DISPATCH_DIM(s->dim, launch_edge_error, s, s->pos[pc.buf].p, s->state.p);
+      push_partials(s, error_parts(s), tab);
     }
     if (!exchange()) return false;
-    for (int b : G.blocks) {
-      topolow_session* s = R.ss[b];
-      ProfScope prof(s, &s->prof_check);
-      launch_controller(s, s->pos[buf].p, iter1, k_after, s->rank_sum.p + tab, s->rank_cnt.p + tab, s->n_ranks);
-    }
+    controllers(pc, tab);
     return true;
   };
-  for (; iter < R.n_iter; ++iter) {
+  for (; iter < lead->n_iter; ++iter) {
     if (seen != 0) break;
     if (R.warmup_iters > 0 && iter == R.warmup_iters) {   // measurement only: drain, meet, start the clock
       HIP_TRY(hipStreamSynchronize(G.stream));
@@ -167,37 +171,23 @@ inline void sharded_worker(ShardedRun& R, int r) {
     }
     if (r == 0 && R.interrupt_cb != nullptr && iter > 0 && iter % 50 == 0 && !R.interrupted)   // reference :364
       R.interrupted = R.interrupt_cb(R.interrupt_user) != 0;   // published at the next exchange
-    const int stages = R.fixed_stages > 0 ? R.fixed_stages : slab_stages_at(iter, k, lead->dim);
-    const SlabGeom geo = slab_geom(lead->n, stages);
-    const bool fuse_now = pend && geo.n_stages == 1;
-    if (pend && !fuse_now) { if (!separate_check(pend_buf, pend_iter1, pend_k)) return; pend = false; }
-    const int tab = (int)(n_check & 1) * R.P;   // the table of the check this sweep carries, if any
+    // the session loop's plan: ONE block (the whole matrix) takes its symmetric forms, a block of several is row-owner
+    const IterPlan plan = plan_iteration(lead, iter, k);
+    const bool fuse_now = pend.active && plan.geo.n_stages == 1;
+    if (pend.active && !fuse_now) { if (!separate_check(pend)) return; pend.active = false; }
+    const int tab = (int)(n_check & 1) * P;   // the table of the check this sweep carries, if any
     if (fuse_now) ++n_check;
-    // ONE block = the whole matrix: its iterations take the forms of the session's own loop (sym_form)
-    const SymForm form = R.P == 1 ? sym_form(lead, geo.n_stages) : SymForm::kRowOwner;
-    if (R.pair_sharded && geo.n_stages == 1) {
+    if (R.pair_sharded && plan.geo.n_stages == 1) {
       // every session sweeps its segment of the tile list and folds its partials into the owners' inboxes; barrier;
       // the owners move their points and store them into every session's next buffer; barrier
       const int nxt = (cur + 1) % 3;
       for (int b : G.blocks) {
         topolow_session* s = R.ss[b];
         TL_DISPATCH_SYM(s->dim, sym_sharded_sweep, s, s->pos[cur].p, iter, k, fuse_now);
-        if (fuse_now) {
-          ProfScope prof(s, &s->prof_check);
-          hipLaunchKernelGGL(reduce_push_kernel, dim3(1), dim3(1024), 0, s->stream, s->part_sum.p, s->part_cnt.p,
-                             s->sym.plan.n_units, s->rsum_tab.p, s->rcnt_tab.p, s->n_ranks, tab + s->rank, s->state.p);
-          HIP_TRY(hipGetLastError());
-        }
+        if (fuse_now) { ProfScope prof(s, &s->prof_check); push_partials(s, s->sym.plan.n_units, tab); }
       }
       if (!exchange()) return;
-      if (fuse_now) {
-        for (int b : G.blocks) {
-          topolow_session* s = R.ss[b];
-          ProfScope prof(s, &s->prof_check);
-          launch_controller(s, s->pos[pend_buf].p, pend_iter1, pend_k, s->rank_sum.p + tab, s->rank_cnt.p + tab, s->n_ranks);
-        }
-        pend = false;
-      }
+      if (fuse_now) { controllers(pend, tab); pend.active = false; }
       for (int b : G.blocks) {
         topolow_session* s = R.ss[b];
         TL_DISPATCH_SYM(s->dim, sym_owner_apply, s, s->pos[cur].p, s->pos[nxt].p, s->row_begin, s->row_end, s->push_tab[nxt].p,
@@ -205,57 +195,28 @@ inline void sharded_worker(ShardedRun& R, int r) {
       }
       if (!exchange()) return;
       cur = nxt;
-    } else if (form == SymForm::kStages) {   // a 2-, 4- or 8-stage iteration as symmetric sweeps over the tiles of one stage each
-      const int S = geo.n_stages;
-      int order[8];
-      sym_rr_order(lead->seed, iter, S, order);
-      for (int t = 0; t < S; ++t) {
-        TL_DISPATCH_SYM(lead->dim, sym_iteration, lead, lead->pos[cur].p, lead->pos[(cur + 1) % 3].p, iter, k, false, S,
-                        order[t], t == S - 1);
-        if (!exchange()) return;
-        cur = (cur + 1) % 3;
-      }
     } else
-    for (int slot = 0; slot < geo.n_stages; ++slot) {
-      const SlabRanges rg = slab_ranges(geo, lead->seed, iter, slot);
+    for (int t = 0; t < plan.geo.n_stages; ++t) {
+      const int nxt = (cur + 1) % 3;
       for (int b : G.blocks) {
         topolow_session* s = R.ss[b];
-        int stage_blocks = (s->rows() + CfgProd::ROWS - 1) / CfgProd::ROWS;
-        if (form == SymForm::kSweep) {   // (relax_symm.h) its error partials are one per unit
-          TL_DISPATCH_SYM(s->dim, sym_iteration, s, s->pos[cur].p, s->pos[(cur + 1) % 3].p, iter, k, fuse_now);
-          stage_blocks = s->sym.plan.n_units;
-        } else {
-          TL_DISPATCH_DIM(s->dim, launch_stage, s, s->pos[cur].p, s->pos[(cur + 1) % 3].p, s->state.p, rg, iter + 1, k,
-                          s->push_tab[(cur + 1) % 3].p, s->n_push, fuse_now);
-        }
-        if (fuse_now) {   // the sweep's per-workgroup partials -> this block's slot of every rank table
-          ProfScope prof(s, &s->prof_check);
-          hipLaunchKernelGGL(reduce_push_kernel, dim3(1), dim3(1024), 0, s->stream, s->part_sum.p, s->part_cnt.p,
-                             stage_blocks, s->rsum_tab.p, s->rcnt_tab.p, s->n_ranks, tab + s->rank, s->state.p);
-          HIP_TRY(hipGetLastError());
-        }
+        const int parts = enqueue_stage(s, plan, t, s->pos[cur].p, s->pos[nxt].p, iter, k, s->push_tab[nxt].p, s->n_push,
+                                        fuse_now);
+        if (fuse_now) { ProfScope prof(s, &s->prof_check); push_partials(s, parts, tab); }
       }
       if (!exchange()) return;
-      if (fuse_now) {
-        for (int b : G.blocks) {
-          topolow_session* s = R.ss[b];
-          ProfScope prof(s, &s->prof_check);
-          launch_controller(s, s->pos[pend_buf].p, pend_iter1, pend_k, s->rank_sum.p + tab, s->rank_cnt.p + tab, s->n_ranks);
-        }
-        pend = false;
-      }
-      cur = (cur + 1) % 3;
+      if (fuse_now) { controllers(pend, tab); pend.active = false; }
+      cur = nxt;
     }
-    k *= (1.0 - R.cooling);   // reference :289
-    if ((iter + 1) % R.check_freq == 0 || iter == R.n_iter - 1) {   // reference :294
-      const bool fuse = (fusable || fusable_pair) && iter + 1 < R.n_iter &&
-                        slab_geom(lead->n, R.fixed_stages > 0 ? R.fixed_stages
-                                                              : slab_stages_at(iter + 1, k, lead->dim)).n_stages == 1;
-      if (fuse) { pend = true; pend_iter1 = iter + 1; pend_k = k; pend_buf = cur; }
-      else if (!separate_check(cur, iter + 1, k)) return;
+    k *= (1.0 - lead->cooling);   // reference :289
+    if (check_after(lead, iter)) {
+      const PendingCheck pc{true, iter + 1, k, cur};
+      const bool fuse = (fusable || fusable_pair) && iter + 1 < lead->n_iter && iteration_stages(lead, iter + 1, k) == 1;
+      if (fuse) pend = pc;
+      else if (!separate_check(pc)) return;
     }
   }
-  if (pend) { if (!separate_check(pend_buf, pend_iter1, pend_k)) return; pend = false; }   // the loop ended early
+  if (pend.active && !separate_check(pend)) return;   // the loop ended early
   for (int b : G.blocks) R.ss[b]->cur = cur;
   if (r == 0) { R.iters_enqueued = iter; R.exchanges = g; }
   HIP_TRY(hipStreamSynchronize(G.stream));

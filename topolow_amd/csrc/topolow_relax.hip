@@ -194,6 +194,12 @@ bool edges_are_the_matrix(const double* D, const int32_t* T, int n, const int32_
 // =========================================================================================
 // Session (slab path)
 // =========================================================================================
+// A convergence check whose error pass has not been launched yet: when the NEXT iteration is a single
+// stage, that stage's kernel reduces the MAE of the positions it reads (exactly this check's positions)
+// on its way (slab_stage_pipe_kernel<..., ERR = true>) and the separate 2 N^2-byte pass is dropped.
+// beside: the session's own loop runs it on the check stream (launch_check).
+struct PendingCheck { bool active = false; int iter1 = 0; double k_after = 0.0; int buf = -1; bool beside = false; };
+
 struct topolow_session {
   int n = 0, dim = 0, udim = 0, row_begin = 0, row_end = 0, ld = 0;   // dim: coordinates the kernels carry, udim: the caller's ndim
   int precision = TOPOLOW_PRECISION_F32;
@@ -206,10 +212,7 @@ struct topolow_session {
   hipStream_t check_stream = nullptr;
   hipEvent_t ev_iter_done = nullptr, ev_check_done = nullptr;
   int held = -1;
-  // A convergence check whose error pass has not been launched yet: when the NEXT iteration is a single
-  // stage, that stage's kernel reduces the MAE of the positions it reads (exactly this check's positions)
-  // on its way (slab_stage_pipe_kernel<..., ERR = true>) and the separate 2 N^2-byte pass is dropped.
-  struct PendingCheck { bool active = false; int iter1 = 0; double k_after = 0.0; int buf = -1; bool beside = false; } pcheck;
+  PendingCheck pcheck;
   bool fuse_checks = true;      // TOPOLOW_FUSE_CHECKS=0: always the separate pass
   bool serial_checks = false;   // TOPOLOW_SERIAL_CHECKS=1: keep every check on the main stream
 
@@ -1003,6 +1006,47 @@ SymForm sym_form(topolow_session* s, int n_stages) {
              : SymForm::kRowOwner;
 }
 
+// The stages of iteration `iter` at k: the run's fixed count or the schedule's, as the slab geometry of n points has them.
+int iteration_stages(const topolow_session* s, int iter, double k) {
+  return slab_geom(s->n, s->fixed_stages > 0 ? s->fixed_stages : slab_stages_at(iter, k, s->dim)).n_stages;
+}
+
+// Whether a convergence check follows iteration `iter` (reference :294).
+bool check_after(const topolow_session* s, int iter) { return (iter + 1) % s->check_freq == 0 || iter == s->n_iter - 1; }
+
+// How iteration `iter` runs at k: its stages, their form (a row block of several has n_push > 0: always row-owner), and
+// for SymForm::kStages the order of the stages (drawn per iteration).
+struct IterPlan {
+  SlabGeom geo;
+  SymForm form;
+  int order[8];
+};
+IterPlan plan_iteration(topolow_session* s, int iter, double k) {
+  IterPlan p;
+  p.geo = slab_geom(s->n, iteration_stages(s, iter, k));
+  p.form = sym_form(s, p.geo.n_stages);
+  if (p.form == SymForm::kStages) sym_rr_order(s->seed, iter, p.geo.n_stages, p.order);
+  return p;
+}
+
+// Enqueues stage t of iteration `iter` in the form p names, from pin into pout: the whole sweep, stage t's sweep, or the
+// row-owner slab t (push: the other blocks' copies of pout, n_push of them).  err: the launch also reduces the pending
+// check's MAE of pin.  Returns the error partials it wrote (0 without err).
+int enqueue_stage(topolow_session* s, const IterPlan& p, int t, const void* pin, void* pout, int iter, double k,
+                  const void* push, int n_push, bool err) {
+  if (p.form == SymForm::kRowOwner) {
+    TL_DISPATCH_DIM(s->dim, launch_stage, s, pin, pout, s->state.p, slab_ranges(p.geo, s->seed, iter, t), iter + 1, k,
+                    push, n_push, err);
+    if (err) s->fused_parts = (s->rows() + CfgProd::ROWS - 1) / CfgProd::ROWS;
+  } else if (p.form == SymForm::kSweep) {   // one sweep over the upper triangle moves both ends of every pair
+    TL_DISPATCH_SYM(s->dim, sym_iteration, s, pin, pout, iter, k, err);
+  } else {   // S symmetric sweeps over the tiles of one stage each, in random order
+    const int S = p.geo.n_stages;
+    TL_DISPATCH_SYM(s->dim, sym_iteration, s, pin, pout, iter, k, err, S, p.order[t], t == S - 1);
+  }
+  return err ? s->fused_parts : 0;
+}
+
 // Whether a check may be fused into an iteration of n_stages stages: the iteration's one sweep reduces the MAE of the
 // positions it reads.  The row-owner ERR instance pairs rows two by two (an odd block keeps the separate pass), the
 // symmetric sweep's has no such rule; f64 fuses into the symmetric sweep only, exact through its delta tiles (asked
@@ -1174,7 +1218,7 @@ void sym_segment_build(topolow_session* s, int segment, int P, const uint32_t* d
 // One convergence check of the session's own loop.  error_pass = true: the separate pass over the block (or
 // the edge list) + the controller; false: the partials were written by the stage kernel just launched
 // (ERR launch), only the controller follows.  pc.beside: on the check stream, beside the next stages.
-void launch_check(topolow_session* s, topolow_session::PendingCheck& pc, bool error_pass) {
+void launch_check(topolow_session* s, PendingCheck& pc, bool error_pass) {
   hipStream_t check_on = s->stream;
   if (pc.beside) {
     HIP_TRY(hipEventRecord(s->ev_iter_done, s->stream));
@@ -1203,6 +1247,15 @@ void launch_check(topolow_session* s, topolow_session::PendingCheck& pc, bool er
 // enqueueing, or asks for results): run it as a separate pass now.
 void flush_pending_check(topolow_session* s) {
   if (s->pcheck.active) launch_check(s, s->pcheck, /*error_pass=*/true);
+}
+
+// Reference :359-361: positions are inspected after every 10th iteration, after that iteration's convergence check
+// (which may already have stopped the run).  The iteration to report for the first non-finite result (0x7fffffff:
+// none) of a run that ran `ran` iterations, or 0.
+int nonfinite_report(int first_nonfinite, int ran, bool stopped) {
+  if (first_nonfinite == 0x7fffffff) return 0;
+  const int t = ((first_nonfinite + 9) / 10) * 10;
+  return t <= ran && !(stopped && t == ran) ? t : 0;
 }
 
 template <typename F>
@@ -1678,48 +1731,22 @@ int topolow_session_enqueue(topolow_session* s, int32_t max_iters, int32_t* enqu
       if (s->schedule == TOPOLOW_SCHEDULE_GS) {
         TL_DISPATCH_DIM(s->dim, launch_tilegs_iteration, s, s->pos[s->cur].p, iter, s->k_host);
       } else {
-        const int stages = s->fixed_stages > 0 ? s->fixed_stages : slab_stages_at(iter, s->k_host, s->dim);
-        const SlabGeom g = slab_geom(s->n, stages);
-        const bool fuse_now = s->pcheck.active && check_fusable(s, g.n_stages);
+        const IterPlan plan = plan_iteration(s, iter, s->k_host);
+        const bool fuse_now = s->pcheck.active && check_fusable(s, plan.geo.n_stages);
         if (s->pcheck.active && !fuse_now) flush_pending_check(s);
-        const SymForm form = sym_form(s, g.n_stages);
-        if (form == SymForm::kSweep) {   // one sweep over the upper triangle moves both ends of every pair
-          int out = 0;
-          while (out == s->cur || out == s->held) ++out;
-          TL_DISPATCH_SYM(s->dim, sym_iteration, s, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host, fuse_now);
-          s->cur = out;
-        } else if (form == SymForm::kStages) {   // S symmetric sweeps over the tiles of one stage each, in random order
-          const int S = g.n_stages;
-          int order[8];
-          sym_rr_order(s->seed, iter, S, order);
-          for (int t = 0; t < S; ++t) {
-            int out = 0;
-            while (out == s->cur || out == s->held) ++out;
-            TL_DISPATCH_SYM(s->dim, sym_iteration, s, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host, false, S, order[t],
-                            t == S - 1);
-            s->cur = out;
-          }
-        } else
-        for (int slot = 0; slot < g.n_stages; ++slot) {
-          const SlabRanges rg = slab_ranges(g, s->seed, iter, slot);
+        for (int t = 0; t < plan.geo.n_stages; ++t) {
           int out = 0;   // a buffer that is neither the input nor the one a running check reads
           while (out == s->cur || out == s->held) ++out;
-          TL_DISPATCH_DIM(s->dim, launch_stage, s, s->pos[s->cur].p, s->pos[out].p, s->state.p, rg,
-                          iter + 1, s->k_host, nullptr, 0, fuse_now);
+          enqueue_stage(s, plan, t, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host, nullptr, 0, fuse_now);
           s->cur = out;
-          if (fuse_now) s->fused_parts = (s->rows() + CfgProd::ROWS - 1) / CfgProd::ROWS;
         }
         if (fuse_now) launch_check(s, s->pcheck, /*error_pass=*/false);
       }
       s->iters_enqueued = iter + 1;
       s->k_host *= (1.0 - s->cooling);  // reference :289
       ++done;
-      if ((iter + 1) % s->check_freq == 0 || iter == s->n_iter - 1) {  // reference :294
-        topolow_session::PendingCheck pc;
-        pc.active = true;
-        pc.iter1 = iter + 1;
-        pc.k_after = s->k_host;
-        pc.buf = s->cur;
+      if (check_after(s, iter)) {
+        PendingCheck pc{true, iter + 1, s->k_host, s->cur};
         pc.beside = s->schedule == TOPOLOW_SCHEDULE_SLAB && s->stream == s->own_stream &&
                     !s->profiling && !s->serial_checks;
         // The check reads this iteration's positions while the next iteration's stages run.  Its
@@ -1734,8 +1761,7 @@ int topolow_session_enqueue(topolow_session* s, int32_t max_iters, int32_t* enqu
         //  symmetric sweep's, exact through its delta tiles)
         const bool fuse = s->fuse_checks && s->schedule == TOPOLOW_SCHEDULE_SLAB && iter + 1 < s->n_iter &&
                           (s->dense_mae || s->precision == TOPOLOW_PRECISION_F64) &&
-                          check_fusable(s, slab_geom(s->n, s->fixed_stages > 0 ? s->fixed_stages
-                                                                               : slab_stages_at(iter + 1, s->k_host, s->dim)).n_stages);
+                          check_fusable(s, iteration_stages(s, iter + 1, s->k_host));
         if (fuse) s->pcheck = pc;
         else launch_check(s, pc, /*error_pass=*/true);
       }
@@ -1788,17 +1814,11 @@ int topolow_session_finish(topolow_session* s, double* positions_out, int32_t* c
     poll_checks(s, 0);
     RunState st;
     HIP_TRY(hipMemcpy(&st, s->state.p, sizeof st, hipMemcpyDeviceToHost));
-    // Reference :359-361 -- positions are inspected after every 10th iteration (after that
-    // iteration's convergence check, which may already have stopped the run).
-    const int ran = st.stopped ? st.iter_base : s->iters_enqueued;
-    if (st.first_nonfinite != 0x7fffffff) {
-      const int t = ((st.first_nonfinite + 9) / 10) * 10;
-      if (t <= ran && !(st.stopped && t == ran)) {
-        set_err(errbuf, errlen,
-                "Numerical instability at iteration %d. Reduce k0 or c_repulsion.", t);
-        rc_nonfinite = TOPOLOW_ERR_NONFINITE;
-        return;
-      }
+    const int t = nonfinite_report(st.first_nonfinite, st.stopped ? st.iter_base : s->iters_enqueued, st.stopped);
+    if (t != 0) {
+      set_err(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.", t);
+      rc_nonfinite = TOPOLOW_ERR_NONFINITE;
+      return;
     }
     if (positions_out) download_positions(s, s->best.p, positions_out);
     if (converged) *converged = st.converged;
@@ -2411,7 +2431,6 @@ int topolow_sessions_run_sharded(topolow_session** sessions, int32_t count, cons
   int rc_extra = TOPOLOW_OK;
   const int rc = guarded(errbuf, errlen, [&] {
     ShardedRun R;
-    R.P = count;
     R.ss.assign(sessions, sessions + count);
     const int n = R.ss[0]->n;
     int expect = 0;
@@ -2468,11 +2487,6 @@ int topolow_sessions_run_sharded(topolow_session** sessions, int32_t count, cons
     }
     for (const ShardedGroup& G : R.groups)
       for (int b : G.blocks) R.ss[b]->stream = G.stream;   // (idle: set_positions / begin have synchronised)
-    R.n_iter = n_iter;
-    R.check_freq = convergence_check_freq < 1 ? 10 : convergence_check_freq;
-    R.k0 = k0;
-    R.cooling = cooling_rate;
-    R.fixed_stages = slab_stages;
     R.interrupt_cb = interrupt_cb;
     R.interrupt_user = interrupt_user;
     R.flag[0].store(0);
@@ -2561,10 +2575,8 @@ int topolow_sessions_run_sharded(topolow_session** sessions, int32_t count, cons
       if (R.interrupted) {
         set_err(errbuf, errlen, "interrupted by the caller");
         rc_extra = TOPOLOW_ERR_INTERRUPTED;
-      } else if (first_bad != 0x7fffffff && ((first_bad + 9) / 10) * 10 <= ran &&
-                 !(st.stopped && ((first_bad + 9) / 10) * 10 == ran)) {   // reference :359-361
-        set_err(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.",
-                ((first_bad + 9) / 10) * 10);
+      } else if (const int t = nonfinite_report(first_bad, ran, st.stopped)) {
+        set_err(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.", t);
         rc_extra = TOPOLOW_ERR_NONFINITE;
       } else {
         if (positions_out) download_positions(s0, s0->best.p, positions_out);

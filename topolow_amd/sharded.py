@@ -18,6 +18,7 @@ product backend is `HipBackend` (libtopolow_relax.so, no fallback).
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import math
 import os
@@ -338,96 +339,88 @@ class ShardedRelaxation:
             self.fusable = not timers     # the sweep's ERR instance has no even-rows rule
         self.pending = None   # (iter1, k_after, buffer index): a check that rides on the next iteration's single stage
 
-    def _n_slots_of(self, it_, k_):
+    def _stages(self, it_, k_):
+        """(asked, run): the stages iteration it_ asks for at k_, and how many its slab geometry has."""
         st = self.slab_stages if self.slab_stages > 0 else _native.slab_stages_at(it_, k_, self.ndim)
-        return st, len(_native.slab_plan(self.n, st, self.seed, it_))
+        return st, _native.slab_stage_count(self.n, st)
 
-    def _separate_check(self, buf, iter1, k_after):
-        total = self.backend.check_partial(self.pos[buf])
+    @contextlib.contextmanager
+    def _timed(self, field: str):
+        """timers=True (breakdown pass: host-synchronised, so slower than the timed pass): adds the time of the
+        enclosed work to self.<field>."""
+        if not self.timers:
+            yield
+            return
+        self.backend.synchronize()
+        t0 = time.perf_counter()
+        yield
+        self.backend.synchronize()
+        setattr(self, field, getattr(self, field) + time.perf_counter() - t0)
+
+    def _check(self, iter1, k_after, buf, total=None):
+        """A convergence check of pos[buf]: `total` is its MAE as the sweep just enqueued reduced it, None: a separate
+        pass over the block.  Summed over the ranks, then the controller."""
+        if total is None:
+            total = self.backend.check_partial(self.pos[buf])
         self.coll.all_reduce_tensor(total)
         self.backend.controller_step(total, self.pos[buf], iter1, k_after)
 
+    def flush(self, total=None):
+        """The pending check, if any: it rides on the sweep that reduced `total`, or (None) runs as a separate pass --
+        the next iteration has several stages, or the caller wants the state."""
+        if self.pending is not None:
+            self._check(*self.pending, total)
+            self.pending = None
+
     def advance(self, max_iters: int) -> int:
         """Enqueues up to max_iters further iterations; returns how many (0: the run is over)."""
-        backend, coll, pos, per, rank, timers = self.backend, self.coll, self.pos, self.per, self.rank, self.timers
+        backend, coll, pos, per, rank = self.backend, self.coll, self.pos, self.per, self.rank
         done = 0
         while done < max_iters and self.it < self.n_iter and not self.stopped:
             it, k = self.it, self.k
-            stages, n_slots = self._n_slots_of(it, k)
+            stages, n_slots = self._stages(it, k)
             fuse_now = self.pending is not None and n_slots == 1
-            if self.pending is not None and not fuse_now:
-                self._separate_check(self.pending[2], self.pending[0], self.pending[1])
-                self.pending = None
+            if not fuse_now:
+                self.flush()
             if self.symmetric and n_slots == 1:
                 cur = self.cur
-                if timers:
-                    backend.synchronize()
-                    t0 = time.perf_counter()
-                moves, total = backend.symm_sweep(pos[cur], it, k, fuse_now)
-                if timers:
-                    backend.synchronize()
-                    t1 = time.perf_counter()
-                coll.all_reduce_tensor(moves)
-                if fuse_now:
-                    coll.all_reduce_tensor(total)
-                    backend.controller_step(total, pos[self.pending[2]], self.pending[0], self.pending[1])
-                    self.pending = None
-                if timers:
-                    backend.synchronize()
-                    t2 = time.perf_counter()
-                backend.symm_apply(pos[cur], pos[cur ^ 1], moves, it)
-                if timers:
-                    backend.synchronize()
-                    self.t_stage += (t1 - t0) + (time.perf_counter() - t2)
-                    self.t_gather += t2 - t1
+                with self._timed("t_stage"):
+                    moves, total = backend.symm_sweep(pos[cur], it, k, fuse_now)
+                with self._timed("t_gather"):
+                    coll.all_reduce_tensor(moves)
+                    if fuse_now:
+                        self.flush(total)
+                with self._timed("t_stage"):
+                    backend.symm_apply(pos[cur], pos[cur ^ 1], moves, it)
                 self.cur ^= 1
                 n_slots = 0
             for slot in range(n_slots):
                 cur = self.cur
-                if timers:   # breakdown pass: host-synchronised, so slower than the timed pass
-                    backend.synchronize()
-                    t0 = time.perf_counter()
-                    backend.stage(pos[cur], pos[cur ^ 1], it, slot, stages, k)
-                    backend.synchronize()
-                    t1 = time.perf_counter()
+                # fuse_now: one sweep -- the stage, the MAE of the positions it reads (= the pending check), the gather
+                # of the new slices, the all-reduce of the two MAE scalars, the controller -- all enqueued
+                with self._timed("t_stage"):
+                    if fuse_now:
+                        total = backend.stage_fused(pos[cur], pos[cur ^ 1], it, k)
+                    else:
+                        backend.stage(pos[cur], pos[cur ^ 1], it, slot, stages, k)
+                with self._timed("t_gather"):
                     coll.all_gather_rows(pos[cur ^ 1], per, rank)
-                    backend.synchronize()
-                    self.t_stage += t1 - t0
-                    self.t_gather += time.perf_counter() - t1
-                elif fuse_now:
-                    # one sweep: the stage, the MAE of the positions it reads (= the pending check), the gather of the
-                    # new slices, the all-reduce of the two MAE scalars, the controller -- all enqueued
-                    total = backend.stage_fused(pos[cur], pos[cur ^ 1], it, k)
-                    coll.all_gather_rows(pos[cur ^ 1], per, rank)
-                    coll.all_reduce_tensor(total)
-                    backend.controller_step(total, pos[self.pending[2]], self.pending[0], self.pending[1])
-                    self.pending = None
-                else:
-                    backend.stage(pos[cur], pos[cur ^ 1], it, slot, stages, k)
-                    coll.all_gather_rows(pos[cur ^ 1], per, rank)
+                if fuse_now:
+                    self.flush(total)
                 self.cur ^= 1
             self.k = k = k * (1.0 - self.cooling_rate)
             self.it = it + 1
             done += 1
             if (it + 1) % self.freq == 0 or it == self.n_iter - 1:
-                t0 = time.perf_counter() if timers else 0.0
-                if self.fusable and it + 1 < self.n_iter and self._n_slots_of(it + 1, k)[1] == 1:
-                    self.pending = (it + 1, k, self.cur)
-                else:
-                    self._separate_check(self.cur, it + 1, k)
+                with self._timed("t_check"):
+                    if self.fusable and it + 1 < self.n_iter and self._stages(it + 1, k)[1] == 1:
+                        self.pending = (it + 1, k, self.cur)
+                    else:
+                        self._check(it + 1, k, self.cur)
                 self.checks += 1
-                if timers:
-                    backend.synchronize()
-                    self.t_check += time.perf_counter() - t0
                 if self.checks % max(1, self.sync_every) == 0 and backend.poll()[0]:
                     self.stopped = True
         return done
-
-    def flush(self):
-        """A check still waiting for a sweep to ride on runs as a separate pass (the caller wants the state)."""
-        if self.pending is not None:
-            self._separate_check(self.pending[2], self.pending[0], self.pending[1])
-            self.pending = None
 
     def finish(self) -> ShardedResult:
         backend = self.backend
