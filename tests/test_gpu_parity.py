@@ -614,17 +614,19 @@ def test_interrupt_callback_and_verbose(capfd):
         _native.optimize_layout_exact_arrays(*layout_call_args(call), seed=1, schedule="slab",
                                              interrupt=stop_after_two)
     assert ei.value.code == _native.ERR_INTERRUPTED and len(calls) == 2
-    got = _native.optimize_layout_exact_arrays(*layout_call_args(call), True, seed=1, schedule="slab")
-    out = capfd.readouterr().out
-    # the reference's lines (:183-188, :298-301, :334-336 / :351-353), from the device's check trace
-    assert "Points: 1200, Pairs per iteration: 719400" in out and "Parameters: k0=3, cooling=0.05, c_rep=0.02" in out
-    assert "Iter 30/400, MAE=" in out and ", k=" in out and got.iterations > 0
-    assert ("Converged (plateau) at iter %d, MAE=" % got.iterations in out or
-            "Converged (MAE worsening, best restored) at iter %d, MAE=" % got.iterations in out)
-    lines = []      # a caller-supplied sink (what the R shim maps to Rprintf) takes the lines instead of stdout
-    again = _native.optimize_layout_exact_arrays(*layout_call_args(call), True, seed=1, schedule="slab",
-                                                 **{"print": lines.append})
-    assert "".join(lines) == out and capfd.readouterr().out == "" and again.iterations == got.iterations
+    for schedule, path in (("slab", "row-owner slabs"), ("gs", "one-workgroup Gauss-Seidel")):
+        got = _native.optimize_layout_exact_arrays(*layout_call_args(call), True, seed=1, schedule=schedule)
+        out = capfd.readouterr().out
+        # the reference's lines (:183-188, :298-301, :334-336 / :351-353), from the device's check trace
+        assert "=== Exact Algorithm (O(N^2) Full Pairwise) on HIP: %s ===\n" % path in out
+        assert "Points: 1200, Pairs per iteration: 719400" in out and "Parameters: k0=3, cooling=0.05, c_rep=0.02" in out
+        assert "Iter 30/400, MAE=" in out and ", k=" in out and got.iterations > 0
+        assert ("Converged (plateau) at iter %d, MAE=" % got.iterations in out or
+                "Converged (MAE worsening, best restored) at iter %d, MAE=" % got.iterations in out)
+        lines = []      # a caller-supplied sink (what the R shim maps to Rprintf) takes the lines instead of stdout
+        again = _native.optimize_layout_exact_arrays(*layout_call_args(call), True, seed=1, schedule=schedule,
+                                                     **{"print": lines.append})
+        assert "".join(lines) == out and capfd.readouterr().out == "" and again.iterations == got.iterations
     # the one-workgroup kernel is a single launch: its abort word reaches it through pinned memory
     small, _ = _random_problem(300, 3, 0.5, seed=4, n_iter=100000, eps=1e-12, window=10 ** 6)
     polls = []

@@ -24,15 +24,15 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <numeric>
-#include <atomic>
 #include <chrono>
-#include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/topolow_relax.h"
 #include "relax_common.h"
+#include "relax_host.h"
 
 namespace topolow {
 
@@ -530,31 +530,6 @@ __global__ __launch_bounds__(1024) void gs_embed_kernel(const GsDev<real>* __res
 // ---------------------------------------------------------------------------------------
 // Host driver
 // ---------------------------------------------------------------------------------------
-struct GsProblem {
-  const double* initial_positions;  // n x dim col-major
-  const double* D;                  // n x n col-major, Inf = unmeasured
-  const int32_t* T;                 // n x n col-major
-  const int32_t* degrees;
-  const int32_t* edge_i; const int32_t* edge_j; const double* edge_dist; const int32_t* edge_thresh;
-  int64_t n_edges;
-  int n, dim, n_iter, window, check_freq;
-  double k0, cooling, c_rep, eps;
-  uint64_t seed;
-  // D == T == nullptr: the edge list DEFINES the matrix (every unlisted pair is unmeasured)
-  const int32_t* hold_i = nullptr; const int32_t* hold_j = nullptr; const double* hold_truth = nullptr;
-  int64_t n_hold = 0;
-};
-
-struct GsResult {
-  double* positions;  // n x dim col-major (caller-owned)
-  int converged, iterations, iters_run, n_checks;
-  int nonfinite_iter = 0;  // != 0: the non-finite guard fired at this iteration
-  int aborted = 0;
-  double final_mae, final_k;
-  double hold_sum = 0.0;
-  long long hold_count = 0;
-};
-
 inline size_t gs_lds_bytes(int n, int dim, size_t real_size, long long csr_edges = 0) {
   size_t off = ((size_t)n * dim * real_size + 15) & ~(size_t)15;
   off += ((size_t)(n + 1) * 4 + 15) & ~(size_t)15;
@@ -575,53 +550,27 @@ inline size_t gs_lds_bytes(int n, int dim, size_t real_size, long long csr_edges
 // LDS budget under which the sparse (LDS-resident) table is used; two workgroups per CU still fit.
 constexpr size_t kGsSparseLdsBudget = 78 * 1024;
 
-struct GsHipError { int code; std::string msg; };
-#define GS_TRY(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) throw GsHipError{TOPOLOW_ERR_HIP, std::string(#expr) + ": " +   \
-                                                                hipGetErrorString(e_)};   \
-  } while (0)
-
 template <int DIM, typename real>
 void gs_launch(const GsDev<real>* d_problems, int count, int threads, size_t lds, bool sparse,
                hipStream_t st) {
   auto go = [&](auto kern) {
     if (lds > 64 * 1024)
-      GS_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(count), dim3(threads), lds, st, d_problems);
-    GS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   };
   if (sparse) go(&gs_embed_kernel<DIM, real, true>);
   else go(&gs_embed_kernel<DIM, real, false>);
 }
 
-// The measured upper-triangle cells of the dense inputs are exactly the caller's edge list (same
-// pairs, targets and codes)?  True for everything the reference's R driver builds (R/core.R:383-402
-// and :429-436 derive both from one matrix); required before the edge list may stand in for the
-// matrix in the LDS-resident table.
-inline bool gs_edges_match_matrix(const GsProblem& p) {
-  const int n = p.n;
-  long long measured = 0;
-  for (int j = 1; j < n; ++j)
-    for (int i = 0; i < j; ++i)
-      if (std::isfinite(p.D[(size_t)i + (size_t)j * n])) ++measured;
-  if (measured != p.n_edges) return false;
-  for (long long e = 0; e < p.n_edges; ++e) {
-    const int a = p.edge_i[e], b = p.edge_j[e];
-    if (a < 0 || b <= a || b >= n) return false;
-    const size_t cell = (size_t)a + (size_t)b * n;
-    if (!(p.D[cell] == p.edge_dist[e])) return false;
-    const int tc = p.T[cell], ec = p.edge_thresh[e];
-    const int tn = tc == 0 ? 0 : (tc == 1 ? 1 : -1), en = ec == 0 ? 0 : (ec == 1 ? 1 : -1);
-    if (tn != en) return false;
-  }
-  return true;
+// Held-out pairs count only when all three holdout pointers are set.
+inline int64_t gs_holdouts(const topolow_problem& p) {
+  return p.holdout_i && p.holdout_j && p.holdout_truth ? p.n_holdout : 0;
 }
 
 // An edge list that may stand for the matrix: 0 <= i < j < n, finite targets, no pair twice.
-inline bool gs_edges_well_formed(const GsProblem& p) {
+inline bool gs_edges_well_formed(const topolow_problem& p) {
   const int n = p.n;
   std::vector<long long> key((size_t)p.n_edges);
   for (long long e = 0; e < p.n_edges; ++e) {
@@ -631,36 +580,6 @@ inline bool gs_edges_well_formed(const GsProblem& p) {
   }
   std::sort(key.begin(), key.end());
   return std::adjacent_find(key.begin(), key.end()) == key.end();
-}
-
-// Host-side loops over the problems of a batch are independent: spread them over a few threads (a
-// sweep stages thousands of small problems; sorting and packing them serially took as long as the
-// kernel).  `fn(b)` may throw GsHipError; the first one is rethrown on the caller's thread.
-template <typename Fn>
-void gs_parallel_for(int count, Fn fn) {
-  const unsigned hw = std::thread::hardware_concurrency();
-  const int workers = std::max(1, std::min({count / 16, (int)(hw ? hw : 1), 16}));
-  if (workers <= 1) {
-    for (int b = 0; b < count; ++b) fn(b);
-    return;
-  }
-  std::atomic<int> next{0};
-  std::atomic<bool> failed{false};
-  GsHipError first{TOPOLOW_OK, ""};
-  std::vector<std::thread> pool;
-  for (int w = 0; w < workers; ++w) {
-    pool.emplace_back([&] {
-      for (int b = next.fetch_add(1); b < count && !failed.load(); b = next.fetch_add(1)) {
-        try {
-          fn(b);
-        } catch (const GsHipError& e) {
-          if (!failed.exchange(true)) first = e;
-        }
-      }
-    });
-  }
-  for (auto& t : pool) t.join();
-  if (failed.load()) throw first;
 }
 
 // Host/device staging of a whole batch: every array of every problem lives in ONE host buffer that
@@ -678,10 +597,10 @@ class GsArena {
   template <typename T> T* host(size_t off) { return reinterpret_cast<T*>(host_.data() + off); }
   template <typename T> T* dev(size_t off) const { return reinterpret_cast<T*>(dev_ + off); }
   void upload() {
-    GS_TRY(hipMalloc((void**)&dev_, size_ ? size_ : 256));
-    GS_TRY(hipMemcpy(dev_, host_.data(), size_, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc((void**)&dev_, size_ ? size_ : 256));
+    HIP_TRY(hipMemcpy(dev_, host_.data(), size_, hipMemcpyHostToDevice));
   }
-  void download_front(size_t bytes) { GS_TRY(hipMemcpy(host_.data(), dev_, bytes, hipMemcpyDeviceToHost)); }
+  void download_front(size_t bytes) { HIP_TRY(hipMemcpy(host_.data(), dev_, bytes, hipMemcpyDeviceToHost)); }
   ~GsArena() { (void)hipFree(dev_); }
  private:
   size_t size_ = 0;
@@ -689,87 +608,109 @@ class GsArena {
   unsigned char* dev_ = nullptr;
 };
 
-// One grid of the exact-GS kernel (all problems share ndim and precision), in three steps so that
-// several grids can be staged, run side by side on their own streams, and collected afterwards.
-struct GsBatchBase {
-  virtual ~GsBatchBase() {}
-  // host mailbox shared by every problem of the grid (see GsDev::ctrl / trace); call before stage()
-  virtual void set_mailbox(int* ctrl_dev, double* trace_dev, int trace_cap) = 0;
-  virtual void stage(const GsProblem* pbs, int count) = 0;   // validate, pack, upload
-  virtual void launch(hipStream_t st) = 0;
-  virtual int collect(GsResult* res, char* errbuf, size_t errlen) = 0;   // after the stream is idle
+// Host mailbox of a one-launch GS grid: abort word + progress counter + check trace, in pinned memory.
+struct GsMailbox {
+  int* ctrl = nullptr;       // [0] abort, [1] iterations completed
+  double* trace = nullptr;   // 3 doubles per check
+  int* ctrl_dev = nullptr;
+  double* trace_dev = nullptr;
+  int trace_cap = 0;
+  void alloc(int cap) {
+    trace_cap = cap;
+    HIP_TRY(hipHostMalloc((void**)&ctrl, 64, hipHostMallocMapped));
+    std::memset(ctrl, 0, 64);
+    HIP_TRY(hipHostGetDevicePointer((void**)&ctrl_dev, ctrl, 0));
+    if (cap > 0) {
+      HIP_TRY(hipHostMalloc((void**)&trace, sizeof(double) * 3 * (size_t)cap, hipHostMallocMapped));
+      std::memset(trace, 0, sizeof(double) * 3 * (size_t)cap);
+      HIP_TRY(hipHostGetDevicePointer((void**)&trace_dev, trace, 0));
+    }
+  }
+  ~GsMailbox() {
+    if (ctrl) (void)hipHostFree(ctrl);
+    if (trace) (void)hipHostFree(trace);
+  }
 };
 
+// One grid of the exact-GS kernel: the problems idx[] of the caller's arrays, which share ndim.  stage()
+// validates, packs and uploads them, launch() runs them, collect() writes their results once the grid is done.
 template <typename real>
-class GsBatch : public GsBatchBase {
+class GsBatch {
   struct Off {
     size_t pos, gplus, tm = 0, cm = 0, ei = 0, ej = 0, et = 0, ec, roff = 0, ecol = 0, erow = 0, etgt = 0,
            hi = 0, hj = 0, ht = 0, best;
   };
-  const GsProblem* pbs = nullptr;
+  const topolow_problem* pbs = nullptr;
+  std::vector<int> idx;
   int count = 0, dim = 0, udim = 0, n_max = 0;   // dim: coordinates the kernel carries (11 -> 12, 13..15 -> 16, zero-padded)
   size_t lds_max = 0, o_out = 0, o_prob = 0;
   bool sparse = false;
   std::vector<Off> off;
   GsArena A;
   unsigned char* d_scratch = nullptr;   // best snapshots: device only
-  int* ctrl_dev = nullptr;
-  double* trace_dev = nullptr;
-  int trace_cap = 0;
 
  public:
-  ~GsBatch() override { (void)hipFree(d_scratch); }
-  void set_mailbox(int* c, double* t, int cap) override { ctrl_dev = c; trace_dev = t; trace_cap = cap; }
+  GsBatch() = default;
+  GsBatch(const GsBatch&) = delete;
+  GsBatch& operator=(const GsBatch&) = delete;
+  ~GsBatch() { (void)hipFree(d_scratch); }
 
-  void stage(const GsProblem* pbs_, int count_) override {
-    pbs = pbs_;
-    count = count_;
-    udim = pbs[0].dim;
+  // mb: host mailbox shared by every problem of the grid (see GsDev::ctrl / trace; the trace follows problem 0)
+  void stage(const topolow_problem* problems, std::vector<int> members, const GsMailbox& mb) {
+    pbs = problems;
+    idx = std::move(members);
+    count = (int)idx.size();
+    udim = pbs[idx[0]].ndim;
+    if (udim < 1 || udim > 16) throw HipError{TOPOLOW_ERR_UNSUPPORTED, "ndim must be between 1 and 16"};
     dim = udim <= 10 ? udim : (udim <= 12 ? 12 : 16);
-    lds_max = 0;
-    n_max = 0;
     // one kernel instance per launch: the LDS-resident table is used when EVERY problem of the
     // batch qualifies (edge list == matrix, or edge list given as the matrix; n <= 2048; table
     // within the LDS budget)
     sparse = getenv("TOPOLOW_GS_DENSE") == nullptr;
+    // the problems are independent: a few host threads check and pack them (a sweep stages thousands of
+    // small problems; serially, that took as long as the kernel)
     {
       std::vector<char> ok_sparse(count, 1);
       const bool want_sparse = sparse;
-      gs_parallel_for(count, [&](int b) {
-        const GsProblem& p = pbs[b];
-        if (p.dim != udim) throw GsHipError{TOPOLOW_ERR_BAD_ARGUMENT, "batch must share ndim"};
-        if (p.dim < 1 || p.dim > 16) throw GsHipError{TOPOLOW_ERR_UNSUPPORTED, "ndim must be between 1 and 16"};
-        if (p.n < 2) throw GsHipError{TOPOLOW_ERR_TOO_FEW_POINTS, "Need at least 2 points for embedding"};
-        if ((p.D == nullptr) != (p.T == nullptr))
-          throw GsHipError{TOPOLOW_ERR_BAD_ARGUMENT, "dissimilarity and threshold matrices come together"};
-        if (p.D == nullptr && !gs_edges_well_formed(p))
-          throw GsHipError{TOPOLOW_ERR_BAD_ARGUMENT,
+      host_parallel(count, 16, [&](size_t b0, size_t b1) {
+        for (size_t b = b0; b < b1; ++b) {
+          const topolow_problem& p = pbs[idx[b]];
+          const bool listed = p.dissimilarity_matrix == nullptr;
+          if (listed != (p.threshold_matrix == nullptr))
+            throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, "dissimilarity and threshold matrices come together"};
+          if (listed && !gs_edges_well_formed(p))
+            throw HipError{TOPOLOW_ERR_BAD_ARGUMENT,
                            "edge list that stands for the matrix needs 0 <= i < j < n, finite targets, no pair twice"};
-        for (long long e = 0; e < p.n_hold; ++e)
-          if (p.hold_i[e] < 0 || p.hold_i[e] >= p.n || p.hold_j[e] < 0 || p.hold_j[e] >= p.n)
-            throw GsHipError{TOPOLOW_ERR_BAD_ARGUMENT, "holdout pair out of range"};
-        if (want_sparse)
-          ok_sparse[b] = p.n <= 2048 && p.n_edges > 0 && p.n_edges < 65535 &&
-                         gs_lds_bytes(p.n, dim, sizeof(real), p.n_edges) <= kGsSparseLdsBudget &&
-                         (p.D == nullptr || gs_edges_match_matrix(p));
+          const int64_t nh = gs_holdouts(p);
+          for (long long e = 0; e < nh; ++e)
+            if (p.holdout_i[e] < 0 || p.holdout_i[e] >= p.n || p.holdout_j[e] < 0 || p.holdout_j[e] >= p.n)
+              throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, "holdout pair out of range"};
+          // (already on a worker of this loop: the edge-list test runs serially)
+          if (want_sparse)
+            ok_sparse[b] = p.n <= 2048 && p.n_edges > 0 && p.n_edges < 65535 &&
+                           gs_lds_bytes(p.n, dim, sizeof(real), p.n_edges) <= kGsSparseLdsBudget &&
+                           (listed || edges_are_the_matrix(p.dissimilarity_matrix, p.threshold_matrix, p.n, p.edge_i,
+                                                           p.edge_j, p.edge_dist, p.edge_thresh, p.n_edges, false));
+        }
       });
       for (int b = 0; b < count; ++b) sparse = sparse && ok_sparse[b];
     }
     // ---- layout ----
     off.assign(count, Off{});
     size_t best_total = 0;
-    for (int b = 0; b < count; ++b) off[b].pos = A.reserve((size_t)pbs[b].n * dim * sizeof(real));
+    for (int b = 0; b < count; ++b) off[b].pos = A.reserve((size_t)pbs[idx[b]].n * dim * sizeof(real));
     o_out = A.reserve(sizeof(GsOut) * count);
     o_prob = A.reserve(sizeof(GsDev<real>) * count);
     for (int b = 0; b < count; ++b) {
-      const GsProblem& p = pbs[b];
+      const topolow_problem& p = pbs[idx[b]];
       const size_t lds = gs_lds_bytes(p.n, dim, sizeof(real), sparse ? p.n_edges : 0);
       if (lds > 160 * 1024)
-        throw GsHipError{TOPOLOW_ERR_UNSUPPORTED,
-                         "problem too large for the single-workgroup GS kernel (LDS); use the slab schedule"};
+        throw HipError{TOPOLOW_ERR_UNSUPPORTED,
+                       "problem too large for the single-workgroup GS kernel (LDS); use the slab schedule"};
       lds_max = std::max(lds_max, lds);
       n_max = std::max(n_max, p.n);
       const size_t nn = (size_t)p.n * p.n, ne = (size_t)p.n_edges, ne1 = ne ? ne : 1;
+      const int64_t nh = gs_holdouts(p);
       Off& o = off[b];
       o.gplus = A.reserve(p.n * 8);
       o.ec = A.reserve(ne1);
@@ -785,83 +726,88 @@ class GsBatch : public GsBatchBase {
         o.ej = A.reserve(ne1 * 4);
         o.et = A.reserve(ne1 * 8);
       }
-      if (p.n_hold > 0) {
-        o.hi = A.reserve(p.n_hold * 4);
-        o.hj = A.reserve(p.n_hold * 4);
-        o.ht = A.reserve(p.n_hold * 8);
+      if (nh > 0) {
+        o.hi = A.reserve(nh * 4);
+        o.hj = A.reserve(nh * 4);
+        o.ht = A.reserve(nh * 8);
       }
       o.best = best_total;
       best_total += ((size_t)p.n * dim * sizeof(real) + 255) & ~(size_t)255;
     }
     A.commit();
     // ---- fill ----
-    gs_parallel_for(count, [&](int b) {
-      const GsProblem& p = pbs[b];
-      const Off& o = off[b];
-      const size_t nn = (size_t)p.n * p.n, ne = (size_t)p.n_edges;
-      real* pos = A.host<real>(o.pos);
-      double* g = A.host<double>(o.gplus);
-      for (int i = 0; i < p.n; ++i) {
-        g[i] = (double)p.degrees[i] + 1.0;   // reference :137-140
-        for (int d = 0; d < udim; ++d) pos[(size_t)i * dim + d] = (real)p.initial_positions[i + (size_t)d * p.n];
-      }
-      auto code_of = [](int c) { return (int8_t)(c == 0 ? 0 : (c == 1 ? 1 : -1)); };  // else-branch = "<"
-      // edge codes keep "neither 0, 1 nor -1" apart: such a pair moves like "<" (:236-242) but never
-      // counts in the error (:68-76 compares with -1 exactly)
-      auto edge_code = [](int c) { return (int8_t)(c == 0 ? 0 : (c == 1 ? 1 : (c == -1 ? -1 : 2))); };
-      int8_t* ec = A.host<int8_t>(o.ec);
-      if (sparse) {
-        // CSR over rows (entries sorted by row, then column); the caller's list is column-major
-        std::vector<long long> order(ne);
-        std::iota(order.begin(), order.end(), 0ll);
-        std::sort(order.begin(), order.end(), [&](long long x, long long y) {
-          return p.edge_i[x] != p.edge_i[y] ? p.edge_i[x] < p.edge_i[y] : p.edge_j[x] < p.edge_j[y];
-        });
-        int* roff = A.host<int>(o.roff);
-        unsigned short* col = A.host<unsigned short>(o.ecol);
-        unsigned short* row = A.host<unsigned short>(o.erow);
-        real* tgt = A.host<real>(o.etgt);
-        for (size_t q = 0; q < ne; ++q) {
-          const long long e = order[q];
-          row[q] = (unsigned short)p.edge_i[e];
-          col[q] = (unsigned short)p.edge_j[e];
-          tgt[q] = (real)p.edge_dist[e];
-          ec[q] = edge_code(p.edge_thresh[e]);
-          roff[p.edge_i[e] + 1] += 1;
+    host_parallel(count, 16, [&](size_t b0, size_t b1) {
+      for (size_t b = b0; b < b1; ++b) {
+        const topolow_problem& p = pbs[idx[b]];
+        const Off& o = off[b];
+        const size_t nn = (size_t)p.n * p.n, ne = (size_t)p.n_edges;
+        const int64_t nh = gs_holdouts(p);
+        real* pos = A.host<real>(o.pos);
+        double* g = A.host<double>(o.gplus);
+        for (int i = 0; i < p.n; ++i) {
+          g[i] = (double)p.degrees[i] + 1.0;   // reference :137-140
+          for (int d = 0; d < udim; ++d) pos[(size_t)i * dim + d] = (real)p.initial_positions[i + (size_t)d * p.n];
         }
-        for (int i = 0; i < p.n; ++i) roff[i + 1] += roff[i];
-      } else {
-        real* tm = A.host<real>(o.tm);
-        int8_t* cm = A.host<int8_t>(o.cm);
-        if (p.D != nullptr) {
-          for (size_t q = 0; q < nn; ++q) { tm[q] = (real)p.D[q]; cm[q] = code_of(p.T[q]); }
-        } else {   // the edge list is the matrix: unlisted pairs are unmeasured, the diagonal is 0
-          for (size_t q = 0; q < nn; ++q) tm[q] = (real)INFINITY;
-          for (int i = 0; i < p.n; ++i) tm[(size_t)i * p.n + i] = 0;
-          for (size_t e = 0; e < ne; ++e) {
-            const size_t up = (size_t)p.edge_i[e] + (size_t)p.edge_j[e] * p.n;
-            const size_t lo = (size_t)p.edge_j[e] + (size_t)p.edge_i[e] * p.n;
-            tm[up] = tm[lo] = (real)p.edge_dist[e];
-            cm[up] = cm[lo] = code_of(p.edge_thresh[e]);
+        auto code_of = [](int c) { return (int8_t)(c == 0 ? 0 : (c == 1 ? 1 : -1)); };  // else-branch = "<"
+        // edge codes keep "neither 0, 1 nor -1" apart: such a pair moves like "<" (:236-242) but never
+        // counts in the error (:68-76 compares with -1 exactly)
+        auto edge_code = [](int c) { return (int8_t)(c == 0 ? 0 : (c == 1 ? 1 : (c == -1 ? -1 : 2))); };
+        int8_t* ec = A.host<int8_t>(o.ec);
+        if (sparse) {
+          // CSR over rows (entries sorted by row, then column); the caller's list is column-major
+          std::vector<long long> order(ne);
+          std::iota(order.begin(), order.end(), 0ll);
+          std::sort(order.begin(), order.end(), [&](long long x, long long y) {
+            return p.edge_i[x] != p.edge_i[y] ? p.edge_i[x] < p.edge_i[y] : p.edge_j[x] < p.edge_j[y];
+          });
+          int* roff = A.host<int>(o.roff);
+          unsigned short* col = A.host<unsigned short>(o.ecol);
+          unsigned short* row = A.host<unsigned short>(o.erow);
+          real* tgt = A.host<real>(o.etgt);
+          for (size_t q = 0; q < ne; ++q) {
+            const long long e = order[q];
+            row[q] = (unsigned short)p.edge_i[e];
+            col[q] = (unsigned short)p.edge_j[e];
+            tgt[q] = (real)p.edge_dist[e];
+            ec[q] = edge_code(p.edge_thresh[e]);
+            roff[p.edge_i[e] + 1] += 1;
           }
+          for (int i = 0; i < p.n; ++i) roff[i + 1] += roff[i];
+        } else {
+          real* tm = A.host<real>(o.tm);
+          int8_t* cm = A.host<int8_t>(o.cm);
+          if (p.dissimilarity_matrix != nullptr) {
+            const double* D = p.dissimilarity_matrix;
+            const int32_t* T = p.threshold_matrix;
+            for (size_t q = 0; q < nn; ++q) { tm[q] = (real)D[q]; cm[q] = code_of(T[q]); }
+          } else {   // the edge list is the matrix: unlisted pairs are unmeasured, the diagonal is 0
+            for (size_t q = 0; q < nn; ++q) tm[q] = (real)INFINITY;
+            for (int i = 0; i < p.n; ++i) tm[(size_t)i * p.n + i] = 0;
+            for (size_t e = 0; e < ne; ++e) {
+              const size_t up = (size_t)p.edge_i[e] + (size_t)p.edge_j[e] * p.n;
+              const size_t lo = (size_t)p.edge_j[e] + (size_t)p.edge_i[e] * p.n;
+              tm[up] = tm[lo] = (real)p.edge_dist[e];
+              cm[up] = cm[lo] = code_of(p.edge_thresh[e]);
+            }
+          }
+          std::memcpy(A.host<int>(o.ei), p.edge_i, ne * 4);
+          std::memcpy(A.host<int>(o.ej), p.edge_j, ne * 4);
+          std::memcpy(A.host<double>(o.et), p.edge_dist, ne * 8);
+          for (size_t e = 0; e < ne; ++e) ec[e] = edge_code(p.edge_thresh[e]);
         }
-        std::memcpy(A.host<int>(o.ei), p.edge_i, ne * 4);
-        std::memcpy(A.host<int>(o.ej), p.edge_j, ne * 4);
-        std::memcpy(A.host<double>(o.et), p.edge_dist, ne * 8);
-        for (size_t e = 0; e < ne; ++e) ec[e] = edge_code(p.edge_thresh[e]);
-      }
-      if (p.n_hold > 0) {
-        std::memcpy(A.host<int>(o.hi), p.hold_i, (size_t)p.n_hold * 4);
-        std::memcpy(A.host<int>(o.hj), p.hold_j, (size_t)p.n_hold * 4);
-        std::memcpy(A.host<double>(o.ht), p.hold_truth, (size_t)p.n_hold * 8);
+        if (nh > 0) {
+          std::memcpy(A.host<int>(o.hi), p.holdout_i, (size_t)nh * 4);
+          std::memcpy(A.host<int>(o.hj), p.holdout_j, (size_t)nh * 4);
+          std::memcpy(A.host<double>(o.ht), p.holdout_truth, (size_t)nh * 8);
+        }
       }
     });
-    GS_TRY(hipMalloc((void**)&d_scratch, best_total ? best_total : 256));
+    HIP_TRY(hipMalloc((void**)&d_scratch, best_total ? best_total : 256));
     A.upload();   // device addresses exist from here on; the problem table follows with its own copy
     {
       std::vector<GsDev<real>> h(count);
       for (int b = 0; b < count; ++b) {
-        const GsProblem& p = pbs[b];
+        const topolow_problem& p = pbs[idx[b]];
         const Off& o = off[b];
         GsDev<real>& k = h[b];
         std::memset(&k, 0, sizeof k);
@@ -874,23 +820,23 @@ class GsBatch : public GsBatchBase {
           k.tm = A.dev<real>(o.tm); k.cm = A.dev<int8_t>(o.cm);
           k.ei = A.dev<int>(o.ei); k.ej = A.dev<int>(o.ej); k.et = A.dev<double>(o.et);
         }
-        if (p.n_hold > 0) { k.hi = A.dev<int>(o.hi); k.hj = A.dev<int>(o.hj); k.ht = A.dev<double>(o.ht); }
-        k.n_hold = p.n_hold;
+        k.n_hold = gs_holdouts(p);
+        if (k.n_hold > 0) { k.hi = A.dev<int>(o.hi); k.hj = A.dev<int>(o.hj); k.ht = A.dev<double>(o.ht); }
         k.pos = A.dev<real>(o.pos);
         k.best = reinterpret_cast<real*>(d_scratch + o.best);
         k.out = A.dev<GsOut>(o_out) + b;
         k.n_edges = p.n_edges;
-        k.k0 = p.k0; k.cooling = p.cooling; k.c_rep = p.c_rep; k.eps = p.eps; k.seed = p.seed;
-        k.n = p.n; k.n_iter = p.n_iter; k.check_freq = p.check_freq; k.window = p.window;
-        k.ctrl = ctrl_dev;
-        k.trace = b == 0 ? trace_dev : nullptr;   // the trace follows the grid's first problem
-        k.trace_cap = trace_cap;
+        k.k0 = p.k0; k.cooling = p.cooling_rate; k.c_rep = p.c_repulsion; k.eps = p.relative_epsilon; k.seed = p.seed;
+        k.n = p.n; k.n_iter = p.n_iter; k.check_freq = p.convergence_check_freq; k.window = p.convergence_window;
+        k.ctrl = mb.ctrl_dev;
+        k.trace = b == 0 ? mb.trace_dev : nullptr;
+        k.trace_cap = mb.trace_cap;
       }
-      GS_TRY(hipMemcpy(A.dev<GsDev<real>>(o_prob), h.data(), sizeof(GsDev<real>) * count, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(A.dev<GsDev<real>>(o_prob), h.data(), sizeof(GsDev<real>) * count, hipMemcpyHostToDevice));
     }
   }
 
-  void launch(hipStream_t st) override {
+  void launch(hipStream_t st) {
     const GsDev<real>* d_problems = A.dev<GsDev<real>>(o_prob);
     int threads = (((n_max + 1) / 2) + 63) & ~63;
     threads = std::max(128, std::min(1024, threads));
@@ -899,93 +845,86 @@ class GsBatch : public GsBatchBase {
       GS_CASE(1) GS_CASE(2) GS_CASE(3) GS_CASE(4) GS_CASE(5) GS_CASE(6) GS_CASE(7) GS_CASE(8)
       GS_CASE(9) GS_CASE(10) GS_CASE(12) GS_CASE(16)
 #undef GS_CASE
-      default: throw GsHipError{TOPOLOW_ERR_UNSUPPORTED, "ndim must be between 1 and 16"};
+      default: throw HipError{TOPOLOW_ERR_UNSUPPORTED, "ndim must be between 1 and 16"};
     }
   }
 
-  int collect(GsResult* res, char* errbuf, size_t errlen) override {
-    int rc = TOPOLOW_OK;
+  // error_code: TOPOLOW_ERR_NONFINITE (the guard fired at error_iteration) or TOPOLOW_ERR_INTERRUPTED (the
+  // mailbox's abort word stopped the run)
+  void collect(topolow_result* results) {
     A.download_front(o_out + sizeof(GsOut) * count);   // positions and results
     const GsOut* outs = A.host<GsOut>(o_out);
     for (int b = 0; b < count; ++b) {
-      const GsProblem& p = pbs[b];
+      const topolow_problem& p = pbs[idx[b]];
       const GsOut& o = outs[b];
-      if (o.nonfinite_iter != 0 && rc == TOPOLOW_OK) {
-        if (errbuf && errlen)
-          snprintf(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.",
-                   o.nonfinite_iter);
-        rc = TOPOLOW_ERR_NONFINITE;
-      }
+      topolow_result& r = results[idx[b]];
       const real* pos = A.host<real>(off[b].pos);
       for (int i = 0; i < p.n; ++i)
-        for (int d = 0; d < udim; ++d) res[b].positions[i + (size_t)d * p.n] = (double)pos[(size_t)i * dim + d];
-      res[b].converged = o.converged; res[b].iterations = o.iterations; res[b].iters_run = o.iters_run;
-      res[b].n_checks = o.n_checks; res[b].final_mae = o.final_mae; res[b].final_k = o.final_k;
-      res[b].nonfinite_iter = o.nonfinite_iter;
-      res[b].aborted = o.aborted;
-      res[b].hold_sum = o.hold_sum; res[b].hold_count = (long long)o.hold_cnt;
+        for (int d = 0; d < udim; ++d) r.positions_out[i + (size_t)d * p.n] = (double)pos[(size_t)i * dim + d];
+      r.converged = o.converged; r.iterations = o.iterations; r.iterations_run = o.iters_run;
+      r.n_checks = o.n_checks; r.final_mae = o.final_mae; r.final_k = o.final_k;
+      r.error_code = o.nonfinite_iter ? TOPOLOW_ERR_NONFINITE : (o.aborted ? TOPOLOW_ERR_INTERRUPTED : TOPOLOW_OK);
+      r.error_iteration = o.nonfinite_iter;
+      r.holdout_sum_abs = o.hold_sum; r.holdout_count = (int64_t)o.hold_cnt;
     }
-    return rc;
   }
 };
 
-inline GsBatchBase* gs_new_batch(int precision) {
-  if (precision == TOPOLOW_PRECISION_F32) return new GsBatch<float>();
-  return new GsBatch<double>();
-}
-
-// Host mailbox of a one-launch GS grid: abort word + progress counter + check trace, in pinned memory.
-struct GsMailbox {
-  int* ctrl = nullptr;       // [0] abort, [1] iterations completed
-  double* trace = nullptr;   // 3 doubles per check
-  int* ctrl_dev = nullptr;
-  double* trace_dev = nullptr;
-  int trace_cap = 0;
-  void alloc(int cap) {
-    trace_cap = cap;
-    GS_TRY(hipHostMalloc((void**)&ctrl, 64, hipHostMallocMapped));
-    std::memset(ctrl, 0, 64);
-    GS_TRY(hipHostGetDevicePointer((void**)&ctrl_dev, ctrl, 0));
-    if (cap > 0) {
-      GS_TRY(hipHostMalloc((void**)&trace, sizeof(double) * 3 * (size_t)cap, hipHostMallocMapped));
-      std::memset(trace, 0, sizeof(double) * 3 * (size_t)cap);
-      GS_TRY(hipHostGetDevicePointer((void**)&trace_dev, trace, 0));
-    }
+// Relaxes problems[0, count) into results[0, count): one grid per distinct ndim.  The grids are independent
+// and run SIDE BY SIDE on their own streams (a sweep over ndim 2..10 would otherwise run nine under-filled
+// grids back to back, each with its own tail of slow embeddings); a grid is launched as soon as it is staged,
+// the costliest (largest ndim) first, so the host's staging of the next grid hides behind the device's work
+// on the previous ones.  device_seconds: first launch -> last completion (the later grids' staging runs
+// inside this span).  A one-problem call may also take
+//   interrupt_cb: polled while the grid runs, once per 50 iterations of progress (reference :364) and at
+//   least every 50 ms; a non-zero return raises the kernel's abort word;
+//   trace_out: (iteration, MAE, k) of every check, 3 doubles each;
+// either one puts the host mailbox in place.  Throws HipError.
+template <typename real>
+void gs_relax(const topolow_problem* problems, topolow_result* results, int count, double* device_seconds,
+              int32_t (*interrupt_cb)(void*) = nullptr, void* interrupt_user = nullptr,
+              std::vector<double>* trace_out = nullptr) {
+  std::vector<int> dims;
+  for (int b = 0; b < count; ++b)
+    if (std::find(dims.begin(), dims.end(), problems[b].ndim) == dims.end()) dims.push_back(problems[b].ndim);
+  std::sort(dims.begin(), dims.end(), std::greater<int>());
+  GsMailbox mb;   // declared ahead of the grids: freed after every grid's stream has been synchronised
+  if (interrupt_cb != nullptr || trace_out != nullptr) {
+    const int freq = problems[0].convergence_check_freq < 1 ? 10 : problems[0].convergence_check_freq;
+    mb.alloc(trace_out != nullptr ? problems[0].n_iter / freq + 2 : 0);
   }
-  ~GsMailbox() {
-    if (ctrl) (void)hipHostFree(ctrl);
-    if (trace) (void)hipHostFree(trace);
-  }
-};
-
-// One grid, start to finish (the single-embedding path of topolow_optimize_layout_exact).
-//   interrupt_cb: polled while the launch runs, once per 50 iterations of progress (reference :364)
-//   and at least every 50 ms; a non-zero return raises the kernel's abort word.
-//   trace_out (3 doubles per check: iteration, MAE, k) / n_trace: the first problem's checks.
-inline int gs_run_batch(const GsProblem* pbs, GsResult* res, int count, int precision,
-                        double* device_seconds, char* errbuf, size_t errlen,
-                        int32_t (*interrupt_cb)(void*) = nullptr, void* interrupt_user = nullptr,
-                        std::vector<double>* trace_out = nullptr) {
-  int rc = TOPOLOW_OK;
-  GsBatchBase* batch = gs_new_batch(precision);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  GsMailbox mb;   // outlives the launch on every path (the kernel reads and writes it)
-  try {
-    if (interrupt_cb != nullptr || trace_out != nullptr) {
-      const int freq = pbs[0].check_freq < 1 ? 10 : pbs[0].check_freq;
-      mb.alloc(trace_out != nullptr ? pbs[0].n_iter / freq + 2 : 0);
-      batch->set_mailbox(mb.ctrl_dev, mb.trace_dev, mb.trace_cap);
+  struct Grid {
+    GsBatch<real> batch;   // its arena and best snapshots are freed after the body below has synchronised
+    hipStream_t stream = nullptr;
+    hipEvent_t start = nullptr, done = nullptr;
+    ~Grid() {
+      if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+      if (start) (void)hipEventDestroy(start);
+      if (done) (void)hipEventDestroy(done);
     }
-    batch->stage(pbs, count);
-    GS_TRY(hipEventCreate(&e0));
-    GS_TRY(hipEventCreate(&e1));
-    GS_TRY(hipEventRecord(e0, 0));
-    batch->launch(0);
-    GS_TRY(hipEventRecord(e1, 0));
+  };
+  std::vector<Grid> grids(dims.size());
+  for (size_t q = 0; q < dims.size(); ++q) {
+    Grid& g = grids[q];
+    std::vector<int> idx;
+    for (int b = 0; b < count; ++b)
+      if (problems[b].ndim == dims[q]) idx.push_back(b);
+    g.batch.stage(problems, std::move(idx), mb);
+    HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&g.done));
+    if (q == 0) {
+      HIP_TRY(hipEventCreate(&g.start));
+      HIP_TRY(hipEventRecord(g.start, g.stream));
+    }
+    g.batch.launch(g.stream);
+    HIP_TRY(hipEventRecord(g.done, g.stream));
+  }
+  double secs = 0.0;
+  for (Grid& g : grids) {
     if (interrupt_cb != nullptr) {
       int polled_at = 0;
       auto last_poll = std::chrono::steady_clock::now();
-      while (hipEventQuery(e1) == hipErrorNotReady) {
+      while (hipEventQuery(g.done) == hipErrorNotReady) {
         std::this_thread::sleep_for(std::chrono::microseconds(200));
         const int progress = __atomic_load_n(mb.ctrl + 1, __ATOMIC_RELAXED);
         const auto now = std::chrono::steady_clock::now();
@@ -996,29 +935,17 @@ inline int gs_run_batch(const GsProblem* pbs, GsResult* res, int count, int prec
         }
       }
     }
-    GS_TRY(hipEventSynchronize(e1));
+    HIP_TRY(hipEventSynchronize(g.done));
     float ms = 0.f;
-    GS_TRY(hipEventElapsedTime(&ms, e0, e1));
-    if (device_seconds) *device_seconds = ms * 1e-3;
-    rc = batch->collect(res, errbuf, errlen);
-    if (trace_out != nullptr) {
-      const int nc = std::min(res[0].n_checks, mb.trace_cap);
-      trace_out->assign(mb.trace, mb.trace + 3 * (size_t)nc);
-    }
-    for (int b = 0; b < count && rc == TOPOLOW_OK; ++b)
-      if (res[b].aborted) {
-        if (errbuf && errlen) snprintf(errbuf, errlen, "interrupted by the caller");
-        rc = TOPOLOW_ERR_INTERRUPTED;
-      }
-  } catch (const GsHipError& e) {
-    if (errbuf && errlen) snprintf(errbuf, errlen, "%s", e.msg.c_str());
-    rc = e.code;
-    (void)hipStreamSynchronize(0);
+    HIP_TRY(hipEventElapsedTime(&ms, grids[0].start, g.done));
+    secs = std::max(secs, (double)ms * 1e-3);
+    g.batch.collect(results);   // null-stream copies: only now that the grid's non-blocking stream is done
   }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) { (void)hipEventSynchronize(e1); (void)hipEventDestroy(e1); }
-  delete batch;
-  return rc;
+  if (device_seconds) *device_seconds = secs;
+  if (trace_out != nullptr) {
+    const int nc = std::min(results[0].n_checks, mb.trace_cap);
+    trace_out->assign(mb.trace, mb.trace + 3 * (size_t)nc);
+  }
 }
 
 }  // namespace topolow

@@ -26,6 +26,7 @@
 
 #include "../../include/topolow_relax.h"
 #include "relax_common.h"
+#include "relax_host.h"
 #include "relax_kernels.h"
 #include "relax_fold.h"
 #include "relax_gs.h"
@@ -44,19 +45,6 @@ constexpr int kMaxTunedDim = 16;
 // receives 0 of every move)
 constexpr int kernel_dim(int ndim) { return ndim <= 10 ? ndim : (ndim <= 12 ? 12 : (ndim <= 16 ? 16 : (ndim <= 32 ? 32 : 64))); }
 constexpr int kDefaultGsMaxN = 1024;
-
-struct HipError {
-  int code;
-  std::string msg;
-};
-
-void set_err(char* errbuf, size_t errlen, const char* fmt, ...) {
-  if (!errbuf || errlen == 0) return;
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(errbuf, errlen, fmt, ap);
-  va_end(ap);
-}
 
 // verbose lines go to the caller's sink (topolow_options.print_cb) or stdout
 void emit(const topolow_options& opt, const char* fmt, ...) {
@@ -91,17 +79,6 @@ void emit_converged(const topolow_options& opt, bool plateau, int best_iter, dou
   if (plateau) emit(opt, "Converged (plateau) at iter %d, MAE=%g\n", best_iter, best_mae);
   else emit(opt, "Converged (MAE worsening, best restored) at iter %d, MAE=%g\n", best_iter, best_mae);
 }
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      throw HipError{e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice              \
-                         ? TOPOLOW_ERR_NO_DEVICE                                        \
-                         : TOPOLOW_ERR_HIP,                                             \
-                     std::string(#expr) + ": " + hipGetErrorString(e_)};                \
-    }                                                                                   \
-  } while (0)
 
 int select_device(int device) {
   int count = 0;
@@ -140,53 +117,6 @@ struct DevBuf {
 double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch())
       .count();
-}
-
-// Splits [0, n) over a few host threads (the one-shot call's host passes over 10^7..10^8 edges);
-// small ranges run on the calling thread.  fn(begin, end) must be thread-safe.
-template <typename Fn>
-void host_parallel(size_t n, Fn fn) {
-  const unsigned hw = std::thread::hardware_concurrency();
-  const size_t workers = std::max<size_t>(1, std::min<size_t>({n / (1u << 18), (size_t)(hw ? hw : 1), (size_t)16}));
-  if (workers <= 1) { fn((size_t)0, n); return; }
-  std::vector<std::thread> pool;
-  const size_t step = (n + workers - 1) / workers;
-  for (size_t w = 0; w < workers; ++w) {
-    const size_t lo = w * step, hi = std::min(n, lo + step);
-    if (lo >= hi) break;
-    pool.emplace_back([=, &fn] { fn(lo, hi); });
-  }
-  for (auto& t : pool) t.join();
-}
-
-// Is the edge list exactly the measured strict-upper-triangle of the dense inputs (same pairs, same
-// targets, same threshold codes)?  Host only, a few threads: one streaming pass over the upper
-// triangle to count its finite cells, one gather per edge.  (A pair listed twice is not detected here;
-// the caller cross-checks the count on the device.)
-bool edges_are_the_matrix(const double* D, const int32_t* T, int n, const int32_t* ei, const int32_t* ej,
-                          const double* ed, const int32_t* et, int64_t n_edges) {
-  std::atomic<long long> finite{0};
-  host_parallel((size_t)n, [&](size_t lo, size_t hi) {   // columns; work grows with j, close enough
-    long long c = 0;
-    for (size_t j = lo; j < hi; ++j) {
-      const double* col = D + j * (size_t)n;
-      for (size_t i = 0; i < j; ++i) c += std::isfinite(col[i]) ? 1 : 0;
-    }
-    finite.fetch_add(c);
-  });
-  if (finite.load() != (long long)n_edges) return false;
-  std::atomic<bool> ok{true};
-  host_parallel((size_t)n_edges, [&](size_t lo, size_t hi) {
-    for (size_t e = lo; e < hi; ++e) {
-      const int a = ei[e], b = ej[e];
-      if (a < 0 || b <= a || b >= n) { ok.store(false); return; }
-      const size_t cell = (size_t)a + (size_t)b * n;
-      const int tc = T[cell], ec = et[e];
-      const int tn = tc == 0 ? 0 : (tc == 1 ? 1 : -1), en = ec == 0 ? 0 : (ec == 1 ? 1 : -1);
-      if (!(D[cell] == ed[e]) || !std::isfinite(ed[e]) || tn != en) { ok.store(false); return; }
-    }
-  });
-  return ok.load();
 }
 
 }  // namespace
@@ -1258,20 +1188,6 @@ int nonfinite_report(int first_nonfinite, int ran, bool stopped) {
   return t <= ran && !(stopped && t == ran) ? t : 0;
 }
 
-template <typename F>
-int guarded(char* errbuf, size_t errlen, F&& body) {
-  try {
-    body();
-    return TOPOLOW_OK;
-  } catch (const HipError& e) {
-    set_err(errbuf, errlen, "%s", e.msg.c_str());
-    return e.code;
-  } catch (const std::bad_alloc&) {
-    set_err(errbuf, errlen, "out of host memory");
-    return TOPOLOW_ERR_HIP;
-  }
-}
-
 #include "relax_sharded_engine.h"
 
 }  // namespace
@@ -1565,7 +1481,7 @@ int topolow_session_set_edges(topolow_session* s, const int32_t* edge_i, const i
     if (s->gplus.p && !(force && atoi(force) != 0)) {
       std::atomic<bool> owned{true};
       std::atomic<unsigned long long> fp_total{0};
-      host_parallel(m, [&](size_t lo_e, size_t hi_e) {
+      host_parallel(m, kEdgeGrain, [&](size_t lo_e, size_t hi_e) {
         unsigned long long fp = 0;
         for (size_t e = lo_e; e < hi_e; ++e) {
           int a = edge_i[e], b = edge_j[e];
@@ -1608,7 +1524,7 @@ int topolow_session_set_edges(topolow_session* s, const int32_t* edge_i, const i
     std::vector<int8_t> codes(m);
     std::vector<int> li, lj;
     if (inv) { li.resize(m); lj.resize(m); }
-    host_parallel(m, [&](size_t lo_e, size_t hi_e) {
+    host_parallel(m, kEdgeGrain, [&](size_t lo_e, size_t hi_e) {
       for (size_t e = lo_e; e < hi_e; ++e) {
         const int c = edge_thresh[e];
         codes[e] = (int8_t)(c == 0 ? 0 : (c == 1 ? 1 : (c == -1 ? -1 : 2)));  // others never count
@@ -1629,7 +1545,7 @@ int topolow_session_set_edges(topolow_session* s, const int32_t* edge_i, const i
       if (m) HIP_TRY(hipMemcpy(s->et.p, edge_dist, m * 8, hipMemcpyHostToDevice));
     } else {
       std::vector<float> t(m);
-      host_parallel(m, [&](size_t lo_e, size_t hi_e) {
+      host_parallel(m, kEdgeGrain, [&](size_t lo_e, size_t hi_e) {
         for (size_t e = lo_e; e < hi_e; ++e) t[e] = (float)edge_dist[e];
       });
       s->et.alloc(m * 4);
@@ -2152,103 +2068,13 @@ int topolow_optimize_layout_exact_batch(const topolow_problem* problems, topolow
   if (count < 0 || (count > 0 && (!problems || !results))) return TOPOLOW_ERR_BAD_ARGUMENT;
   if (device_seconds) *device_seconds = 0.0;
   if (count == 0) return TOPOLOW_OK;
-  const int prec = precision == TOPOLOW_PRECISION_F32 ? TOPOLOW_PRECISION_F32 : TOPOLOW_PRECISION_F64;
-  int rc_all = TOPOLOW_OK;
-  const int rc = guarded(errbuf, errlen, [&] {
+  return guarded(errbuf, errlen, [&] {
     select_device(device);
-    // The kernel is instantiated per ndim: one grid per distinct ndim.  The grids are independent and run
-    // SIDE BY SIDE on their own streams (a sweep over ndim 2..10 would otherwise run nine under-filled grids
-    // back to back, each with its own tail of slow embeddings); a grid is launched as soon as it is staged,
-    // the costliest (largest ndim) first, so the host's staging of the next grid hides behind the device's
-    // work on the previous ones.
-    std::vector<int> dims;
-    for (int b = 0; b < count; ++b) {
+    for (int b = 0; b < count; ++b)
       if (problems[b].n < 2) throw HipError{TOPOLOW_ERR_TOO_FEW_POINTS, "Need at least 2 points for embedding"};
-      if (std::find(dims.begin(), dims.end(), problems[b].ndim) == dims.end()) dims.push_back(problems[b].ndim);
-    }
-    std::sort(dims.begin(), dims.end(), std::greater<int>());
-    struct Grid {
-      std::vector<GsProblem> pbs;
-      std::vector<GsResult> res;
-      std::vector<int> idx;
-      std::unique_ptr<GsBatchBase> batch;
-      hipStream_t stream = nullptr;
-      hipEvent_t done = nullptr;
-    };
-    std::vector<Grid> grids(dims.size());
-    hipEvent_t start = nullptr;
-    auto release = [&] {
-      for (Grid& g : grids) {
-        if (g.stream) { (void)hipStreamSynchronize(g.stream); (void)hipStreamDestroy(g.stream); }
-        if (g.done) (void)hipEventDestroy(g.done);
-        g.batch.reset();
-      }
-      if (start) (void)hipEventDestroy(start);
-    };
-    try {
-      for (size_t q = 0; q < dims.size(); ++q) {
-        Grid& g = grids[q];
-        for (int b = 0; b < count; ++b) {
-          const topolow_problem& p = problems[b];
-          if (p.ndim != dims[q]) continue;
-          GsProblem pb;
-          pb.initial_positions = p.initial_positions; pb.D = p.dissimilarity_matrix; pb.T = p.threshold_matrix;
-          pb.degrees = p.degrees; pb.edge_i = p.edge_i; pb.edge_j = p.edge_j; pb.edge_dist = p.edge_dist;
-          pb.edge_thresh = p.edge_thresh; pb.n_edges = p.n_edges; pb.n = p.n; pb.dim = p.ndim;
-          pb.n_iter = p.n_iter; pb.window = p.convergence_window; pb.check_freq = p.convergence_check_freq;
-          pb.k0 = p.k0; pb.cooling = p.cooling_rate; pb.c_rep = p.c_repulsion; pb.eps = p.relative_epsilon;
-          pb.seed = p.seed;
-          pb.hold_i = p.holdout_i; pb.hold_j = p.holdout_j; pb.hold_truth = p.holdout_truth;
-          pb.n_hold = (p.holdout_i && p.holdout_j && p.holdout_truth) ? p.n_holdout : 0;
-          GsResult r;
-          r.positions = results[b].positions_out;
-          g.pbs.push_back(pb); g.res.push_back(r); g.idx.push_back(b);
-        }
-        g.batch.reset(gs_new_batch(prec));
-        g.batch->stage(g.pbs.data(), (int)g.pbs.size());
-        HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreate(&g.done));
-        if (q == 0) {
-          HIP_TRY(hipEventCreate(&start));
-          HIP_TRY(hipEventRecord(start, g.stream));
-        }
-        g.batch->launch(g.stream);
-        HIP_TRY(hipEventRecord(g.done, g.stream));
-      }
-      double secs = 0.0;   // first launch -> last completion (the later grids' staging runs inside this span)
-      for (Grid& g : grids) {
-        HIP_TRY(hipEventSynchronize(g.done));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, start, g.done));
-        secs = std::max(secs, (double)ms * 1e-3);
-      }
-      if (device_seconds) *device_seconds = secs;
-      for (Grid& g : grids) {
-        char local_err[256];
-        local_err[0] = 0;
-        const int rcb = g.batch->collect(g.res.data(), local_err, sizeof local_err);
-        if (rcb != TOPOLOW_OK && rcb != TOPOLOW_ERR_NONFINITE) throw HipError{rcb, local_err};
-        for (size_t q = 0; q < g.idx.size(); ++q) {
-          topolow_result& o = results[g.idx[q]];
-          const GsResult& r = g.res[q];
-          o.final_mae = r.final_mae; o.final_k = r.final_k; o.converged = r.converged;
-          o.iterations = r.iterations; o.iterations_run = r.iters_run; o.n_checks = r.n_checks;
-          o.error_code = r.nonfinite_iter ? TOPOLOW_ERR_NONFINITE : TOPOLOW_OK;
-          o.error_iteration = r.nonfinite_iter;
-          o.holdout_sum_abs = r.hold_sum;
-          o.holdout_count = r.hold_count;
-        }
-      }
-    } catch (const GsHipError& e) {
-      release();
-      throw HipError{e.code, e.msg};
-    } catch (...) {
-      release();
-      throw;
-    }
-    release();
+    if (precision == TOPOLOW_PRECISION_F32) gs_relax<float>(problems, results, count, device_seconds);
+    else gs_relax<double>(problems, results, count, device_seconds);
   });
-  return rc != TOPOLOW_OK ? rc : rc_all;
 }
 
 // ---- post metric -----------------------------------------------------------------------
@@ -2315,41 +2141,39 @@ int topolow_cv_sweep(const topolow_cell_list* cells, int32_t named, int32_t pres
     int64_t ne = 0, nh = 0;
     int rc = TOPOLOW_OK;
   };
-  std::vector<Fold> F((size_t)n_folds);
-  try {
-    gs_parallel_for(n_folds, [&](int f) {
-      Fold& x = F[(size_t)f];
-      x.order.resize(n); x.deg.resize(n);
-      x.ei.resize(m); x.ej.resize(m); x.et.resize(m); x.ed.resize(m);
-      x.hi.resize(m); x.hj.resize(m); x.ht.resize(m);
-      double vmax = 0.0;
-      x.rc = fold_problem(cells, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named,
-                          x.order.data(), x.deg.data(), x.ei.data(), x.ej.data(), x.ed.data(), x.et.data(), &x.ne,
-                          x.hi.data(), x.hj.data(), x.ht.data(), &x.nh, &vmax);
-      if (x.rc == TOPOLOW_OK && (x.ne == 0 || !(vmax == vmax))) x.rc = TOPOLOW_ERR_BAD_ARGUMENT;   // no valid measurements
-      if (x.rc != TOPOLOW_OK) return;
-      const int d_ = ndim[f];
-      if (d_ < 1 || draws_offset[f + 1] - draws_offset[f] != (int64_t)d_ * (n - 1)) { x.rc = TOPOLOW_ERR_BAD_ARGUMENT; return; }
-      const double* u = unit_draws + draws_offset[f];             // (ndim, n - 1), row-major
-      const double step = vmax / (double)n;
-      x.pos.assign((size_t)n * d_, 0.0);                          // column-major n x ndim
-      x.out.assign((size_t)n * d_, 0.0);
-      for (int d = 0; d < d_; ++d) {
-        double acc = 0.0;
-        for (int i = 1; i < n; ++i) {
-          const double st_ = 0.0 + (2.0 * step - 0.0) * u[(size_t)d * (n - 1) + (i - 1)];   // Generator.uniform's arithmetic
-          acc = i == 1 ? st_ : acc + st_;                         // cumsum
-          x.pos[(size_t)i + (size_t)d * n] = acc;
+  std::vector<Fold> F;
+  const int rc_folds = guarded(errbuf, errlen, [&] {
+    F.resize((size_t)n_folds);
+    host_parallel(n_folds, 16, [&](size_t lo, size_t hi) {
+      for (size_t f = lo; f < hi; ++f) {
+        Fold& x = F[f];
+        x.order.resize(n); x.deg.resize(n);
+        x.ei.resize(m); x.ej.resize(m); x.et.resize(m); x.ed.resize(m);
+        x.hi.resize(m); x.hj.resize(m); x.ht.resize(m);
+        double vmax = 0.0;
+        x.rc = fold_problem(cells, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named,
+                            x.order.data(), x.deg.data(), x.ei.data(), x.ej.data(), x.ed.data(), x.et.data(), &x.ne,
+                            x.hi.data(), x.hj.data(), x.ht.data(), &x.nh, &vmax);
+        if (x.rc == TOPOLOW_OK && (x.ne == 0 || !(vmax == vmax))) x.rc = TOPOLOW_ERR_BAD_ARGUMENT;   // no valid measurements
+        if (x.rc != TOPOLOW_OK) continue;
+        const int d_ = ndim[f];
+        if (d_ < 1 || draws_offset[f + 1] - draws_offset[f] != (int64_t)d_ * (n - 1)) { x.rc = TOPOLOW_ERR_BAD_ARGUMENT; continue; }
+        const double* u = unit_draws + draws_offset[f];             // (ndim, n - 1), row-major
+        const double step = vmax / (double)n;
+        x.pos.assign((size_t)n * d_, 0.0);                          // column-major n x ndim
+        x.out.assign((size_t)n * d_, 0.0);
+        for (int d = 0; d < d_; ++d) {
+          double acc = 0.0;
+          for (int i = 1; i < n; ++i) {
+            const double st_ = 0.0 + (2.0 * step - 0.0) * u[(size_t)d * (n - 1) + (i - 1)];   // Generator.uniform's arithmetic
+            acc = i == 1 ? st_ : acc + st_;                         // cumsum
+            x.pos[(size_t)i + (size_t)d * n] = acc;
+          }
         }
       }
     });
-  } catch (const GsHipError& e) {
-    set_err(errbuf, errlen, "%s", e.msg.c_str());
-    return e.code;
-  } catch (const std::bad_alloc&) {
-    set_err(errbuf, errlen, "out of host memory");
-    return TOPOLOW_ERR_HIP;
-  }
+  });
+  if (rc_folds != TOPOLOW_OK) return rc_folds;
   std::vector<topolow_problem> P;
   std::vector<topolow_result> R;
   std::vector<int> idx;
@@ -2758,34 +2582,41 @@ int topolow_optimize_layout_exact(
       gs_lds_bytes(n, kernel_dim(ndim), (opt.precision == TOPOLOW_PRECISION_F32) ? 4 : 8) <= 150 * 1024 && n <= 2048;
   const bool tile_gs = schedule == TOPOLOW_SCHEDULE_GS && !gs_fits_lds;
   if (schedule == TOPOLOW_SCHEDULE_GS && !tile_gs) {
-    int precision = opt.precision == TOPOLOW_PRECISION_AUTO ? TOPOLOW_PRECISION_F64 : opt.precision;
-    GsProblem pb;
-    pb.initial_positions = initial_positions; pb.n = n; pb.dim = ndim;
-    pb.D = dissimilarity_matrix; pb.T = threshold_matrix; pb.degrees = degrees;
+    const int precision = opt.precision == TOPOLOW_PRECISION_AUTO ? TOPOLOW_PRECISION_F64 : opt.precision;
+    topolow_problem pb;
+    std::memset(&pb, 0, sizeof pb);
+    pb.initial_positions = initial_positions; pb.n = n; pb.ndim = ndim;
+    pb.dissimilarity_matrix = dissimilarity_matrix; pb.threshold_matrix = threshold_matrix; pb.degrees = degrees;
     pb.edge_i = edge_i; pb.edge_j = edge_j; pb.edge_dist = edge_dist; pb.edge_thresh = edge_thresh;
-    pb.n_edges = n_edges; pb.n_iter = n_iter; pb.k0 = k0; pb.cooling = cooling_rate;
-    pb.c_rep = c_repulsion; pb.eps = relative_epsilon; pb.window = convergence_window;
-    pb.check_freq = convergence_check_freq; pb.seed = opt.seed;
-    GsResult res;
-    res.positions = positions_out;
-    int rc_inner = TOPOLOW_OK;
+    pb.n_edges = n_edges; pb.n_iter = n_iter; pb.k0 = k0; pb.cooling_rate = cooling_rate;
+    pb.c_repulsion = c_repulsion; pb.relative_epsilon = relative_epsilon; pb.convergence_window = convergence_window;
+    pb.convergence_check_freq = convergence_check_freq; pb.seed = opt.seed;
+    topolow_result res;
+    std::memset(&res, 0, sizeof res);
+    res.positions_out = positions_out;
     double dev_s = 0.0;
     std::vector<double> trace;
     if (verbose) emit_header(opt, "one-workgroup Gauss-Seidel", n, k0, cooling_rate, c_repulsion);
     const int rc = guarded(errbuf, errlen, [&] {
       select_device(opt.device);
-      rc_inner = gs_run_batch(&pb, &res, 1, precision, &dev_s, errbuf, errlen, opt.interrupt_cb,
-                              opt.interrupt_user, verbose ? &trace : nullptr);
+      std::vector<double>* trace_out = verbose ? &trace : nullptr;
+      if (precision == TOPOLOW_PRECISION_F32)
+        gs_relax<float>(&pb, &res, 1, &dev_s, opt.interrupt_cb, opt.interrupt_user, trace_out);
+      else
+        gs_relax<double>(&pb, &res, 1, &dev_s, opt.interrupt_cb, opt.interrupt_user, trace_out);
     });
     if (rc != TOPOLOW_OK) return rc;
-    if (rc_inner != TOPOLOW_OK) return rc_inner;
+    if (res.error_code == TOPOLOW_ERR_NONFINITE)
+      set_err(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.", res.error_iteration);
+    if (res.error_code == TOPOLOW_ERR_INTERRUPTED) set_err(errbuf, errlen, "interrupted by the caller");
+    if (res.error_code != TOPOLOW_OK) return res.error_code;
     *converged = res.converged; *iterations = res.iterations; *final_mae = res.final_mae;
     *final_k = res.final_k;
     if (stats) {
       std::memset(stats, 0, sizeof *stats);
       stats->schedule_used = TOPOLOW_SCHEDULE_GS;
       stats->precision_used = precision;
-      stats->iterations_run = res.iters_run;
+      stats->iterations_run = res.iterations_run;
       stats->n_checks = res.n_checks;
       stats->device_seconds = dev_s;
       stats->total_seconds = now_s() - t_start;
@@ -2828,7 +2659,8 @@ int topolow_optimize_layout_exact(
     // the bytes over PCIe -- and the dense arrays are only read on the host, once, to verify it.
     bool from_edges = false;
     if (precision == TOPOLOW_PRECISION_F32 && getenv("TOPOLOW_DENSE_UPLOAD") == nullptr &&
-        edges_are_the_matrix(dissimilarity_matrix, threshold_matrix, n, edge_i, edge_j, edge_dist, edge_thresh, n_edges)) {
+        edges_are_the_matrix(dissimilarity_matrix, threshold_matrix, n, edge_i, edge_j, edge_dist, edge_thresh, n_edges,
+                             true)) {
       rc = topolow_session_load_coo(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, degrees, errbuf, errlen);
       if (rc) break;
       rc = topolow_session_set_edges(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, errbuf, errlen);
