@@ -71,7 +71,9 @@ extern "C" {
  *         columns, S times": every point still meets one slab of partners per stage, both ends of a pair move together as
  *         in the reference; equal to a CPU model of that schedule (f64: 1e-12 per stage), final-MAE statistics unchanged
  *         on the pinned problems and seed for seed (profiles/r03_two_stage_study.txt); TOPOLOW_SYMMETRIC_TWO_STAGE=0
- *         keeps the row-owner form.
+ *         keeps the row-owner form.  The fp32 sweep's waves run at an issue priority that falls with the share of
+ *         their run still to do, so that the two waves of a SIMD end together (results unchanged bit for bit;
+ *         TOPOLOW_SYM_PRIO=0 at session creation leaves every wave at priority 0; a sharded sweep's segments always do).
  * The deterministic pieces -- controller, cooling, error rule, guards, messages -- are exact. */
 
 /* Schedules (topolow_options.schedule). */

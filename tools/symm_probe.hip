@@ -1,7 +1,7 @@
 // Probe of the symmetric sweep (topolow_amd/csrc/relax_symm.h) on synthetic data of config 3's shape:
 // checks one sweep + apply against a plain row-owner evaluation of the same update and times them.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I topolow_amd/csrc -o tools/symm_probe tools/symm_probe.hip
-// Run:   tools/symm_probe [n=10000] [workgroups per CU, 0 = occupancy] [reps=50]
+// Run:   tools/symm_probe [n=10000] [workgroups per CU, 0 = occupancy] [reps=50] [issue priority by work left, 1 = on]
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -46,6 +46,7 @@ int main(int argc, char** argv) {
   const int n = argc > 1 ? atoi(argv[1]) : 10000;
   const int KT = argc > 2 ? atoi(argv[2]) : 0;
   const int reps = argc > 3 ? atoi(argv[3]) : 50;
+  const int prio = argc > 4 ? atoi(argv[4]) : 1;
   const int npad = (n + 63) & ~63, ld = (n + 63) & ~63, TR = npad / kSymRows, TC = npad / kSymCols;
   const double k = 2.3, c_rep = 0.01;
   std::mt19937_64 rng(1);
@@ -77,7 +78,8 @@ int main(int argc, char** argv) {
   const std::vector<SymUnit>& units = plan.units;
   const std::vector<int2>& row_units = plan.row_units;
   const int n_units = (int)units.size();
-  printf("n %d  tile-rows %d  occupancy %d WG/CU  grid %d  units %d  colpart %.1f MB rowpart %.1f MB\n", n, TR, occ, grid, n_units,
+  printf("n %d  tile-rows %d  occupancy %d WG/CU  grid %d  units %d  priority by work left %s  colpart %.1f MB rowpart %.1f MB\n", n, TR, occ, grid, n_units,
+         prio ? "on" : "off",
          (double)TR * npad * DIM * 4 / 1e6, (double)n_units * kSymRows * DIM * 4 / 1e6);
 
   // tile-major copy of the upper triangle
@@ -102,6 +104,8 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&d_units, n_units * sizeof(SymUnit))); CK(hipMemcpy(d_units, units.data(), n_units * sizeof(SymUnit), hipMemcpyHostToDevice));
   CK(hipMalloc(&d_ru, TR * sizeof(int2))); CK(hipMemcpy(d_ru, row_units.data(), TR * sizeof(int2), hipMemcpyHostToDevice));
   const std::vector<SymRun> runs = plan.runs();
+  RunState* d_state;   // the sweep reads its stop flag: a cleared state
+  CK(hipMalloc(&d_state, sizeof(RunState))); CK(hipMemset(d_state, 0, sizeof(RunState)));
   CK(hipMalloc(&d_wf, runs.size() * sizeof(SymRun))); CK(hipMemcpy(d_wf, runs.data(), runs.size() * sizeof(SymRun), hipMemcpyHostToDevice));
 
   hipLaunchKernelGGL((symm_records_kernel<DIM, float>), dim3((npad + 255) / 256), dim3(256), 0, 0, d_pos, d_g, d_rec, n, npad, k, c_rep);
@@ -110,10 +114,10 @@ int main(int argc, char** argv) {
   hipLaunchKernelGGL(ref_kernel<DIM>, dim3((n + 63) / 64), dim3(64), 0, 0, d_enc, ld, d_pos, d_g, n, k, c_rep, d_ref, d_err);
   CK(hipDeviceSynchronize()); printf("ref done\n");
   hipLaunchKernelGGL((symm_sweep_kernel<DIM, false, true>), dim3(grid), dim3(64 * kSymWaves), 0, 0, d_tenc, d_rec, d_units,
-                     d_wf, d_rowp, d_colp, npad, (const RunState*)nullptr, d_psum, d_pcnt, 0ull, 0);
+                     d_wf, d_rowp, d_colp, npad, (const RunState*)d_state, d_psum, d_pcnt, 0ull, 0, prio);
   CK(hipDeviceSynchronize()); printf("sweep done\n");
   hipLaunchKernelGGL((symm_apply_kernel<DIM, float>), dim3(TC), dim3(32 * kSymApplyParts), 0, 0, d_rec, d_rec2, d_out, d_g, d_rowp, d_colp, d_ru, n, npad,
-                     k * 0.99, c_rep, 1, (RunState*)nullptr);
+                     k * 0.99, c_rep, 1, d_state);
   CK(hipDeviceSynchronize()); printf("apply done\n");
   std::vector<float> out(pos.size()), ref(pos.size());
   std::vector<double> err(n), psum(n_units);
@@ -141,11 +145,11 @@ int main(int argc, char** argv) {
   };
   auto sweep = [&](auto err_tag) {
     hipLaunchKernelGGL((symm_sweep_kernel<DIM, false, decltype(err_tag)::value>), dim3(grid), dim3(64 * kSymWaves), 0, 0, d_tenc, d_rec,
-                       d_units, d_wf, d_rowp, d_colp, npad, (const RunState*)nullptr, d_psum, d_pcnt, 0ull, 0);
+                       d_units, d_wf, d_rowp, d_colp, npad, (const RunState*)d_state, d_psum, d_pcnt, 0ull, 0, prio);
   };
   auto apply = [&]() {
     hipLaunchKernelGGL((symm_apply_kernel<DIM, float>), dim3(TC), dim3(32 * kSymApplyParts), 0, 0, d_rec, d_rec2, d_out, d_g, d_rowp, d_colp, d_ru, n, npad,
-                       k * 0.99, c_rep, 1, (RunState*)nullptr);
+                       k * 0.99, c_rep, 1, d_state);
   };
   time([&]() { sweep(std::false_type{}); }, "sweep");
   time([&]() { apply(); }, "apply");
@@ -182,6 +186,17 @@ int main(int argc, char** argv) {
     printf("in-kernel clock (last sweep of 25000 back-to-back iterations): median %.0f MHz [%.0f, %.0f]\n", pct(clk, .5), pct(clk, 0), pct(clk, 1));
     printf("wave start us: p50 %.2f p99 %.2f max %.2f | end us: p1 %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f | lifetime p50 %.1f max %.1f\n",
            pct(t0s, .5), pct(t0s, .99), pct(t0s, 1), pct(t1s, .01), pct(t1s, .1), pct(t1s, .5), pct(t1s, .9), pct(t1s, .99), pct(t1s, 1), pct(life, .5), pct(life, 1));
+    {   // the two waves of a SIMD: when the first of them ends, when the second, and how far apart
+      std::vector<double> e_first, e_second, gap;
+      for (auto& kv : by_simd) if (kv.second.size() == 2) {
+        const double x = (stv[4 * kv.second[0] + 2] - first) / 100.0, y = (stv[4 * kv.second[1] + 2] - first) / 100.0;
+        e_first.push_back(std::min(x, y)); e_second.push_back(std::max(x, y)); gap.push_back(std::fabs(x - y));
+      }
+      if (!gap.empty())
+        printf("SIMDs with two waves: first wave ends p10 %.1f p50 %.1f p90 %.1f | second p10 %.1f p50 %.1f p90 %.1f max %.1f | gap p50 %.1f p90 %.1f us\n",
+               pct(e_first, .1), pct(e_first, .5), pct(e_first, .9), pct(e_second, .1), pct(e_second, .5), pct(e_second, .9), pct(e_second, 1),
+               pct(gap, .5), pct(gap, .9));
+    }
     std::map<int, int> hist; double worst = 0; int worst_tiles = 0, worst_n = 0;
     std::map<int, std::vector<double>> end_by_load;
     for (auto& kv : by_simd) {

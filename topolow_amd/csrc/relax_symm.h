@@ -66,9 +66,11 @@ TL_HD inline size_t sym_word_in_tile(int r, int c) {   // r in [0, 64), c in [0,
 //   units      : tile-row-major; unit u covers column blocks [j0, j1) of tile-row R
 //   wave_first : n_waves + 1 entries, wave w sweeps units [wave_first[w], wave_first[w + 1]) (the kernel reads runs())
 //   row_units  : per tile-row (first unit, number of units)
-struct SymRun {      // one wave's run: units [u0, u1), the first of them inline (one load instead of two dependent ones)
+struct alignas(32) SymRun {   // one wave's run: units [u0, u1), the first of them inline (one load instead of two dependent ones)
   int u0, u1;
   SymUnit first;
+  int tiles;         // tiles of the whole run: the sweep's issue priority follows the share of them still to do
+  int reserved;      // (32 bytes: one aligned scalar load)
 };
 struct SymPlan {
   std::vector<SymUnit> units;
@@ -80,6 +82,9 @@ struct SymPlan {
       r[w].u0 = wave_first[w];
       r[w].u1 = wave_first[w + 1];
       r[w].first = r[w].u0 < r[w].u1 ? units[r[w].u0] : SymUnit{0, 0, 0, 0};
+      r[w].tiles = 0;
+      for (int u = r[w].u0; u < r[w].u1; ++u) r[w].tiles += units[u].j1 - units[u].j0;
+      r[w].reserved = 0;
     }
     return r;
   }
@@ -307,13 +312,39 @@ __device__ __forceinline__ void sym_pair(const float (&pc)[DIM], float ksc, floa
 //          the diagonal square is met from both sides, possibly by two units, and counts once per visit, every other pair
 //          twice at its one visit; fixed_cnt: twice the count of a threshold-free block (every measured pair contributes
 //          whatever the positions are: the number of measured cells), stored in slot 0
+// prio   : != 0: a wave's issue priority follows the share of ITS RUN that is still to do -- 3 down to 0 in steps of a
+//          quarter run.  The grid is one resident round of two waves per SIMD, and between equal priorities the vector
+//          pipe goes to the older wave: left alone it runs out 10 - 15 us before the younger one, which does the rest of
+//          its run with nobody to cover its waits.  With the priority the wave that is behind outranks the one that is
+//          ahead and the two end together.  Only for a launch that has the GPU to itself (the host decides).
 template <int DIM, bool ANYTHR, bool ERR>
 __global__ __launch_bounds__(64 * kSymWaves, TOPOLOW_SYM_MINW) void symm_sweep_kernel(
     const uint32_t* __restrict__ enc, const float* __restrict__ rec, const SymUnit* __restrict__ units,
     const SymRun* __restrict__ runs, float* __restrict__ rowpart, float* __restrict__ colpart, int npad,
     const RunState* st, double* __restrict__ part_sum, unsigned long long* __restrict__ part_cnt,
-    unsigned long long fixed_cnt, int col_row0) {
-  if (st != nullptr && st->stopped) return;
+    unsigned long long fixed_cnt, int col_row0, int prio) {
+  // units are dealt statically: wave w of the grid sweeps units [runs[w].u0, runs[w].u1) -- the host
+  // cuts the tile-row-major list of upper-triangle tiles into equal runs, one per wave (relax_symm_plan).
+  // The run is requested BEFORE the stop flag is looked at: both addresses need only the kernel arguments, so the two
+  // loads travel together and one wait serves both (a stopped launch still returns before it stores anything)
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int gw = blockIdx.x * kSymWaves + wave;
+  const SymRun run = runs[gw];
+  int stopped = st->stopped;   // (st is never null here: the probe passes a cleared RunState)
+  // ... and everything the wave needs up to its first vector load is pinned in scalar registers in front of the
+  // branch: left free, the optimiser sinks each load behind the branch that first needs it -- the flag, then the run,
+  // then the other kernel arguments, every one a round trip of its own behind the one before.  (The flag passes
+  // THROUGH the statement, which is not volatile: a volatile one counts as a store to anything, and the loads of
+  // units[] behind it would no longer be scalar loads.)
+  if constexpr (ERR)
+    asm("" : "+s"(stopped) : "s"(run.u0), "s"(run.u1), "s"(run.first.tile_row), "s"(run.first.j0), "s"(run.first.j1),
+        "s"(run.first.tile0), "s"(run.tiles), "s"(enc), "s"(rec), "s"(units),
+        "s"(rowpart), "s"(colpart), "s"(npad), "s"(col_row0), "s"(prio), "s"(part_sum), "s"(part_cnt), "s"(fixed_cnt));
+  else
+    asm("" : "+s"(stopped) : "s"(run.u0), "s"(run.u1), "s"(run.first.tile_row), "s"(run.first.j0), "s"(run.first.j1),
+        "s"(run.first.tile0), "s"(run.tiles), "s"(enc), "s"(rec), "s"(units),
+        "s"(rowpart), "s"(colpart), "s"(npad), "s"(col_row0), "s"(prio));
+  if (stopped) return;
 #ifdef TOPOLOW_SYM_STAMPS   // diagnostic build (tools/symm_probe.hip): shader clock against the 100-MHz real-time counter, per wave
   const unsigned long long stamp_c0 = __builtin_amdgcn_s_memtime(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -326,21 +357,23 @@ __global__ __launch_bounds__(64 * kSymWaves, TOPOLOW_SYM_MINW) void symm_sweep_k
   __shared__ uint4 lds[kSymWaves][2][kLdsVec];
   auto lds_slot = [](int q) { return q + (q / (4 * kRecVec)); };   // q = record * kRecVec + piece
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int a = lane & 7, b = lane >> 3;
 
-  // units are dealt statically: wave w of the grid sweeps units [runs[w].u0, runs[w].u1) -- the host
-  // cuts the tile-row-major list of upper-triangle tiles into equal runs, one per wave (relax_symm_plan)
-  const int gw = blockIdx.x * kSymWaves + wave;
-  const SymRun run = runs[gw];
   const int u_begin = __builtin_amdgcn_readfirstlane(run.u0);
   const int u_end = __builtin_amdgcn_readfirstlane(run.u1);
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const __amdgpu_buffer_rsrc_t rec_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rec), 0, npad * W * 4, 0x00020000);
+  // tiles of the run still to do, and the counts above which the priority is 3, 2, 1 (more than 3/4, 1/2, 1/4 of the run)
+  int left = __builtin_amdgcn_readfirstlane(run.tiles);
+  const int lv3 = (3 * left) >> 2, lv2 = left >> 1, lv1 = left >> 2;
+  SymUnit U_next = run.first;
   for (int u = u_begin; u < u_end; ++u) {
-    const SymUnit U = u == u_begin ? run.first : units[u];
+    const SymUnit U = U_next;
+    // the next unit's descriptor is fetched while this one is swept: the next unit starts with its row records
+    U_next = units[u + 1 < u_end ? u + 1 : u];
     const int R = __builtin_amdgcn_readfirstlane(U.tile_row);
     const int J0 = __builtin_amdgcn_readfirstlane(U.j0), J1 = __builtin_amdgcn_readfirstlane(U.j1);
+    __builtin_assume(J0 < J1);   // (a unit holds a tile: without a guard around the tile loop the unit's head is one block, all its loads issued together)
     const int slot = u;
     const int tile0 = __builtin_amdgcn_readfirstlane(U.tile0);
 
@@ -411,6 +444,13 @@ __global__ __launch_bounds__(64 * kSymWaves, TOPOLOW_SYM_MINW) void symm_sweep_k
     read_rec(J0, 0, f_first);
 #pragma unroll 1
     for (int J = J0; J < J1; ++J) {
+      if (prio) {   // wave-uniform: scalar compares and branches around s_setprio with an immediate
+        if (left > lv3) __builtin_amdgcn_s_setprio(3);
+        else if (left > lv2) __builtin_amdgcn_s_setprio(2);
+        else if (left > lv1) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+      }
+      --left;
       const int Jn = J + 1 < J1 ? J + 1 : J;
       // requests first: the second half's words, the next column block's records (buffer loads: the optimiser leaves
       // them where they are written; a plain load of the records was sunk down to its use at the end of the tile)
@@ -564,12 +604,20 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
     const real* __restrict__ rec, real* __restrict__ rec_next, real* __restrict__ pos_out, const float* __restrict__ gplus,
     const real* __restrict__ rowpart, const real* __restrict__ colpart, const int2* __restrict__ row_units, int n,
     int npad, double k_next, double c_rep, int iter1, RunState* st, int rr_stages = 0, int rr_stage = 0) {
-  if (st != nullptr && st->stopped) return;
+  const int R = blockIdx.x >> 1;                   // the tile-row of this column block's points
+  // the tile-row's units are requested together with the stop flag, and what the first strips need is pinned in scalar
+  // registers in front of the branch, as in the sweep: kernel arguments, then these two, where the optimiser left to
+  // itself waits for the flag's pointer, the flag, the other arguments and row_units[R] one after the other
+  // (st is never null here)
+  const int2 ru = row_units[R];
+  int stopped = st->stopped;
+  asm("" : "+s"(stopped) : "s"(ru.x), "s"(ru.y), "s"(rec), "s"(rowpart), "s"(colpart), "s"(n), "s"(npad), "s"(rr_stages), "s"(rr_stage),
+      "s"(rec_next), "s"(pos_out), "s"(gplus), "s"(k_next), "s"(c_rep));
+  if (stopped) return;
   using T = SymReal<DIM, real>;
   constexpr int W = T::W;
   constexpr int kWavesA = kSymApplyParts / 2;
   __shared__ real red[kWavesA][kSymCols][DIM];
-  const int R = blockIdx.x >> 1;                   // the tile-row of this column block's points
   const int part = threadIdx.x >> 5, pt = threadIdx.x & 31;
   const int i = blockIdx.x * kSymCols + pt;
   real acc[DIM];
@@ -586,7 +634,6 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
 #pragma unroll
     for (int d = 0; d < DIM; ++d) acc[d] += src[d];
   }
-  const int2 ru = row_units[R];
   const int row_in_tile = i - R * kSymRows;
   for (int q = part; q < ru.y; q += kSymApplyParts) {
     const real* src = rowpart + ((size_t)(ru.x + q) * kSymRows + row_in_tile) * DIM;
@@ -621,7 +668,7 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
     const real g = (real)gplus[i];
     rec_next[(size_t)i * W + DIM] = T::ks(k_next, g);
     rec_next[(size_t)i * W + DIM + 1] = T::cg(c_rep, g);
-    if (!finite && st != nullptr) atomicMin(&st->first_nonfinite, iter1);
+    if (!finite) atomicMin(&st->first_nonfinite, iter1);
   }
 }
 

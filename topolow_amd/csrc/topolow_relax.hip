@@ -239,6 +239,7 @@ struct topolow_session {
     std::vector<Plan> rr[4];
     bool whole = false;            // the buffers describe the whole triangle (not a segment): stage plans may be cut from it
     bool two_stage = true;         // TOPOLOW_SYMMETRIC_TWO_STAGE=0: multi-stage iterations stay on the row-owner kernel
+    bool prio = true;              // TOPOLOW_SYM_PRIO=0: the fp32 sweep's waves all stay at issue priority 0
     int rr_min_tiles = 5;          // tiles per resident wave a stage must have (TOPOLOW_SYMMETRIC_STAGE_MIN_TILES; tests: 0)
     DevBuf<const uint32_t*> src_tab;   // the row blocks the tile-major copy is gathered from (one: the session's own)
     DevBuf<int> src_row0;
@@ -833,10 +834,11 @@ void sym_records(topolow_session* s, const void* pin, void* rec, double k) {
 
 // The sweep of `plan` over the records `rec` into the partials.  err: it also reduces the pending check's MAE into
 // part_sum / part_cnt (one partial per unit); block_cells: the count of a threshold-free block (0: none reduced);
-// col_row0: the first tile-row of the column partials (a segment's; 0 for the whole triangle).
+// col_row0: the first tile-row of the column partials (a segment's; 0 for the whole triangle); prio: the fp32 sweep's
+// issue priority follows the work a wave has left (relax_symm.h) -- for a launch that has the GPU to itself.
 template <int DIM>
 void sym_sweep(topolow_session* s, const SymPlanDev& plan, const void* rec, bool thr, bool err,
-               unsigned long long block_cells, int col_row0) {
+               unsigned long long block_cells, int col_row0, bool prio) {
   auto& y = s->sym;
   sym_real(s, [&](auto r) {
     using real = decltype(r);
@@ -848,7 +850,7 @@ void sym_sweep(topolow_session* s, const SymPlanDev& plan, const void* rec, bool
       else
         hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, (const float*)rec,
                            plan.units.p, plan.runs.p, (float*)y.rowpart.p, (float*)y.colpart.p, y.npad, s->state.p,
-                           s->part_sum.p, s->part_cnt.p, block_cells, col_row0);
+                           s->part_sum.p, s->part_cnt.p, block_cells, col_row0, prio && y.prio ? 1 : 0);
     });
   });
 }
@@ -916,7 +918,7 @@ void sym_iteration(topolow_session* s, const void* pin, void* pout, int iter, do
       sym_records<DIM>(s, pin, y.rec[b].p, k);
     y.rec_cur = 0;
   }
-  sym_sweep<DIM>(s, plan, y.rec[y.rec_cur].p, s->any_threshold, err, S == 0 ? s->block_cells : 0ull, 0);
+  sym_sweep<DIM>(s, plan, y.rec[y.rec_cur].p, s->any_threshold, err, S == 0 ? s->block_cells : 0ull, 0, true);
   sym_apply<DIM>(s, plan, y.rec[y.rec_cur].p, y.rec[y.rec_cur ^ 1].p, pout, last ? k * (1.0 - s->cooling) : k, iter, S, st);
   HIP_TRY(hipGetLastError());
   y.rec_cur ^= 1;
@@ -1095,7 +1097,8 @@ void sym_sharded_sweep(topolow_session* s, const void* pin, int iter, double k, 
   auto& y = s->sym;
   ProfScope prof(s, err ? &s->prof_sym_err : &s->prof_sym);
   sym_records<DIM>(s, pin, y.rec[0].p, k);
-  if (y.tiles > 0) sym_sweep<DIM>(s, y.plan, y.rec[0].p, y.seg_thr, err, s->block_cells, y.seg_first);
+  if (y.tiles > 0) sym_sweep<DIM>(s, y.plan, y.rec[0].p, y.seg_thr, err, s->block_cells, y.seg_first,
+                                  false);   // several sessions may share a GPU here: every wave stays at priority 0
   hipLaunchKernelGGL(symm_partial_kernel<DIM>, dim3(y.npad / kSymCols), dim3(32 * 32), 0, s->stream, (const float*)y.rowpart.p,
                      (const float*)y.colpart.p, y.plan.row_units.p, y.seg_first, y.seg_last, s->n, y.npad, y.inbox_tab.p,
                      y.own0.p, y.seg_slots, y.seg_slot, s->state.p);
@@ -1314,6 +1317,8 @@ int topolow_session_create(topolow_session** out, int32_t n, int32_t ndim, int32
     s->sym.two_stage = !(symm2 != nullptr && symm2[0] == '0');
     const char* rr_min = getenv("TOPOLOW_SYMMETRIC_STAGE_MIN_TILES");
     if (rr_min != nullptr) s->sym.rr_min_tiles = std::max(0, atoi(rr_min));
+    const char* sym_prio = getenv("TOPOLOW_SYM_PRIO");
+    s->sym.prio = !(sym_prio != nullptr && sym_prio[0] == '0');
     s->enc.alloc((size_t)((s->rows() + kEncRowAlign - 1) / kEncRowAlign * kEncRowAlign) * s->ld);
     const size_t pos_bytes = (size_t)s->pos_rows() * s->dim * s->real_size();
     for (auto& b : s->pos) b.alloc(pos_bytes);
