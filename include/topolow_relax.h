@@ -250,6 +250,48 @@ int topolow_cv_sweep(const topolow_cell_list* cells, int32_t named, int32_t pres
                      int32_t* error_code, double* device_seconds, char* errbuf, size_t errlen);
 
 
+/* 1 when a problem of n points in ndim dimensions with n_edges measured pairs fits the one-workgroup kernel of
+ * topolow_optimize_layout_exact_batch / topolow_cv_sweep (its LDS: 160 KB; about 2 900 points in f64 at ndim 5), 0 when
+ * those calls would answer TOPOLOW_ERR_UNSUPPORTED -- the problems topolow_cv_sweep_session is for.  precision AUTO = f64,
+ * as in the batch call.  Host only. */
+int32_t topolow_batch_problem_fits(int32_t n, int32_t ndim, int32_t precision, int64_t n_edges);
+
+/* topolow_cv_fold without the fold's edge list, for folds that are held out of a resident session
+ * (topolow_session_hold_out): the same fold -- same ordering, degrees, numeric_max, scored cells -- with every index in
+ * the CALLER's labels and host memory O(n + picks):
+ *   order        n entries as topolow_cv_fold (order[0] = -1: input order kept); the fold's start positions are laid out
+ *                along it: point i of the random walk is the caller's point order[i]
+ *   degrees      n entries per CALLER's point (topolow_cv_fold's degrees[q] is the degree of point order[q])
+ *   n_edges      measured upper-triangle cells the fold keeps (0: no valid measurements)
+ *   pair_i/_j    the unique held-out unordered pairs, i < j (up to n_picks entries)
+ *   score_i/_j/_truth  the scored cells: held out AND numeric, each non-NA mirror on its own (up to 2 n_picks entries);
+ *                an unnamed matrix is scored in the returned numbering (R/error_metrics.R:100-112), i.e. cell (r, c)
+ *                against the points order[r], order[c]
+ * The cell list must be symmetric -- every off-diagonal cell has its mirror with the same value and code; with
+ * asymmetric NA the reference reads the upper triangle of the per-fold reordered matrix, which one fixed block cannot
+ * represent: TOPOLOW_ERR_UNSUPPORTED.  No device work. */
+int topolow_cv_fold_pairs(const topolow_cell_list* cells, const int64_t* picks, int64_t n_picks, int32_t preserve_order,
+                          int32_t named, int32_t* order, int32_t* degrees, double* numeric_max, int64_t* n_edges,
+                          int32_t* pair_i, int32_t* pair_j, int64_t* n_pairs, int32_t* score_i, int32_t* score_j,
+                          double* score_truth, int64_t* n_scored, char* errbuf, size_t errlen);
+
+/* topolow_cv_sweep for problems beyond one workgroup: arguments and outputs as topolow_cv_sweep, plus `schedule`
+ * (TOPOLOW_SCHEDULE_AUTO / _SLAB: the slab schedule; _GS: the tile Gauss-Seidel schedule of topolow_session_set_schedule;
+ * precision AUTO: f32 for slab, f64 for GS, as the one-shot call).  The folds are grouped by ndim; a group shares ONE
+ * device-resident session, relabelled as the one-shot call does (from the group's first seed) and loaded once with the
+ * full matrix (the upper triangle of the cell list, which must be symmetric: see topolow_cv_fold_pairs).  Per fold:
+ * topolow_session_hold_out, start positions from unit_draws (topolow_cv_sweep's arithmetic, laid out along the fold's
+ * order), begin(seeds[f]), the run, finish without a download, topolow_session_score_pairs, restore -- the next fold is
+ * prepared on a host thread meanwhile, host memory per fold O(n + picks).  error_code[f] as topolow_cv_sweep; the
+ * session is the full matrix again before the next fold starts in every case. */
+int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int32_t preserve_order, int32_t n_folds,
+                             const int32_t* ndim, const double* k0, const double* cooling_rate, const double* c_repulsion,
+                             const int64_t* picks, const int64_t* picks_offset, const double* unit_draws,
+                             const int64_t* draws_offset, const uint64_t* seeds, int32_t n_iter, double relative_epsilon,
+                             int32_t convergence_window, int32_t convergence_check_freq, int32_t precision, int32_t device,
+                             int32_t schedule, double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations,
+                             int32_t* converged, int32_t* error_code, double* device_seconds, char* errbuf, size_t errlen);
+
 /* Replaces `as.matrix(stats::dist(positions))` (reference R/core.R:474):
  * positions n x ndim float64 column-major (host) -> est_distances n x n float64 (host). */
 int topolow_est_distances(const double* positions, int32_t n, int32_t ndim,
@@ -342,6 +384,30 @@ int topolow_session_finish(topolow_session* s, double* positions_out, int32_t* c
  * cooling) -- the values behind the reference's verbose lines (src/optimization.cpp:298-301).
  * Waits for the enqueued work.  *n_checks = checks recorded; at most max_checks are copied. */
 int topolow_session_check_trace(topolow_session* s, double* out, int32_t max_checks, int32_t* n_checks);
+/* A cross-validation fold on a loaded whole-problem session (row_begin = 0, row_end = n; edges set; slab or tile
+ * Gauss-Seidel schedule, fp32 or f64), outside a run -- before topolow_session_begin or after topolow_session_finish.
+ * A fold differs from the full matrix in at most floor(#nonNA / (2 folds)) cells: they are patched on the device and put
+ * back afterwards; nothing of size n x n crosses PCIe.  Pairs are in the caller's labels.
+ *   hold_out    the listed unordered pairs (any orientation; duplicates, unmeasured pairs and i == j are ignored) become
+ *               unmeasured cells for the coming runs, `degrees` (n entries) the degrees.  Both mirrors of the encoded
+ *               block, the symmetric sweep's tile-major copy and the f64 delta tiles are patched at those cells and what
+ *               they held is saved; rowflags, the threshold bit and the cell count are recomputed on the device (the
+ *               sweep's plan is rebuilt only when the threshold bit flips: another kernel instance); a session that
+ *               gathers its edge list for the convergence MAE runs on a stable compaction of that list (the full one is
+ *               parked on the device).  The session then is what a fresh session loaded with the fold's list would be:
+ *               same block, same runs bit for bit.  A second hold_out without a restore: TOPOLOW_ERR_BAD_ARGUMENT;
+ *               during a run: TOPOLOW_ERR_BAD_ARGUMENT; a row-block session: TOPOLOW_ERR_UNSUPPORTED.
+ *   restore_held_out  puts the saved words, deltas and the full edge list back, with the full matrix's `degrees`: block,
+ *               tile-major copy, flags and cell count are bit for bit what they were.
+ *   score_pairs sum |truth - ||p_i - p_j||| and the number of pairs on the positions topolow_session_finish restores (the
+ *               device's best snapshot: finish may be called with positions_out = NULL, nothing is downloaded).
+ *               Distances and sums in f64 whatever the session's precision; deterministic (one partial per workgroup,
+ *               summed in index order); i == j counts with distance 0, as the batch call's holdout_* fields. */
+int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const int32_t* pair_j, int64_t n_pairs,
+                             const int32_t* degrees, char* errbuf, size_t errlen);
+int topolow_session_restore_held_out(topolow_session* s, const int32_t* degrees, char* errbuf, size_t errlen);
+int topolow_session_score_pairs(topolow_session* s, const int32_t* pair_i, const int32_t* pair_j, const double* truth,
+                                int64_t n_pairs, double* sum_abs, int64_t* count, char* errbuf, size_t errlen);
 /* Per-kernel timing for roofline accounting: while enabled, every slab-stage launch and
  * every convergence check is bracketed by HIP events on the session stream.
  * topolow_session_profile waits for the stream, returns the summed durations (ms) and launch

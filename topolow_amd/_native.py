@@ -154,6 +154,21 @@ def load() -> C.CDLL:
     lib.topolow_cv_sweep.argtypes = [C.POINTER(TopolowCellList), C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, i64p, i64p,
                                      dp, i64p, u64p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      dp, i64p, ip, ip, ip, dp, C.c_char_p, C.c_size_t]
+    lib.topolow_cv_sweep_session.restype = C.c_int
+    lib.topolow_cv_sweep_session.argtypes = [C.POINTER(TopolowCellList), C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, i64p,
+                                             i64p, dp, i64p, u64p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, dp, i64p, ip, ip, ip, dp, C.c_char_p, C.c_size_t]
+    lib.topolow_cv_fold_pairs.restype = C.c_int
+    lib.topolow_cv_fold_pairs.argtypes = [C.POINTER(TopolowCellList), i64p, C.c_int64, C.c_int32, C.c_int32, ip, ip, dp, i64p,
+                                          ip, ip, i64p, ip, ip, dp, i64p, C.c_char_p, C.c_size_t]
+    lib.topolow_batch_problem_fits.restype = C.c_int32
+    lib.topolow_batch_problem_fits.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
+    lib.topolow_session_hold_out.restype = C.c_int
+    lib.topolow_session_hold_out.argtypes = [C.c_void_p, ip, ip, C.c_int64, ip, C.c_char_p, C.c_size_t]
+    lib.topolow_session_restore_held_out.restype = C.c_int
+    lib.topolow_session_restore_held_out.argtypes = [C.c_void_p, ip, C.c_char_p, C.c_size_t]
+    lib.topolow_session_score_pairs.restype = C.c_int
+    lib.topolow_session_score_pairs.argtypes = [C.c_void_p, ip, ip, dp, C.c_int64, dp, i64p, C.c_char_p, C.c_size_t]
     lib.topolow_session_profile_symmetric.restype = C.c_int
     lib.topolow_session_profile_symmetric.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                                       C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
@@ -553,6 +568,67 @@ def cv_sweep(cells: CellList, named: bool, preserve_order: bool, ndims, k0s, coo
     return hsum, hcnt, its, conv, ec, float(secs.value)
 
 
+def cv_fold_pairs(cells: CellList, picks, preserve_order: bool, named: bool):
+    """One fold as a resident session holds it out (topolow_cv_fold_pairs): everything in the caller's labels, no edge
+    list.  Returns (order or None, degrees, numeric_max, n_edges, (pair_i, pair_j), (score_i, score_j, score_truth))."""
+    lib = load()
+    picks = np.ascontiguousarray(picks, dtype=np.int64)
+    n, k = cells.n, int(picks.shape[0])
+    order, deg = np.empty(n, np.int32), np.empty(n, np.int32)
+    pi, pj = np.empty(max(k, 1), np.int32), np.empty(max(k, 1), np.int32)
+    si, sj, st = np.empty(max(2 * k, 1), np.int32), np.empty(max(2 * k, 1), np.int32), np.empty(max(2 * k, 1), np.float64)
+    ne, npair, ns, vmax = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+    err = C.create_string_buffer(512)
+    _check(lib.topolow_cv_fold_pairs(C.byref(cells.c), picks.ctypes.data_as(C.POINTER(C.c_int64)), k,
+                                     int(bool(preserve_order)), int(bool(named)), _ip(order), _ip(deg), C.byref(vmax),
+                                     C.byref(ne), _ip(pi), _ip(pj), C.byref(npair), _ip(si), _ip(sj), _dp(st), C.byref(ns),
+                                     err, len(err)), err)
+    p, q = int(npair.value), int(ns.value)
+    return (None if order[0] < 0 else order.astype(np.int64), deg, float(vmax.value), int(ne.value),
+            (pi[:p].copy(), pj[:p].copy()), (si[:q].copy(), sj[:q].copy(), st[:q].copy()))
+
+
+def batch_problem_fits(n: int, ndim: int, precision: str = "f64", n_edges: int = 0) -> bool:
+    """Does a problem fit the one-workgroup kernel of optimize_layout_exact_batch / cv_sweep (its LDS)?  When not, those
+    calls raise ERR_UNSUPPORTED and cv_sweep_session is the path."""
+    return bool(load().topolow_batch_problem_fits(int(n), int(ndim), _PRECISIONS[precision], int(n_edges)))
+
+
+def cv_sweep_session(cells: CellList, named: bool, preserve_order: bool, ndims, k0s, cooling_rates, c_repulsions, picks,
+                     unit_draws, seeds, n_iter: int, relative_epsilon: float, convergence_window: int = 5,
+                     convergence_check_freq: int = 3, precision: str = "auto", device: int = -1, schedule: str = "auto"):
+    """`cv_sweep` on device-resident sessions (topolow_cv_sweep_session): one session per ndim holds the full matrix, a
+    fold is held out of it, run, scored and put back.  schedule "auto" / "slab": the slab schedule, "gs": tile
+    Gauss-Seidel; precision "auto": f32 for slab, f64 for gs.  Same returns as cv_sweep."""
+    lib = load()
+    nf = len(picks)
+    nd = np.ascontiguousarray(ndims, dtype=np.int32)
+    k0 = np.ascontiguousarray(k0s, dtype=np.float64)
+    cr = np.ascontiguousarray(cooling_rates, dtype=np.float64)
+    cp = np.ascontiguousarray(c_repulsions, dtype=np.float64)
+    p_off = np.zeros(nf + 1, dtype=np.int64)
+    d_off = np.zeros(nf + 1, dtype=np.int64)
+    if nf:
+        np.cumsum([len(p) for p in picks], out=p_off[1:])
+        np.cumsum([u.size for u in unit_draws], out=d_off[1:])
+    p_all = np.ascontiguousarray(np.concatenate(picks) if nf else np.zeros(0), dtype=np.int64)
+    d_all = np.ascontiguousarray(np.concatenate([np.ravel(u) for u in unit_draws]) if nf else np.zeros(0), dtype=np.float64)
+    sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+    hsum, hcnt = np.zeros(nf, np.float64), np.zeros(nf, np.int64)
+    its, conv, ec = np.zeros(nf, np.int32), np.zeros(nf, np.int32), np.zeros(nf, np.int32)
+    secs = C.c_double(0.0)
+    err = C.create_string_buffer(512)
+    i64 = C.POINTER(C.c_int64)
+    rc = lib.topolow_cv_sweep_session(C.byref(cells.c), int(bool(named)), int(bool(preserve_order)), nf, _ip(nd), _dp(k0),
+                                      _dp(cr), _dp(cp), p_all.ctypes.data_as(i64), p_off.ctypes.data_as(i64), _dp(d_all),
+                                      d_off.ctypes.data_as(i64), sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_iter),
+                                      float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
+                                      _PRECISIONS[precision], int(device), _SCHEDULES[schedule], _dp(hsum),
+                                      hcnt.ctypes.data_as(i64), _ip(its), _ip(conv), _ip(ec), C.byref(secs), err, len(err))
+    _check(rc, err)
+    return hsum, hcnt, its, conv, ec, float(secs.value)
+
+
 def symm_stage_bounds(n: int, stages: int):
     """Slab boundaries (labels) of the symmetric form of an S-stage iteration, or None (topolow_symm_stage_bounds)."""
     out = np.zeros(stages + 1, dtype=np.int32)
@@ -846,15 +922,43 @@ class Session:
                                              self._err, len(self._err)), self._err)
         return int(it.value), bool(st.value), float(mae.value)
 
-    def finish(self) -> NativeResult:
-        out = np.zeros((self.n, self.ndim), dtype=np.float64, order="F")
+    def finish(self, download: bool = True) -> NativeResult:
+        """download = False: the positions stay on the device (score_pairs reads them there); `positions` is None."""
+        out = np.zeros((self.n, self.ndim), dtype=np.float64, order="F") if download else None
         conv, iters = C.c_int32(0), C.c_int32(0)
         fmae, fk = C.c_double(0.0), C.c_double(0.0)
-        _check(self.lib.topolow_session_finish(self._h, _dp(out), C.byref(conv), C.byref(iters),
+        _check(self.lib.topolow_session_finish(self._h, _dp(out) if download else None, C.byref(conv), C.byref(iters),
                                                C.byref(fmae), C.byref(fk), self._err,
                                                len(self._err)), self._err)
-        return NativeResult(np.ascontiguousarray(out), bool(conv.value), int(iters.value),
+        return NativeResult(np.ascontiguousarray(out) if download else None, bool(conv.value), int(iters.value),
                             float(fmae.value), float(fk.value))
+
+    def hold_out(self, pair_i, pair_j, degrees):
+        """The listed pairs (caller's labels) become unmeasured for the coming runs, `degrees` the fold's degrees
+        (topolow_session_hold_out); outside a run only."""
+        pi = np.ascontiguousarray(pair_i, dtype=np.int32)
+        pj = np.ascontiguousarray(pair_j, dtype=np.int32)
+        deg = np.ascontiguousarray(degrees, dtype=np.int32)
+        assert pi.shape == pj.shape and deg.shape[0] == self.n
+        _check(self.lib.topolow_session_hold_out(self._h, _ip(pi), _ip(pj), int(pi.shape[0]), _ip(deg), self._err,
+                                                 len(self._err)), self._err)
+
+    def restore_held_out(self, degrees):
+        """Puts the held-out cells back, with the full matrix's degrees."""
+        deg = np.ascontiguousarray(degrees, dtype=np.int32)
+        assert deg.shape[0] == self.n
+        _check(self.lib.topolow_session_restore_held_out(self._h, _ip(deg), self._err, len(self._err)), self._err)
+
+    def score_pairs(self, pair_i, pair_j, truth):
+        """(sum |truth - distance|, count) over the pairs on the positions finish() restores, on the device."""
+        pi = np.ascontiguousarray(pair_i, dtype=np.int32)
+        pj = np.ascontiguousarray(pair_j, dtype=np.int32)
+        t = np.ascontiguousarray(truth, dtype=np.float64)
+        assert pi.shape == pj.shape == t.shape
+        total, cnt = C.c_double(0.0), C.c_int64(0)
+        _check(self.lib.topolow_session_score_pairs(self._h, _ip(pi), _ip(pj), _dp(t), int(pi.shape[0]), C.byref(total),
+                                                    C.byref(cnt), self._err, len(self._err)), self._err)
+        return float(total.value), int(cnt.value)
 
     def run(self, chunk=64):
         while self.enqueue(chunk) > 0:

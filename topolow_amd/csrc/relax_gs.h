@@ -547,6 +547,9 @@ inline size_t gs_lds_bytes(int n, int dim, size_t real_size, long long csr_edges
   return off;
 }
 
+// LDS the kernel may ask for: a problem beyond it does not fit the single-workgroup schedule.
+constexpr size_t kGsLdsLimit = 160 * 1024;
+
 // LDS budget under which the sparse (LDS-resident) table is used; two workgroups per CU still fit.
 constexpr size_t kGsSparseLdsBudget = 78 * 1024;
 
@@ -704,7 +707,7 @@ class GsBatch {
     for (int b = 0; b < count; ++b) {
       const topolow_problem& p = pbs[idx[b]];
       const size_t lds = gs_lds_bytes(p.n, dim, sizeof(real), sparse ? p.n_edges : 0);
-      if (lds > 160 * 1024)
+      if (lds > kGsLdsLimit)
         throw HipError{TOPOLOW_ERR_UNSUPPORTED,
                        "problem too large for the single-workgroup GS kernel (LDS); use the slab schedule"};
       lds_max = std::max(lds_max, lds);

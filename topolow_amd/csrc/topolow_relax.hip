@@ -18,6 +18,7 @@
 #include <array>
 #include <atomic>
 #include <deque>
+#include <future>
 #include <mutex>
 #include <string>
 #include <memory>
@@ -33,6 +34,7 @@
 #include "relax_tilegs.h"
 #include "relax_symm.h"
 #include "relax_symm64.h"
+#include "relax_cv.h"
 
 using namespace topolow;
 
@@ -190,6 +192,7 @@ struct topolow_session {
   int cur = 0;
   bool host_seen_stop = false;
   bool began = false;
+  bool in_run = false;          // between topolow_session_begin and _finish
   long long stage_launches = 0;
   std::deque<hipEvent_t> pending;
   std::vector<hipEvent_t> event_pool;
@@ -213,6 +216,7 @@ struct topolow_session {
     int rec_cur = 0, rec_iter = -1;   // rec[rec_cur] holds the records of iteration rec_iter
     DevBuf<float> tdelta;          // f64: exact target - decoded word per cell of tenc: the fused check's MAE is exact
     bool delta_ready = false;
+    int generation = 0;            // counts the builds of the copy: a patch of it is only put back into the build it was made on
     // A sweep plan on the device (relax_symm.h: SymPlan): units, every wave's run of them, per tile-row its units.
     struct Plan {
       DevBuf<SymUnit> units;
@@ -266,6 +270,28 @@ struct topolow_session {
       inbox.release(); inbox_tab.release(); own0.release();
     }
   } sym;
+  // A fold held out of the resident block (topolow_session_hold_out, relax_cv.h): the pairs in session labels, what
+  // their cells held, and -- sessions that gather their edge list -- the full list, parked while the fold's compacted
+  // copy takes its place.
+  struct CvHold {
+    bool active = false;
+    long long n_pairs = 0;
+    DevBuf<int> lo, hi;
+    DevBuf<uint32_t> words;        // 2 per pair: the mirrors (lo, hi) and (hi, lo)
+    DevBuf<float> deltas;          // f64 delta tiles: 1 per pair
+    bool tiles_patched = false;    // the tile-major copy of build `generation` carries the patch
+    int generation = 0;
+    bool list_compacted = false;
+    DevBuf<int> ei, ej;            // the spare edge list: the compacted copy is written here, then swapped in
+    DevBuf<unsigned char> et;
+    DevBuf<int8_t> ec;
+    long long full_edges = 0;
+    int full_parts = 0;
+    DevBuf<int> blk_count;
+    DevBuf<long long> blk_offset;
+    DevBuf<int> sc_i, sc_j;        // topolow_session_score_pairs: the pairs, their truths, the partial sums
+    DevBuf<double> sc_t, sc_part;
+  } cv;
   int fused_parts = 0;             // partial sums the last ERR launch wrote (stage kernel: workgroups; sweep: units)
   // profiling (roofline accounting)
   bool profiling = false;
@@ -488,6 +514,14 @@ void launch_dense_error(topolow_session* s, const void* pos, const RunState* st)
   }
 }
 
+// Workgroups (= partial sums) of the edge-list MAE pass over n_edges edges.
+int edge_error_blocks(long long n_edges) {
+  long long blocks = (n_edges + (long long)kThreads * 8 - 1) / ((long long)kThreads * 8);
+  if (blocks < 1) blocks = 1;
+  if (blocks > 2048) blocks = 2048;
+  return (int)blocks;
+}
+
 // Number of partial sums the last launched error kernel produced.
 int error_parts(const topolow_session* s) { return s->dense_mae ? s->dense_blocks : s->n_parts; }
 
@@ -579,10 +613,8 @@ void download_positions(topolow_session* s, const void* src, double* host_colmaj
   }
 }
 
-void compute_row_flags(topolow_session* s) {
-  s->sym.ready = false;   // the encoded block changed: the symmetric sweep's copy is rebuilt on first use
-  s->sym.seg_ready = false;
-  s->rowflags.alloc(s->rows());
+// rowflags, any_threshold and block_cells of the block as it is now, into the buffers the session has.
+void scan_row_flags(topolow_session* s) {
   DevBuf<unsigned long long> measured;
   measured.alloc(1);
   HIP_TRY(hipMemsetAsync(measured.p, 0, sizeof(unsigned long long), s->stream));
@@ -597,10 +629,18 @@ void compute_row_flags(topolow_session* s) {
   for (unsigned char f : h) s->any_threshold = s->any_threshold || f != 0;
 }
 
+void compute_row_flags(topolow_session* s) {
+  s->cv.active = false;   // a new block: whatever was held out of the old one is gone with it
+  s->sym.ready = false;   // the encoded block changed: the symmetric sweep's copy is rebuilt on first use
+  s->sym.seg_ready = false;
+  s->rowflags.alloc(s->rows());
+  scan_row_flags(s);
+}
+
 void upload_degrees(topolow_session* s, const int32_t* degrees) {
   std::vector<float> g(s->n);
   for (int i = 0; i < s->n; ++i) g[i] = (float)degrees[s->perm.empty() ? i : s->perm[i]] + 1.0f;  // reference :137-140
-  s->gplus.alloc(s->n);
+  if (s->gplus.p == nullptr || s->gplus.n != (size_t)s->n) s->gplus.alloc(s->n);
   HIP_TRY(hipMemcpy(s->gplus.p, g.data(), (size_t)s->n * 4, hipMemcpyHostToDevice));
 }
 
@@ -797,6 +837,7 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
     s->part_cnt.alloc(y.plan.n_units);
   }
   y.rec_iter = -1;
+  y.generation += 1;
 }
 
 template <int DIM>
@@ -1191,6 +1232,76 @@ int nonfinite_report(int first_nonfinite, int ran, bool stopped) {
   return t <= ran && !(stopped && t == ran) ? t : 0;
 }
 
+// ---- a cross-validation fold on a resident session (relax_cv.h) ---------------------------
+template <typename T>
+void swap_buf(DevBuf<T>& a, DevBuf<T>& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); }
+
+template <typename T>
+void grow_buf(DevBuf<T>& b, size_t count) { if (b.p == nullptr || b.n < count) b.alloc(count); }
+
+unsigned pair_grid(long long n_pairs) { return (unsigned)((n_pairs + kThreads - 1) / kThreads); }
+
+// The device edge list without the edges whose cell carries kHeldMark: written to the spare list, swapped in.
+void cv_compact_edges(topolow_session* s) {
+  auto& h = s->cv;
+  const long long m = s->n_edges;
+  const int nb = (int)std::max<long long>(1, (m + kThreads - 1) / kThreads);
+  grow_buf(h.blk_count, (size_t)nb);
+  grow_buf(h.blk_offset, (size_t)nb + 1);
+  grow_buf(h.ei, (size_t)m); grow_buf(h.ej, (size_t)m); grow_buf(h.ec, (size_t)m);
+  grow_buf(h.et, (size_t)m * s->real_size());
+  hipLaunchKernelGGL(cv_edges_count_kernel, dim3(nb), dim3(kThreads), 0, s->stream, s->ei.p, s->ej.p, m, s->enc.p, s->ld,
+                     s->n, h.blk_count.p);
+  hipLaunchKernelGGL(cv_scan_kernel, dim3(1), dim3(1024), 0, s->stream, h.blk_count.p, nb, h.blk_offset.p);
+  if (s->precision == TOPOLOW_PRECISION_F64)
+    hipLaunchKernelGGL((cv_edges_compact_kernel<double>), dim3(nb), dim3(kThreads), 0, s->stream, s->ei.p, s->ej.p,
+                       (const double*)s->et.p, s->ec.p, m, s->enc.p, s->ld, s->n, h.blk_offset.p, h.ei.p, h.ej.p,
+                       (double*)h.et.p, h.ec.p);
+  else
+    hipLaunchKernelGGL((cv_edges_compact_kernel<float>), dim3(nb), dim3(kThreads), 0, s->stream, s->ei.p, s->ej.p,
+                       (const float*)s->et.p, s->ec.p, m, s->enc.p, s->ld, s->n, h.blk_offset.p, h.ei.p, h.ej.p,
+                       (float*)h.et.p, h.ec.p);
+  HIP_TRY(hipGetLastError());
+  long long kept = 0;
+  HIP_TRY(hipMemcpyAsync(&kept, h.blk_offset.p + nb, sizeof kept, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  swap_buf(s->ei, h.ei); swap_buf(s->ej, h.ej); swap_buf(s->et, h.et); swap_buf(s->ec, h.ec);
+  h.full_edges = m;
+  h.full_parts = s->n_parts;
+  s->n_edges = kept;
+  s->n_parts = edge_error_blocks(kept);
+  h.list_compacted = true;
+}
+
+// Flags, threshold bit and cell count of the patched block; a flipped threshold bit changes the sweep's kernel instance
+// and with it its grid and plan: the copy is rebuilt (from the block as it is now) on first use.
+void cv_refresh_flags(topolow_session* s) {
+  const bool before = s->any_threshold;
+  scan_row_flags(s);
+  if (s->any_threshold != before) {
+    s->sym.ready = false;
+    s->cv.tiles_patched = false;
+  }
+  s->sym.seg_ready = false;
+}
+
+int cv_check_session(const topolow_session* s, char* errbuf, size_t errlen) {
+  if (!(s->row_begin == 0 && s->row_end == s->n)) {
+    set_err(errbuf, errlen, "folds are held out of whole-problem sessions only (this one holds rows [%d, %d) of %d)",
+            s->row_begin, s->row_end, s->n);
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
+  if (!s->gplus.p || !s->part_sum.p) {
+    set_err(errbuf, errlen, "session needs its targets loaded and its edges set first");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (s->in_run) {
+    set_err(errbuf, errlen, "not during a run: between topolow_session_finish and the next topolow_session_begin only");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  return TOPOLOW_OK;
+}
+
 #include "relax_sharded_engine.h"
 
 }  // namespace
@@ -1458,15 +1569,13 @@ int topolow_session_set_edges(topolow_session* s, const int32_t* edge_i, const i
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
     s->n_edges = n_edges;
+    s->cv.list_compacted = false;
     if (s->precision == TOPOLOW_PRECISION_F64) {   // the f64 sweep's delta tiles are made from this list: rebuilt on first use
       s->sym.ready = false;
       s->sym.delta_ready = false;
     }
     const size_t m = (size_t)n_edges;
-    long long blocks = (n_edges + (long long)kThreads * 8 - 1) / ((long long)kThreads * 8);
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    s->n_parts = (int)blocks;
+    s->n_parts = edge_error_blocks(n_edges);
     // dense MAE pass: one workgroup per (column chunk, 64-row tile)
     s->dense_grid_x = (((s->n + 3) & ~3) + ErrCfg::CHUNK - 1) / ErrCfg::CHUNK;
     s->dense_grid_y = (s->rows() + kErrTileRows - 1) / kErrTileRows;
@@ -1623,6 +1732,7 @@ int topolow_session_begin(topolow_session* s, int32_t n_iter, double k0, double 
     s->pcheck.active = false;
     s->sym.rec_iter = -1;
     s->began = true;
+    s->in_run = true;
     RunState st;
     std::memset(&st, 0, sizeof st);
     st.ctl.init(k0, convergence_window, relative_epsilon);
@@ -1727,6 +1837,7 @@ int topolow_session_finish(topolow_session* s, double* positions_out, int32_t* c
                            char* errbuf, size_t errlen) {
   if (!s) return TOPOLOW_ERR_BAD_ARGUMENT;
   int rc_nonfinite = TOPOLOW_OK;
+  s->in_run = false;
   const int rc = guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
     flush_pending_check(s);
@@ -2211,6 +2322,356 @@ int topolow_cv_sweep(const topolow_cell_list* cells, int32_t named, int32_t pres
     error_code[f] = R[q].error_code;
     holdout_sum_abs[f] = R[q].holdout_sum_abs; holdout_count[f] = R[q].holdout_count;
     iterations[f] = R[q].iterations; converged[f] = R[q].converged;
+  }
+  return TOPOLOW_OK;
+}
+
+// ---- a cross-validation fold on a resident session (relax_cv.h) ---------------------------
+int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const int32_t* pair_j, int64_t n_pairs,
+                             const int32_t* degrees, char* errbuf, size_t errlen) {
+  if (!s || !degrees || n_pairs < 0 || (n_pairs > 0 && (!pair_i || !pair_j))) return TOPOLOW_ERR_BAD_ARGUMENT;
+  const int rc0 = cv_check_session(s, errbuf, errlen);
+  if (rc0 != TOPOLOW_OK) return rc0;
+  if (s->cv.active) {
+    set_err(errbuf, errlen, "a fold is held out already: topolow_session_restore_held_out first");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  for (int64_t q = 0; q < n_pairs; ++q)
+    if (pair_i[q] < 0 || pair_i[q] >= s->n || pair_j[q] < 0 || pair_j[q] >= s->n) {
+      set_err(errbuf, errlen, "held-out pair %lld out of range", (long long)q);
+      return TOPOLOW_ERR_BAD_ARGUMENT;
+    }
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(s->device));
+    auto& h = s->cv;
+    // session labels, lo < hi, every pair once (i == j: nothing to hold out)
+    std::vector<long long> key;
+    key.reserve((size_t)n_pairs);
+    for (int64_t q = 0; q < n_pairs; ++q) {
+      int a = pair_i[q], b = pair_j[q];
+      if (a == b) continue;
+      if (!s->inv.empty()) { a = s->inv[a]; b = s->inv[b]; }
+      key.push_back((long long)std::min(a, b) * s->n + std::max(a, b));
+    }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    const long long np = (long long)key.size();
+    std::vector<int> lo((size_t)np), hi((size_t)np);
+    for (long long q = 0; q < np; ++q) { lo[(size_t)q] = (int)(key[(size_t)q] / s->n); hi[(size_t)q] = (int)(key[(size_t)q] % s->n); }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipStreamSynchronize(s->check_stream));
+    // the sweep's copy is built from the FULL block once and patched fold after fold
+    if (sym_eligible(s)) (void)sym_available(s);
+    grow_buf(h.lo, (size_t)np); grow_buf(h.hi, (size_t)np); grow_buf(h.words, 2 * (size_t)np); grow_buf(h.deltas, (size_t)np);
+    h.n_pairs = np;
+    h.tiles_patched = false;
+    h.list_compacted = false;
+    const bool gathers = !s->dense_mae;
+    if (np > 0) {
+      HIP_TRY(hipMemcpyAsync(h.lo.p, lo.data(), (size_t)np * 4, hipMemcpyHostToDevice, s->stream));
+      HIP_TRY(hipMemcpyAsync(h.hi.p, hi.data(), (size_t)np * 4, hipMemcpyHostToDevice, s->stream));
+      hipLaunchKernelGGL(cv_mask_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np, s->enc.p,
+                         s->ld, h.words.p, gathers ? kHeldMark : kInfWord);
+      HIP_TRY(hipGetLastError());
+    }
+    if (gathers) {
+      cv_compact_edges(s);
+      if (np > 0)
+        hipLaunchKernelGGL(cv_mask_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
+                           s->enc.p, s->ld, (uint32_t*)nullptr, kInfWord);
+      HIP_TRY(hipGetLastError());
+    }
+    if (s->sym.ready && s->sym.whole) {
+      if (np > 0)
+        hipLaunchKernelGGL(cv_tiles_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
+                           s->sym.tenc.p, s->sym.delta_ready ? s->sym.tdelta.p : (float*)nullptr, s->sym.npad / kSymCols,
+                           (const uint32_t*)nullptr, h.deltas.p);
+      HIP_TRY(hipGetLastError());
+      h.tiles_patched = true;
+      h.generation = s->sym.generation;
+    } else if (s->sym.ready) {
+      s->sym.ready = false;
+    }
+    cv_refresh_flags(s);
+    upload_degrees(s, degrees);
+    HIP_TRY(hipStreamSynchronize(s->stream));   // (the host arrays of the pairs go out of scope)
+    h.active = true;
+  });
+}
+
+int topolow_session_restore_held_out(topolow_session* s, const int32_t* degrees, char* errbuf, size_t errlen) {
+  if (!s || !degrees) return TOPOLOW_ERR_BAD_ARGUMENT;
+  const int rc0 = cv_check_session(s, errbuf, errlen);
+  if (rc0 != TOPOLOW_OK) return rc0;
+  if (!s->cv.active) {
+    set_err(errbuf, errlen, "nothing is held out");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(s->device));
+    auto& h = s->cv;
+    const long long np = h.n_pairs;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipStreamSynchronize(s->check_stream));
+    if (np > 0)
+      hipLaunchKernelGGL(cv_unmask_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np, s->enc.p,
+                         s->ld, h.words.p);
+    HIP_TRY(hipGetLastError());
+    if (h.list_compacted) {
+      swap_buf(s->ei, h.ei); swap_buf(s->ej, h.ej); swap_buf(s->et, h.et); swap_buf(s->ec, h.ec);
+      s->n_edges = h.full_edges;
+      s->n_parts = h.full_parts;
+      h.list_compacted = false;
+    }
+    if (s->sym.ready && h.tiles_patched && h.generation == s->sym.generation) {
+      if (np > 0)
+        hipLaunchKernelGGL(cv_tiles_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
+                           s->sym.tenc.p, s->sym.delta_ready ? s->sym.tdelta.p : (float*)nullptr, s->sym.npad / kSymCols,
+                           (const uint32_t*)h.words.p, h.deltas.p);
+      HIP_TRY(hipGetLastError());
+    } else {
+      s->sym.ready = false;   // built from the fold's block meanwhile: rebuilt from the full one on first use
+    }
+    h.tiles_patched = false;
+    cv_refresh_flags(s);
+    upload_degrees(s, degrees);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    h.active = false;
+  });
+}
+
+int topolow_session_score_pairs(topolow_session* s, const int32_t* pair_i, const int32_t* pair_j, const double* truth,
+                                int64_t n_pairs, double* sum_abs, int64_t* count, char* errbuf, size_t errlen) {
+  if (!s || n_pairs < 0 || (n_pairs > 0 && (!pair_i || !pair_j || !truth))) return TOPOLOW_ERR_BAD_ARGUMENT;
+  if (!s->began) {
+    set_err(errbuf, errlen, "no run to score: the pairs are scored on the positions topolow_session_finish restores");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  for (int64_t q = 0; q < n_pairs; ++q)
+    if (pair_i[q] < 0 || pair_i[q] >= s->n || pair_j[q] < 0 || pair_j[q] >= s->n) {
+      set_err(errbuf, errlen, "scored pair %lld out of range", (long long)q);
+      return TOPOLOW_ERR_BAD_ARGUMENT;
+    }
+  if (sum_abs) *sum_abs = 0.0;
+  if (count) *count = 0;
+  if (n_pairs == 0) return TOPOLOW_OK;
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(s->device));
+    auto& h = s->cv;
+    const size_t np = (size_t)n_pairs;
+    const int blocks = (int)std::min<long long>(1024, (n_pairs + kThreads - 1) / kThreads);   // fixed by n_pairs alone
+    grow_buf(h.sc_i, np); grow_buf(h.sc_j, np); grow_buf(h.sc_t, np); grow_buf(h.sc_part, 1024);
+    std::vector<int> si, sj;
+    const int32_t* pi = pair_i;
+    const int32_t* pj = pair_j;
+    if (!s->inv.empty()) {
+      si.resize(np); sj.resize(np);
+      for (size_t q = 0; q < np; ++q) { si[q] = s->inv[pair_i[q]]; sj[q] = s->inv[pair_j[q]]; }
+      pi = si.data(); pj = sj.data();
+    }
+    HIP_TRY(hipMemcpyAsync(h.sc_i.p, pi, np * 4, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(h.sc_j.p, pj, np * 4, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(h.sc_t.p, truth, np * 8, hipMemcpyHostToDevice, s->stream));
+    if (s->precision == TOPOLOW_PRECISION_F64)
+      hipLaunchKernelGGL((cv_score_kernel<double>), dim3(blocks), dim3(kThreads), 0, s->stream, (const double*)s->best.p,
+                         s->dim, h.sc_i.p, h.sc_j.p, h.sc_t.p, (long long)n_pairs, h.sc_part.p);
+    else
+      hipLaunchKernelGGL((cv_score_kernel<float>), dim3(blocks), dim3(kThreads), 0, s->stream, (const float*)s->best.p,
+                         s->dim, h.sc_i.p, h.sc_j.p, h.sc_t.p, (long long)n_pairs, h.sc_part.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> part((size_t)blocks);
+    HIP_TRY(hipMemcpyAsync(part.data(), h.sc_part.p, (size_t)blocks * 8, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    double total = 0.0;
+    for (int b = 0; b < blocks; ++b) total += part[(size_t)b];
+    if (sum_abs) *sum_abs = total;
+    if (count) *count = n_pairs;
+  });
+}
+
+int32_t topolow_batch_problem_fits(int32_t n, int32_t ndim, int32_t precision, int64_t n_edges) {
+  if (n < 2 || ndim < 1 || ndim > kMaxTunedDim) return 0;
+  const int dim = kernel_dim(ndim);
+  const size_t rs = precision == TOPOLOW_PRECISION_F32 ? 4 : 8;   // AUTO: f64, as the batch call
+  // GsBatch::stage: the LDS-resident edge table when it fits its budget, the dense form otherwise
+  const bool sparse = n <= 2048 && n_edges > 0 && n_edges < 65535 && gs_lds_bytes(n, dim, rs, n_edges) <= kGsSparseLdsBudget;
+  return gs_lds_bytes(n, dim, rs, sparse ? n_edges : 0) <= kGsLdsLimit ? 1 : 0;
+}
+
+int topolow_cv_fold_pairs(const topolow_cell_list* cells, const int64_t* picks, int64_t n_picks, int32_t preserve_order,
+                          int32_t named, int32_t* order, int32_t* degrees, double* numeric_max, int64_t* n_edges,
+                          int32_t* pair_i, int32_t* pair_j, int64_t* n_pairs, int32_t* score_i, int32_t* score_j,
+                          double* score_truth, int64_t* n_scored, char* errbuf, size_t errlen) {
+  if (!cells || (!picks && n_picks > 0) || !order || !degrees || !numeric_max || !n_edges || !pair_i || !pair_j ||
+      !n_pairs || !score_i || !score_j || !score_truth || !n_scored)
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  int rc = TOPOLOW_OK;
+  const int rcg = guarded(errbuf, errlen, [&] {
+    if (!fold_cells_symmetric(cells))
+      throw HipError{TOPOLOW_ERR_UNSUPPORTED, kAsymmetricCells};
+    FoldPairs fp;
+    rc = fold_pairs(cells, picks, n_picks, preserve_order, named, fp);
+    if (rc != TOPOLOW_OK) return;
+    std::copy(fp.order.begin(), fp.order.end(), order);
+    std::copy(fp.degrees.begin(), fp.degrees.end(), degrees);
+    *numeric_max = fp.numeric_max;
+    *n_edges = fp.n_edges;
+    std::copy(fp.pair_i.begin(), fp.pair_i.end(), pair_i);
+    std::copy(fp.pair_j.begin(), fp.pair_j.end(), pair_j);
+    *n_pairs = (int64_t)fp.pair_i.size();
+    std::copy(fp.score_i.begin(), fp.score_i.end(), score_i);
+    std::copy(fp.score_j.begin(), fp.score_j.end(), score_j);
+    std::copy(fp.score_truth.begin(), fp.score_truth.end(), score_truth);
+    *n_scored = (int64_t)fp.score_i.size();
+  });
+  return rcg != TOPOLOW_OK ? rcg : rc;
+}
+
+// The sweep of topolow_cv_sweep on resident sessions: one session per ndim, loaded once with the full matrix; a fold is
+// held out of it, run, scored on the device and put back.  The next fold is prepared on a host thread meanwhile.
+int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int32_t preserve_order, int32_t n_folds,
+                             const int32_t* ndim, const double* k0, const double* cooling_rate, const double* c_repulsion,
+                             const int64_t* picks, const int64_t* picks_offset, const double* unit_draws,
+                             const int64_t* draws_offset, const uint64_t* seeds, int32_t n_iter, double relative_epsilon,
+                             int32_t convergence_window, int32_t convergence_check_freq, int32_t precision, int32_t device,
+                             int32_t schedule, double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations,
+                             int32_t* converged, int32_t* error_code, double* device_seconds, char* errbuf, size_t errlen) {
+  if (!cells || n_folds < 0 || (n_folds > 0 && (!ndim || !k0 || !cooling_rate || !c_repulsion || !picks_offset ||
+      !unit_draws || !draws_offset || !seeds || !holdout_sum_abs || !holdout_count || !iterations || !converged ||
+      !error_code)))
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  if (schedule != TOPOLOW_SCHEDULE_AUTO && schedule != TOPOLOW_SCHEDULE_SLAB && schedule != TOPOLOW_SCHEDULE_GS)
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  if (device_seconds) *device_seconds = 0.0;
+  if (n_folds == 0) return TOPOLOW_OK;
+  const int n = cells->n;
+  const bool tile_gs = schedule == TOPOLOW_SCHEDULE_GS;
+  const int prec = precision == TOPOLOW_PRECISION_AUTO ? (tile_gs ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32) : precision;
+  struct Prep {
+    int rc = TOPOLOW_OK;
+    FoldPairs fp;
+    std::vector<double> pos;   // start positions, n x ndim column-major, caller's labels
+  };
+  auto prepare = [&](int f) {
+    auto p = std::make_unique<Prep>();
+    try {
+      p->rc = fold_pairs(cells, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named, p->fp);
+      const double vmax = p->fp.numeric_max;
+      if (p->rc == TOPOLOW_OK && (p->fp.n_edges == 0 || !(vmax == vmax))) p->rc = TOPOLOW_ERR_BAD_ARGUMENT;   // no valid measurements
+      const int d_ = ndim[f];
+      if (p->rc == TOPOLOW_OK && (d_ < 1 || draws_offset[f + 1] - draws_offset[f] != (int64_t)d_ * (n - 1)))
+        p->rc = TOPOLOW_ERR_BAD_ARGUMENT;
+      if (p->rc != TOPOLOW_OK) return p;
+      // the random walk of topolow_cv_sweep, point i of the fold's order = the caller's point order[i]
+      const double* u = unit_draws + draws_offset[f];             // (ndim, n - 1), row-major
+      const double step = vmax / (double)n;
+      const bool reordered = p->fp.order[0] >= 0;
+      p->pos.assign((size_t)n * d_, 0.0);
+      for (int d = 0; d < d_; ++d) {
+        double acc = 0.0;
+        for (int i = 1; i < n; ++i) {
+          const double st_ = 0.0 + (2.0 * step - 0.0) * u[(size_t)d * (n - 1) + (i - 1)];   // Generator.uniform's arithmetic
+          acc = i == 1 ? st_ : acc + st_;                         // cumsum
+          p->pos[(size_t)(reordered ? p->fp.order[i] : i) + (size_t)d * n] = acc;
+        }
+      }
+    } catch (const std::bad_alloc&) {
+      p->rc = TOPOLOW_ERR_HIP;
+    }
+    return p;
+  };
+  // the full matrix as the sessions load it: the upper triangle of the (symmetric) list, its degrees
+  std::vector<int32_t> fi, fj, ft, fdeg((size_t)n);
+  std::vector<double> fd;
+  const int rc_list = guarded(errbuf, errlen, [&] {
+    if (n < 2) throw HipError{TOPOLOW_ERR_TOO_FEW_POINTS, "Need at least 2 points for embedding"};
+    if (!fold_cells_symmetric(cells)) throw HipError{TOPOLOW_ERR_UNSUPPORTED, kAsymmetricCells};
+    for (int i = 0; i < n; ++i) fdeg[(size_t)i] = (int32_t)(cells->row_ptr[i + 1] - cells->row_ptr[i]);
+    for (int64_t q = 0; q < cells->n_cells; ++q)
+      if (cells->row[q] < cells->col[q]) {
+        fi.push_back(cells->row[q]); fj.push_back(cells->col[q]); fd.push_back(cells->value[q]); ft.push_back(cells->code[q]);
+      }
+  });
+  if (rc_list != TOPOLOW_OK) return rc_list;
+  for (int f = 0; f < n_folds; ++f) {
+    holdout_sum_abs[f] = 0.0; holdout_count[f] = 0; iterations[f] = 0; converged[f] = 0;
+    error_code[f] = TOPOLOW_OK;
+  }
+  std::vector<char> done((size_t)n_folds, 0);
+  for (int g0 = 0; g0 < n_folds; ++g0) {
+    if (done[(size_t)g0]) continue;
+    std::vector<int> members;   // the folds that share this ndim, in the caller's order
+    for (int f = g0; f < n_folds; ++f)
+      if (!done[(size_t)f] && ndim[f] == ndim[g0]) { members.push_back(f); done[(size_t)f] = 1; }
+    if (ndim[g0] < 1) {
+      for (int f : members) error_code[f] = TOPOLOW_ERR_BAD_ARGUMENT;
+      continue;
+    }
+    topolow_session* s = nullptr;
+    int rc = topolow_session_create(&s, n, ndim[g0], 0, n, prec, device, errbuf, errlen);
+    if (rc != TOPOLOW_OK) return rc;
+    std::future<std::unique_ptr<Prep>> next = std::async(std::launch::async, prepare, members[0]);
+    bool next_valid = true;
+    do {
+      if (tile_gs) {
+        if (ndim[g0] > kMaxTunedDim) {
+          set_err(errbuf, errlen, "schedule gs: ndim must be between 1 and %d (wider embeddings run the slab schedule)", kMaxTunedDim);
+          rc = TOPOLOW_ERR_UNSUPPORTED;
+          break;
+        }
+        rc = topolow_session_set_schedule(s, TOPOLOW_SCHEDULE_GS);
+        if (rc) break;
+      }
+      rc = topolow_session_set_relabel(s, mix64(seeds[members[0]] ^ 0x1abe15eedull) | 1ull, errbuf, errlen);
+      if (rc) break;
+      rc = topolow_session_load_coo(s, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), fdeg.data(), errbuf, errlen);
+      if (rc) break;
+      rc = topolow_session_set_edges(s, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), errbuf, errlen);
+      if (rc) break;
+      for (size_t q = 0; q < members.size() && rc == TOPOLOW_OK; ++q) {
+        const int f = members[q];
+        std::unique_ptr<Prep> p = next.get();
+        next_valid = false;
+        if (q + 1 < members.size()) { next = std::async(std::launch::async, prepare, members[q + 1]); next_valid = true; }
+        error_code[f] = p->rc;
+        if (p->rc != TOPOLOW_OK) continue;
+        const FoldPairs& fp = p->fp;
+        rc = topolow_session_hold_out(s, fp.pair_i.data(), fp.pair_j.data(), (int64_t)fp.pair_i.size(), fp.degrees.data(),
+                                      errbuf, errlen);
+        if (rc) break;
+        const double t0 = now_s();
+        int rcf = topolow_session_set_positions(s, p->pos.data(), errbuf, errlen);
+        if (rcf == TOPOLOW_OK)
+          rcf = topolow_session_begin(s, n_iter, k0[f], cooling_rate[f], c_repulsion[f], relative_epsilon, convergence_window,
+                                      convergence_check_freq, seeds[f], 0, errbuf, errlen);
+        while (rcf == TOPOLOW_OK) {   // 50 iterations at a time, the one-shot loop's cadence
+          int enq = 0;
+          rcf = topolow_session_enqueue(s, 50, &enq, errbuf, errlen);
+          if (rcf || enq == 0) break;
+        }
+        if (rcf == TOPOLOW_OK)
+          rcf = topolow_session_finish(s, nullptr, &converged[f], &iterations[f], nullptr, nullptr, errbuf, errlen);
+        else
+          (void)topolow_session_finish(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);   // the run is over either way
+        if (device_seconds) *device_seconds += now_s() - t0;
+        if (rcf == TOPOLOW_OK)
+          rcf = topolow_session_score_pairs(s, fp.score_i.data(), fp.score_j.data(), fp.score_truth.data(),
+                                            (int64_t)fp.score_i.size(), &holdout_sum_abs[f], &holdout_count[f], errbuf, errlen);
+        // the session is the full matrix again before the next fold starts, whatever this one did
+        char rerr[256] = "";
+        const int rcr = topolow_session_restore_held_out(s, fdeg.data(), rerr, sizeof rerr);
+        if (rcf == TOPOLOW_ERR_NONFINITE) {   // a diverged fold is this fold's result, not the call's
+          error_code[f] = TOPOLOW_ERR_NONFINITE;
+          iterations[f] = 0; converged[f] = 0;
+          rcf = TOPOLOW_OK;
+        }
+        if (rcf != TOPOLOW_OK) { rc = rcf; break; }
+        if (rcr != TOPOLOW_OK) { set_err(errbuf, errlen, "%s", rerr); rc = rcr; break; }
+      }
+    } while (0);
+    if (next_valid) (void)next.get();
+    topolow_session_destroy(s);
+    if (rc != TOPOLOW_OK) return rc;
   }
   return TOPOLOW_OK;
 }

@@ -328,7 +328,7 @@ def _pooled(per_set):
     for rows in per_set:
         rows = [r for r in rows if r["n_samples"] > 0]
         if not rows:
-            out.append(dict(Holdout_MAE=math.nan, NLL=math.nan, mean_iter=math.nan, pct_converged=math.nan, fold_mae=[]))
+            out.append(dict(Holdout_MAE=math.nan, NLL=math.nan, mean_iter=math.nan, pct_converged=math.nan, fold_mae=[], fold_n_samples=[]))
             continue
         total = sum(r["n_samples"] for r in rows)
         tot_err = sum(r["sum_abs_errors"] for r in rows)
@@ -336,13 +336,17 @@ def _pooled(per_set):
         nll = total * (1 + math.log(2 * mae)) if not math.isnan(mae) and mae > 0 else math.nan
         out.append(dict(Holdout_MAE=mae, NLL=nll, mean_iter=float(np.mean([r["iter"] for r in rows])),
                         pct_converged=100.0 * float(np.mean([r["converged"] for r in rows])),
-                        fold_mae=[r["sum_abs_errors"] / r["n_samples"] for r in rows]))
+                        fold_mae=[r["sum_abs_errors"] / r["n_samples"] for r in rows],
+                        fold_n_samples=[r["n_samples"] for r in rows]))
     return out
 
 
 def _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon, preserve_order,
-                          precision, convergence_counter: int = 5):
-    """The sweep as ONE library call.  Draws from `rng` exactly what the fold-by-fold loop draws when no fold fails
+                          precision, convergence_counter: int = 5, session: Optional[bool] = None,
+                          schedule: str = "auto"):
+    """The sweep as ONE library call: the batch (topolow_cv_sweep), or -- session = True, or None and a fold does not
+    fit the batch kernel's one workgroup -- resident sessions (topolow_cv_sweep_session; a fold without valid
+    measurements is then left out instead of handing the sweep back).  Draws from `rng` exactly what the fold-by-fold loop draws when no fold fails
     (per set: the fold picks, then per fold its start positions' numbers; then one seed per fold); returns None --
     with the stream spent, the caller rewinds it -- when a fold has no valid measurements, because such a fold draws
     nothing in the reference's order."""
@@ -365,11 +369,19 @@ def _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, 
                 nd.append(int(ps["N"])); k0.append(float(ps["k0"])); cr.append(float(ps["cooling_rate"]))
                 cp.append(float(ps["c_repulsion"]))
     seeds = [int(rng.integers(0, 2 ** 63 - 1)) for _ in picks]
-    hsum, hcnt, its, conv, ec, secs = _native.cv_sweep(builder.cells(), m.names is not None, preserve_order, nd, k0, cr, cp,
-                                                       picks, draws, seeds, mapping_max_iter, relative_epsilon,
-                                                       convergence_counter, 3, precision)
-    if np.any(ec == _native.ERR_BAD_ARGUMENT):
-        return None
+    if session is None:
+        n_edges = int(np.sum(builder.rows < builder.cols))
+        session = not all(_native.batch_problem_fits(n, d, precision or "f64", n_edges) for d in set(nd))
+    if session:
+        hsum, hcnt, its, conv, ec, secs = _native.cv_sweep_session(
+            builder.cells(), m.names is not None, preserve_order, nd, k0, cr, cp, picks, draws, seeds, mapping_max_iter,
+            relative_epsilon, convergence_counter, 3, precision or "auto", schedule=schedule)
+    else:
+        hsum, hcnt, its, conv, ec, secs = _native.cv_sweep(builder.cells(), m.names is not None, preserve_order, nd, k0, cr,
+                                                           cp, picks, draws, seeds, mapping_max_iter, relative_epsilon,
+                                                           convergence_counter, 3, precision or "f64")
+        if np.any(ec == _native.ERR_BAD_ARGUMENT):
+            return None
     per_set: List[List[dict]] = [[] for _ in param_sets]
     for f, owner in enumerate(owners):
         if ec[f] != _native.OK:
@@ -381,8 +393,8 @@ def _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, 
 
 def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]], mapping_max_iter: int,
                      relative_epsilon: float, folds: int = 20, preserve_order: bool = False,
-                     rng: Optional[np.random.Generator] = None, precision: str = "f64",
-                     path: str = "sparse", convergence_counter: int = 5):
+                     rng: Optional[np.random.Generator] = None, precision: Optional[str] = None,
+                     path: str = "sparse", convergence_counter: int = 5, schedule: str = "auto"):
     """`likelihood_function` for MANY parameter sets at once: all folds of all sets are relaxed
     in ONE batched launch, and the held-out cells are scored on the device (no est_distances, no
     n x n arrays).  param_sets: dicts with N (ndim), k0, cooling_rate, c_repulsion.
@@ -390,12 +402,20 @@ def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]
     threads from the picks and the start positions' unit draws, one batch, only the scores come back);
     "sparse-calls" builds one call object per fold here and relaxes them with optimize_layout_exact_batch -- same
     draws, same seeds, same numbers (tests/test_gpu_assays.py);
+    A matrix too large for one workgroup (_native.batch_problem_fits: about 2 900 points in f64 at ndim 5) is routed
+    from "sparse" to the session sweep below instead of raising;
+    path = "session" runs the sweep on device-resident sessions whatever the size (topolow_cv_sweep_session: one session
+    per ndim holds the full matrix, a fold is held out of it on the device, run, scored there and put back; `schedule`
+    "auto" / "slab": the slab schedule, "gs": tile Gauss-Seidel; the matrix must be symmetric).  It draws from `rng`
+    exactly what "sparse" draws, so the stream is left in the same place;
+    precision: None = "f64" on the batch paths and, on sessions, f32 for the slab schedule / f64 for "gs";
     path = "dense" runs the reference's own sequence per fold instead (masked n x n matrix ->
     prepare_layout_call -> est_distances -> error_calculator_comparison): same folds, same start
     positions, same pooled numbers; kept as the cross-check.
     convergence_counter: 5 is what likelihood_function passes (R/adaptive_sampling.R:2620-2631); the reference's
     notebooks run the same folds with 3 (inst/examples/methods-comparison-h3n2-hiv-denv.Rmd:1894-1902).
-    Each result dict carries likelihood_function's four fields plus `fold_mae` (mean |error| per fold).
+    Each result dict carries likelihood_function's four fields plus `fold_mae` (mean |error| per fold) and
+    `fold_n_samples` (scored cells per fold).
     Returns (list of result dicts, device_seconds, embeddings)."""
     rng = rng if rng is not None else _native.host_rng()
     if not hasattr(rng, "choice"):   # R-stream generator: fold sampling uses a NumPy stream seeded from it
@@ -403,20 +423,22 @@ def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]
     m = core.coded_matrix(dissimilarity_matrix)   # strings are parsed once, not once per fold
     if m is None:
         raise ValueError("dissimilarity_matrix must be a matrix")
-    if path not in ("sparse", "sparse-calls", "dense"):
-        raise ValueError("path must be 'sparse', 'sparse-calls' or 'dense'")
+    if path not in ("sparse", "sparse-calls", "dense", "session"):
+        raise ValueError("path must be 'sparse', 'sparse-calls', 'dense' or 'session'")
     builder = FoldBuilder(m) if path != "dense" else None
     if builder is not None:      # the matrix half of R/core.R:202-264 once; per set only the parameters
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             core._validate(m, 2, 1, 1.0, 0.5, 1.0, 1.0, 1, 1, None)
     state0 = rng.bit_generator.state
-    if path == "sparse":
+    if path in ("sparse", "session"):
         fused = _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon,
-                                      preserve_order, precision, convergence_counter)
+                                      preserve_order, precision, convergence_counter,
+                                      session=True if path == "session" else None, schedule=schedule)
         if fused is not None:
             return fused
         rng.bit_generator.state = state0      # a fold failed: the fold-by-fold order of draws decides (below)
+    precision = precision or "f64"
     try:
         calls, owners, inputs, holds = build_fold_calls(
             m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon, preserve_order,
@@ -503,4 +525,4 @@ def likelihood_function(dissimilarity_matrix, mapping_max_iter, relative_epsilon
     res, _, _ = likelihood_sweep(dissimilarity_matrix,
                                  [dict(N=N, k0=k0, cooling_rate=cooling_rate, c_repulsion=c_repulsion)],
                                  mapping_max_iter, relative_epsilon, folds, preserve_order)
-    return {k: v for k, v in res[0].items() if k != "fold_mae"}      # the reference's four fields
+    return {k: v for k, v in res[0].items() if k not in ("fold_mae", "fold_n_samples")}      # the reference's four fields

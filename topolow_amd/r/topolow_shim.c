@@ -11,6 +11,7 @@
  *     _topolow_cv_fold                      one fold's payload from the list of non-NA cells
  *                                           (R/adaptive_sampling.R:2608-2616 + R/core.R:269-436)
  *     _topolow_cv_sweep                     all folds of all parameter sets in one call: per-fold out-of-sample scores
+ *     _topolow_cv_sweep_session             the same sweep on device-resident sessions: matrices beyond one workgroup
  *     _topolow_est_distances                as.matrix(dist(positions))  (R/core.R:474)
  *     _topolow_est_distances_cols           a block of its columns, for n x n results too large to hold
  *
@@ -403,7 +404,9 @@ static SEXP cv_sweep_args(SEXP a) {
   return out;
 }
 
-SEXP _topolow_cv_sweep(SEXP arg) {
+/* The sweep of both entries: session == 0: topolow_cv_sweep (one batch); otherwise topolow_cv_sweep_session with
+ * `schedule`. */
+static SEXP cv_sweep_run(SEXP arg, int session, int schedule) {
   SEXP a = PROTECT(cv_sweep_args(arg));
 #define CV_SWEEP_FAIL(msg) do { UNPROTECT(1); Rf_error(msg); } while (0)
   SEXP row = VECTOR_ELT(a, 0), col = VECTOR_ELT(a, 1), value = VECTOR_ELT(a, 2), code = VECTOR_ELT(a, 3);
@@ -446,17 +449,25 @@ SEXP _topolow_cv_sweep(SEXP arg) {
   double secs = 0.0;
   char err[512];
   err[0] = 0;
+  /* precision unset: f64 for the batch; on sessions f32 for the slab schedule, f64 for "gs" (the library's AUTO) */
   const int precision = opt_choice("topolow.precision", "f32", TOPOLOW_PRECISION_F32, "f64", TOPOLOW_PRECISION_F64,
-                                   TOPOLOW_PRECISION_F64);
-  const int rc = topolow_cv_sweep(&cells, Rf_asLogical(VECTOR_ELT(a, 5)), Rf_asLogical(VECTOR_ELT(a, 6)), F, INTEGER(ndim),
-                                  REAL(k0), REAL(cool), REAL(crep), picks, p_off, REAL(VECTOR_ELT(a, 13)), d_off, seeds,
-                                  Rf_asInteger(VECTOR_ELT(a, 16)), Rf_asReal(VECTOR_ELT(a, 17)),
-                                  Rf_asInteger(VECTOR_ELT(a, 18)), Rf_asInteger(VECTOR_ELT(a, 19)), precision,
-                                  opt_int("topolow.device", -1), REAL(hs), hcount, INTEGER(it), INTEGER(cv), INTEGER(ec),
-                                  &secs, err, sizeof err);
+                                   session ? TOPOLOW_PRECISION_AUTO : TOPOLOW_PRECISION_F64);
+  const int rc =
+      session ? topolow_cv_sweep_session(&cells, Rf_asLogical(VECTOR_ELT(a, 5)), Rf_asLogical(VECTOR_ELT(a, 6)), F,
+                                         INTEGER(ndim), REAL(k0), REAL(cool), REAL(crep), picks, p_off,
+                                         REAL(VECTOR_ELT(a, 13)), d_off, seeds, Rf_asInteger(VECTOR_ELT(a, 16)),
+                                         Rf_asReal(VECTOR_ELT(a, 17)), Rf_asInteger(VECTOR_ELT(a, 18)),
+                                         Rf_asInteger(VECTOR_ELT(a, 19)), precision, opt_int("topolow.device", -1), schedule,
+                                         REAL(hs), hcount, INTEGER(it), INTEGER(cv), INTEGER(ec), &secs, err, sizeof err)
+              : topolow_cv_sweep(&cells, Rf_asLogical(VECTOR_ELT(a, 5)), Rf_asLogical(VECTOR_ELT(a, 6)), F, INTEGER(ndim),
+                                 REAL(k0), REAL(cool), REAL(crep), picks, p_off, REAL(VECTOR_ELT(a, 13)), d_off, seeds,
+                                 Rf_asInteger(VECTOR_ELT(a, 16)), Rf_asReal(VECTOR_ELT(a, 17)),
+                                 Rf_asInteger(VECTOR_ELT(a, 18)), Rf_asInteger(VECTOR_ELT(a, 19)), precision,
+                                 opt_int("topolow.device", -1), REAL(hs), hcount, INTEGER(it), INTEGER(cv), INTEGER(ec),
+                                 &secs, err, sizeof err);
   if (rc != TOPOLOW_OK) {
     UNPROTECT(7);
-    Rf_error("%s", err[0] ? err : "topolow_cv_sweep failed");
+    Rf_error("%s", err[0] ? err : (session ? "topolow_cv_sweep_session failed" : "topolow_cv_sweep failed"));
   }
   for (int f = 0; f < F; ++f) REAL(hc)[f] = (double)hcount[f];
   SET_VECTOR_ELT(out, 0, hs); SET_VECTOR_ELT(out, 1, hc); SET_VECTOR_ELT(out, 2, it); SET_VECTOR_ELT(out, 3, cv);
@@ -464,6 +475,25 @@ SEXP _topolow_cv_sweep(SEXP arg) {
   UNPROTECT(7);
 #undef CV_SWEEP_FAIL
   return out;
+}
+
+SEXP _topolow_cv_sweep(SEXP arg) { return cv_sweep_run(arg, 0, TOPOLOW_SCHEDULE_AUTO); }
+
+/* The same sweep on device-resident sessions (topolow_cv_sweep_session): for matrices beyond one workgroup
+ * (topolow_batch_problem_fits; _topolow_cv_sweep stops with "problem too large ..." there).  The list of
+ * _topolow_cv_sweep plus schedule: "auto" / "slab" (the slab schedule) or "gs" (tile Gauss-Seidel).  The matrix must be
+ * symmetric.  Same returned list. */
+SEXP _topolow_cv_sweep_session(SEXP arg, SEXP scheduleSEXP) {
+  int schedule = TOPOLOW_SCHEDULE_AUTO;
+  if (Rf_isString(scheduleSEXP) && Rf_length(scheduleSEXP) == 1) {
+    const char* s = CHAR(STRING_ELT(scheduleSEXP, 0));
+    if (strcmp(s, "slab") == 0) schedule = TOPOLOW_SCHEDULE_SLAB;
+    else if (strcmp(s, "gs") == 0) schedule = TOPOLOW_SCHEDULE_GS;
+    else if (strcmp(s, "auto") != 0) Rf_error("schedule must be \"auto\", \"slab\" or \"gs\"");
+  } else if (scheduleSEXP != R_NilValue) {
+    Rf_error("schedule must be one string");
+  }
+  return cv_sweep_run(arg, 1, schedule);
 }
 
 /* Optional: as.matrix(dist(positions)) on the GPU (reference R/core.R:474). */
@@ -505,6 +535,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_topolow_optimize_layout_exact_batch", (DL_FUNC)&_topolow_optimize_layout_exact_batch, 1},
     {"_topolow_cv_fold", (DL_FUNC)&_topolow_cv_fold, 8},
     {"_topolow_cv_sweep", (DL_FUNC)&_topolow_cv_sweep, 1},
+    {"_topolow_cv_sweep_session", (DL_FUNC)&_topolow_cv_sweep_session, 2},
     {"_topolow_est_distances", (DL_FUNC)&_topolow_est_distances, 1},
     {"_topolow_est_distances_cols", (DL_FUNC)&_topolow_est_distances_cols, 3},
     {NULL, NULL, 0}};
