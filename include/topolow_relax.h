@@ -614,6 +614,24 @@ int32_t topolow_slab_stages_for_k(double k, int32_t ndim);
  * TOPOLOW_SYMMETRIC_TWO_STAGE=0 keeps the row-owner stages. */
 int32_t topolow_symm_stage_bounds(int32_t n, int32_t stages, int32_t* first_label);
 int32_t topolow_symm_stage_order(uint64_t seed, int32_t iter, int32_t stages, int32_t* order);
+/* Host only: per tile-row R (64 points) of an n-point problem, what stage `stage` of a `stages`-stage iteration sweeps
+ * and sums -- rows_out[4 R ..] = (j0, j1, rp0, rp1): the column blocks [j0, j1) of 32 points that the stage sweeps in
+ * tile-row R (empty when j0 >= j1), and the tile-rows [rp0, rp1) whose column sums of that stage belong to the points
+ * of tile-row R.  Returns the number of tile-rows (rows_out may be NULL), -1 where topolow_symm_stage_bounds gives 0. */
+int32_t topolow_symm_stage_rows(int32_t n, int32_t stages, int32_t stage, int32_t* rows_out);
+/* Host only: the plan the symmetric sweep of an n-point problem loads for a grid of n_waves waves (4 per workgroup) --
+ *   stages == 0, n_segments <= 1   the whole upper triangle;
+ *   stages in {2, 4, 8}            the tiles of stage `stage` (n_segments <= 1);
+ *   n_segments >= 2                segment `segment` of the sharded sweep: tiles [total b / P, total (b + 1) / P).
+ * units_out: 4 int32 per unit (tile_row, j0, j1, tile0): the column blocks [j0, j1) of tile-row tile_row, the first of
+ * them at index tile0 of the plan's tile-major copy; at most max_units units are written.  wave_first_out: n_waves + 1
+ * entries, wave w sweeps the units [wave_first[w], wave_first[w + 1]).  Either may be NULL (to size the other).
+ * Returns the number of units, -1 for arguments no session would plan with. */
+int32_t topolow_symm_plan(int32_t n, int32_t n_waves, int32_t stages, int32_t stage, int32_t segment, int32_t n_segments,
+                          int32_t* units_out, int32_t max_units, int32_t* wave_first_out);
+/* Workgroups of the symmetric sweep this session has built (whole triangle or segment), 0 if none: one resident round
+ * of the device, or fewer under TOPOLOW_SYMMETRIC_GRID (a test knob). */
+int32_t topolow_session_symm_grid(const topolow_session* s);
 /* Stage count of iteration `iter` (0-based) when slab_stages = 0: the policy above, and at least 16 stages
  * during the first 8 iterations, while the layout unfolds from its start. */
 int32_t topolow_slab_stages_at(int32_t iter, double k, int32_t ndim);

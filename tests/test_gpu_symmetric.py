@@ -151,9 +151,11 @@ def _with_thresholds(call, frac, seed=3):
     return call
 
 
-def _symmetric_session(call, n, dim, iters, k0, cooling, c_rep, check_freq, profile, relabel=0, precision="f32"):
-    """A whole-matrix session forced onto the symmetric sweep: ONE stage per iteration, no early stop."""
-    with _Env(TOPOLOW_SYMMETRIC="1", TOPOLOW_SYMMETRIC_MIN_N="0"):
+def _symmetric_session(call, n, dim, iters, k0, cooling, c_rep, check_freq, profile, relabel=0, precision="f32", env=None,
+                       after_run=None):
+    """A whole-matrix session forced onto the symmetric sweep: ONE stage per iteration, no early stop.  env: further
+    variables the session is created under; after_run(session): looks at the session before it is closed."""
+    with _Env(TOPOLOW_SYMMETRIC="1", TOPOLOW_SYMMETRIC_MIN_N="0", **(env or {})):
         s = _native.Session(n, dim, precision=precision)
     if relabel:
         s.set_relabel(relabel)
@@ -167,6 +169,8 @@ def _symmetric_session(call, n, dim, iters, k0, cooling, c_rep, check_freq, prof
     pos = s.get_positions()
     trace = s.check_trace()
     counts = s.profile_symmetric() if profile else None
+    if after_run is not None:
+        after_run(s)
     s.close()
     return pos, trace, counts
 

@@ -229,6 +229,12 @@ def load() -> C.CDLL:
     lib.topolow_symm_stage_bounds.argtypes = [C.c_int32, C.c_int32, ip]
     lib.topolow_symm_stage_order.restype = C.c_int32
     lib.topolow_symm_stage_order.argtypes = [C.c_uint64, C.c_int32, C.c_int32, ip]
+    lib.topolow_symm_stage_rows.restype = C.c_int32
+    lib.topolow_symm_stage_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip]
+    lib.topolow_symm_plan.restype = C.c_int32
+    lib.topolow_symm_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, ip]
+    lib.topolow_session_symm_grid.restype = C.c_int32
+    lib.topolow_session_symm_grid.argtypes = [vp]
     lib.topolow_symm_segment_rows.restype = C.c_int32
     lib.topolow_symm_segment_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip]
     lib.topolow_session_has_thresholds.restype = C.c_int32
@@ -642,6 +648,34 @@ def symm_stage_order(seed: int, it: int, stages: int):
     return out.tolist()
 
 
+def symm_stage_rows(n: int, stages: int, stage: int):
+    """Per tile-row R the int32 row (j0, j1, rp0, rp1): the column blocks stage `stage` of a `stages`-stage iteration
+    sweeps in R and the tile-rows whose column sums it adds to R's points; None where the problem is too small
+    (topolow_symm_stage_rows; host only)."""
+    lib = load()
+    tr = lib.topolow_symm_stage_rows(int(n), int(stages), int(stage), None)
+    if tr < 0:
+        return None
+    out = np.zeros((tr, 4), dtype=np.int32)
+    assert lib.topolow_symm_stage_rows(int(n), int(stages), int(stage), _ip(out)) == tr
+    return out
+
+
+def symm_plan(n: int, n_waves: int, stages: int = 0, stage: int = 0, segment: int = 0, n_segments: int = 1):
+    """The symmetric sweep's plan for a grid of n_waves waves: (units[n_units, 4] = (tile_row, j0, j1, tile0),
+    wave_first[n_waves + 1]) of the whole triangle, of one stage of a 2-, 4- or 8-stage iteration, or of one segment of
+    the sharded sweep (topolow_symm_plan; host only)."""
+    lib = load()
+    args = (int(n), int(n_waves), int(stages), int(stage), int(segment), int(n_segments))
+    n_units = lib.topolow_symm_plan(*args, None, 0, None)
+    if n_units < 0:
+        raise ValueError("symm_plan: no such plan for %r" % (args,))
+    units = np.zeros((n_units, 4), dtype=np.int32)
+    wave_first = np.zeros(int(n_waves) + 1, dtype=np.int32)
+    assert lib.topolow_symm_plan(*args, _ip(units), n_units, _ip(wave_first)) == n_units
+    return units, wave_first
+
+
 def symm_segment_rows(n: int, segment: int, n_segments: int):
     """Rows (first, end) of the matrix that hold segment `segment` of `n_segments` of the symmetric sweep's tile list;
     None when a problem of n points has too few tiles to cut (topolow_symm_segment_rows; host only)."""
@@ -1037,6 +1071,11 @@ class Session:
     @property
     def stage_launches(self) -> int:
         return int(self.lib.topolow_session_stage_launches(self._h))
+
+    @property
+    def symm_grid(self) -> int:
+        """Workgroups of the symmetric sweep this session has built, 0 if none (topolow_session_symm_grid)."""
+        return int(self.lib.topolow_session_symm_grid(self._h))
 
     @property
     def bytes_per_iteration(self) -> int:

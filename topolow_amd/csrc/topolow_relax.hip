@@ -245,6 +245,7 @@ struct topolow_session {
     bool two_stage = true;         // TOPOLOW_SYMMETRIC_TWO_STAGE=0: multi-stage iterations stay on the row-owner kernel
     bool prio = true;              // TOPOLOW_SYM_PRIO=0: the fp32 sweep's waves all stay at issue priority 0
     int rr_min_tiles = 5;          // tiles per resident wave a stage must have (TOPOLOW_SYMMETRIC_STAGE_MIN_TILES; tests: 0)
+    int grid_cap = 0;              // > 0: at most this many workgroups (TOPOLOW_SYMMETRIC_GRID; tests: long runs on small problems)
     DevBuf<const uint32_t*> src_tab;   // the row blocks the tile-major copy is gathered from (one: the session's own)
     DevBuf<int> src_row0;
     // the sweep sharded over the row-block sessions of a run (relax_sharded_engine.h): this session's segment
@@ -797,6 +798,7 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
     sym_sweep_instance<DIM, decltype(r)>(any_thr, true, probe);
   });
   y.grid = occ * prop.multiProcessorCount;
+  if (y.grid_cap > 0) y.grid = std::min(y.grid, y.grid_cap);
   y.plan.load(relax_symm_plan(y.npad, y.grid * kSymWaves, t0, t1, &y.seg_first, &y.seg_last));
   y.whole = t0 == 0 && (long long)y.tiles == (long long)TR * (TR + 1);
   for (auto& v : y.rr) v.clear();
@@ -920,6 +922,12 @@ void sym_apply(topolow_session* s, const SymPlanDev& plan, const void* rec, void
 bool sym_rr_stages_ok(int S) { return S == 2 || S == 4 || S == 8; }
 int sym_rr_log2(int S) { return S == 2 ? 1 : (S == 4 ? 2 : 3); }
 
+// The plan of stage st of an S-stage iteration over npad points for n_waves waves (sym_rr_row: one interval per tile-row).
+SymPlan sym_rr_plan(int npad, int n_waves, int S, int st) {
+  const int TR = npad / kSymRows;
+  return relax_symm_plan_rows(npad, n_waves, [&](int R, int& j0, int& j1) { sym_rr_row(TR, S, st, R, j0, j1); });
+}
+
 bool sym_rr_available(topolow_session* s, int S) {
   auto& y = s->sym;
   if (!sym_rr_stages_ok(S) || !y.whole) return false;
@@ -934,7 +942,7 @@ bool sym_rr_available(topolow_session* s, int S) {
   if (!y.rr[lg].empty()) return true;
   std::vector<SymPlanDev> plans(S);
   for (int st = 0; st < S; ++st) {
-    const SymPlan hp = relax_symm_plan_rows(y.npad, y.grid * kSymWaves, [&](int R, int& j0, int& j1) { sym_rr_row(TR, S, st, R, j0, j1); });
+    const SymPlan hp = sym_rr_plan(y.npad, y.grid * kSymWaves, S, st);
     if (hp.units.size() * kSymRows * s->dim * s->real_size() > y.rowpart.n) return false;   // (never: sym_build sizes for it)
     plans[st].load(hp);
   }
@@ -1428,6 +1436,8 @@ int topolow_session_create(topolow_session** out, int32_t n, int32_t ndim, int32
     s->sym.two_stage = !(symm2 != nullptr && symm2[0] == '0');
     const char* rr_min = getenv("TOPOLOW_SYMMETRIC_STAGE_MIN_TILES");
     if (rr_min != nullptr) s->sym.rr_min_tiles = std::max(0, atoi(rr_min));
+    const char* sym_grid = getenv("TOPOLOW_SYMMETRIC_GRID");   // tests cap the grid: a small problem then gives every wave a long run
+    s->sym.grid_cap = sym_grid != nullptr ? std::max(0, atoi(sym_grid)) : 0;
     const char* sym_prio = getenv("TOPOLOW_SYM_PRIO");
     s->sym.prio = !(sym_prio != nullptr && sym_prio[0] == '0');
     s->enc.alloc((size_t)((s->rows() + kEncRowAlign - 1) / kEncRowAlign * kEncRowAlign) * s->ld);
@@ -2071,6 +2081,52 @@ int32_t topolow_symm_stage_order(uint64_t seed, int32_t iter, int32_t stages, in
   sym_rr_order(seed, iter, stages, perm);
   for (int q = 0; q < stages; ++q) order[q] = perm[q];
   return 1;
+}
+
+int32_t topolow_symm_stage_rows(int32_t n, int32_t stages, int32_t stage, int32_t* rows_out) {
+  if (n < 2 || !(stages == 2 || stages == 4 || stages == 8) || stage < 0 || stage >= stages) return -1;
+  const int npad = (n + kSymRows - 1) & ~(kSymRows - 1), TR = npad / kSymRows;
+  if (TR < 2 * stages) return -1;
+  for (int R = 0; rows_out && R < TR; ++R) {
+    int j0 = 0, j1 = 0, rp0 = 0, rp1 = 0;
+    sym_rr_row(TR, stages, stage, R, j0, j1);
+    sym_rr_above(TR, stages, stage, R, rp0, rp1);
+    rows_out[4 * R] = j0;
+    rows_out[4 * R + 1] = j1;
+    rows_out[4 * R + 2] = rp0;
+    rows_out[4 * R + 3] = rp1;
+  }
+  return TR;
+}
+
+int32_t topolow_symm_plan(int32_t n, int32_t n_waves, int32_t stages, int32_t stage, int32_t segment, int32_t n_segments,
+                          int32_t* units_out, int32_t max_units, int32_t* wave_first_out) {
+  if (n < 2 || n_waves < 1 || (units_out && max_units < 0)) return -1;
+  const int npad = (n + kSymRows - 1) & ~(kSymRows - 1), TR = npad / kSymRows;
+  SymPlan plan;
+  if (stages != 0) {            // one stage of a multi-stage iteration (sym_rr_available)
+    if (!sym_rr_stages_ok(stages) || stage < 0 || stage >= stages || TR < 2 * stages || n_segments > 1) return -1;
+    plan = sym_rr_plan(npad, n_waves, stages, stage);
+  } else if (n_segments >= 2) {   // a segment of the sharded sweep (sym_sharded_build, sym_segment_build)
+    if (segment < 0 || segment >= n_segments) return -1;
+    const SymSegment g = sym_segment(n, segment, n_segments);
+    plan = relax_symm_plan(npad, n_waves, g.t0, g.t1);
+  } else {                        // the whole triangle (sym_prepare)
+    plan = relax_symm_plan(npad, n_waves, 0, -1);
+  }
+  const int n_units = (int)plan.units.size();
+  for (int u = 0; units_out && u < std::min(n_units, (int)max_units); ++u) {
+    units_out[4 * u] = plan.units[u].tile_row;
+    units_out[4 * u + 1] = plan.units[u].j0;
+    units_out[4 * u + 2] = plan.units[u].j1;
+    units_out[4 * u + 3] = plan.units[u].tile0;
+  }
+  for (int w = 0; wave_first_out && w <= n_waves; ++w) wave_first_out[w] = plan.wave_first[w];
+  return n_units;
+}
+
+int32_t topolow_session_symm_grid(const topolow_session* s) {
+  return s && (s->sym.ready || s->sym.seg_ready) ? s->sym.grid : 0;
 }
 
 int32_t topolow_symm_segment_rows(int32_t n, int32_t segment, int32_t n_segments, int32_t* row_first,
