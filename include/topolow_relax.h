@@ -54,8 +54,11 @@ extern "C" {
  *         further than max(4 sd_oracle, 3 %) from the oracle's mean (plain sd 0.9-1.8 x the oracle's, 3.3 x at
  *         N = 2048: DESIGN.md section 2b); the MAE it reports is the reference's edge MAE of the positions
  *         it returns to 2e-5; stop iteration within max(3 sd, 10 %) of the oracle's except on 2-D data
- *         (+55 %, same MAE).  Iterations that are ONE stage (k <= 3) of an fp32 problem with ndim 2..6 and
- *         >= 7168 points run as a symmetric sweep (csrc/relax_symm.h): the same update -- every
+ *         (+55 %, same MAE).  Iterations that are ONE stage (k <= 3) of a problem with ndim 2..10 in fp32, 2..6 in f64,
+ *         and >= 7168 points run as a symmetric sweep (csrc/relax_symm.h; fp32 ndim 7..10: csrc/relax_symm_wide.h, the
+ *         same sweep with the lane's rows in LDS, same tests in tests/test_gpu_symmetric_wide.py; at ndim 7..10
+ *         it is on by default at ndim 7..10 -- where it measured faster than the row-owner kernel by more than the spread of
+ *         repeated runs: at N = 10 000 (70 % missing) sweep + apply takes 68.8 / 71.3 / 76.1 / 82.4 us per iteration at ndim 7 / 8 / 9 / 10 against 96.0 / 107.4 / 108.7 / 116.0 us of the row-owner kernel, which ran these dims before (x1.40 / 1.51 / 1.43 / 1.41; with 15 % thresholds x1.69 / 1.75 / 1.71 / 1.66; spreads 5-12 us), so the >= 1.25x hoped for is met (profiles/r05_symm_wide.txt); TOPOLOW_SYMMETRIC=1 switches it on at every ndim it exists for): the same update -- every
  *         point moved by the sum of its own halves of all its pairs at the positions the previous iteration
  *         left -- with each pair's distance and factor computed once; checked against a CPU model of that
  *         iteration in f64 (positions: mean 5e-5, max 5e-3 of the displacement scale; the fused check's MAE against
@@ -64,7 +67,8 @@ extern "C" {
  *         a row-sharded run shards it over its sessions (same band against one block); f64 sessions take an f64 form
  *         of it (csrc/relax_symm64.h; equal to the f64 CPU model to 1e-12 per iteration; its fused check is exact --
  *         the sweep also reads exact-minus-rounded target differences -- and equals the reference's edge MAE to 1e-11);
- *         TOPOLOW_SYMMETRIC=0 / TOPOLOW_SHARD_SYMMETRIC=0 switch it off.  Where the sweep applies, 2-, 4- and 8-stage
+ *         TOPOLOW_SYMMETRIC=0 / TOPOLOW_SHARD_SYMMETRIC=0 switch it off; TOPOLOW_SYMMETRIC=1 is not the same as leaving
+ *         the variable unset: it also switches the sweep on at an ndim whose default is off (none at present).  Where the sweep applies, 2-, 4- and 8-stage
  *         iterations whose stages leave a resident wave >= 5 tiles (config 3: the two-stage ones, 3 < k <= 6) run as S
  *         symmetric sweeps that split the PAIRS -- stage st: the pairs between slabs a and b of the randomly labelled
  *         points with (a + b) mod S == st, stages in random order -- instead of "all points against one slab of the
@@ -481,7 +485,7 @@ int32_t topolow_session_can_fuse_checks(const topolow_session* s);
 int topolow_session_stage_fused(topolow_session* s, const void* d_pos_in, void* d_pos_out, int32_t iter,
                                 double k, double* d_out2, char* errbuf, size_t errlen);
 /* ONE-stage iterations of a row-sharded run as the SYMMETRIC sweep sharded over the processes (one per GPU; fp32,
- * ndim 2..6, >= 7168 points: csrc/relax_symm.h).  Every unordered pair is visited once instead of twice (reference
+ * ndim 2..10, >= 7168 points: csrc/relax_symm.h, relax_symm_wide.h).  Every unordered pair is visited once instead of twice (reference
  * src/optimization.cpp:198-283 visits each pair once and moves both ends), so a rank reads half the bytes of its
  * row-owner sweep.  Rank r of P owns SEGMENT r of the tile list of the upper triangle (equal tile counts), not a
  * row block, so the caller first brings the rows that hold the segment's tiles together:
@@ -506,7 +510,7 @@ int topolow_session_stage_fused(topolow_session* s, const void* d_pos_in, void* 
  * Nothing here waits for the device (build does, once). */
 int32_t topolow_symm_segment_rows(int32_t n, int32_t segment, int32_t n_segments, int32_t* row_first,
                                   int32_t* row_end);
-/* 1 when the session can take the path cut into n_segments (fp32 slab schedule, ndim 2..6, size gate, targets loaded). */
+/* 1 when the session can take the path cut into n_segments (fp32 slab schedule, ndim 2..10, size gate, targets loaded). */
 int32_t topolow_session_symm_segment_eligible(const topolow_session* s, int32_t n_segments);
 float* topolow_session_degree_terms(topolow_session* s);
 /* 1 when some target of the session's block carries a threshold code ('>' / '<'): the any_threshold of the ranks is
@@ -535,7 +539,7 @@ int topolow_session_edge_error(topolow_session* s, const void* d_pos, double* su
  * per stage or per check (csrc/relax_sharded_engine.h).  Results equal the one-session run of the
  * same seed: positions bit for bit, the MAE to rounding (its partial sums are grouped by block) -- on
  * the multi-stage iterations and wherever the row-owner kernel runs.  ONE-stage iterations of fp32 runs with
- * ndim 2..6 and >= 7168 points run as the symmetric sweep sharded over the sessions (csrc/relax_symm.h): session b
+ * ndim 2..10 and >= 7168 points run as the symmetric sweep sharded over the sessions (csrc/relax_symm.h): session b
  * sweeps segment b of the tile list of the upper triangle (equal tile counts; gathered once from all row blocks),
  * folds its partials per point and stores them into the inbox of the session that owns the point; behind the
  * barrier the owners move their points and store them into every session's positions (two barriers per
@@ -605,7 +609,7 @@ int32_t topolow_slab_plan(int32_t n, int32_t slab_stages, uint64_t seed, int32_t
 /* Stage count the adaptive policy picks for spring constant k in ndim dimensions: the smallest power of two
  * with k / stages <= min(3, ndim) (a stage is a Jacobi step, stable for k / stages < 2 ndim). */
 int32_t topolow_slab_stages_for_k(double k, int32_t ndim);
-/* 2-, 4- and 8-stage iterations of sessions that take the symmetric sweep (fp32 / f64 slab schedule, ndim 2..6, >= 7168
+/* 2-, 4- and 8-stage iterations of sessions that take the symmetric sweep (slab schedule, ndim 2..10 in fp32, 2..6 in f64, >= 7168
  * points, whole matrix) run as symmetric sweeps that split the PAIRS: the (randomly labelled) points are cut into S slabs
  * of labels [first_label[q], first_label[q + 1]) and stage st sweeps the pairs between slabs a and b with
  * (a + b) mod S == st, so every point meets one slab of partners per stage, as in the row-owner form, and both ends of a

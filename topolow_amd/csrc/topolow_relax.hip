@@ -34,6 +34,7 @@
 #include "relax_tilegs.h"
 #include "relax_symm.h"
 #include "relax_symm64.h"
+#include "relax_symm_wide.h"
 #include "relax_cv.h"
 
 using namespace topolow;
@@ -206,7 +207,8 @@ struct topolow_session {
   int n_ranks = 0, rank = 0;
   // Symmetric sweep (relax_symm.h, relax_symm64.h): one-stage iterations of a whole-matrix session.
   struct SymState {
-    bool allowed = false;          // TOPOLOW_SYMMETRIC=1 (session creation)
+    bool allowed = false;          // TOPOLOW_SYMMETRIC != 0 (session creation)
+    bool forced = false;           // TOPOLOW_SYMMETRIC=1: also at an ndim whose default is off (sym_dim_default)
     int min_n = 0;                 // size gate (TOPOLOW_SYMMETRIC_MIN_N at session creation; default kSymMinPoints)
     bool ready = false;            // plan + tile-major copy built for the current block
     int npad = 0, tiles = 0, grid = 0;   // npad = roundup(n, 64): whole 64-row tiles
@@ -724,14 +726,22 @@ void launch_tilegs_finite(topolow_session* s, const void* pos, int iter1) {
   HIP_TRY(hipGetLastError());
 }
 
-// ---- symmetric sweep (relax_symm.h, relax_symm64.h) --------------------------------------------------------
-// Which sessions take it: the whole matrix on one GPU (no row block, nothing to push), fp32 or f64 slab schedule, ndim
-// 2..6 (the register-tiled kernel keeps eight rows' coordinates, constants and sums in VGPRs: 20 x ndim + 16 of
-// them), at least kSymMinPoints points.  Row-sharded runs shard it over their sessions (sym_sharded_*, below).
+// ---- symmetric sweep (relax_symm.h, relax_symm_wide.h, relax_symm64.h) -------------------------------------
+// Which sessions take it: the whole matrix on one GPU (no row block, nothing to push), slab schedule, ndim 2..10 in
+// fp32 and 2..6 in f64, at least kSymMinPoints points.  Up to ndim 6 the register-tiled kernel keeps eight rows'
+// coordinates, constants and sums in VGPRs (20 x ndim + 16 of them); fp32 sessions of ndim 7..10 run
+// symm_sweep_wide_kernel, which keeps the rows in LDS and only their sums in VGPRs (relax_symm_wide.h); f64 sessions of
+// ndim 7..10 stay on the row-owner kernel.  Row-sharded runs shard it over their sessions (sym_sharded_*, below).
 // Everything else stays on the row-owner stage kernel.
-constexpr int kSymMinPoints = 7168;   // below ~7000 points a resident wave gets fewer than 8 tiles and the row-owner sweep is faster (tests/study/symm_crossover.py)
+constexpr int kSymMinPoints = 7168;   // below ~7000 points a resident wave gets fewer than 8 tiles and the row-owner sweep is faster (tests/study/symm_crossover.py; at ndim 10 the two meet near 4 100 points and the sweep leads by 1.11 at 6 144, 1.27 at 7 168: the gate stays, profiles/r05_symm_wide.txt)
 
-// The sweep's host functions exist for ndim 2..6 only, the dims its kernels are instantiated for.
+// The sweep's host functions exist for ndim 2..10 only, the dims its kernels are instantiated for (f64: 2..6).
+constexpr int kSymMaxDimF32 = kSymWideMaxDim, kSymMaxDimF64 = 6;
+// Whether the sweep is on by default at this ndim: where its iteration measured faster than the row-owner kernel's by
+// more than the spread of repeated runs.  ndim 2..6: profiles/r03_symm_crossover.txt; ndim 7..10: at N = 10 000 the
+// parent's row-owner iteration takes 1.40 .. 1.75 times the sweep's, 27 .. 58 us more at spreads of 5 .. 12 us
+// (profiles/r05_symm_wide.txt) -- all on.  A dimension that is off would stay reachable with TOPOLOW_SYMMETRIC=1.
+constexpr bool sym_dim_default(int dim) { return dim >= 2 && dim <= kSymMaxDimF32; }
 #define TL_DISPATCH_SYM(dim, FN, ...)                                                 \
   switch (dim) {                                                                      \
     case 2: FN<2>(__VA_ARGS__); break;                                                \
@@ -739,26 +749,37 @@ constexpr int kSymMinPoints = 7168;   // below ~7000 points a resident wave gets
     case 4: FN<4>(__VA_ARGS__); break;                                                \
     case 5: FN<5>(__VA_ARGS__); break;                                                \
     case 6: FN<6>(__VA_ARGS__); break;                                                \
+    case 7: FN<7>(__VA_ARGS__); break;                                                \
+    case 8: FN<8>(__VA_ARGS__); break;                                                \
+    case 9: FN<9>(__VA_ARGS__); break;                                                \
+    case 10: FN<10>(__VA_ARGS__); break;                                              \
     default: throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim"};        \
   }
 
 using SymPlanDev = topolow_session::SymState::Plan;
 
 // The shape every form of the sweep needs; the eligibility of each form adds its own terms.
+// The precision term is part of the shape: the largest ndim differs (fp32: 10, f64: 6).
 bool sym_shape_ok(const topolow_session* s) {
-  return s->sym.allowed && s->schedule == TOPOLOW_SCHEDULE_SLAB && s->dim >= 2 && s->dim <= 6 && s->dim == s->udim &&
-         s->n >= s->sym.min_n;
+  const int max_dim = s->precision == TOPOLOW_PRECISION_F32 ? kSymMaxDimF32
+                      : s->precision == TOPOLOW_PRECISION_F64 ? kSymMaxDimF64 : 0;
+  return s->sym.allowed && s->schedule == TOPOLOW_SCHEDULE_SLAB && s->dim >= 2 && s->dim <= max_dim &&
+         (sym_dim_default(s->dim) || s->sym.forced) && s->dim == s->udim && s->n >= s->sym.min_n;
 }
 
 bool sym_eligible(const topolow_session* s) {
-  return sym_shape_ok(s) && (s->precision == TOPOLOW_PRECISION_F32 || s->precision == TOPOLOW_PRECISION_F64) &&
-         s->row_begin == 0 && s->row_end == s->n && s->n_push == 0;
+  return sym_shape_ok(s) && s->row_begin == 0 && s->row_end == s->n && s->n_push == 0;
 }
 
-// f(real{}) in the session's precision.
-template <typename F>
+// f(real{}) in the session's precision; from ndim 7 there is fp32 only (sym_shape_ok keeps f64 sessions away).
+template <int DIM, typename F>
 void sym_real(const topolow_session* s, F&& f) {
-  if (s->precision == TOPOLOW_PRECISION_F64) f(double{}); else f(float{});
+  if constexpr (DIM <= kSymMaxDimF64) {
+    if (s->precision == TOPOLOW_PRECISION_F64) { f(double{}); return; }
+  } else if (s->precision != TOPOLOW_PRECISION_F32) {
+    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep: ndim 7..10 in fp32 only"};
+  }
+  f(float{});
 }
 
 // f(kernel) with the sweep instance for (real, thresholds, err): the one list of instances, for the launches and the
@@ -768,6 +789,9 @@ void sym_sweep_instance(bool thr, bool err, F&& f) {
   if constexpr (std::is_same<real, double>::value) {
     if (thr) { if (err) f(&symm64_sweep_kernel<DIM, true, true>); else f(&symm64_sweep_kernel<DIM, true, false>); }
     else { if (err) f(&symm64_sweep_kernel<DIM, false, true>); else f(&symm64_sweep_kernel<DIM, false, false>); }
+  } else if constexpr (DIM >= kSymWideMinDim) {   // same arguments, rows in LDS (relax_symm_wide.h)
+    if (thr) { if (err) f(&symm_sweep_wide_kernel<DIM, true, true>); else f(&symm_sweep_wide_kernel<DIM, true, false>); }
+    else { if (err) f(&symm_sweep_wide_kernel<DIM, false, true>); else f(&symm_sweep_wide_kernel<DIM, false, false>); }
   } else {
     if (thr) { if (err) f(&symm_sweep_kernel<DIM, true, true>); else f(&symm_sweep_kernel<DIM, true, false>); }
     else { if (err) f(&symm_sweep_kernel<DIM, false, true>); else f(&symm_sweep_kernel<DIM, false, false>); }
@@ -793,7 +817,7 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
     occ = std::min(occ, std::max(1, per_cu));
   };
   const bool f64 = s->precision == TOPOLOW_PRECISION_F64;
-  sym_real(s, [&](auto r) {
+  sym_real<DIM>(s, [&](auto r) {
     sym_sweep_instance<DIM, decltype(r)>(any_thr, false, probe);
     sym_sweep_instance<DIM, decltype(r)>(any_thr, true, probe);
   });
@@ -815,7 +839,9 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
   HIP_TRY(hipGetLastError());
   const int seg_rows = y.seg_last >= y.seg_first ? y.seg_last - y.seg_first + 1 : 1;
   const size_t rs = s->real_size();
-  for (auto& r : y.rec) r.alloc((size_t)y.npad * (f64 ? SymRec64<DIM>::W : SymRec<DIM>::W) * rs);
+  size_t rec_w = SymRec<DIM>::W;
+  if constexpr (DIM <= kSymMaxDimF64) { if (f64) rec_w = SymRec64<DIM>::W; }
+  for (auto& r : y.rec) r.alloc((size_t)y.npad * rec_w * rs);
   y.rowpart.alloc((size_t)std::max(max_units, 1) * kSymRows * DIM * rs);
   y.colpart.alloc((size_t)seg_rows * y.npad * DIM * rs);
   // (a segment's first and last tile-row are partial: the columns its tiles never reach must read as zero)
@@ -868,7 +894,7 @@ bool sym_available(topolow_session* s) {
 // The records of iteration `k` from plain positions (all npad of them: the phantom ones too).
 template <int DIM>
 void sym_records(topolow_session* s, const void* pin, void* rec, double k) {
-  sym_real(s, [&](auto r) {
+  sym_real<DIM>(s, [&](auto r) {
     using real = decltype(r);
     hipLaunchKernelGGL((symm_records_kernel<DIM, real>), dim3((s->sym.npad + 255) / 256), dim3(256), 0, s->stream,
                        (const real*)pin, s->gplus.p, (real*)rec, s->n, s->sym.npad, k, s->c_rep);
@@ -883,7 +909,7 @@ template <int DIM>
 void sym_sweep(topolow_session* s, const SymPlanDev& plan, const void* rec, bool thr, bool err,
                unsigned long long block_cells, int col_row0, bool prio) {
   auto& y = s->sym;
-  sym_real(s, [&](auto r) {
+  sym_real<DIM>(s, [&](auto r) {
     using real = decltype(r);
     sym_sweep_instance<DIM, real>(thr, err, [&](auto kern) {
       if constexpr (std::is_same<real, double>::value)
@@ -904,7 +930,7 @@ template <int DIM>
 void sym_apply(topolow_session* s, const SymPlanDev& plan, const void* rec, void* rec_next, void* pout, double k_next,
                int iter, int rr_stages, int rr_stage) {
   auto& y = s->sym;
-  sym_real(s, [&](auto r) {
+  sym_real<DIM>(s, [&](auto r) {
     using real = decltype(r);
     hipLaunchKernelGGL((symm_apply_kernel<DIM, real>), dim3(y.npad / kSymCols), dim3(32 * kSymApplyParts), 0, s->stream,
                        (const real*)rec, (real*)rec_next, (real*)pout, s->gplus.p, (const real*)y.rowpart.p,
@@ -1430,6 +1456,7 @@ int topolow_session_create(topolow_session** out, int32_t n, int32_t ndim, int32
     s->fuse_checks = !(fuse != nullptr && fuse[0] == '0');
     const char* symm = getenv("TOPOLOW_SYMMETRIC");
     s->sym.allowed = !(symm != nullptr && symm[0] == '0');   // TOPOLOW_SYMMETRIC=0: row-owner sweeps only
+    s->sym.forced = symm != nullptr && symm[0] == '1';       // TOPOLOW_SYMMETRIC=1: also at an ndim that is off by default
     const char* symm_min = getenv("TOPOLOW_SYMMETRIC_MIN_N");   // tests lower the size gate to reach the sweep on small problems
     s->sym.min_n = symm_min != nullptr ? atoi(symm_min) : kSymMinPoints;
     const char* symm2 = getenv("TOPOLOW_SYMMETRIC_TWO_STAGE");
@@ -2156,7 +2183,7 @@ int topolow_session_symm_segment_build(topolow_session* s, int32_t segment, int3
       row_first + n_rows > s->n)
     return TOPOLOW_ERR_BAD_ARGUMENT;
   if (!topolow_session_symm_segment_eligible(s, n_segments)) {
-    set_err(errbuf, errlen, "this session cannot take the symmetric sweep (fp32 slab schedule, ndim 2..6, at least %d "
+    set_err(errbuf, errlen, "this session cannot take the symmetric sweep (fp32 slab schedule, ndim 2..10, at least %d "
                             "points, targets loaded)", s->sym.min_n);
     return TOPOLOW_ERR_UNSUPPORTED;
   }
