@@ -56,7 +56,8 @@ extern "C" {
  *         it returns to 2e-5; stop iteration within max(3 sd, 10 %) of the oracle's except on 2-D data
  *         (+55 %, same MAE).  Iterations that are ONE stage (k <= 3) of a problem with ndim 2..10 in fp32, 2..6 in f64,
  *         and >= 7168 points run as a symmetric sweep (csrc/relax_symm.h; fp32 ndim 7..10: csrc/relax_symm_wide.h, the
- *         same sweep with the lane's rows in LDS, same tests in tests/test_gpu_symmetric_wide.py; at ndim 7..10
+ *         same sweep with the lane's rows in LDS, same tests in tests/test_gpu_symmetric_wide.py and,
+ *         on plans with long runs, tests/test_gpu_symmetric_wide_long_runs.py; at ndim 7..10
  *         it is on by default at ndim 7..10 -- where it measured faster than the row-owner kernel by more than the spread of
  *         repeated runs: at N = 10 000 (70 % missing) sweep + apply takes 68.8 / 71.3 / 76.1 / 82.4 us per iteration at ndim 7 / 8 / 9 / 10 against 96.0 / 107.4 / 108.7 / 116.0 us of the row-owner kernel, which ran these dims before (x1.40 / 1.51 / 1.43 / 1.41; with 15 % thresholds x1.69 / 1.75 / 1.71 / 1.66; spreads 5-12 us), so the >= 1.25x hoped for is met (profiles/r05_symm_wide.txt); TOPOLOW_SYMMETRIC=1 switches it on at every ndim it exists for): the same update -- every
  *         point moved by the sum of its own halves of all its pairs at the positions the previous iteration

@@ -1,5 +1,6 @@
 """The symmetric sweep (csrc/relax_symm.h, csrc/relax_symm64.h) on plans shaped like production's, at 200 and 1 000 points
-(run with -m gpu).
+(run with -m gpu).  The same for the fp32 kernel of ndim 7..10 (csrc/relax_symm_wide.h), with this file's helpers:
+tests/test_gpu_symmetric_wide_long_runs.py; that the needle assertions see one pair: tests/test_symm_needle_one_pair.py.
 
 A resident grid is 2 048 waves, so a problem of a few thousand points gives every wave one tile: nothing the kernels carry
 from one tile or unit to the next (the prefetched words and records, the two LDS slots, the row sums kept along a unit, the
@@ -224,6 +225,11 @@ def test_needle_problem_one_pair_is_an_error_of_order_one(n, dim, thresholded, p
     Measured on an MI355X, fp32, the largest error / band of (ii) per case (three seeds, both grids): 0.06 to 0.18 --
     0.179 at (1000, 2, plain), 0.167 at (1000, 3, thresholded), 0.152 at (200, 2, thresholded); the model's own fp32
     arithmetic against its f64 gives 0.05 to 0.19 on the same problems.  f64: 0.001 of its band at the most."""
+    _needle_on_the_whole_triangle(n, dim, thresholded, precision)
+
+
+def _needle_on_the_whole_triangle(n, dim, thresholded, precision):
+    """What test_needle_problem_one_pair_is_an_error_of_order_one states, at any ndim; returns the largest error / band."""
     worst = 0.0
     for seed in range(3):
         call, call_r, active = _needle(n, dim, seed, thresholded, "whole", (1, 3))
@@ -237,6 +243,7 @@ def test_needle_problem_one_pair_is_an_error_of_order_one(n, dim, thresholded, p
                                      (n, dim, thresholded, seed))
             worst = max(worst, _idle_and_moved(got[1], want[0], call.initial_positions, active, precision))
     print("needle n=%d dim=%d thr=%d %s: largest error / band %.3f" % (n, dim, thresholded, precision, worst))
+    return worst
 
 
 # ----------------------------------------------------------------------------------------
@@ -274,6 +281,10 @@ def _assert_stage_plans(n, g, stages):
 def test_multi_stage_iterations_on_long_runs_against_the_model(stages, dim, thr, precision):
     """1 000 points (the smallest with 16 tile-rows, two per slab of eight) on one workgroup: four S-stage iterations
     against the model of that schedule, in the bands of test_multi_stage_iterations_as_symmetric_sweeps_against_the_model."""
+    _stage_iterations_against_the_model(stages, dim, thr, precision)
+
+
+def _stage_iterations_against_the_model(stages, dim, thr, precision):
     n, g, seed, iters = 1000, 1, 5, 4
     k0 = 2.0 * stages
     _assert_stage_plans(n, g, stages)
@@ -305,7 +316,12 @@ def test_needle_problem_through_the_stages_of_one_iteration(stages, precision):
     older sweep wrote, added by mistake, moves it), every other point is where the model of the schedule puts it.
     Measured on an MI355X, largest error / band of (ii) over three seeds: fp32 0.098 (S = 2) and 0.187 (S = 8), f64
     0.001."""
-    n, dim, g, seed = 1000, 5, 1, 5
+    _needle_through_the_stages(stages, 5, precision)
+
+
+def _needle_through_the_stages(stages, dim, precision):
+    """What test_needle_problem_through_the_stages_of_one_iteration states, at any ndim; returns the largest error / band."""
+    n, g, seed = 1000, 1, 5
     _assert_stage_plans(n, g, stages)
     worst = 0.0
     for problem_seed in range(3):
@@ -318,7 +334,8 @@ def test_needle_problem_through_the_stages_of_one_iteration(stages, precision):
         got, _, launches = _stage_session(call, n, dim, precision, 1, K0, 0.0, 3, seed, stages, g)
         assert launches == stages
         worst = max(worst, _idle_and_moved(got, want, call.initial_positions, moved, precision))
-    print("needle stages=%d %s: largest error / band %.3f" % (stages, precision, worst))
+    print("needle stages=%d dim=%d %s: largest error / band %.3f" % (stages, dim, precision, worst))
+    return worst
 
 
 # ----------------------------------------------------------------------------------------
@@ -335,6 +352,12 @@ def test_needle_problem_over_sharded_segments(dim, thresholded, blocks, thread_p
     Measured on an MI355X, largest error / band of (ii): 0.112 (ndim 3, plain), 0.050 and 0.070 (ndim 5, thresholded, two
     and three blocks), the same with and without a thread per block."""
     monkeypatch.setenv("TOPOLOW_SHARD_THREAD_PER_BLOCK", thread_per_block)
+    _needle_over_segments(dim, thresholded, blocks, thread_per_block)
+
+
+def _needle_over_segments(dim, thresholded, blocks, thread_per_block):
+    """What test_needle_problem_over_sharded_segments states (TOPOLOW_SHARD_THREAD_PER_BLOCK set by the caller), at any
+    ndim; returns the largest error / band of (ii)."""
     n, g = 1000, 1
     for b in range(blocks):
         sh = _shape(n, g, segment=b, n_segments=blocks)
@@ -365,3 +388,4 @@ def test_needle_problem_over_sharded_segments(dim, thresholded, blocks, thread_p
             for row in trace:
                 sm, c = orc.edge_error(want[int(row[0]) - 1], call.edge_i, call.edge_j, call.edge_dist, call.edge_thresh)
                 assert row[1] == pytest.approx(sm / c, rel=2e-5), (row, sm / c)
+    return ratio

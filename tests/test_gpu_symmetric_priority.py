@@ -25,7 +25,7 @@ def problem():
     return call, res.positions
 
 
-def _six_iterations(call, start, stages, prio, grid=None):
+def _six_iterations(call, start, stages, prio, grid=None, n=2048, dim=5):
     env = dict(TOPOLOW_SYMMETRIC="1", TOPOLOW_SYMMETRIC_MIN_N="0", TOPOLOW_SYMMETRIC_STAGE_MIN_TILES="0")
     if prio is not None:
         env["TOPOLOW_SYM_PRIO"] = prio
@@ -36,7 +36,7 @@ def _six_iterations(call, start, stages, prio, grid=None):
     os.environ.pop("TOPOLOW_SYMMETRIC_GRID", None)
     os.environ.update(env)
     try:
-        s = _native.Session(2048, 5, precision="f32")
+        s = _native.Session(n, dim, precision="f32")
     finally:
         for k, v in old.items():
             os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)

@@ -1,7 +1,9 @@
 """The symmetric sweep at ndim 7..10 (topolow_amd/csrc/relax_symm_wide.h: fp32, the lane's rows in LDS) -- run with
 -m gpu.  The same statements as tests/test_gpu_symmetric.py makes for ndim 2..6, at the sizes where this kernel can go
 wrong: phantom rows and columns (n = 33, 66), fewer tiles than waves, ragged n % 32, the diagonal squares met from both
-sides; every instance (threshold-free / thresholds x plain / ERR) at the smallest and the largest ndim."""
+sides; every instance (threshold-free / thresholds x plain / ERR) at the smallest and the largest ndim.  Here a wave has
+one tile or none (but for the 7 205-point cases): what the kernel carries from one tile or unit of a run to the next is
+held to the model on capped grids, with the needle problem, in tests/test_gpu_symmetric_wide_long_runs.py."""
 import dataclasses
 import functools
 
