@@ -79,6 +79,21 @@ extern "C" {
  *         keeps the row-owner form.  The fp32 sweep's waves run at an issue priority that falls with the share of
  *         their run still to do, so that the two waves of a SIMD end together (results unchanged bit for bit;
  *         TOPOLOW_SYM_PRIO=0 at session creation leaves every wave at priority 0; a sharded sweep's segments always do).
+ *   F64 and F64_EXACT beyond one workgroup.  The session stores every target as a 4-byte word: fp32 rounded to 4 ulp,
+ *         up to 3e-7 relative off the caller's f64 value.  With precision F64 positions, sums and the pair update are
+ *         double, the convergence MAE is exact (f64 edge list; delta tiles in the fused check), but the FORCES come from
+ *         the words: the result sits about 1e-7 of the displacement scale from what the caller's own targets give.  With
+ *         precision F64_EXACT the session also keeps what the rounding took away, one fp32 delta per cell, and every
+ *         kernel that runs reads target = word + delta, exact to 2e-14 relative: the row-owner stage kernel
+ *         (csrc/relax_exact.h), the symmetric sweep and its multi-stage form (csrc/relax_symm64.h: symm64x_sweep_kernel)
+ *         and tile Gauss-Seidel -- equal to the CPU model / the oracle fed the caller's UNROUNDED matrix in the bands
+ *         the F64 tests hold against the rounded one (tests/test_gpu_exact_f64.py).  It costs 4 n ld more bytes of
+ *         device memory and the time stated in DESIGN.md section 6.  The one-workgroup GS paths (small n, the batch,
+ *         topolow_cv_sweep) read f64 targets at either value: there F64_EXACT is F64, reported back as asked.
+ *         F64_EXACT answers TOPOLOW_ERR_UNSUPPORTED for: a row-block session (row_begin != 0 or row_end != n) and so
+ *         every row-sharded path and a `devices` list; ndim > 16; topolow_session_commit_encoded (the caller's words
+ *         carry no deltas); topolow_session_hold_out and topolow_cv_sweep_session (their patches do not cover the delta
+ *         block).  F64 and AUTO are unchanged bit for bit.
  * The deterministic pieces -- controller, cooling, error rule, guards, messages -- are exact. */
 
 /* Schedules (topolow_options.schedule). */
@@ -90,6 +105,7 @@ extern "C" {
 #define TOPOLOW_PRECISION_AUTO 0  /* f64 for the GS kernel, f32 for the slab kernel */
 #define TOPOLOW_PRECISION_F32 1
 #define TOPOLOW_PRECISION_F64 2
+#define TOPOLOW_PRECISION_F64_EXACT 3  /* F64 with every target read as word + delta (2e-14 relative): see the parity statement */
 
 typedef struct topolow_options {
   uint64_t seed;        /* seeds the pair-order / slab-order stream (the reference uses

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libtopolow_relax.so")
 
 SCHEDULE_AUTO, SCHEDULE_SLAB, SCHEDULE_GS = 0, 1, 2
-PRECISION_AUTO, PRECISION_F32, PRECISION_F64 = 0, 1, 2
+PRECISION_AUTO, PRECISION_F32, PRECISION_F64, PRECISION_F64_EXACT = 0, 1, 2, 3
 
 FAR_F32 = 1.0e18   # phantom coordinate of padding points (relax_common.h)
 
@@ -97,7 +97,8 @@ options: Dict[str, Any] = dict(seed=None, schedule="auto", precision="auto", sla
 _host_rng = np.random.default_rng()
 
 _SCHEDULES = {"auto": SCHEDULE_AUTO, "slab": SCHEDULE_SLAB, "gs": SCHEDULE_GS}
-_PRECISIONS = {"auto": PRECISION_AUTO, "f32": PRECISION_F32, "f64": PRECISION_F64}
+_PRECISIONS = {"auto": PRECISION_AUTO, "f32": PRECISION_F32, "f64": PRECISION_F64, "f64_exact": PRECISION_F64_EXACT}
+_PRECISION_NAMES = {v: k for k, v in _PRECISIONS.items() if k != "auto"}
 
 
 def set_seed(seed: Optional[int]) -> None:
@@ -416,7 +417,7 @@ def optimize_layout_exact_arrays(initial_positions, dissimilarity_matrix, thresh
         C.byref(fk), C.byref(stats), err, len(err))
     _check(rc, err)
     info = dict(schedule={SCHEDULE_SLAB: "slab", SCHEDULE_GS: "gs"}.get(stats.schedule_used),
-                precision={PRECISION_F32: "f32", PRECISION_F64: "f64"}.get(stats.precision_used),
+                precision=_PRECISION_NAMES.get(stats.precision_used),
                 iterations_run=stats.iterations_run, n_checks=stats.n_checks,
                 device_seconds=stats.device_seconds, total_seconds=stats.total_seconds,
                 setup_seconds=stats.setup_seconds, stage_launches=stats.stage_launches, seed=int(opt.seed))

@@ -57,6 +57,15 @@ TL_HD inline double decode_target(uint32_t w, int* code) {
   return (double)bits_f32(w & ~kCodeMask);
 }
 
+// What the word's rounding took from a measured target, as fp32: target = decode(word) + delta to 2e-14 relative (the
+// word is within 3e-7 of the target, the fp32 delta within 6e-8 of that).  0 for an unmeasured cell, and for a target so
+// large that its word was clamped.  Sessions of precision f64_exact keep one per cell beside the words (the "delta block").
+TL_HD inline float encode_delta(double t, uint32_t w) {
+  if (w == kInfWord) return 0.0f;
+  const float d = (float)(t - (double)bits_f32(w & ~kCodeMask));
+  return __builtin_isfinite(d) ? d : 0.0f;
+}
+
 // ---------------------------------------------------------------------------------------
 // Layout of an encoded block in HBM.  Production: row-major, rows x ld words, ld % 64 == 0.
 // Every kernel addresses the block through enc_index / enc_col_offset_bytes, so a layout is one

@@ -1063,20 +1063,24 @@ __global__ __launch_bounds__(kCtlThreads) void controller_kernel(
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void encode_dense_kernel(
     const double* __restrict__ D, const int* __restrict__ T, int n, int row_begin, int row_end,
-    int ld, uint32_t* __restrict__ out, const int* __restrict__ perm) {
+    int ld, uint32_t* __restrict__ out, const int* __restrict__ perm, float* __restrict__ dout) {
   // grid: x = row of the block (no 65535 limit), y = 256-column group
   // perm (nullable): session label -> caller's label (the block is stored in session labels)
+  // dout (nullable): the delta block of an f64_exact session (relax_common.h: encode_delta), same indexing as out
   const int c = blockIdx.y * kThreads + threadIdx.x;
   const int i = row_begin + blockIdx.x;
   if (c >= ld || i >= row_end) return;
   uint32_t w = kInfWord;  // diagonal and padding: see relax_common.h
+  float dl = 0.0f;
   if (c < n && c != i) {
     const int oi = perm ? perm[i] : i, oc = perm ? perm[c] : c;
     const int lo = oi < oc ? oi : oc, hi = oi < oc ? oc : oi;
     const size_t cell = (size_t)lo + (size_t)hi * n;
     w = encode_target(D[cell], T[cell]);
+    dl = encode_delta(D[cell], w);
   }
   out[enc_index(i - row_begin, c, ld)] = w;
+  if (dout != nullptr) dout[enc_index(i - row_begin, c, ld)] = dl;
 }
 
 // Order-independent fingerprint of the measured cells the dense MAE pass would reduce, used to
@@ -1138,18 +1142,19 @@ __global__ __launch_bounds__(kThreads) void row_flags_kernel(const uint32_t* __r
 }
 
 __global__ __launch_bounds__(kThreads) void fill_unmeasured_kernel(
-    int n, int row_begin, int row_end, int ld, uint32_t* __restrict__ out) {
+    int n, int row_begin, int row_end, int ld, uint32_t* __restrict__ out, float* __restrict__ dout) {
   const int c = blockIdx.y * kThreads + threadIdx.x;   // grid: x = row, y = 256-column group
   const int i = row_begin + blockIdx.x;
   if (c >= ld || i >= row_end) return;
   out[enc_index(i - row_begin, c, ld)] = kInfWord;
+  if (dout != nullptr) dout[enc_index(i - row_begin, c, ld)] = 0.0f;   // (dout: see encode_dense_kernel)
 }
 
 __global__ __launch_bounds__(kThreads) void scatter_edges_kernel(
     const int* __restrict__ ei, const int* __restrict__ ej, const double* __restrict__ ed,
     const int* __restrict__ ec, long long n_edges, int n, int row_begin, int row_end, int ld,
-    uint32_t* __restrict__ out, const int* __restrict__ inv) {
-  // inv (nullable): caller's label -> session label
+    uint32_t* __restrict__ out, const int* __restrict__ inv, float* __restrict__ dout) {
+  // inv (nullable): caller's label -> session label; dout (nullable): see encode_dense_kernel
   const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (e >= n_edges) return;
   int a = ei[e], b = ej[e];
@@ -1158,6 +1163,11 @@ __global__ __launch_bounds__(kThreads) void scatter_edges_kernel(
   const uint32_t w = encode_target(ed[e], ec[e]);
   if (a >= row_begin && a < row_end) out[enc_index(a - row_begin, b, ld)] = w;
   if (b >= row_begin && b < row_end) out[enc_index(b - row_begin, a, ld)] = w;
+  if (dout != nullptr) {
+    const float dl = encode_delta(ed[e], w);
+    if (a >= row_begin && a < row_end) dout[enc_index(a - row_begin, b, ld)] = dl;
+    if (b >= row_begin && b < row_end) dout[enc_index(b - row_begin, a, ld)] = dl;
+  }
 }
 
 // est_distances = as.matrix(dist(positions)) (reference R/core.R:474), f64, rows [row0, row0 + rows).

@@ -701,10 +701,11 @@ __global__ __launch_bounds__(256) void symm_records_kernel(const real* __restric
 // The tile-major copy of tiles [t_first, t_first + gridDim.x) of the upper triangle from the row-major encoded matrix,
 // which lies in n_src row blocks (one on a single GPU; the row-block sessions of a sharded run otherwise -- on other
 // GPUs of the node their words arrive as peer reads, once per loaded matrix): block q holds rows [row0[q], row0[q + 1])
-// of ld words each.  One workgroup per tile, 8 words per thread; rows and columns past the matrix read as unmeasured.
+// of ld words each.  One workgroup per tile, 8 words per thread; rows and columns past the matrix read as `fill`:
+// the unmeasured word, or 0 when the 4-byte words permuted are the fp32 deltas of an f64_exact session.
 __global__ __launch_bounds__(256) void symm_tiles_kernel(const uint32_t* const* __restrict__ src, const int* __restrict__ row0,
                                                         int n_src, int ld, uint32_t* __restrict__ tenc, int TC,
-                                                        long long t_first) {
+                                                        long long t_first, uint32_t fill) {
   // tile index -> (R, J): tile-row R starts at R TC - R (R - 1) and is TC - 2 R tiles long
   const long long t = t_first + blockIdx.x;
   int R = 0;
@@ -724,7 +725,7 @@ __global__ __launch_bounds__(256) void symm_tiles_kernel(const uint32_t* const* 
     const int cell = threadIdx.x + q * 256;          // 64 x 32 cells, row-major: coalesced reads of 128 bytes per row
     const int r = cell >> 5, c = cell & 31;
     const int row = R * kSymRows + r, col = J * kSymCols + c;
-    uint32_t w = kInfWord;
+    uint32_t w = fill;
     if (row < rows && col < ld) {
       int blk = 0;
       while (blk + 1 < n_src && row >= row0[blk + 1]) ++blk;

@@ -15,6 +15,9 @@
 // tilegs_pair_order() -- which is how the tests check it against the CPU oracle.  Targets are the
 // session's encoded fp32 words (4-ulp rounded; the oracle replay is given the same rounded
 // targets), positions and arithmetic are the session's precision, contraction off in f64.
+// Sessions of precision f64_exact (EXACT instances) stage the tile of fp32 deltas beside the word
+// tile and relax towards word + delta: the caller's f64 target to 2e-14 relative, so their oracle
+// replay is given the caller's own targets.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -100,9 +103,9 @@ inline int64_t tilegs_pair_order(int n, uint64_t seed, int iter, int32_t* pairs_
 // Pair update on an encoded target word (same operations as gs_pair_update / the reference).
 template <int DIM, typename real>
 __device__ __forceinline__ void tile_pair(real* pa, real* pb, uint32_t w, double ga, double gb, double k,
-                                          double c_rep) {
+                                          double c_rep, float delta = 0.0f) {
   const uint32_t c = w & kCodeMask;
-  const real target = (w == kInfWord) ? (real)INFINITY : (real)bits_f32(w & ~kCodeMask);
+  const real target = (w == kInfWord) ? (real)INFINITY : (real)bits_f32(w & ~kCodeMask) + (real)delta;
   const int code = c == 0 ? 0 : (c == 1 ? 1 : -1);
   gs_pair_dispatch<DIM, real>(pa, pb, target, code, ga, gb, k, c_rep);
 }
@@ -125,16 +128,28 @@ __global__ __launch_bounds__(256) void tilegs_perm_kernel(uint64_t seed, int ite
   }
 }
 
-// One round: block pair (I < J) per 64-thread workgroup (one wavefront).
-template <int DIM, typename real>
+// Row i's 64 words of a tile (16-byte loads) into row `lane` of its LDS copy.
+__device__ __forceinline__ void tile_stage_row(const uint32_t* __restrict__ row_words, uint32_t (&dst)[kTile + 1]) {
+  const uint4* src = reinterpret_cast<const uint4*>(row_words);
+#pragma unroll
+  for (int q = 0; q < kTile / 4; ++q) {
+    const uint4 v = src[q];
+    dst[4 * q + 0] = v.x; dst[4 * q + 1] = v.y;
+    dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w;
+  }
+}
+
+// One round: block pair (I < J) per 64-thread workgroup (one wavefront).  EXACT: denc = the session's delta block.
+template <int DIM, typename real, bool EXACT = false>
 __global__ __launch_bounds__(kTile) void tilegs_pair_kernel(
-    const uint32_t* __restrict__ enc, int ld, int n, real* __restrict__ pos,
+    const uint32_t* __restrict__ enc, const float* __restrict__ denc, int ld, int n, real* __restrict__ pos,
     const float* __restrict__ gplus, const int* __restrict__ bperm, int n_blocks, int round,
     const RunState* st, uint64_t seed, int iter, double k, double c_rep) {
   if (st != nullptr && st->stopped) return;
   __shared__ real pj[kTile][DIM];
   __shared__ float gj[kTile];
   __shared__ uint32_t tile[kTile][kTile + 1];
+  __shared__ uint32_t dtile[EXACT ? kTile : 1][kTile + 1];   // the deltas' bits
   const int lane = threadIdx.x;
   int bi, bj;
   {
@@ -159,13 +174,8 @@ __global__ __launch_bounds__(kTile) void tilegs_pair_kernel(
   gj[lane] = j_own < n ? gplus[j_own] : 1.0f;
   // row i of the tile: 64 consecutive words (16-byte loads), into LDS row `lane`
   if (vi) {
-    const uint4* src = reinterpret_cast<const uint4*>(enc + enc_index(i, bj * kTile, ld));
-#pragma unroll
-    for (int q = 0; q < kTile / 4; ++q) {
-      const uint4 v = src[q];
-      tile[lane][4 * q + 0] = v.x; tile[lane][4 * q + 1] = v.y;
-      tile[lane][4 * q + 2] = v.z; tile[lane][4 * q + 3] = v.w;
-    }
+    tile_stage_row(enc + enc_index(i, bj * kTile, ld), tile[lane]);
+    if constexpr (EXACT) tile_stage_row(reinterpret_cast<const uint32_t*>(denc) + enc_index(i, bj * kTile, ld), dtile[lane]);
   }
   __syncthreads();
   for (int s = 0; s < kTile; ++s) {
@@ -175,7 +185,7 @@ __global__ __launch_bounds__(kTile) void tilegs_pair_kernel(
       real pjt[DIM];
 #pragma unroll
       for (int d = 0; d < DIM; ++d) pjt[d] = pj[t][d];
-      tile_pair<DIM, real>(pi, pjt, tile[lane][t], gi, (double)gj[t], k, c_rep);
+      tile_pair<DIM, real>(pi, pjt, tile[lane][t], gi, (double)gj[t], k, c_rep, EXACT ? bits_f32(dtile[EXACT ? lane : 0][t]) : 0.0f);
 #pragma unroll
       for (int d = 0; d < DIM; ++d) pj[t][d] = pjt[d];
     }
@@ -191,15 +201,16 @@ __global__ __launch_bounds__(kTile) void tilegs_pair_kernel(
   }
 }
 
-// Last launch of an iteration: the pairs inside each block.
-template <int DIM, typename real>
+// Last launch of an iteration: the pairs inside each block.  EXACT: as tilegs_pair_kernel.
+template <int DIM, typename real, bool EXACT = false>
 __global__ __launch_bounds__(kTile) void tilegs_intra_kernel(
-    const uint32_t* __restrict__ enc, int ld, int n, real* __restrict__ pos,
+    const uint32_t* __restrict__ enc, const float* __restrict__ denc, int ld, int n, real* __restrict__ pos,
     const float* __restrict__ gplus, const RunState* st, uint64_t seed, int iter, double k, double c_rep) {
   if (st != nullptr && st->stopped) return;
   __shared__ real pb[kTile][DIM];
   __shared__ float gb[kTile];
   __shared__ uint32_t tile[kTile][kTile + 1];
+  __shared__ uint32_t dtile[EXACT ? kTile : 1][kTile + 1];
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
   const int i = b * kTile + lane;
@@ -208,13 +219,8 @@ __global__ __launch_bounds__(kTile) void tilegs_intra_kernel(
   for (int d = 0; d < DIM; ++d) pb[lane][d] = vi ? pos[(size_t)i * DIM + d] : (real)0;
   gb[lane] = vi ? gplus[i] : 1.0f;
   if (vi) {
-    const uint4* src = reinterpret_cast<const uint4*>(enc + enc_index(i, b * kTile, ld));
-#pragma unroll
-    for (int q = 0; q < kTile / 4; ++q) {
-      const uint4 v = src[q];
-      tile[lane][4 * q + 0] = v.x; tile[lane][4 * q + 1] = v.y;
-      tile[lane][4 * q + 2] = v.z; tile[lane][4 * q + 3] = v.w;
-    }
+    tile_stage_row(enc + enc_index(i, b * kTile, ld), tile[lane]);
+    if constexpr (EXACT) tile_stage_row(reinterpret_cast<const uint32_t*>(denc) + enc_index(i, b * kTile, ld), dtile[lane]);
   }
   __syncthreads();
   const int r0 = tile_intra_round0(seed, iter, b);
@@ -228,7 +234,7 @@ __global__ __launch_bounds__(kTile) void tilegs_intra_kernel(
         real pa[DIM], pc[DIM];
 #pragma unroll
         for (int d = 0; d < DIM; ++d) { pa[d] = pb[lo][d]; pc[d] = pb[hi][d]; }
-        tile_pair<DIM, real>(pa, pc, tile[lo][hi], (double)gb[lo], (double)gb[hi], k, c_rep);
+        tile_pair<DIM, real>(pa, pc, tile[lo][hi], (double)gb[lo], (double)gb[hi], k, c_rep, EXACT ? bits_f32(dtile[EXACT ? lo : 0][hi]) : 0.0f);
 #pragma unroll
         for (int d = 0; d < DIM; ++d) { pb[lo][d] = pa[d]; pb[hi][d] = pc[d]; }
       }

@@ -29,6 +29,7 @@
 #include "relax_common.h"
 #include "relax_host.h"
 #include "relax_kernels.h"
+#include "relax_exact.h"
 #include "relax_fold.h"
 #include "relax_gs.h"
 #include "relax_tilegs.h"
@@ -136,6 +137,7 @@ struct PendingCheck { bool active = false; int iter1 = 0; double k_after = 0.0; 
 struct topolow_session {
   int n = 0, dim = 0, udim = 0, row_begin = 0, row_end = 0, ld = 0;   // dim: coordinates the kernels carry, udim: the caller's ndim
   int precision = TOPOLOW_PRECISION_F32;
+  bool exact = false;           // TOPOLOW_PRECISION_F64_EXACT: an F64 session whose kernels read word + delta (denc)
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;
@@ -157,6 +159,7 @@ struct topolow_session {
   std::vector<int> perm, inv;      // session -> caller, caller -> session; empty = identity
   DevBuf<int> d_perm, d_inv;
   DevBuf<uint32_t> enc;
+  DevBuf<float> denc;          // exact sessions: fp32 (target - decoded word) per cell of enc, same layout, 0 where unmeasured
   DevBuf<float> gplus;
   DevBuf<unsigned char> rowflags;
   bool any_threshold = true;   // does any row of the block hold a ">" / "<" target?
@@ -455,6 +458,31 @@ void launch_stage_pipe(topolow_session* s, const void* pin, void* pout, RunState
   }
 }
 
+// The row-owner stage of an f64_exact session (relax_exact.h): the f64 pipe kernel's geometry, targets = word + delta.
+template <int DIM>
+void launch_stage_exact(topolow_session* s, const void* pin, void* pout, RunState* st, SlabRanges rg, int iter1, double k,
+                        int n_push) {
+  using CFG = StageCfg<256, 2, 0, 1>;
+  if (n_push > 0) throw HipError{TOPOLOW_ERR_UNSUPPORTED, "precision f64_exact: no row blocks (the stage kernel pushes to no peer)"};
+  const int blocks = (s->rows() + CFG::ROWS - 1) / CFG::ROWS;
+  auto launch = [&](auto kern, int which) {
+    static int resident[2] = {0, 0};     // as launch_stage_pipe: falling priority only when the whole grid is resident
+    if (resident[which] == 0) {
+      hipDeviceProp_t prop;
+      HIP_TRY(hipGetDeviceProperties(&prop, s->device));
+      int per_cu = 0;
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, CFG::THREADS, 0));
+      resident[which] = std::max(1, per_cu) * prop.multiProcessorCount;
+    }
+    const int falling = blocks <= resident[which] ? 1 : 0;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(CFG::THREADS), 0, s->stream, s->enc.p, s->denc.p, s->ld, s->row_begin,
+                       s->row_end, s->n, (const double*)pin, (double*)pout, s->gplus.p, s->rowflags.p, st, rg, iter1, k,
+                       s->c_rep, falling);
+  };
+  if (s->any_threshold) launch(&slab_stage_exact_kernel<DIM, CFG, true>, 1);
+  else launch(&slab_stage_exact_kernel<DIM, CFG, false>, 0);
+}
+
 template <int DIM>
 void launch_stage(topolow_session* s, const void* pin, void* pout, RunState* st, SlabRanges rg,
                   int iter1, double k, const void* push = nullptr, int n_push = 0, bool err = false) {
@@ -462,6 +490,7 @@ void launch_stage(topolow_session* s, const void* pin, void* pout, RunState* st,
   ProfScope prof(s, err ? &s->prof_stage_err : &s->prof_stage);
   if constexpr (DIM > kMaxTunedDim) {      // wide embeddings: the plain stage kernel (never an ERR launch: no dense MAE there)
     const int blocks = (s->rows() + kWaves - 1) / kWaves;
+    if (s->exact) throw HipError{TOPOLOW_ERR_UNSUPPORTED, "precision f64_exact: ndim must be between 1 and 16"};   // (refused at creation)
     if (s->precision == TOPOLOW_PRECISION_F64)
       hipLaunchKernelGGL((slab_stage_wide_kernel<DIM, double>), dim3(blocks), dim3(kThreads), 0, s->stream, s->enc.p, s->ld,
                          s->row_begin, s->row_end, s->n, (const double*)pin, (double*)pout, s->gplus.p, st, rg, iter1, k,
@@ -474,7 +503,9 @@ void launch_stage(topolow_session* s, const void* pin, void* pout, RunState* st,
     s->stage_launches += 1;
     return;
   } else
-  if (s->precision == TOPOLOW_PRECISION_F64) {
+  if (s->exact) {
+    launch_stage_exact<DIM>(s, pin, pout, st, rg, iter1, k, n_push);
+  } else if (s->precision == TOPOLOW_PRECISION_F64) {
     launch_stage_pipe<DIM, double, StageCfg<256, 2, 0, 1>>(s, pin, pout, st, rg, iter1, k, push, n_push, false);
   } else {
 #ifdef TOPOLOW_TUNING
@@ -693,22 +724,30 @@ void launch_tilegs_iteration(topolow_session* s, void* pos, int iter, double k) 
   hipLaunchKernelGGL(tilegs_perm_kernel, dim3(1), dim3(256), 0, s->stream, s->seed, iter, nb, s->bperm.p,
                      s->state.p);
   const int M = nb + (nb & 1), m1 = M - 1;
+  const float* no_delta = nullptr;
   for (int r = 0; r < m1 && nb >= 2; ++r) {
-    if (s->precision == TOPOLOW_PRECISION_F64)
+    if (s->exact)
+      hipLaunchKernelGGL((tilegs_pair_kernel<DIM, double, true>), dim3(M / 2), dim3(kTile), 0, s->stream, s->enc.p,
+                         s->denc.p, s->ld, s->n, (double*)pos, s->gplus.p, s->bperm.p, nb, r, s->state.p, s->seed, iter, k,
+                         s->c_rep);
+    else if (s->precision == TOPOLOW_PRECISION_F64)
       hipLaunchKernelGGL((tilegs_pair_kernel<DIM, double>), dim3(M / 2), dim3(kTile), 0, s->stream, s->enc.p,
-                         s->ld, s->n, (double*)pos, s->gplus.p, s->bperm.p, nb, r, s->state.p, s->seed, iter, k,
+                         no_delta, s->ld, s->n, (double*)pos, s->gplus.p, s->bperm.p, nb, r, s->state.p, s->seed, iter, k,
                          s->c_rep);
     else
       hipLaunchKernelGGL((tilegs_pair_kernel<DIM, float>), dim3(M / 2), dim3(kTile), 0, s->stream, s->enc.p,
-                         s->ld, s->n, (float*)pos, s->gplus.p, s->bperm.p, nb, r, s->state.p, s->seed, iter, k,
+                         no_delta, s->ld, s->n, (float*)pos, s->gplus.p, s->bperm.p, nb, r, s->state.p, s->seed, iter, k,
                          s->c_rep);
     s->stage_launches += 1;
   }
-  if (s->precision == TOPOLOW_PRECISION_F64)
-    hipLaunchKernelGGL((tilegs_intra_kernel<DIM, double>), dim3(nb), dim3(kTile), 0, s->stream, s->enc.p, s->ld,
+  if (s->exact)
+    hipLaunchKernelGGL((tilegs_intra_kernel<DIM, double, true>), dim3(nb), dim3(kTile), 0, s->stream, s->enc.p, s->denc.p,
+                       s->ld, s->n, (double*)pos, s->gplus.p, s->state.p, s->seed, iter, k, s->c_rep);
+  else if (s->precision == TOPOLOW_PRECISION_F64)
+    hipLaunchKernelGGL((tilegs_intra_kernel<DIM, double>), dim3(nb), dim3(kTile), 0, s->stream, s->enc.p, no_delta, s->ld,
                        s->n, (double*)pos, s->gplus.p, s->state.p, s->seed, iter, k, s->c_rep);
   else
-    hipLaunchKernelGGL((tilegs_intra_kernel<DIM, float>), dim3(nb), dim3(kTile), 0, s->stream, s->enc.p, s->ld,
+    hipLaunchKernelGGL((tilegs_intra_kernel<DIM, float>), dim3(nb), dim3(kTile), 0, s->stream, s->enc.p, no_delta, s->ld,
                        s->n, (float*)pos, s->gplus.p, s->state.p, s->seed, iter, k, s->c_rep);
   s->stage_launches += 1;
   HIP_TRY(hipGetLastError());
@@ -785,8 +824,12 @@ void sym_real(const topolow_session* s, F&& f) {
 // f(kernel) with the sweep instance for (real, thresholds, err): the one list of instances, for the launches and the
 // occupancy probe alike.
 template <int DIM, typename real, typename F>
-void sym_sweep_instance(bool thr, bool err, F&& f) {
+void sym_sweep_instance(bool thr, bool err, bool exact, F&& f) {
   if constexpr (std::is_same<real, double>::value) {
+    if (exact) {   // f64_exact sessions: targets = word + delta in every instance (relax_symm64.h: symm64x_sweep_kernel)
+      if (thr) { if (err) f(&symm64x_sweep_kernel<DIM, true, true>); else f(&symm64x_sweep_kernel<DIM, true, false>); }
+      else { if (err) f(&symm64x_sweep_kernel<DIM, false, true>); else f(&symm64x_sweep_kernel<DIM, false, false>); }
+    } else
     if (thr) { if (err) f(&symm64_sweep_kernel<DIM, true, true>); else f(&symm64_sweep_kernel<DIM, true, false>); }
     else { if (err) f(&symm64_sweep_kernel<DIM, false, true>); else f(&symm64_sweep_kernel<DIM, false, false>); }
   } else if constexpr (DIM >= kSymWideMinDim) {   // same arguments, rows in LDS (relax_symm_wide.h)
@@ -818,8 +861,8 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
   };
   const bool f64 = s->precision == TOPOLOW_PRECISION_F64;
   sym_real<DIM>(s, [&](auto r) {
-    sym_sweep_instance<DIM, decltype(r)>(any_thr, false, probe);
-    sym_sweep_instance<DIM, decltype(r)>(any_thr, true, probe);
+    sym_sweep_instance<DIM, decltype(r)>(any_thr, false, s->exact, probe);
+    sym_sweep_instance<DIM, decltype(r)>(any_thr, true, s->exact, probe);
   });
   y.grid = occ * prop.multiProcessorCount;
   if (y.grid_cap > 0) y.grid = std::min(y.grid, y.grid_cap);
@@ -835,7 +878,7 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
   y.tenc.alloc((size_t)std::max(y.tiles, 1) * kSymTileWords);
   if (y.tiles > 0)
     hipLaunchKernelGGL(symm_tiles_kernel, dim3(y.tiles), dim3(256), 0, s->stream, y.src_tab.p, y.src_row0.p, (int)src.size(),
-                       s->ld, y.tenc.p, TC, t0);
+                       s->ld, y.tenc.p, TC, t0, kInfWord);
   HIP_TRY(hipGetLastError());
   const int seg_rows = y.seg_last >= y.seg_first ? y.seg_last - y.seg_first + 1 : 1;
   const size_t rs = s->real_size();
@@ -846,7 +889,24 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
   y.colpart.alloc((size_t)seg_rows * y.npad * DIM * rs);
   // (a segment's first and last tile-row are partial: the columns its tiles never reach must read as zero)
   HIP_TRY(hipMemsetAsync(y.colpart.p, 0, (size_t)seg_rows * y.npad * DIM * rs, s->stream));
-  if (f64) {
+  if (s->exact) {
+    // the delta tiles come from the session's delta block, permuted like the words (4-byte cells either way); every
+    // instance reads them.  (A fused check also needs the edge list to be the block's measured cells: sym_fused_ok.)
+    if (!(src.size() == 1 && src[0] == s->enc.p))
+      throw HipError{TOPOLOW_ERR_UNSUPPORTED, "precision f64_exact: the sweep is built from the session's own block only"};
+    y.delta_ready = false;
+    y.tdelta.alloc((size_t)std::max(y.tiles, 1) * kSymTileWords);
+    DevBuf<const uint32_t*> dsrc;
+    dsrc.alloc(1);
+    const uint32_t* dp = reinterpret_cast<const uint32_t*>(s->denc.p);
+    HIP_TRY(hipMemcpy(dsrc.p, &dp, sizeof dp, hipMemcpyHostToDevice));
+    if (y.tiles > 0)
+      hipLaunchKernelGGL(symm_tiles_kernel, dim3(y.tiles), dim3(256), 0, s->stream, dsrc.p, y.src_row0.p, 1, s->ld,
+                         reinterpret_cast<uint32_t*>(y.tdelta.p), TC, t0, 0u);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->stream));   // (dsrc goes out of scope)
+    y.delta_ready = true;
+  } else if (f64) {
     // the fused check needs the edge list to BE the block's measured cells and to be on the device in f64
     y.delta_ready = false;
     if (s->list_is_block && !s->dense_mae && s->n_edges > 0 && y.whole) {
@@ -911,7 +971,7 @@ void sym_sweep(topolow_session* s, const SymPlanDev& plan, const void* rec, bool
   auto& y = s->sym;
   sym_real<DIM>(s, [&](auto r) {
     using real = decltype(r);
-    sym_sweep_instance<DIM, real>(thr, err, [&](auto kern) {
+    sym_sweep_instance<DIM, real>(thr, err, s->exact, [&](auto kern) {
       if constexpr (std::is_same<real, double>::value)
         hipLaunchKernelGGL(kern, dim3(y.grid), dim3(64 * kSymWaves), 0, s->stream, y.tenc.p, (const double*)rec,
                            plan.units.p, plan.runs.p, (double*)y.rowpart.p, (double*)y.colpart.p, y.npad, s->state.p,
@@ -922,6 +982,14 @@ void sym_sweep(topolow_session* s, const SymPlanDev& plan, const void* rec, bool
                            s->part_sum.p, s->part_cnt.p, block_cells, col_row0, prio && y.prio ? 1 : 0);
     });
   });
+}
+
+// f64: whether a sweep may reduce a check's MAE.  Plain f64 sessions: the delta tiles exist (they are made from the edge
+// list when it is the block's measured cells).  Exact sessions always have delta tiles, from the matrix; the fused
+// check's sum and count run over the block's measured cells, so the list must still be exactly those.
+bool sym_fused_ok(const topolow_session* s) {
+  if (!s->sym.delta_ready) return false;
+  return !s->exact || (s->list_is_block && s->n_edges > 0 && s->sym.whole);
 }
 
 // The apply of the whole triangle (rr_stages = 0) or of stage rr_stage of an rr_stages-stage iteration: positions into
@@ -986,7 +1054,7 @@ void sym_iteration(topolow_session* s, const void* pin, void* pout, int iter, do
   auto& y = s->sym;
   const SymPlanDev& plan = S == 0 ? y.plan : y.rr[sym_rr_log2(S)][st];
   ProfScope prof(s, S > 0 ? &s->prof_stage : err ? &s->prof_sym_err : &s->prof_sym);
-  if (err && s->precision == TOPOLOW_PRECISION_F64 && !y.delta_ready)
+  if (err && s->precision == TOPOLOW_PRECISION_F64 && !sym_fused_ok(s))
     throw HipError{TOPOLOW_ERR_UNSUPPORTED, "symmetric sweep (f64): no delta tiles for a fused check"};
   if (y.rec_iter != iter) {
     for (int b = 0; b < 2; ++b)   // both buffers need the phantom records; the second one's points are overwritten by the apply
@@ -1060,7 +1128,7 @@ int enqueue_stage(topolow_session* s, const IterPlan& p, int t, const void* pin,
 // first: an f64 session builds its sweep at its first check).
 bool check_fusable(topolow_session* s, int n_stages) {
   if (s->precision == TOPOLOW_PRECISION_F64)
-    return sym_form(s, 1) == SymForm::kSweep && s->sym.delta_ready && n_stages == 1;
+    return sym_form(s, 1) == SymForm::kSweep && sym_fused_ok(s) && n_stages == 1;
   return n_stages == 1 && (s->rows() % 2 == 0 || sym_form(s, 1) == SymForm::kSweep);
 }
 
@@ -1432,6 +1500,17 @@ int topolow_session_create(topolow_session** out, int32_t n, int32_t ndim, int32
     set_err(errbuf, errlen, "bad row block [%d,%d) for n=%d", row_begin, row_end, n);
     return TOPOLOW_ERR_BAD_ARGUMENT;
   }
+  const bool exact = precision == TOPOLOW_PRECISION_F64_EXACT;
+  if (exact && (row_begin != 0 || row_end != n)) {
+    set_err(errbuf, errlen, "precision f64_exact: whole-problem sessions only (rows [%d,%d) of %d asked for): the row-sharded "
+            "paths have no exact kernels", row_begin, row_end, n);
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
+  if (exact && ndim > kMaxTunedDim) {
+    set_err(errbuf, errlen, "precision f64_exact: ndim must be between 1 and %d (the plain stage kernel of wider embeddings "
+            "reads the 4-byte targets only)", kMaxTunedDim);
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
   topolow_session* s = nullptr;
   const int rc = guarded(errbuf, errlen, [&] {
     const int dev = select_device(device);
@@ -1443,8 +1522,8 @@ int topolow_session_create(topolow_session** out, int32_t n, int32_t ndim, int32
     s->row_begin = row_begin;
     s->row_end = row_end;
     s->ld = (n + kEncLdAlign - 1) & ~(kEncLdAlign - 1);
-    s->precision = precision == TOPOLOW_PRECISION_F64 ? TOPOLOW_PRECISION_F64
-                                                      : TOPOLOW_PRECISION_F32;
+    s->precision = precision == TOPOLOW_PRECISION_F64 || exact ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32;
+    s->exact = exact;
     HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
     s->stream = s->own_stream;
     HIP_TRY(hipStreamCreateWithFlags(&s->check_stream, hipStreamNonBlocking));
@@ -1468,6 +1547,7 @@ int topolow_session_create(topolow_session** out, int32_t n, int32_t ndim, int32
     const char* sym_prio = getenv("TOPOLOW_SYM_PRIO");
     s->sym.prio = !(sym_prio != nullptr && sym_prio[0] == '0');
     s->enc.alloc((size_t)((s->rows() + kEncRowAlign - 1) / kEncRowAlign * kEncRowAlign) * s->ld);
+    if (s->exact) s->denc.alloc(s->enc.n);
     const size_t pos_bytes = (size_t)s->pos_rows() * s->dim * s->real_size();
     for (auto& b : s->pos) b.alloc(pos_bytes);
     s->best.alloc(pos_bytes);
@@ -1539,7 +1619,8 @@ int topolow_session_load_dense(topolow_session* s, const double* D, const int32_
     HIP_TRY(hipMemcpy(dT.p, T, nn * 4, hipMemcpyHostToDevice));
     dim3 grid(s->rows(), (s->ld + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(encode_dense_kernel, grid, dim3(kThreads), 0, s->stream, dD.p, dT.p, s->n,
-                       s->row_begin, s->row_end, s->ld, s->enc.p, s->perm.empty() ? nullptr : s->d_perm.p);
+                       s->row_begin, s->row_end, s->ld, s->enc.p, s->perm.empty() ? nullptr : s->d_perm.p,
+                       s->exact ? s->denc.p : (float*)nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s->stream));
     compute_row_flags(s);
@@ -1556,7 +1637,7 @@ int topolow_session_load_coo(topolow_session* s, const int32_t* edge_i, const in
     HIP_TRY(hipSetDevice(s->device));
     dim3 grid(s->rows(), (s->ld + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(fill_unmeasured_kernel, grid, dim3(kThreads), 0, s->stream, s->n,
-                       s->row_begin, s->row_end, s->ld, s->enc.p);
+                       s->row_begin, s->row_end, s->ld, s->enc.p, s->exact ? s->denc.p : (float*)nullptr);
     HIP_TRY(hipGetLastError());
     const int64_t chunk = 1 << 24;
     DevBuf<int> di, dj, dc;
@@ -1571,7 +1652,8 @@ int topolow_session_load_coo(topolow_session* s, const int32_t* edge_i, const in
       HIP_TRY(hipMemcpyAsync(dc.p, edge_thresh + off, m * 4, hipMemcpyHostToDevice, s->stream));
       hipLaunchKernelGGL(scatter_edges_kernel, dim3((unsigned)((m + kThreads - 1) / kThreads)),
                          dim3(kThreads), 0, s->stream, di.p, dj.p, dd.p, dc.p, (long long)m, s->n,
-                         s->row_begin, s->row_end, s->ld, s->enc.p, s->inv.empty() ? nullptr : s->d_inv.p);
+                         s->row_begin, s->row_end, s->ld, s->enc.p, s->inv.empty() ? nullptr : s->d_inv.p,
+                         s->exact ? s->denc.p : (float*)nullptr);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipStreamSynchronize(s->stream));
     }
@@ -1590,6 +1672,11 @@ int topolow_session_commit_encoded(topolow_session* s, const int32_t* degrees, c
   if (!s->perm.empty()) {
     set_err(errbuf, errlen, "a block filled by the caller is in the caller's labels: not with a relabelled session");
     return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (s->exact) {
+    set_err(errbuf, errlen, "precision f64_exact: a block of 4-byte words filled by the caller carries no deltas; load the "
+            "targets with topolow_session_load_dense or topolow_session_load_coo");
+    return TOPOLOW_ERR_UNSUPPORTED;
   }
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
@@ -2415,6 +2502,10 @@ int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const in
   if (!s || !degrees || n_pairs < 0 || (n_pairs > 0 && (!pair_i || !pair_j))) return TOPOLOW_ERR_BAD_ARGUMENT;
   const int rc0 = cv_check_session(s, errbuf, errlen);
   if (rc0 != TOPOLOW_OK) return rc0;
+  if (s->exact) {
+    set_err(errbuf, errlen, "precision f64_exact: folds cannot be held out of the session (the patch does not cover the delta block)");
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
   if (s->cv.active) {
     set_err(errbuf, errlen, "a fold is held out already: topolow_session_restore_held_out first");
     return TOPOLOW_ERR_BAD_ARGUMENT;
@@ -2626,6 +2717,11 @@ int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int3
   if (schedule != TOPOLOW_SCHEDULE_AUTO && schedule != TOPOLOW_SCHEDULE_SLAB && schedule != TOPOLOW_SCHEDULE_GS)
     return TOPOLOW_ERR_BAD_ARGUMENT;
   if (device_seconds) *device_seconds = 0.0;
+  if (precision == TOPOLOW_PRECISION_F64_EXACT) {
+    set_err(errbuf, errlen, "precision f64_exact: no cross-validation on resident sessions (holding a fold out does not "
+            "cover the delta block); topolow_cv_sweep runs it on the one-workgroup kernel");
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
   if (n_folds == 0) return TOPOLOW_OK;
   const int n = cells->n;
   const bool tile_gs = schedule == TOPOLOW_SCHEDULE_GS;
@@ -3004,6 +3100,10 @@ int topolow_optimize_layout_exact_sharded(
   if (opt_in) opt = *opt_in; else topolow_default_options(&opt);
   if (opt.schedule == TOPOLOW_SCHEDULE_GS) {
     set_err(errbuf, errlen, "the row-sharded path runs the slab schedule; exact Gauss-Seidel is a one-GPU schedule");
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
+  if (opt.precision == TOPOLOW_PRECISION_F64_EXACT) {
+    set_err(errbuf, errlen, "precision f64_exact: one GPU only (the row-sharded engine has no exact kernels)");
     return TOPOLOW_ERR_UNSUPPORTED;
   }
   const int want = opt.n_devices > 0 ? opt.n_devices : 1;

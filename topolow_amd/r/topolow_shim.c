@@ -21,7 +21,7 @@
  *     R CMD SHLIB topolow_shim.c -L<dir> -ltopolow_relax -I<repo>/include
  * Backend options travel through R options(), never through the function signatures:
  *     options(topolow.seed = 1L, topolow.schedule = "auto"|"slab"|"gs",
- *             topolow.precision = "auto"|"f32"|"f64", topolow.device = 0L,
+ *             topolow.precision = "auto"|"f32"|"f64"|"f64_exact", topolow.device = 0L,
  *             topolow.devices = c(0L, 1L, ...))      # ONE embedding row-sharded over these GPUs
  */
 #include <R.h>
@@ -64,6 +64,14 @@ static int opt_choice(const char* name, const char* a, int va, const char* b, in
   return dflt;
 }
 
+/* options(topolow.precision): "f32", "f64", "f64_exact"; anything else (or unset) = dflt */
+static int opt_precision(int dflt) {
+  SEXP v = Rf_GetOption1(Rf_install("topolow.precision"));
+  if (v != R_NilValue && Rf_isString(v) && Rf_length(v) >= 1 && strcmp(CHAR(STRING_ELT(v, 0)), "f64_exact") == 0)
+    return TOPOLOW_PRECISION_F64_EXACT;
+  return opt_choice("topolow.precision", "f32", TOPOLOW_PRECISION_F32, "f64", TOPOLOW_PRECISION_F64, dflt);
+}
+
 static uint64_t mix64(uint64_t z) {
   z += 0x9e3779b97f4a7c15ull;
   z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
@@ -99,8 +107,7 @@ static void fill_options(topolow_options* opt, int32_t* devices, int max_devices
   opt->seed = order_seed();
   opt->schedule = opt_choice("topolow.schedule", "slab", TOPOLOW_SCHEDULE_SLAB, "gs",
                              TOPOLOW_SCHEDULE_GS, TOPOLOW_SCHEDULE_AUTO);
-  opt->precision = opt_choice("topolow.precision", "f32", TOPOLOW_PRECISION_F32, "f64",
-                              TOPOLOW_PRECISION_F64, TOPOLOW_PRECISION_AUTO);
+  opt->precision = opt_precision(TOPOLOW_PRECISION_AUTO);
   opt->device = opt_int("topolow.device", -1);
   opt->slab_stages = opt_int("topolow.slab_stages", 0);
   opt->gs_max_n = opt_int("topolow.gs_max_n", 0);
@@ -247,8 +254,7 @@ SEXP _topolow_optimize_layout_exact_batch(SEXP callsSEXP) {
   }
   char err[512];
   err[0] = '\0';
-  const int precision = opt_choice("topolow.precision", "f32", TOPOLOW_PRECISION_F32, "f64",
-                                   TOPOLOW_PRECISION_F64, TOPOLOW_PRECISION_F64);
+  const int precision = opt_precision(TOPOLOW_PRECISION_F64);
   const int rc = topolow_optimize_layout_exact_batch(pb, rs, count, precision, opt_int("topolow.device", -1),
                                                      NULL, err, sizeof err);
   if (rc != TOPOLOW_OK) {
@@ -450,8 +456,7 @@ static SEXP cv_sweep_run(SEXP arg, int session, int schedule) {
   char err[512];
   err[0] = 0;
   /* precision unset: f64 for the batch; on sessions f32 for the slab schedule, f64 for "gs" (the library's AUTO) */
-  const int precision = opt_choice("topolow.precision", "f32", TOPOLOW_PRECISION_F32, "f64", TOPOLOW_PRECISION_F64,
-                                   session ? TOPOLOW_PRECISION_AUTO : TOPOLOW_PRECISION_F64);
+  const int precision = opt_precision(session ? TOPOLOW_PRECISION_AUTO : TOPOLOW_PRECISION_F64);
   const int rc =
       session ? topolow_cv_sweep_session(&cells, Rf_asLogical(VECTOR_ELT(a, 5)), Rf_asLogical(VECTOR_ELT(a, 6)), F,
                                          INTEGER(ndim), REAL(k0), REAL(cool), REAL(crep), picks, p_off,
