@@ -324,6 +324,43 @@ int topolow_est_distances(const double* positions, int32_t n, int32_t ndim,
 int topolow_est_distances_rows(const double* positions, int32_t n, int32_t ndim, int32_t row_begin,
                                int32_t row_end, double* out, int32_t device, char* errbuf, size_t errlen);
 
+/* Replaces the reference's post-processing (R/core.R:474-481) in one pass over the device:
+ * est_distances = as.matrix(dist(positions)) and the two terms of mae = mean(|as.numeric(D) - est|).
+ *   positions      n x ndim f64 column-major (host), any ndim >= 1
+ *   values         n x n f64 column-major (host)
+ *   codes          n x n i32 column-major (host), or NULL
+ *   est_distances  n x n f64 out (host), or NULL: not wanted.  Bit-identical to topolow_est_distances.
+ * A cell counts iff values[cell] is finite (not NaN, not +-Inf) and (codes == NULL or codes[cell] == 0); the
+ * diagonal counts like any other cell.  So the same rule reads both forms of the input: as.numeric(D) with NaN
+ * for NA and for threshold strings and codes = NULL, or the matrices of the 16-argument call (+Inf = unmeasured,
+ * threshold_mask as codes).
+ *   *sum_abs = sum over the counting cells of |values[i,j] - ||p_i - p_j|||,  *count = their number.
+ * mae = sum_abs / count is the caller's division (count 0: R's mean of nothing, NaN).  Non-finite positions
+ * propagate: sum_abs is NaN.
+ * The sum is reproducible: one partial per column, reduced in a fixed order on the device, the columns added in
+ * index order on the host -- the same bits whatever the tile size, and whether or not est_distances is asked for.
+ * The matrices travel in tiles of columns (device buffers and pinned memory bounded, uploads, kernels and
+ * downloads overlapped); TOPOLOW_POST_TILE_COLS=<c> in the environment caps the columns per tile (a test knob,
+ * read per call).
+ * TOPOLOW_ERR_BAD_ARGUMENT, before any device call: NULL positions, values, sum_abs or count; n < 1; ndim < 1. */
+int topolow_post_metrics(const double* positions, int32_t n, int32_t ndim, const double* values,
+                         const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
+                         int32_t device, char* errbuf, size_t errlen);
+
+/* How topolow_post_metrics_ex reaches the caller's pageable matrices. */
+#define TOPOLOW_POST_STAGING_DEFAULT 0   /* what topolow_post_metrics uses */
+#define TOPOLOW_POST_STAGING_PINNED 1    /* through pinned staging buffers that host threads fill and drain */
+#define TOPOLOW_POST_STAGING_REGISTER 2  /* hipHostRegister on the caller's matrices for the length of the call */
+#define TOPOLOW_POST_STAGING_PAGEABLE 3  /* asynchronous copies on the pageable memory as it is */
+
+/* The same call with the staging chosen by the caller and the time of each phase measured (a study entry:
+ * tests/study/post_metrics_timing.py).  phase_seconds: NULL, or 3 doubles out -- the sums over all tiles of the
+ * host-to-device copies, the kernels and the device-to-host copies, from device events (the phases overlap, so
+ * they do not add up to the call's wall-clock time).  Every staging computes the same bits. */
+int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, const double* values,
+                            const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
+                            int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen);
+
 /* ---------------------------------------------------------------------------------------
  * Device-resident session: the same relaxation with inputs kept in HBM, for callers that
  * run many iterations / many embeddings on data they already hold on the GPU (bench.py, the

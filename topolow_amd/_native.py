@@ -215,6 +215,12 @@ def load() -> C.CDLL:
     lib.topolow_est_distances_rows.restype = C.c_int
     lib.topolow_est_distances_rows.argtypes = [dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32,
                                                C.c_char_p, C.c_size_t]
+    lib.topolow_post_metrics.restype = C.c_int
+    lib.topolow_post_metrics.argtypes = [dp, C.c_int32, C.c_int32, dp, ip, dp, dp, i64p, C.c_int32, C.c_char_p,
+                                         C.c_size_t]
+    lib.topolow_post_metrics_ex.restype = C.c_int
+    lib.topolow_post_metrics_ex.argtypes = [dp, C.c_int32, C.c_int32, dp, ip, dp, dp, i64p, C.c_int32, C.c_int32, dp,
+                                            C.c_char_p, C.c_size_t]
     vp = C.c_void_p
     lib.topolow_session_create.restype = C.c_int
     lib.topolow_session_create.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, C.c_int32,
@@ -791,6 +797,55 @@ def est_distances_rows(positions, row_begin: int, row_end: int) -> np.ndarray:
                                         int(options.get("device", -1)), err, len(err))
     _check(rc, err)
     return out
+
+
+POST_STAGINGS = {"default": 0, "pinned": 1, "register": 2, "pageable": 3}
+
+
+def mae_of(sum_abs: float, count: int) -> float:
+    """mae = sum_abs / count; no counting cell is R's mean of nothing, NaN (no warning)."""
+    return float(sum_abs) / int(count) if int(count) > 0 else float("nan")
+
+
+def post_metrics(positions, values, codes=None, want_est: bool = True, staging: str = "default",
+                 phases: Optional[list] = None):
+    """The reference's post-processing (R/core.R:474-481) in one pass on the GPU: returns
+    (est_distances or None, sum_abs, count) with sum_abs = sum |values - est| over the cells whose value is
+    finite and whose code (if codes are given) is 0, the diagonal included; mae = mae_of(sum_abs, count).
+    est_distances is bit-identical to est_distances(positions).
+
+    `values` (and `codes`) are used where they lie when they are contiguous.  The library reads column-major
+    matrices, so a C-contiguous pair is read as its transpose: est_distances is symmetric bit for bit, so the
+    count and the set of summed terms are the same and only the order of the additions (the last bits of
+    sum_abs) follows the transposed matrix; an n x n transposing copy is spared.  `staging` and `phases`
+    (a list that receives the seconds of the upload, kernel and download phases) are for
+    tests/study/post_metrics_timing.py."""
+    lib = load()
+    pos = _f64F(positions)
+    n, dim = pos.shape
+    vals = np.asarray(values, dtype=np.float64)
+    if vals.shape != (n, n):
+        raise ValueError("values must be an n x n matrix with one row per position")
+    c_order = vals.flags.c_contiguous and not vals.flags.f_contiguous
+    need = ["C", "A"] if c_order else ["F", "A"]
+    vals = np.require(vals, requirements=need)
+    cds = None
+    if codes is not None:
+        cds = np.require(np.asarray(codes, dtype=np.int32), requirements=need)
+        if cds.shape != (n, n):
+            raise ValueError("codes must have the shape of values")
+    est = np.empty((n, n), dtype=np.float64) if want_est else None
+    s, c = C.c_double(0.0), C.c_int64(0)
+    ph = (C.c_double * 3)()
+    err = C.create_string_buffer(512)
+    rc = lib.topolow_post_metrics_ex(_dp(pos), n, dim, _dp(vals), _ip(cds) if cds is not None else None,
+                                     _dp(est) if est is not None else None, C.byref(s), C.byref(c),
+                                     int(options.get("device", -1)), POST_STAGINGS[staging],
+                                     ph if phases is not None else None, err, len(err))
+    _check(rc, err)
+    if phases is not None:
+        phases[:] = [ph[0], ph[1], ph[2]]
+    return est, float(s.value), int(c.value)
 
 
 # ---- host-side helpers (no GPU needed) ---------------------------------------------------

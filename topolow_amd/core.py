@@ -429,11 +429,24 @@ def write_positions_csv(path: str, positions: np.ndarray, names: Optional[Sequen
 # --------------------------------------------------------------------------------------
 # public entry points
 # --------------------------------------------------------------------------------------
+def device_post(call: LayoutCall, positions: np.ndarray):
+    """R/core.R:474-481 in one fused pass on the GPU (_native.post_metrics): (est_distances, mae).
+    est_distances is what _native.est_distances returns, bit for bit; mae is post_mae's to 1e-12 (the sum is
+    grouped by columns).  One deviation: a cell that holds +-Inf is left out, as the relaxation leaves it out
+    (post_mae counts it, and returns Inf or NaN)."""
+    from . import _native
+    est, sum_abs, count = _native.post_metrics(positions, call.reordered_matrix.as_numeric())
+    return est, _native.mae_of(sum_abs, count)
+
+
 def _finish(call: LayoutCall, native_result, ndim, k0, cooling_rate, c_repulsion,
-            write_positions_to_csv, output_dir, verbose, pdist_fn) -> Topolow:
+            write_positions_to_csv, output_dir, verbose, pdist_fn, post_fn=None) -> Topolow:
     positions = np.asarray(native_result.positions, dtype=np.float64)
-    est = pdist_fn(positions)
-    mae = post_mae(call.reordered_matrix, est)
+    if post_fn is None:
+        est = pdist_fn(positions)
+        mae = post_mae(call.reordered_matrix, est)
+    else:
+        est, mae = post_fn(call, positions)
     if write_positions_to_csv:
         if output_dir is None or output_dir is _MISSING:
             raise ValueError("An 'output_dir' must be provided when 'write_positions_to_csv' "
@@ -458,7 +471,8 @@ def _finish(call: LayoutCall, native_result, ndim, k0, cooling_rate, c_repulsion
 def _embed_with(native_fn, pdist_fn, dissimilarity_matrix, ndim, mapping_max_iter, k0,
                 cooling_rate, c_repulsion, relative_epsilon, convergence_counter,
                 initial_positions, write_positions_to_csv, output_dir, verbose,
-                convergence_check_freq, preserve_order, rng=None) -> Topolow:
+                convergence_check_freq, preserve_order, rng=None, post_fn=None) -> Topolow:
+    """post_fn(call, positions) -> (est_distances, mae) replaces pdist_fn + post_mae when given."""
     for nm, val in (("k0", k0), ("cooling_rate", cooling_rate), ("c_repulsion", c_repulsion)):
         if val is _MISSING:
             raise TypeError(f'argument "{nm}" is missing, with no default')
@@ -474,7 +488,7 @@ def _embed_with(native_fn, pdist_fn, dissimilarity_matrix, ndim, mapping_max_ite
     if verbose:
         print("Optimization finished in %.2f seconds." % (time.time() - t0))
     return _finish(call, res, ndim, k0, cooling_rate, c_repulsion, write_positions_to_csv,
-                   output_dir, verbose, pdist_fn)
+                   output_dir, verbose, pdist_fn, post_fn)
 
 
 def euclidean_embedding(dissimilarity_matrix, ndim, mapping_max_iter=1000, k0=_MISSING,
@@ -489,7 +503,7 @@ def euclidean_embedding(dissimilarity_matrix, ndim, mapping_max_iter=1000, k0=_M
                        dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
                        c_repulsion, relative_epsilon, convergence_counter, initial_positions,
                        write_positions_to_csv, output_dir, verbose, convergence_check_freq,
-                       preserve_order, _native.host_rng())
+                       preserve_order, _native.host_rng(), post_fn=device_post)
 
 
 def create_topolow_map(distance_matrix, ndim, mapping_max_iter=1000, k0=_MISSING,

@@ -1,0 +1,67 @@
+// topolow_amd/csrc/relax_post.h -- the post-metrics kernel: est_distances and the terms of mae in one pass
+// (reference R/core.R:474-481; host pipeline: topolow_post_metrics in topolow_relax.hip).
+#pragma once
+
+#include "relax_common.h"
+
+namespace topolow {
+
+constexpr int kPostThreads = 256;
+
+// One workgroup per column of a tile of columns [col0, col0 + cols) of the caller's column-major n x n matrices.
+//   vals   cols x n f64: the tile of `values`, column after column (the caller's own layout)
+//   codes  cols x n i32 or nullptr
+//   est    cols x n f64 out or nullptr: est[c * n + i] = ||p_i - p_(col0 + c)||
+//   col_sum / col_cnt   n entries each; this launch writes [col0, col0 + cols)
+// Lane l of the workgroup walks rows l, l + 256, ...: 8-byte accesses, consecutive lanes on consecutive
+// addresses.  The distance is pdist_kernel's own arithmetic (a sequential s += dev * dev over the coordinates,
+// then ::sqrt), so est is bit-identical to topolow_est_distances.
+// A column's partial is reduced in one fixed order -- each lane over its rows in ascending order, the 64 lanes
+// of a wave by a shuffle tree, the four waves in wave order -- and belongs to the column alone: it does not
+// depend on the tile the column arrived in, nor on whether est is written.  No atomics.
+__global__ __launch_bounds__(kPostThreads) void post_metrics_kernel(
+    const double* __restrict__ pos, int n, int dim, int col0, int cols, const double* __restrict__ vals,
+    const int32_t* __restrict__ codes, double* __restrict__ est, double* __restrict__ col_sum,
+    uint32_t* __restrict__ col_cnt) {
+  __shared__ double wave_sum[kPostThreads / 64];
+  __shared__ uint32_t wave_cnt[kPostThreads / 64];
+  const int c = blockIdx.x;
+  if (c >= cols) return;
+  const int j = col0 + c;
+  const size_t base = (size_t)c * (size_t)n;
+  const double* pj = pos + (size_t)j * dim;
+  double sum = 0.0;
+  uint32_t cnt = 0;
+  for (int i = threadIdx.x; i < n; i += kPostThreads) {
+    const double* pi = pos + (size_t)i * dim;
+    double s = 0.0;
+    for (int d = 0; d < dim; ++d) {
+      const double dev = pj[d] - pi[d];
+      s += dev * dev;
+    }
+    const double r = ::sqrt(s);
+    if (est != nullptr) est[base + i] = r;
+    const double v = vals[base + i];
+    const bool counts = __builtin_isfinite(v) && (codes == nullptr || codes[base + i] == 0);
+    if (counts) {
+      sum += ::fabs(v - r);
+      ++cnt;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_down(sum, off, 64);
+    cnt += __shfl_down(cnt, off, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { wave_sum[wave] = sum; wave_cnt[wave] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = wave_sum[0];
+    uint32_t k = wave_cnt[0];
+    for (int w = 1; w < kPostThreads / 64; ++w) { t += wave_sum[w]; k += wave_cnt[w]; }
+    col_sum[j] = t;
+    col_cnt[j] = k;
+  }
+}
+
+}  // namespace topolow

@@ -37,6 +37,7 @@
 #include "relax_symm64.h"
 #include "relax_symm_wide.h"
 #include "relax_cv.h"
+#include "relax_post.h"
 
 using namespace topolow;
 
@@ -2884,6 +2885,218 @@ int topolow_est_distances_rows(const double* positions, int32_t n, int32_t ndim,
 int topolow_est_distances(const double* positions, int32_t n, int32_t ndim,
                           double* est_distances, int32_t device, char* errbuf, size_t errlen) {
   return topolow_est_distances_rows(positions, n, ndim, 0, n, est_distances, device, errbuf, errlen);
+}
+
+// ---- post-metrics: est_distances and the terms of mae in one pass (R/core.R:474-481) ----
+// The caller's matrices travel in tiles of whole columns (contiguous in column-major storage).  A tile's upload, the
+// kernel of the tile before it and the download of the est tile before that run on three streams and overlap; kPostSlots
+// sets of buffers go round, ordered by events.  What is allocated is bounded whatever n is: per slot one tile of values,
+// of codes and of est on the device (<= kPostTileBytes each while a column fits in that), and as much pinned memory when
+// the staging is PINNED.
+namespace {
+
+constexpr int kPostSlots = 3;
+constexpr size_t kPostTileBytes = (size_t)32 << 20;   // of `values` per tile
+constexpr int kPostDefaultStaging = TOPOLOW_POST_STAGING_PINNED;
+
+struct PinBuf {
+  void* p = nullptr;
+  void alloc(size_t bytes) { HIP_TRY(hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault)); }
+  ~PinBuf() { if (p) (void)hipHostFree(p); }
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+};
+
+// hipHostRegister on a range of the caller's memory for as long as this object lives
+struct HostRegistration {
+  void* p = nullptr;
+  void pin(const void* q, size_t bytes) {
+    HIP_TRY(hipHostRegister(const_cast<void*>(q), bytes, hipHostRegisterDefault));
+    p = const_cast<void*>(q);
+  }
+  ~HostRegistration() { if (p) (void)hipHostUnregister(p); }
+  HostRegistration() = default;
+  HostRegistration(const HostRegistration&) = delete;
+  HostRegistration& operator=(const HostRegistration&) = delete;
+};
+
+// The three streams and the events that order the slots.  Destroyed before the buffers it worked on (declare it after
+// them): the destructor waits for the streams first, so nothing is in flight when a buffer goes.
+struct PostPipe {
+  hipStream_t up = nullptr, run = nullptr, down = nullptr;
+  hipEvent_t up_done[kPostSlots] = {}, run_done[kPostSlots] = {}, down_done[kPostSlots] = {};
+  std::vector<hipEvent_t> timing;   // per tile: begin and end of upload, kernel, download (only when asked for)
+  void create(int slots, int timed_tiles) {
+    HIP_TRY(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&run, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&down, hipStreamNonBlocking));
+    for (int b = 0; b < slots; ++b) {
+      HIP_TRY(hipEventCreateWithFlags(&up_done[b], hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&run_done[b], hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&down_done[b], hipEventDisableTiming));
+    }
+    timing.assign((size_t)timed_tiles * 6, nullptr);
+    for (hipEvent_t& e : timing) HIP_TRY(hipEventCreate(&e));
+  }
+  void mark(int tile, int which, hipStream_t s) {
+    if (!timing.empty()) HIP_TRY(hipEventRecord(timing[(size_t)tile * 6 + which], s));
+  }
+  void sync() {
+    HIP_TRY(hipStreamSynchronize(up));
+    HIP_TRY(hipStreamSynchronize(run));
+    HIP_TRY(hipStreamSynchronize(down));
+  }
+  ~PostPipe() {
+    for (hipStream_t s : {up, run, down})
+      if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    for (int b = 0; b < kPostSlots; ++b)
+      for (hipEvent_t e : {up_done[b], run_done[b], down_done[b]})
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : timing)
+      if (e) (void)hipEventDestroy(e);
+  }
+  PostPipe() = default;
+  PostPipe(const PostPipe&) = delete;
+  PostPipe& operator=(const PostPipe&) = delete;
+};
+
+// pageable <-> pinned on up to 16 host threads (one per MB)
+void post_host_copy(void* dst, const void* src, size_t bytes) {
+  host_parallel(bytes, (size_t)1 << 20, [&](size_t lo, size_t hi) {
+    memcpy(static_cast<char*>(dst) + lo, static_cast<const char*>(src) + lo, hi - lo);
+  });
+}
+
+}  // namespace
+
+int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, const double* values,
+                            const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
+                            int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen) {
+  if (!positions || !values || !sum_abs || !count || n < 1 || ndim < 1 || staging < TOPOLOW_POST_STAGING_DEFAULT ||
+      staging > TOPOLOW_POST_STAGING_PAGEABLE)
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  if (staging == TOPOLOW_POST_STAGING_DEFAULT) staging = kPostDefaultStaging;
+  return guarded(errbuf, errlen, [&] {
+    select_device(device);
+    const bool pinned = staging == TOPOLOW_POST_STAGING_PINNED, want_est = est_distances != nullptr;
+    int tile = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, kPostTileBytes / ((size_t)n * 8)));
+    if (const char* e = getenv("TOPOLOW_POST_TILE_COLS")) {
+      const int cap = atoi(e);
+      if (cap >= 1) tile = std::min(tile, cap);
+    }
+    const int n_tiles = (n + tile - 1) / tile, slots = std::min(kPostSlots, n_tiles);
+    const size_t tile_cells = (size_t)tile * n;
+
+    std::vector<double> rowmajor((size_t)n * ndim);
+    for (int i = 0; i < n; ++i)
+      for (int d = 0; d < ndim; ++d) rowmajor[(size_t)i * ndim + d] = positions[i + (size_t)d * n];
+    DevBuf<double> dp, dsum, dvals[kPostSlots], dest[kPostSlots];
+    DevBuf<uint32_t> dcnt;
+    DevBuf<int32_t> dcodes[kPostSlots];
+    PinBuf pvals[kPostSlots], pcodes[kPostSlots], pest[kPostSlots];
+    HostRegistration reg_values, reg_codes, reg_est;
+    PostPipe P;
+    dp.alloc(rowmajor.size());
+    HIP_TRY(hipMemcpy(dp.p, rowmajor.data(), rowmajor.size() * 8, hipMemcpyHostToDevice));
+    dsum.alloc((size_t)n);
+    dcnt.alloc((size_t)n);
+    for (int b = 0; b < slots; ++b) {
+      dvals[b].alloc(tile_cells);
+      if (codes) dcodes[b].alloc(tile_cells);
+      if (want_est) dest[b].alloc(tile_cells);
+      if (pinned) {
+        pvals[b].alloc(tile_cells * 8);
+        if (codes) pcodes[b].alloc(tile_cells * 4);
+        if (want_est) pest[b].alloc(tile_cells * 8);
+      }
+    }
+    if (staging == TOPOLOW_POST_STAGING_REGISTER) {
+      const size_t cells = (size_t)n * n;
+      reg_values.pin(values, cells * 8);
+      if (codes) reg_codes.pin(codes, cells * 4);
+      if (want_est) reg_est.pin(est_distances, cells * 8);
+    }
+    P.create(slots, phase_seconds ? n_tiles : 0);
+
+    // est tile `t` has arrived in its pinned buffer: hand it to the caller
+    auto drain = [&](int t) {
+      const int b = t % slots, c0 = t * tile, cols = std::min(tile, n - c0);
+      HIP_TRY(hipEventSynchronize(P.down_done[b]));
+      post_host_copy(est_distances + (size_t)c0 * n, pest[b].p, (size_t)cols * n * 8);
+    };
+    for (int t = 0; t < n_tiles; ++t) {
+      const int b = t % slots, c0 = t * tile, cols = std::min(tile, n - c0);
+      const size_t off = (size_t)c0 * n, cells = (size_t)cols * n;
+      const bool reused = t >= slots;   // tile t - slots went through this slot
+      const double* src_v = values + off;
+      const int32_t* src_c = codes ? codes + off : nullptr;
+      if (pinned) {
+        if (reused) HIP_TRY(hipEventSynchronize(P.up_done[b]));   // its upload has left the staging buffers
+        post_host_copy(pvals[b].p, src_v, cells * 8);
+        src_v = static_cast<const double*>(pvals[b].p);
+        if (codes) {
+          post_host_copy(pcodes[b].p, src_c, cells * 4);
+          src_c = static_cast<const int32_t*>(pcodes[b].p);
+        }
+      }
+      if (reused) HIP_TRY(hipStreamWaitEvent(P.up, P.run_done[b], 0));   // its kernel has read the device tile
+      P.mark(t, 0, P.up);
+      HIP_TRY(hipMemcpyAsync(dvals[b].p, src_v, cells * 8, hipMemcpyHostToDevice, P.up));
+      if (codes) HIP_TRY(hipMemcpyAsync(dcodes[b].p, src_c, cells * 4, hipMemcpyHostToDevice, P.up));
+      P.mark(t, 1, P.up);
+      HIP_TRY(hipEventRecord(P.up_done[b], P.up));
+
+      HIP_TRY(hipStreamWaitEvent(P.run, P.up_done[b], 0));
+      if (want_est && reused) HIP_TRY(hipStreamWaitEvent(P.run, P.down_done[b], 0));   // its est tile has left the device
+      P.mark(t, 2, P.run);
+      hipLaunchKernelGGL(post_metrics_kernel, dim3(cols), dim3(kPostThreads), 0, P.run, dp.p, n, ndim, c0, cols,
+                         dvals[b].p, codes ? dcodes[b].p : nullptr, want_est ? dest[b].p : nullptr, dsum.p, dcnt.p);
+      HIP_TRY(hipGetLastError());
+      P.mark(t, 3, P.run);
+      HIP_TRY(hipEventRecord(P.run_done[b], P.run));
+
+      if (want_est) {
+        HIP_TRY(hipStreamWaitEvent(P.down, P.run_done[b], 0));
+        P.mark(t, 4, P.down);
+        HIP_TRY(hipMemcpyAsync(pinned ? pest[b].p : (void*)(est_distances + off), dest[b].p, cells * 8,
+                               hipMemcpyDeviceToHost, P.down));
+        P.mark(t, 5, P.down);
+        HIP_TRY(hipEventRecord(P.down_done[b], P.down));
+        // the tile before this one is drained while this one is on its way: with two slots or more its pinned
+        // buffer is not the one just handed to the download above
+        if (pinned && t >= 1) drain(t - 1);
+      }
+    }
+    if (pinned && want_est) drain(n_tiles - 1);
+    P.sync();
+
+    std::vector<double> col_sum((size_t)n);
+    std::vector<uint32_t> col_cnt((size_t)n);
+    HIP_TRY(hipMemcpy(col_sum.data(), dsum.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(col_cnt.data(), dcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    double total = 0.0;
+    int64_t cells = 0;
+    for (int j = 0; j < n; ++j) { total += col_sum[(size_t)j]; cells += col_cnt[(size_t)j]; }   // columns in index order
+    *sum_abs = total;
+    *count = cells;
+    if (phase_seconds) {
+      for (int q = 0; q < 3; ++q) phase_seconds[q] = 0.0;
+      for (int t = 0; t < n_tiles; ++t)
+        for (int q = 0; q < (want_est ? 3 : 2); ++q) {
+          float ms = 0.0f;
+          HIP_TRY(hipEventElapsedTime(&ms, P.timing[(size_t)t * 6 + 2 * q], P.timing[(size_t)t * 6 + 2 * q + 1]));
+          phase_seconds[q] += 1e-3 * ms;
+        }
+    }
+  });
+}
+
+int topolow_post_metrics(const double* positions, int32_t n, int32_t ndim, const double* values,
+                         const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
+                         int32_t device, char* errbuf, size_t errlen) {
+  return topolow_post_metrics_ex(positions, n, ndim, values, codes, est_distances, sum_abs, count, device,
+                                 TOPOLOW_POST_STAGING_DEFAULT, nullptr, errbuf, errlen);
 }
 
 // ---- ONE embedding row-sharded over several sessions (one process, one host thread per block) ----

@@ -14,6 +14,7 @@
  *     _topolow_cv_sweep_session             the same sweep on device-resident sessions: matrices beyond one workgroup
  *     _topolow_est_distances                as.matrix(dist(positions))  (R/core.R:474)
  *     _topolow_est_distances_cols           a block of its columns, for n x n results too large to hold
+ *     _topolow_post_metrics                 est_distances and mae in one fused pass  (R/core.R:474-481)
  *
  * No logic lives here: unmarshal, call the library, marshal, and turn error codes into R errors
  * AFTER every native resource has been released (Rf_error longjmps).
@@ -27,6 +28,7 @@
 #include <R.h>
 #include <Rinternals.h>
 #include <R_ext/Rdynload.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -535,6 +537,44 @@ SEXP _topolow_est_distances_cols(SEXP positionsSEXP, SEXP firstSEXP, SEXP lastSE
   return out;
 }
 
+/* The reference's post-processing in one pass (R/core.R:474-481): positions, values (as.numeric(D), or
+ * distances_numeric with Inf = missing), codes (NULL, or threshold_mask), want_est ->
+ * list(est_distances = <n x n matrix or NULL>, mae, sum_abs, count); mae is NaN where no cell counts. */
+SEXP _topolow_post_metrics(SEXP positionsSEXP, SEXP valuesSEXP, SEXP codesSEXP, SEXP wantEstSEXP) {
+  if (!Rf_isReal(positionsSEXP) || !Rf_isMatrix(positionsSEXP))
+    Rf_error("positions must be a numeric matrix");
+  const int n = Rf_nrows(positionsSEXP), ndim = Rf_ncols(positionsSEXP);
+  if (!Rf_isReal(valuesSEXP) || !Rf_isMatrix(valuesSEXP) || Rf_nrows(valuesSEXP) != n || Rf_ncols(valuesSEXP) != n)
+    Rf_error("values must be a numeric n x n matrix with one row per position");
+  const int have_codes = codesSEXP != R_NilValue;
+  if (have_codes && (!Rf_isInteger(codesSEXP) || !Rf_isMatrix(codesSEXP) || Rf_nrows(codesSEXP) != n ||
+                     Rf_ncols(codesSEXP) != n))
+    Rf_error("codes must be NULL or an integer n x n matrix");
+  const int want_est = Rf_asLogical(wantEstSEXP) != 0;
+  SEXP est = PROTECT(want_est ? Rf_allocMatrix(REALSXP, n, n) : R_NilValue);
+  double sum_abs = 0.0;
+  int64_t count = 0;
+  char err[512];
+  err[0] = '\0';
+  const int rc = topolow_post_metrics(REAL(positionsSEXP), n, ndim, REAL(valuesSEXP),
+                                      have_codes ? INTEGER(codesSEXP) : NULL, want_est ? REAL(est) : NULL,
+                                      &sum_abs, &count, opt_int("topolow.device", -1), err, sizeof err);
+  if (rc != TOPOLOW_OK) {
+    UNPROTECT(1);
+    Rf_error("%s", err[0] ? err : "libtopolow_relax failed");
+  }
+  static const char* const names[4] = {"est_distances", "mae", "sum_abs", "count"};
+  SEXP out = PROTECT(Rf_allocVector(VECSXP, 4)), nm = PROTECT(Rf_allocVector(STRSXP, 4));
+  for (int q = 0; q < 4; ++q) SET_STRING_ELT(nm, q, Rf_mkChar(names[q]));
+  SET_VECTOR_ELT(out, 0, est);
+  SET_VECTOR_ELT(out, 1, Rf_ScalarReal(count > 0 ? sum_abs / (double)count : (double)NAN));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarReal(sum_abs));
+  SET_VECTOR_ELT(out, 3, Rf_ScalarReal((double)count));
+  Rf_setAttrib(out, R_NamesSymbol, nm);
+  UNPROTECT(3);
+  return out;
+}
+
 static const R_CallMethodDef CallEntries[] = {
     {"_topolow_optimize_layout_exact_cpp", (DL_FUNC)&_topolow_optimize_layout_exact_cpp, 16},
     {"_topolow_optimize_layout_exact_batch", (DL_FUNC)&_topolow_optimize_layout_exact_batch, 1},
@@ -543,6 +583,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_topolow_cv_sweep_session", (DL_FUNC)&_topolow_cv_sweep_session, 2},
     {"_topolow_est_distances", (DL_FUNC)&_topolow_est_distances, 1},
     {"_topolow_est_distances_cols", (DL_FUNC)&_topolow_est_distances_cols, 3},
+    {"_topolow_post_metrics", (DL_FUNC)&_topolow_post_metrics, 4},
     {NULL, NULL, 0}};
 
 void R_init_topolow(DllInfo* dll) {
