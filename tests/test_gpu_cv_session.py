@@ -148,6 +148,46 @@ def test_held_out_session_is_the_fresh_session_of_the_fold(monkeypatch, precisio
             x.close()
 
 
+def test_a_block_loaded_over_a_held_out_fold_is_a_fresh_session(monkeypatch):
+    """A fold is held out and run, then the full matrix is loaded again without a restore: a new block.  The hold is
+    gone with the old one, the sweep's patched copy is invalid, and the next run is a fresh session's of the full
+    matrix, bit for bit.  777 points: 13 tile-rows of the tile-major copy; one-stage iterations, checks on sweeps."""
+    n, ndim = 777, 3
+    call, _ = pp.random_problem(n, ndim, 0.7, seed=43, thresholds=0.0, n_iter=10, k0=1.5)
+    edges = (call.edge_i, call.edge_j, call.edge_dist, call.edge_thresh)
+    take = np.random.default_rng(9).choice(call.edge_i.size, 200, replace=False)
+    fdeg = np.asarray(call.degrees).copy()
+    np.subtract.at(fdeg, call.edge_i[take], 1)
+    np.subtract.at(fdeg, call.edge_j[take], 1)
+
+    def nine(s):
+        s.set_positions(call.initial_positions)
+        s.begin(9, 1.5, 0.01, 0.01, 1e-12, 10 ** 9, 3, 77, 1)
+        s.run()
+        trace = s.check_trace().copy()
+        return s.finish(), trace
+
+    def same(a, b):
+        (ra, ta), (rb, tb) = a, b
+        return (np.array_equal(ra.positions, rb.positions) and np.array_equal(ta, tb) and ta.shape[0] == 3 and
+                (ra.iterations, ra.final_mae, ra.final_k) == (rb.iterations, rb.final_mae, rb.final_k))
+
+    s = make_session(monkeypatch, "f32", "slab", ndim, FULL_SYMMETRIC, edges, call.degrees, n=n)
+    fresh = make_session(monkeypatch, "f32", "slab", ndim, FULL_SYMMETRIC, edges, call.degrees, n=n)
+    try:
+        want = nine(fresh)
+        s.hold_out(call.edge_i[take], call.edge_j[take], fdeg)
+        assert s.symm_grid > 0                                   # the copy the fold was patched into
+        assert not same(nine(s), want)
+        s.load_coo(*edges, call.degrees)
+        assert same(nine(s), want)
+        with pytest.raises(_native.NativeError, match="nothing is held out"):
+            s.restore_held_out(call.degrees)
+    finally:
+        s.close()
+        fresh.close()
+
+
 def test_refusals_leave_the_session_usable(monkeypatch):
     p = problem()
     h = p["holds"]["plain"]

@@ -174,6 +174,15 @@ def test_sharded_fuzz_equals_single_session(thread_per_block, monkeypatch):
 # one-stage iterations as the symmetric sweep sharded over the row-block sessions (csrc/relax_symm.h: segments of the
 # tile list, folded partials peer-stored into the owners' inboxes, the owners move their points)
 # ----------------------------------------------------------------------------------------
+def _load_block(s, call):
+    """The session's row block of the matrix and its share of the edge list."""
+    s.load_coo(call.edge_i, call.edge_j, call.edge_dist, call.edge_thresh, call.degrees)
+    lo, hi = np.minimum(call.edge_i, call.edge_j), np.maximum(call.edge_i, call.edge_j)
+    own = np.where((lo + hi) % 2 == 0, lo, hi)          # the parity rule of the sharded MAE (include/topolow_relax.h)
+    m = (own >= s.row_begin) & (own < s.row_end)
+    s.set_edges(call.edge_i[m], call.edge_j[m], call.edge_dist[m], call.edge_thresh[m])
+
+
 def _sessions(call, n, dim, blocks, env):
     import os
     old = {k: os.environ.get(k) for k in env}
@@ -182,11 +191,7 @@ def _sessions(call, n, dim, blocks, env):
         ss = []
         for rb, re_ in _native.shard_rows(n, blocks):
             s = _native.Session(n, dim, rb, re_, precision="f32")
-            s.load_coo(call.edge_i, call.edge_j, call.edge_dist, call.edge_thresh, call.degrees)
-            lo, hi = np.minimum(call.edge_i, call.edge_j), np.maximum(call.edge_i, call.edge_j)
-            own = np.where((lo + hi) % 2 == 0, lo, hi)          # the parity rule of the sharded MAE (include/topolow_relax.h)
-            m = (own >= rb) & (own < re_)
-            s.set_edges(call.edge_i[m], call.edge_j[m], call.edge_dist[m], call.edge_thresh[m])
+            _load_block(s, call)
             ss.append(s)
     finally:
         for k, v in old.items():
@@ -295,3 +300,49 @@ def test_sharded_symmetric_sweep_fuzz(thread_per_block, monkeypatch):
             assert got.final_mae == pytest.approx(sm / cnt, rel=5e-5, abs=1e-9)
         done += 1
     assert done >= 5
+
+
+@pytest.mark.parametrize("thr", [0.0, 0.15])
+def test_reloading_one_block_of_a_run_rebuilds_every_segment(thr):
+    """Two row-block sessions run matrix A, block 0 alone is reloaded with matrix B, they run again: the second run is
+    the run of a fresh pair loaded with B, bit for bit.  B differs from A in pairs that block 0 stores and owns (parity
+    rule) but session 1's segment gathers: a segment kept because its peers' buffers are where they were sweeps a copy
+    of A's rows.  777 points: 13 tile-rows, the two segments cut one in the middle, the row blocks (392 + 385 rows) do
+    not coincide with tile-rows.  A and B are first shown to lie 100 summation bands apart, so that closeness to the
+    stale answer cannot pass; a rerun without any reload repeats the first run bit for bit (the control)."""
+    import dataclasses
+    n, dim, iters = 777, 3, 9
+    call_a, _ = pp.random_problem(n, dim, 0.7, seed=43, thresholds=0.0, n_iter=10, k0=1.5)
+    if thr > 0:
+        rng = np.random.default_rng(3)
+        code = rng.choice([0, 1, -1], size=call_a.edge_thresh.shape[0], p=[1 - thr, thr / 2, thr / 2])
+        call_a.edge_thresh[:] = code.astype(call_a.edge_thresh.dtype)
+    (b0, e0), seg1 = _native.shard_rows(n, 2)[0], _native.symm_segment_rows(n, 1, 2)
+    first, end = max(b0, seg1[0]), min(e0, seg1[1])          # rows of block 0 that segment 1 reads
+    assert first < end
+    inside = ((call_a.edge_i >= first) & (call_a.edge_i < end) & (call_a.edge_j >= first) & (call_a.edge_j < end))
+    assert inside.sum() >= 100
+    call_b = dataclasses.replace(call_a, edge_dist=np.where(inside, 4.0 * call_a.edge_dist, call_a.edge_dist))
+    env = {"TOPOLOW_SYMMETRIC": "1", "TOPOLOW_SYMMETRIC_MIN_N": "0"}
+    scale = float(np.abs(call_a.initial_positions).max())
+
+    def run(ss):
+        r = _native.run_sharded(ss, call_a.initial_positions, iters, 1.5, 0.01, 0.01, 1e-12, 10 ** 9, 3, 5, 1)
+        assert r.info["symmetric_segments"] == 2
+        return r.positions, ss[0].check_trace().copy()
+
+    def same(x, y):
+        return np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1])
+
+    sa, sb = _sessions(call_a, n, dim, 2, env), _sessions(call_b, n, dim, 2, env)
+    try:
+        fresh_a, fresh_b = run(sa), run(sb)
+        assert fresh_a[1].shape[0] == 3
+        assert np.abs(fresh_a[0] - fresh_b[0]).max() > 100 * 2e-5 * scale * iters
+        assert same(run(sa), fresh_a)                        # the control: a rerun on kept segments
+        _load_block(sa[0], call_b)
+        again = run(sa)
+        assert same(again, fresh_b), np.abs(again[0] - fresh_b[0]).max()
+    finally:
+        for s in sa + sb:
+            s.close()

@@ -111,6 +111,66 @@ def test_single_block_engine_run_takes_the_symmetric_sweep_too():
     assert np.allclose(ta[:, 1], tb[:, 1], rtol=1e-12)
 
 
+@pytest.mark.parametrize("thr", [0.0, 0.15])
+def test_session_moves_between_its_triangle_and_a_caller_built_segment(thr):
+    """One set of sweep buffers holds the session's own triangle or a caller-built segment, never both: the own loop
+    after a segment build rebuilds the triangle and repeats the fresh session's run bit for bit, and what then asks
+    for the segment (its sweep, its moves buffer) is told there is none.  777 points: 13 tile-rows, the last partial."""
+    n, dim = 777, 3
+    call, _ = pp.random_problem(n, dim, 0.7, seed=43, thresholds=0.0, n_iter=10, k0=1.5)
+    if thr > 0:
+        rng = np.random.default_rng(3)
+        code = rng.choice([0, 1, -1], size=call.edge_thresh.shape[0], p=[1 - thr, thr / 2, thr / 2])
+        call.edge_thresh[:] = code.astype(call.edge_thresh.dtype)
+
+    def make():
+        old = {k: os.environ.get(k) for k in ("TOPOLOW_SYMMETRIC", "TOPOLOW_SYMMETRIC_MIN_N")}
+        os.environ.update(TOPOLOW_SYMMETRIC="1", TOPOLOW_SYMMETRIC_MIN_N="0")
+        try:
+            s = _native.Session(n, dim, precision="f32")
+        finally:
+            for k, v in old.items():
+                os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+        s.load_coo(call.edge_i, call.edge_j, call.edge_dist, call.edge_thresh, call.degrees)
+        s.set_edges(call.edge_i, call.edge_j, call.edge_dist, call.edge_thresh)
+        return s
+
+    def own_run(s):
+        s.set_positions(call.initial_positions)
+        s.begin(9, 1.5, 0.01, 0.01, 1e-12, 10 ** 9, 3, 5, 1)     # one stage per iteration; checks at 3 and 6 ride on sweeps
+        s.run()
+        trace = s.check_trace().copy()
+        r = s.finish()
+        assert s.symm_grid > 0
+        return r.positions, trace, (r.converged, r.iterations, r.final_mae, r.final_k)
+
+    def same(x, y):
+        return np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]) and x[2] == y[2]
+
+    def build_segment(s):
+        s.symm_segment_build(0, 1, s.encoded_ptr, 0, n, s.has_thresholds)
+        assert s.symm_grid > 0 and s.symm_moves_ptr != 0
+
+    ref, s, t = make(), make(), make()
+    try:
+        assert ref.has_thresholds == (thr > 0)
+        want = own_run(ref)
+        assert want[1].shape[0] == 3 and want[2][1] == 9
+        assert same(own_run(s), want)                            # (a) triangle, segment, triangle
+        build_segment(s)
+        assert same(own_run(s), want)
+        assert t.symm_grid == 0                                  # (c) the segment first, before any run
+        build_segment(t)
+        assert same(own_run(t), want)
+        for x in (s, t):                                         # (b) the buffers hold the triangle again
+            with pytest.raises(_native.NativeError, match="no segment built"):
+                x.symm_segment_sweep(x.encoded_ptr, 0, 1.5)
+            assert x.symm_moves_ptr == 0
+    finally:
+        for x in (ref, s, t):
+            x.close()
+
+
 # ----------------------------------------------------------------------------------------
 # the symmetric sweep against the CPU model of a one-stage iteration and against the oracle's edge error --
 # directly, not through the row-owner kernel (size gate lowered with TOPOLOW_SYMMETRIC_MIN_N)

@@ -164,6 +164,7 @@ struct topolow_session {
   DevBuf<float> gplus;
   DevBuf<unsigned char> rowflags;
   bool any_threshold = true;   // does any row of the block hold a ">" / "<" target?
+  unsigned long long block_gen = 0;     // counts the fills of enc (compute_row_flags): enc.p itself never changes
   unsigned long long block_cells = 0;   // measured (ordered) cells of the block: 2 x the measured pairs of a whole problem
   int schedule = TOPOLOW_SCHEDULE_SLAB;   // SLAB, or GS = exact tile Gauss-Seidel (relax_tilegs.h)
   DevBuf<int> bperm;
@@ -214,14 +215,22 @@ struct topolow_session {
     bool allowed = false;          // TOPOLOW_SYMMETRIC != 0 (session creation)
     bool forced = false;           // TOPOLOW_SYMMETRIC=1: also at an ndim whose default is off (sym_dim_default)
     int min_n = 0;                 // size gate (TOPOLOW_SYMMETRIC_MIN_N at session creation; default kSymMinPoints)
-    bool ready = false;            // plan + tile-major copy built for the current block
+    // What the buffers below describe, all of them at once.  hold() enters a state, once a build is complete; invalidate()
+    // (the memory stays for the next build) and release() (a build failed: the memory goes too) leave it for kNothing.
+    enum class Holds {
+      kNothing,
+      kTriangle,        // the whole upper triangle of the session's own block (sym_prepare): stage plans may be cut from it
+      kRunSegment,      // this session's segment of a run over several row-block sessions (sym_sharded_prepare)
+      kCallerSegment,   // topolow_session_symm_segment_build's: one slot, one owner, the caller sums the inbox over the processes
+    };
+    Holds holds = Holds::kNothing;
     int npad = 0, tiles = 0, grid = 0;   // npad = roundup(n, 64): whole 64-row tiles
     DevBuf<uint32_t> tenc;
     // records, row and column partials in the session's precision (SymRec<DIM> floats or SymRec64<DIM> doubles)
     DevBuf<unsigned char> rec[2], rowpart, colpart;
-    int rec_cur = 0, rec_iter = -1;   // rec[rec_cur] holds the records of iteration rec_iter
+    int rec_cur = 0, rec_iter = -1;   // rec[rec_cur] holds the records of iteration rec_iter (sym_iteration's cursor; -1 per run)
     DevBuf<float> tdelta;          // f64: exact target - decoded word per cell of tenc: the fused check's MAE is exact
-    bool delta_ready = false;
+    bool delta_ready = false;      // tdelta is built for what the buffers hold
     int generation = 0;            // counts the builds of the copy: a patch of it is only put back into the build it was made on
     // A sweep plan on the device (relax_symm.h: SymPlan): units, every wave's run of them, per tile-row its units.
     struct Plan {
@@ -247,7 +256,6 @@ struct topolow_session {
     // multi-stage iterations (2, 4, 8 stages) as symmetric sweeps over the tiles of one stage each (relax_symm.h:
     // sym_rr_*): rr[log2 S] holds the S plans, built when an iteration first needs them
     std::vector<Plan> rr[4];
-    bool whole = false;            // the buffers describe the whole triangle (not a segment): stage plans may be cut from it
     bool two_stage = true;         // TOPOLOW_SYMMETRIC_TWO_STAGE=0: multi-stage iterations stay on the row-owner kernel
     bool prio = true;              // TOPOLOW_SYM_PRIO=0: the fp32 sweep's waves all stay at issue priority 0
     int rr_min_tiles = 5;          // tiles per resident wave a stage must have (TOPOLOW_SYMMETRIC_STAGE_MIN_TILES; tests: 0)
@@ -255,26 +263,34 @@ struct topolow_session {
     DevBuf<const uint32_t*> src_tab;   // the row blocks the tile-major copy is gathered from (one: the session's own)
     DevBuf<int> src_row0;
     // the sweep sharded over the row-block sessions of a run (relax_sharded_engine.h): this session's segment
-    bool seg_ready = false;        // built for the run's current set of sessions
     bool seg_thr = false;          // some session of the run holds threshold targets: the classifying instance
     int seg_first = 0, seg_last = -1;   // tile-rows that hold a tile of the segment
     int seg_slots = 0;             // sessions of the run (slots of an inbox)
     int seg_slot = 0;              // the slot this session's folded partials go to
-    bool seg_caller = false;       // built by topolow_session_symm_segment_build: one slot, one owner (this session's
-                                   // own moves buffer = inbox), the caller sums it over the processes
     DevBuf<float> inbox;           // [seg_slots][npad][ndim]: every session's folded partials of this session's points
     DevBuf<float*> inbox_tab;      // every session's inbox (self included)
     DevBuf<int> own0;              // first row of every session, then n
-    std::vector<const void*> seg_peers;   // the sessions the segment was built with (their encoded blocks)
+    // what a run segment was gathered from: every session's enc.p (refilled in place: it never changes) and block_gen
+    using Sources = std::vector<std::pair<const void*, unsigned long long>>;
+    Sources seg_from;
 
-    // Frees every sweep buffer (a build that failed: the session keeps the row-owner sweep).  The callers set the flags.
+    void hold(Holds what) { holds = what; }
+    // The buffers no longer describe the block: whatever reads them builds them again first.
+    void invalidate() {
+      holds = Holds::kNothing;
+      delta_ready = false;
+      rec_iter = -1;
+      seg_from.clear();
+    }
+    // Frees every sweep buffer (a build that failed: the session keeps the row-owner sweep).
     void release() {
       tenc.release(); rec[0].release(); rec[1].release(); rowpart.release(); colpart.release();
-      tdelta.release(); delta_ready = false;
+      tdelta.release();
       plan.release();
       for (auto& v : rr) v.clear();
       src_tab.release(); src_row0.release();
       inbox.release(); inbox_tab.release(); own0.release();
+      invalidate();
     }
   } sym;
   // A fold held out of the resident block (topolow_session_hold_out, relax_cv.h): the pairs in session labels, what
@@ -666,8 +682,8 @@ void scan_row_flags(topolow_session* s) {
 
 void compute_row_flags(topolow_session* s) {
   s->cv.active = false;   // a new block: whatever was held out of the old one is gone with it
-  s->sym.ready = false;   // the encoded block changed: the symmetric sweep's copy is rebuilt on first use
-  s->sym.seg_ready = false;
+  s->block_gen += 1;
+  s->sym.invalidate();    // a new block invalidates whatever the sweep holds: rebuilt on first use
   s->rowflags.alloc(s->rows());
   scan_row_flags(s);
 }
@@ -797,6 +813,7 @@ constexpr bool sym_dim_default(int dim) { return dim >= 2 && dim <= kSymMaxDimF3
   }
 
 using SymPlanDev = topolow_session::SymState::Plan;
+using SymHolds = topolow_session::SymState::Holds;
 
 // The shape every form of the sweep needs; the eligibility of each form adds its own terms.
 // The precision term is part of the shape: the largest ndim differs (fp32: 10, f64: 6).
@@ -848,10 +865,12 @@ template <int DIM>
 void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, const std::vector<int>& row0, bool any_thr,
                long long t0, long long t1) {
   auto& y = s->sym;
+  y.invalidate();   // until the caller's hold(): a build that throws half-way leaves nothing that reads as built
   y.npad = (s->n + kSymRows - 1) & ~(kSymRows - 1);
   const int TR = y.npad / kSymRows, TC = y.npad / kSymCols;
   if (t1 < 0) t1 = (long long)TR * (TR + 1);
   y.tiles = (int)(t1 - t0);
+  const bool whole = t0 == 0 && t1 == (long long)TR * (TR + 1);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, s->device));
   int occ = 1 << 30;   // the session's two instances (plain, ERR) share one plan: the smaller occupancy decides the grid
@@ -868,7 +887,6 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
   y.grid = occ * prop.multiProcessorCount;
   if (y.grid_cap > 0) y.grid = std::min(y.grid, y.grid_cap);
   y.plan.load(relax_symm_plan(y.npad, y.grid * kSymWaves, t0, t1, &y.seg_first, &y.seg_last));
-  y.whole = t0 == 0 && (long long)y.tiles == (long long)TR * (TR + 1);
   for (auto& v : y.rr) v.clear();
   // a stage plan has at most one unit per wave and one more per tile-row and interval end
   const int max_units = std::max(y.plan.n_units, y.grid * kSymWaves + 2 * TR + 8);
@@ -895,7 +913,6 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
     // instance reads them.  (A fused check also needs the edge list to be the block's measured cells: sym_fused_ok.)
     if (!(src.size() == 1 && src[0] == s->enc.p))
       throw HipError{TOPOLOW_ERR_UNSUPPORTED, "precision f64_exact: the sweep is built from the session's own block only"};
-    y.delta_ready = false;
     y.tdelta.alloc((size_t)std::max(y.tiles, 1) * kSymTileWords);
     DevBuf<const uint32_t*> dsrc;
     dsrc.alloc(1);
@@ -909,8 +926,7 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
     y.delta_ready = true;
   } else if (f64) {
     // the fused check needs the edge list to BE the block's measured cells and to be on the device in f64
-    y.delta_ready = false;
-    if (s->list_is_block && !s->dense_mae && s->n_edges > 0 && y.whole) {
+    if (s->list_is_block && !s->dense_mae && s->n_edges > 0 && whole) {
       y.tdelta.alloc((size_t)y.tiles * kSymTileWords);
       HIP_TRY(hipMemsetAsync(y.tdelta.p, 0, (size_t)y.tiles * kSymTileWords * sizeof(float), s->stream));
       hipLaunchKernelGGL(symm64_delta_kernel, dim3(2048), dim3(256), 0, s->stream, s->ei.p, s->ej.p, (const double*)s->et.p,
@@ -925,30 +941,27 @@ void sym_build(topolow_session* s, const std::vector<const uint32_t*>& src, cons
     s->part_sum.alloc(y.plan.n_units);
     s->part_cnt.alloc(y.plan.n_units);
   }
-  y.rec_iter = -1;
   y.generation += 1;
 }
 
 template <int DIM>
 void sym_prepare(topolow_session* s) {
   sym_build<DIM>(s, {s->enc.p}, {0, s->rows()}, s->any_threshold, 0, -1);
-  s->sym.ready = true;
-  s->sym.seg_ready = false;
+  s->sym.hold(SymHolds::kTriangle);
 }
 
 // Builds the sweep's buffers on first use.  They cost device memory (half the encoded block again, plus the
 // partials): if the device cannot give it, the session simply keeps the row-owner sweep.
 bool sym_available(topolow_session* s) {
-  if (s->sym.ready) return true;
+  if (s->sym.holds == SymHolds::kTriangle) return true;
   try {
     TL_DISPATCH_SYM(s->dim, sym_prepare, s);
   } catch (const HipError&) {
     (void)hipGetLastError();
     s->sym.release();
-    s->sym.ready = false;
     s->sym.allowed = false;
   }
-  return s->sym.ready;
+  return s->sym.holds == SymHolds::kTriangle;
 }
 
 // ---- launches: records, sweep, apply ----
@@ -990,7 +1003,7 @@ void sym_sweep(topolow_session* s, const SymPlanDev& plan, const void* rec, bool
 // check's sum and count run over the block's measured cells, so the list must still be exactly those.
 bool sym_fused_ok(const topolow_session* s) {
   if (!s->sym.delta_ready) return false;
-  return !s->exact || (s->list_is_block && s->n_edges > 0 && s->sym.whole);
+  return !s->exact || (s->list_is_block && s->n_edges > 0 && s->sym.holds == SymHolds::kTriangle);
 }
 
 // The apply of the whole triangle (rr_stages = 0) or of stage rr_stage of an rr_stages-stage iteration: positions into
@@ -1025,7 +1038,7 @@ SymPlan sym_rr_plan(int npad, int n_waves, int S, int st) {
 
 bool sym_rr_available(topolow_session* s, int S) {
   auto& y = s->sym;
-  if (!sym_rr_stages_ok(S) || !y.whole) return false;
+  if (!sym_rr_stages_ok(S) || y.holds != SymHolds::kTriangle) return false;
   const int TR = y.npad / kSymRows;
   if (TR < 2 * S) return false;
   // a stage must give a resident wave about five tiles: below that a wave's prologue and epilogue and the apply kernel
@@ -1164,49 +1177,58 @@ bool sym_sharded_eligible(const std::vector<topolow_session*>& ss) {
   return true;
 }
 
-// A segment's inbox: `slots` zeroed slots of npad x DIM floats for every session's folded partials of this session's
-// points, and own0: the first row of every owner, then n.  (The table of the inboxes the segment's own partials go to,
-// inbox_tab, needs every owner's inbox: the callers set it.)
+// The table of the inboxes a segment's folded partials go to, one per owner.  With it the segment is complete: the
+// buffers hold `kind`.
+void sym_wire_inboxes(topolow_session* s, const std::vector<float*>& tab, SymHolds kind) {
+  s->sym.inbox_tab.alloc(tab.size());
+  HIP_TRY(hipMemcpy(s->sym.inbox_tab.p, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice));
+  s->sym.hold(kind);
+}
+
+// What follows sym_build for a segment of either kind: its slot, its inbox (`slots` zeroed slots of npad x DIM floats for
+// every session's folded partials of this session's points), own0: the first row of every owner, then n.  Returns with
+// the tile-major copy complete.  A run segment's table needs every session's inbox: sym_sharded_prepare.
 template <int DIM>
-void sym_inbox(topolow_session* s, int slots, const std::vector<int>& own0) {
+void sym_install_segment(topolow_session* s, SymHolds kind, bool any_thr, int slots, int slot, const std::vector<int>& own0,
+                         topolow_session::SymState::Sources from = {}) {
   auto& y = s->sym;
+  if (y.seg_first < 0) { y.seg_first = 0; y.seg_last = -1; }
+  y.seg_thr = any_thr;
+  y.seg_slots = slots;
+  y.seg_slot = slot;
   y.inbox.alloc((size_t)slots * y.npad * DIM);
   HIP_TRY(hipMemsetAsync(y.inbox.p, 0, (size_t)slots * y.npad * DIM * sizeof(float), s->stream));
   y.own0.alloc(own0.size());
   HIP_TRY(hipMemcpy(y.own0.p, own0.data(), own0.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  y.seg_from = std::move(from);
+  if (kind == SymHolds::kCallerSegment) sym_wire_inboxes(s, {y.inbox.p}, kind);
 }
 
 // Session b's segment: tiles [total b / P, total (b + 1) / P) of the tile-row-major list, gathered from every session's
-// row block (peer reads where the sessions sit on different GPUs).  Kept while the same sessions run together again.
+// row block (peer reads where the sessions sit on different GPUs).  Kept while the same sessions, in the same order (so
+// the same slot), run together again on the blocks it was gathered from.
 template <int DIM>
 void sym_sharded_build(std::vector<topolow_session*>& ss, int b) {
   const int P = (int)ss.size();
   topolow_session* s = ss[b];
   std::vector<const uint32_t*> src;
-  std::vector<const void*> peers;
+  topolow_session::SymState::Sources from;
   std::vector<int> row0;
   bool any_thr = false;
   for (topolow_session* q : ss) {
     src.push_back(q->enc.p);
-    peers.push_back(q->enc.p);
+    from.emplace_back(q->enc.p, q->block_gen);
     row0.push_back(q->row_begin);
     any_thr = any_thr || q->any_threshold;
   }
   row0.push_back(s->n);
-  auto& y = s->sym;
-  if (y.seg_ready && !y.seg_caller && y.seg_peers == peers && y.seg_thr == any_thr) { y.seg_slot = s->rank; return; }
+  const auto& y = s->sym;
+  if (y.holds == SymHolds::kRunSegment && y.seg_from == from && y.seg_thr == any_thr) return;
   HIP_TRY(hipSetDevice(s->device));
   const SymSegment g = sym_segment(s->n, b, P);
   sym_build<DIM>(s, src, row0, any_thr, g.t0, g.t1);
-  if (y.seg_first < 0) { y.seg_first = 0; y.seg_last = -1; }
-  y.ready = false;            // the buffers now describe a segment, not the session's own whole-matrix plan
-  y.seg_thr = any_thr;
-  y.seg_slots = P;
-  y.seg_slot = s->rank;
-  y.seg_caller = false;
-  sym_inbox<DIM>(s, P, row0);
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  y.seg_peers = peers;
+  sym_install_segment<DIM>(s, SymHolds::kRunSegment, any_thr, P, s->rank, row0, std::move(from));
 }
 
 void sym_sharded_prepare(std::vector<topolow_session*>& ss) {
@@ -1227,9 +1249,7 @@ void sym_sharded_prepare(std::vector<topolow_session*>& ss) {
                           hipMemcpyDeviceToDevice));
     std::vector<float*> tab;
     for (topolow_session* q : ss) tab.push_back(q->sym.inbox.p);
-    s->sym.inbox_tab.alloc(P);
-    HIP_TRY(hipMemcpy(s->sym.inbox_tab.p, tab.data(), P * sizeof(float*), hipMemcpyHostToDevice));
-    s->sym.seg_ready = true;
+    sym_wire_inboxes(s, tab, SymHolds::kRunSegment);
   }
 }
 
@@ -1271,25 +1291,12 @@ void sym_owner_apply(topolow_session* s, const void* pin, void* pout, int row_be
 template <int DIM>
 void sym_segment_build(topolow_session* s, int segment, int P, const uint32_t* d_rows, int row_first, int n_rows,
                        bool any_thr) {
-  auto& y = s->sym;
   const SymSegment g = sym_segment(s->n, segment, P);
   if (g.r_first >= 0 && (row_first > g.r_first * kSymRows ||
                          row_first + n_rows < std::min<long long>(s->n, (long long)(g.r_last + 1) * kSymRows)))
     throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, "symm_segment_build: d_rows does not hold the rows of the segment's tiles"};
   sym_build<DIM>(s, {d_rows}, {row_first, row_first + n_rows}, any_thr, g.t0, g.t1);
-  if (y.seg_first < 0) { y.seg_first = 0; y.seg_last = -1; }
-  y.ready = false;            // the buffers now describe a segment, not the session's own whole-matrix plan
-  y.seg_thr = any_thr;
-  y.seg_slots = 1;
-  y.seg_slot = 0;
-  y.seg_caller = true;
-  y.seg_peers.clear();
-  sym_inbox<DIM>(s, 1, {0, s->n});
-  float* tab[1] = {y.inbox.p};
-  y.inbox_tab.alloc(1);
-  HIP_TRY(hipMemcpy(y.inbox_tab.p, tab, sizeof tab, hipMemcpyHostToDevice));
-  HIP_TRY(hipStreamSynchronize(s->stream));     // the tile-major copy is complete: the caller may free d_rows
-  y.seg_ready = true;
+  sym_install_segment<DIM>(s, SymHolds::kCallerSegment, any_thr, 1, 0, {0, s->n});   // (the caller may free d_rows now)
 }
 
 // One convergence check of the session's own loop.  error_pass = true: the separate pass over the block (or
@@ -1376,16 +1383,16 @@ void cv_compact_edges(topolow_session* s) {
   h.list_compacted = true;
 }
 
-// Flags, threshold bit and cell count of the patched block; a flipped threshold bit changes the sweep's kernel instance
-// and with it its grid and plan: the copy is rebuilt (from the block as it is now) on first use.
-void cv_refresh_flags(topolow_session* s) {
+// Flags, threshold bit and cell count of the patched block.  copy_patched: the sweep holds the triangle and its copy took
+// the same patch: it stays unless the threshold bit flipped, which changes the sweep's kernel instance and with it its
+// grid and plan.  Anything else the sweep holds is invalid: rebuilt, from the block as it is now, on first use.
+void cv_refresh_flags(topolow_session* s, bool copy_patched) {
   const bool before = s->any_threshold;
   scan_row_flags(s);
-  if (s->any_threshold != before) {
-    s->sym.ready = false;
+  if (!copy_patched || s->any_threshold != before) {
+    s->sym.invalidate();
     s->cv.tiles_patched = false;
   }
-  s->sym.seg_ready = false;
 }
 
 int cv_check_session(const topolow_session* s, char* errbuf, size_t errlen) {
@@ -1695,10 +1702,7 @@ int topolow_session_set_edges(topolow_session* s, const int32_t* edge_i, const i
     HIP_TRY(hipSetDevice(s->device));
     s->n_edges = n_edges;
     s->cv.list_compacted = false;
-    if (s->precision == TOPOLOW_PRECISION_F64) {   // the f64 sweep's delta tiles are made from this list: rebuilt on first use
-      s->sym.ready = false;
-      s->sym.delta_ready = false;
-    }
+    if (s->precision == TOPOLOW_PRECISION_F64) s->sym.invalidate();   // its delta tiles are made from this list: rebuilt on first use
     const size_t m = (size_t)n_edges;
     s->n_parts = edge_error_blocks(n_edges);
     // dense MAE pass: one workgroup per (column chunk, 64-row tile)
@@ -2241,7 +2245,7 @@ int32_t topolow_symm_plan(int32_t n, int32_t n_waves, int32_t stages, int32_t st
 }
 
 int32_t topolow_session_symm_grid(const topolow_session* s) {
-  return s && (s->sym.ready || s->sym.seg_ready) ? s->sym.grid : 0;
+  return s && s->sym.holds != SymHolds::kNothing ? s->sym.grid : 0;
 }
 
 int32_t topolow_symm_segment_rows(int32_t n, int32_t segment, int32_t n_segments, int32_t* row_first,
@@ -2262,7 +2266,9 @@ int32_t topolow_session_symm_segment_eligible(const topolow_session* s, int32_t 
 
 float* topolow_session_degree_terms(topolow_session* s) { return s ? s->gplus.p : nullptr; }
 int32_t topolow_session_has_thresholds(const topolow_session* s) { return s && s->gplus.p && s->any_threshold ? 1 : 0; }
-float* topolow_session_symm_moves(topolow_session* s) { return s && s->sym.seg_caller ? s->sym.inbox.p : nullptr; }
+float* topolow_session_symm_moves(topolow_session* s) {
+  return s && s->sym.holds == SymHolds::kCallerSegment ? s->sym.inbox.p : nullptr;
+}
 
 int topolow_session_symm_segment_build(topolow_session* s, int32_t segment, int32_t n_segments, const void* d_rows,
                                        int32_t row_first, int32_t n_rows, int32_t any_threshold, char* errbuf,
@@ -2282,8 +2288,6 @@ int topolow_session_symm_segment_build(topolow_session* s, int32_t segment, int3
                       any_threshold != 0);
     } catch (const HipError&) {      // e.g. the device cannot hold the extra buffers: the session keeps its row-owner sweep
       s->sym.release();
-      s->sym.seg_ready = false;
-      s->sym.seg_caller = false;
       throw;
     }
   });
@@ -2292,7 +2296,7 @@ int topolow_session_symm_segment_build(topolow_session* s, int32_t segment, int3
 int topolow_session_symm_segment_sweep(topolow_session* s, const void* d_pos_in, int32_t iter, double k,
                                        double* d_out2, char* errbuf, size_t errlen) {
   if (!s || !d_pos_in || !s->began) return TOPOLOW_ERR_BAD_ARGUMENT;
-  if (!(s->sym.seg_ready && s->sym.seg_caller)) {
+  if (s->sym.holds != SymHolds::kCallerSegment) {
     set_err(errbuf, errlen, "no segment built (topolow_session_symm_segment_build)");
     return TOPOLOW_ERR_BAD_ARGUMENT;
   }
@@ -2310,7 +2314,7 @@ int topolow_session_symm_segment_sweep(topolow_session* s, const void* d_pos_in,
 
 int topolow_session_symm_segment_apply(topolow_session* s, const void* d_pos_in, void* d_pos_out, int32_t iter,
                                        char* errbuf, size_t errlen) {
-  if (!s || !d_pos_in || !d_pos_out || !s->began || !(s->sym.seg_ready && s->sym.seg_caller))
+  if (!s || !d_pos_in || !d_pos_out || !s->began || s->sym.holds != SymHolds::kCallerSegment)
     return TOPOLOW_ERR_BAD_ARGUMENT;
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
@@ -2556,7 +2560,7 @@ int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const in
                            s->enc.p, s->ld, (uint32_t*)nullptr, kInfWord);
       HIP_TRY(hipGetLastError());
     }
-    if (s->sym.ready && s->sym.whole) {
+    if (s->sym.holds == SymHolds::kTriangle) {
       if (np > 0)
         hipLaunchKernelGGL(cv_tiles_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
                            s->sym.tenc.p, s->sym.delta_ready ? s->sym.tdelta.p : (float*)nullptr, s->sym.npad / kSymCols,
@@ -2564,10 +2568,8 @@ int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const in
       HIP_TRY(hipGetLastError());
       h.tiles_patched = true;
       h.generation = s->sym.generation;
-    } else if (s->sym.ready) {
-      s->sym.ready = false;
     }
-    cv_refresh_flags(s);
+    cv_refresh_flags(s, h.tiles_patched);
     upload_degrees(s, degrees);
     HIP_TRY(hipStreamSynchronize(s->stream));   // (the host arrays of the pairs go out of scope)
     h.active = true;
@@ -2598,17 +2600,17 @@ int topolow_session_restore_held_out(topolow_session* s, const int32_t* degrees,
       s->n_parts = h.full_parts;
       h.list_compacted = false;
     }
-    if (s->sym.ready && h.tiles_patched && h.generation == s->sym.generation) {
+    // (a copy built meanwhile holds the fold's block: rebuilt from the full one on first use)
+    const bool put_back = s->sym.holds == SymHolds::kTriangle && h.tiles_patched && h.generation == s->sym.generation;
+    if (put_back) {
       if (np > 0)
         hipLaunchKernelGGL(cv_tiles_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
                            s->sym.tenc.p, s->sym.delta_ready ? s->sym.tdelta.p : (float*)nullptr, s->sym.npad / kSymCols,
                            (const uint32_t*)h.words.p, h.deltas.p);
       HIP_TRY(hipGetLastError());
-    } else {
-      s->sym.ready = false;   // built from the fold's block meanwhile: rebuilt from the full one on first use
     }
     h.tiles_patched = false;
-    cv_refresh_flags(s);
+    cv_refresh_flags(s, put_back);
     upload_degrees(s, degrees);
     HIP_TRY(hipStreamSynchronize(s->stream));
     h.active = false;
@@ -3133,11 +3135,7 @@ int topolow_sessions_run_sharded(topolow_session** sessions, int32_t count, cons
         R.pair_sharded = true;
       } catch (const HipError&) {
         (void)hipGetLastError();
-        for (topolow_session* s : R.ss) {
-          s->sym.release();
-          s->sym.ready = false;
-          s->sym.seg_ready = false;
-        }
+        for (topolow_session* s : R.ss) s->sym.release();
         R.pair_sharded = false;
       }
     }
