@@ -362,6 +362,89 @@ int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, co
                             int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen);
 
 /* ---------------------------------------------------------------------------------------
+ * Prepared layout: the reference's pre-processing (R/core.R:269-436) on the device -- ordering means, degrees,
+ * the upper-triangle edge list in which() order, the symmetric dense fill, the scale of the random-walk start.
+ * The edge count is unknown before the first pass, hence a handle: create() uploads the matrix and computes,
+ * info->n_edges sizes the caller's edge arrays, fetch() downloads.
+ *   values   n x n f64, NaN = NA, any threshold prefix stripped
+ *   codes    n x n int8 {0, 1 ">", -1 "<"}, or NULL: all zero
+ *   transposed != 0: the buffers hold the matrix row-major.  The results are those of the matrix itself; no
+ *            transposed n x n copy is made anywhere.  Every n x n output of fetch() is laid out as the inputs are
+ *            (dense and tdense are symmetric bit for bit, so their layout does not show).
+ * First pass: per point the sum and count of its non-NA off-diagonal cells along its row and along its column
+ * (thresholds with their stripped value), per row the non-NA count with the diagonal (the degrees), and info.
+ * The summation order is fixed: one partial per (point, block of 64 cells) -- the cells of the block added in index
+ * order from 0.0, NA and the diagonal as 0.0 -- and a point's partials added in block order.  The same bits
+ * whatever the grid, the chunking of the upload and the layout.
+ * Order: topolow_layout_order_from_sums on those sums (unless preserve_order or order_in decide it).
+ * Second pass, on the matrix gathered through the order: the edge list (non-NA cells of the strict upper triangle
+ * whose distance is not +Inf, column after column, rows ascending: a stable compaction), edge_thresh from the codes,
+ * degrees[i] = row count of point order[i], dense / tdense as the 16-argument call takes them (unmeasured = +Inf,
+ * the lower triangle the transpose of the upper, R/core.R:429-436), and the raw reordered matrix.
+ * Memory: the matrix (9 n^2 bytes, 8 without codes) and the dense fill (12 n^2 bytes; the edge list is compacted from
+ * it) stay on the device between create() and destroy(); fetch() adds the edge list and, when asked for, the
+ * reordered matrix.  A failed device allocation: TOPOLOW_ERR_UNSUPPORTED with a message.
+ * ------------------------------------------------------------------------------------- */
+typedef struct topolow_layout_prep topolow_layout_prep;
+
+#define TOPOLOW_ORDER_PRESERVED 0     /* preserve_order: input order kept */
+#define TOPOLOW_ORDER_DEVICE_EXACT 1  /* the device sums are exact: keys equal NumPy's bit for bit, ties included */
+#define TOPOLOW_ORDER_DEVICE_GAP 2    /* neighbouring keys further apart than both implementations' error */
+#define TOPOLOW_ORDER_DECLINED 3      /* the caller orders (order_in); also reported when order_in was given */
+
+typedef struct topolow_layout_prep_info {
+  int64_t n_edges;            /* measured cells of the strict upper triangle of the (re)ordered matrix; -1: declined */
+  int64_t n_finite_nonzero;   /* cells with code 0, finite, != 0: _validate's warning (R/core.R:202-264) */
+  int64_t n_infinite, n_negative;   /* over every non-NA cell, whatever its code */
+  double  numeric_max;        /* max over non-NA cells with code 0 (as.numeric form); NaN when there is none */
+  int32_t reordered;          /* 0: input order kept (order[0] = -1), as spectral_order() returning None */
+  int32_t order_route;        /* TOPOLOW_ORDER_* */
+  int32_t exact_sums;         /* every non-NA value is k * 2^-10 with 0 <= value < 2^20 */
+  int32_t reserved[5];
+} topolow_layout_prep_info;
+
+/* order_in: NULL, or the caller's order -- n entries, a permutation of 0..n-1, or order_in[0] = -1 for "keep the
+ * input order" (then one entry is read).  preserve_order != 0 wins over it.
+ * With neither, the device keys decide the order where they provably sort as NumPy's do (routes 1 and 2, see
+ * topolow_layout_order_from_sums).  Otherwise the call declines: it returns TOPOLOW_OK with order_route 3,
+ * n_edges = -1 and a handle that holds no second pass (fetch() on it: TOPOLOW_ERR_BAD_ARGUMENT; destroy it); the
+ * caller computes the order as it did before and creates again with order_in.
+ * TOPOLOW_ERR_BAD_ARGUMENT before any device call: NULL out, values or info; n < 2; an order_in that is no
+ * permutation. */
+int topolow_layout_prep_create(topolow_layout_prep** out, const double* values, const int8_t* codes, int32_t n,
+                               int32_t transposed, int32_t preserve_order, const int32_t* order_in, int32_t device,
+                               topolow_layout_prep_info* info, char* errbuf, size_t errlen);
+
+/* order, degrees: n entries each.  edge_*: info.n_edges entries each.  dense (f64), tdense (i32), values_reordered
+ * (f64), codes_reordered (i8): n x n each, or NULL: not wanted -- the other outputs do not depend on it. */
+int topolow_layout_prep_fetch(topolow_layout_prep* p, int32_t* order, int32_t* degrees, int32_t* edge_i,
+                              int32_t* edge_j, double* edge_dist, int32_t* edge_thresh, double* dense, int32_t* tdense,
+                              double* values_reordered, int8_t* codes_reordered, char* errbuf, size_t errlen);
+void topolow_layout_prep_destroy(topolow_layout_prep* p);
+
+/* A study entry (tests/study/prepare_layout_timing.py): wall-clock seconds of {upload overlapped with the first pass,
+ * the ordering rule on the host, the second pass, fetch()'s compaction and reorder gather, fetch()'s downloads} of
+ * this handle; 5 doubles out.  A handle that declined has the first figure only. */
+int topolow_layout_prep_phase_seconds(const topolow_layout_prep* p, double* seconds);
+
+/* Host only: the ordering rule on given sums -- what create() runs after its first pass.
+ * NOTE: exact_sums is three-valued here, unlike the 0 / 1 field of the info struct.  0 asserts that the data hold no
+ * negative and no infinite cell; a caller whose data may hold one passes -1 (create() does, from info.n_negative and
+ * info.n_infinite), or the gap rule would be applied where its error bound does not hold.
+ *   key = (row_sum / row_cnt + col_sum / col_cnt) / 2, NaN (a count of 0) -> 0.
+ *   No reordering (order_out[0] = -1) unless more than one key is > 0; otherwise a stable ascending sort.
+ *   exact_sums > 0: the sums are exact (info.exact_sums, n <= 2^23), the keys are NumPy's bit for bit: route 1.
+ *   exact_sums == 0: no negative and no infinite cell.  Route 2 if every two neighbouring keys of the sorted list are
+ *     further apart than 8 n 2^-53 of the larger one (or both exactly 0) and the smallest positive key is >= 2^-1000:
+ *     with non-negative terms either implementation is within (n + 2) 2^-53 relative of the true key, so keys
+ *     further apart than 4 (n + 2) 2^-53 sort alike in both; the bound is doubled.  Otherwise route 3.
+ *   exact_sums < 0: the data hold a negative or an infinite cell and are not exact: route 3.
+ * Returns the route; on route 3 order_out[0] = -1 and nothing else is written. */
+int32_t topolow_layout_order_from_sums(int32_t n, const double* row_sum, const int64_t* row_cnt,
+                                       const double* col_sum, const int64_t* col_cnt, int32_t exact_sums,
+                                       int32_t* order_out);
+
+/* ---------------------------------------------------------------------------------------
  * Device-resident session: the same relaxation with inputs kept in HBM, for callers that
  * run many iterations / many embeddings on data they already hold on the GPU (bench.py, the
  * row-sharded multi-GPU driver).  Pointers named d_* are DEVICE pointers.

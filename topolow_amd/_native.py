@@ -82,6 +82,12 @@ class TopolowCellList(C.Structure):
                 ("row_ptr", C.POINTER(C.c_int64))]
 
 
+class TopolowLayoutPrepInfo(C.Structure):
+    _fields_ = [("n_edges", C.c_int64), ("n_finite_nonzero", C.c_int64), ("n_infinite", C.c_int64),
+                ("n_negative", C.c_int64), ("numeric_max", C.c_double), ("reordered", C.c_int32),
+                ("order_route", C.c_int32), ("exact_sums", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class TopolowResult(C.Structure):
     _fields_ = [("positions_out", C.POINTER(C.c_double)), ("final_mae", C.c_double),
                 ("final_k", C.c_double), ("converged", C.c_int32), ("iterations", C.c_int32),
@@ -325,6 +331,18 @@ def load() -> C.CDLL:
     lib.topolow_controller_script.restype = C.c_int
     lib.topolow_controller_script.argtypes = [dp, ip, dp, C.c_int32, C.c_double, C.c_int32,
                                               C.c_double, ip, ip, dp, dp, ip]
+    i8p = C.POINTER(C.c_int8)
+    lib.topolow_layout_prep_create.restype = C.c_int
+    lib.topolow_layout_prep_create.argtypes = [C.POINTER(vp), dp, i8p, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32,
+                                               C.POINTER(TopolowLayoutPrepInfo), C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_fetch.restype = C.c_int
+    lib.topolow_layout_prep_fetch.argtypes = [vp, ip, ip, ip, ip, dp, ip, dp, ip, dp, i8p, C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_destroy.restype = None
+    lib.topolow_layout_prep_destroy.argtypes = [vp]
+    lib.topolow_layout_prep_phase_seconds.restype = C.c_int
+    lib.topolow_layout_prep_phase_seconds.argtypes = [vp, dp]
+    lib.topolow_layout_order_from_sums.restype = C.c_int32
+    lib.topolow_layout_order_from_sums.argtypes = [C.c_int32, dp, i64p, dp, i64p, C.c_int32, ip]
     _lib = lib
     return lib
 
@@ -846,6 +864,111 @@ def post_metrics(positions, values, codes=None, want_est: bool = True, staging: 
     if phases is not None:
         phases[:] = [ph[0], ph[1], ph[2]]
     return est, float(s.value), int(c.value)
+
+
+ORDER_PRESERVED, ORDER_DEVICE_EXACT, ORDER_DEVICE_GAP, ORDER_DECLINED = 0, 1, 2, 3
+
+
+@dataclass
+class PreparedLayout:
+    """What topolow_layout_prep_create / _fetch computed.  `info` holds the fields of topolow_layout_prep_info as a
+    dict; order is None where the input order is kept.  On info["order_route"] == ORDER_DECLINED without an `order`
+    given, nothing but `info` is filled: the caller orders and calls again."""
+    info: Dict[str, Any]
+    order: Optional[np.ndarray] = None
+    degrees: Optional[np.ndarray] = None
+    edge_i: Optional[np.ndarray] = None
+    edge_j: Optional[np.ndarray] = None
+    edge_dist: Optional[np.ndarray] = None
+    edge_thresh: Optional[np.ndarray] = None
+    dense: Optional[np.ndarray] = None
+    tdense: Optional[np.ndarray] = None
+    values_reordered: Optional[np.ndarray] = None
+    codes_reordered: Optional[np.ndarray] = None
+    phase_seconds: Optional[list] = None
+
+
+def order_from_sums(row_sum, row_cnt, col_sum, col_cnt, exact_sums: int):
+    """topolow_layout_order_from_sums: (route, order or None).  Host only."""
+    lib = load()
+    rs, cs = np.ascontiguousarray(row_sum, dtype=np.float64), np.ascontiguousarray(col_sum, dtype=np.float64)
+    rc_, cc = np.ascontiguousarray(row_cnt, dtype=np.int64), np.ascontiguousarray(col_cnt, dtype=np.int64)
+    n = rs.shape[0]
+    order = np.empty(max(n, 1), dtype=np.int32)
+    i64p = C.POINTER(C.c_int64)
+    route = lib.topolow_layout_order_from_sums(n, _dp(rs), rc_.ctypes.data_as(i64p), _dp(cs), cc.ctypes.data_as(i64p),
+                                               int(exact_sums), _ip(order))
+    return int(route), (None if order[0] == -1 else order[:n])
+
+
+def prepare_layout(values, codes=None, preserve_order: bool = False, order=None, want_dense: bool = True,
+                   want_reordered: bool = True, layout: Optional[str] = None) -> PreparedLayout:
+    """The reference's pre-processing (R/core.R:269-436) on the GPU: see include/topolow_relax.h, "Prepared layout".
+    `values` (f64, NaN = NA) and `codes` (int8 or None) are used where they lie: a C-contiguous matrix goes with
+    transposed=1, a Fortran-contiguous one with transposed=0 (`layout` = "C" / "F" forces the reading of a matrix that
+    is both); no n x n copy is made of a matrix that is contiguous and of the right dtype.  The n x n outputs come
+    back in the layout of the input; values_reordered / codes_reordered stay None where the input order is kept (the
+    input is then the reordered matrix).  `order`: the caller's order (an int array, or -1 / None-like [-1] for "keep"),
+    for data on which the device declines to order."""
+    lib = load()
+    vals = np.asarray(values)
+    if vals.ndim != 2 or vals.shape[0] != vals.shape[1]:
+        raise ValueError("values must be an n x n matrix")
+    n = vals.shape[0]
+    if layout is None:
+        layout = "F" if (vals.flags.f_contiguous and not vals.flags.c_contiguous) else "C"
+    need = [layout, "A"]
+    vals = np.require(vals, dtype=np.float64, requirements=need)
+    cds = None
+    if codes is not None:
+        cds = np.require(np.asarray(codes), dtype=np.int8, requirements=need)
+        if cds.shape != (n, n):
+            raise ValueError("codes must have the shape of values")
+    oin = None
+    if order is not None:
+        oin = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        if oin.shape[0] != n and not (oin.shape[0] >= 1 and oin[0] == -1):
+            raise ValueError("order must have n entries")
+    i8p = C.POINTER(C.c_int8)
+    info = TopolowLayoutPrepInfo()
+    handle = C.c_void_p()
+    err = C.create_string_buffer(512)
+    rc = lib.topolow_layout_prep_create(C.byref(handle), _dp(vals), cds.ctypes.data_as(i8p) if cds is not None else None,
+                                        n, 1 if layout == "C" else 0, 1 if preserve_order else 0,
+                                        _ip(oin) if oin is not None else None, int(options.get("device", -1)),
+                                        C.byref(info), err, len(err))
+    _check(rc, err)
+    out = None
+    try:
+        out = PreparedLayout(info={k: getattr(info, k) for k, _ in TopolowLayoutPrepInfo._fields_ if k != "reserved"})
+        if info.n_edges < 0:    # declined
+            return out
+        E = int(info.n_edges)
+        o = np.empty(n, dtype=np.int32)
+        out.degrees = np.empty(n, dtype=np.int32)
+        out.edge_i, out.edge_j = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
+        out.edge_dist, out.edge_thresh = np.empty(E, dtype=np.float64), np.empty(E, dtype=np.int32)
+        if want_dense:
+            out.dense = np.empty((n, n), dtype=np.float64, order=layout)
+            out.tdense = np.empty((n, n), dtype=np.int32, order=layout)
+        want_reordered = bool(want_reordered) and bool(info.reordered)
+        if want_reordered:
+            out.values_reordered = np.empty((n, n), dtype=np.float64, order=layout)
+            out.codes_reordered = np.empty((n, n), dtype=np.int8, order=layout)
+        rc = lib.topolow_layout_prep_fetch(
+            handle, _ip(o), _ip(out.degrees), _ip(out.edge_i), _ip(out.edge_j), _dp(out.edge_dist), _ip(out.edge_thresh),
+            _dp(out.dense) if want_dense else None, _ip(out.tdense) if want_dense else None,
+            _dp(out.values_reordered) if want_reordered else None,
+            out.codes_reordered.ctypes.data_as(i8p) if want_reordered else None, err, len(err))
+        _check(rc, err)
+        out.order = None if o[0] == -1 else o
+        return out
+    finally:
+        if out is not None:
+            ph = (C.c_double * 5)()
+            lib.topolow_layout_prep_phase_seconds(handle, ph)
+            out.phase_seconds = list(ph)
+        lib.topolow_layout_prep_destroy(handle)
 
 
 # ---- host-side helpers (no GPU needed) ---------------------------------------------------

@@ -251,16 +251,19 @@ def _is_number(x: Any) -> bool:
 
 def _validate(m: Optional[CodedMatrix], ndim, mapping_max_iter, k0, cooling_rate, c_repulsion,
               relative_epsilon, convergence_counter, convergence_check_freq,
-              initial_positions) -> None:
-    """R/core.R:202-264, messages verbatim."""
+              initial_positions, n_finite_nonzero: Optional[int] = None) -> None:
+    """R/core.R:202-264, messages verbatim.  n_finite_nonzero: the count of finite non-zero dissimilarities where
+    the caller has it already (the device form); otherwise it is taken from the matrix."""
     if m is None:
         _stop("dissimilarity_matrix must be a matrix")
     v = m.values
     if v.shape[0] != v.shape[1]:
         _stop("dissimilarity_matrix must be square")
-    finite = m.as_numeric().copy()
-    finite[np.isinf(finite)] = np.nan
-    if int(np.sum(~np.isnan(finite) & (finite != 0))) == 0:
+    if n_finite_nonzero is None:
+        finite = m.as_numeric().copy()
+        finite[np.isinf(finite)] = np.nan
+        n_finite_nonzero = int(np.sum(~np.isnan(finite) & (finite != 0)))
+    if n_finite_nonzero == 0:
         warnings.warn("No finite non-zero dissimilarities found. Results may be unreliable.",
                       UserWarning, stacklevel=3)
     if not _is_number(ndim) or ndim < 1 or ndim != round(ndim):
@@ -402,6 +405,153 @@ def prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, coolin
         names=names, order=order, reordered_matrix=v)
 
 
+# Smallest matrix for which euclidean_embedding() prepares on the device; None: never by default.  Measured on the
+# MI355X (profiles/r08_prepare_layout.txt): the host form wins at n = 300 (2.2 ms against 3.9 ms), the device form at
+# n = 1 000 (10.9 ms against 26.8 ms) and from there on (106 ms against 3.59 s at n = 10 000).
+# TOPOLOW_DEVICE_PREP=0 / =1 in the environment forces the choice, read per call.
+_DEVICE_PREP_MIN_N: Optional[int] = 1000
+
+
+def prepare_layout_call_device(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
+                               c_repulsion, relative_epsilon, convergence_counter, initial_positions,
+                               verbose, convergence_check_freq, preserve_order,
+                               rng: Optional[np.random.Generator] = None, route: Optional[list] = None) -> LayoutCall:
+    """`prepare_layout_call` with the matrix work on the GPU (_native.prepare_layout): the same LayoutCall, field for
+    field, the same warnings, errors and verbose lines, and the same draws from `rng`.
+
+    The device orders the points where its keys provably sort as spectral_order's do; where it declines
+    (order_route 3) spectral_order runs here and the device takes its order.  `route`, when given, receives the
+    order_route that was used.  A character matrix goes to `prepare_layout_call` as it is: parsing its strings cell
+    by cell on the host costs more than everything the device would then spare, so the simpler form is kept (a
+    CodedMatrix, parsed already, goes to the device).  So does every call that `_validate` rejects, for its shape
+    or for a scalar argument: the host form raises the reference's message, and nothing goes to the device first.
+
+    Every n x n array of the result is laid out as prepare_layout_call's is -- C-contiguous, whatever the layout of
+    the input (a Fortran-contiguous matrix is read where it lies).  A plain array that keeps its order is copied into
+    `reordered_matrix` by the same np.array() call that prepare_layout_call copies it with; a CodedMatrix is passed
+    through by both.
+
+    Where the device declines (route 3) the matrix is uploaded a second time with the host's order: twice the
+    transfer and the first pass, on data that is rare in practice (tied inexact keys, negative or infinite cells)."""
+    from . import _native
+    m, codes, own = None, None, False
+    if isinstance(dissimilarity_matrix, CodedMatrix):
+        m = dissimilarity_matrix
+        own = True
+        codes = m.codes if m.codes.any() else None
+    else:
+        r = _as_rmatrix(dissimilarity_matrix)
+        if r is not None and not _is_character(r.values):   # the matrix itself, not a copy: nothing here writes to it
+            vals = np.asarray(r.values, dtype=np.float64)
+            m = CodedMatrix(vals, np.zeros(vals.shape, dtype=np.int8), r.names, False)
+    ok = m is not None and m.values.ndim == 2 and m.values.shape[0] == m.values.shape[1] and m.values.shape[0] >= 2
+    if ok:   # the checks that do not need the matrix, before anything is uploaded
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
+                          convergence_counter, convergence_check_freq, initial_positions, n_finite_nonzero=1)
+        except Exception:
+            ok = False
+    if not ok:
+        return prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion,
+                                   relative_epsilon, convergence_counter, initial_positions, verbose,
+                                   convergence_check_freq, preserve_order, rng)
+    n = m.values.shape[0]
+    prep = _native.prepare_layout(m.values, codes, bool(preserve_order))
+    if prep.info["order_route"] == _native.ORDER_DECLINED:
+        host_order = spectral_order(m.values)
+        prep = _native.prepare_layout(m.values, codes, False, order=host_order if host_order is not None else [-1])
+    if route is not None:
+        route[:] = [prep.info["order_route"]]
+    _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
+              convergence_counter, convergence_check_freq, initial_positions,
+              n_finite_nonzero=int(prep.info["n_finite_nonzero"]))
+    names = m.names
+    ndim = int(ndim)
+
+    # -- reordering (R/core.R:269-322)
+    order = None
+    if not preserve_order:
+        if prep.order is not None:
+            order = prep.order.astype(np.intp)
+            rcodes = prep.codes_reordered if codes is not None else np.zeros((n, n), dtype=np.int8)
+            m = CodedMatrix(np.ascontiguousarray(prep.values_reordered), np.ascontiguousarray(rcodes),
+                            [m.names[q] for q in order] if m.names is not None else None, m.character)
+            names = m.names
+            if verbose:
+                print("Matrix reordered for spectral pattern (largest values in corners)")
+        elif verbose:
+            print("Insufficient data for meaningful spectral ordering")
+    elif verbose:
+        print("Preserving original row/column order (preserve_order = TRUE)")
+
+    # -- initial positions follow the matrix only through row names (R/core.R:325-333)
+    init = None
+    if initial_positions is not None:
+        ip = _as_rmatrix(initial_positions)
+        init = np.asarray(ip.values, dtype=np.float64)
+        if ip.names is not None and names is not None and list(ip.names) != list(names):
+            lookup = {nm: q for q, nm in enumerate(ip.names)}
+            try:
+                init = init[[lookup[nm] for nm in names], :]
+            except KeyError:
+                raise IndexError("subscript out of bounds") from None
+
+    if int(prep.info["n_edges"]) == 0:
+        _stop("No valid off-diagonal measurements found in dissimilarity matrix")
+    if order is None and not own:
+        m = CodedMatrix(np.array(m.values, dtype=np.float64), m.codes, m.names, False)
+    # dense and tdense are symmetric bit for bit: the transpose of a Fortran-ordered one is the C-ordered one
+    dense, tdense = prep.dense, prep.tdense
+    if not dense.flags.c_contiguous:
+        dense, tdense = dense.T, tdense.T
+
+    # -- initial positions (R/core.R:407-415): the maximum is the same before and after the reordering
+    if init is None:
+        init_step = np.float64(prep.info["numeric_max"]) / n
+        gen = rng if rng is not None else np.random.default_rng()
+        steps = gen.uniform(0.0, 2.0 * init_step, size=(ndim, n - 1)).T
+        init = np.vstack([np.zeros((1, ndim)), np.cumsum(steps, axis=0)])
+
+    return LayoutCall(
+        initial_positions=np.ascontiguousarray(init, dtype=np.float64),
+        dissimilarity_matrix=dense, threshold_matrix=tdense, degrees=prep.degrees,
+        edge_i=prep.edge_i, edge_j=prep.edge_j, edge_dist=prep.edge_dist, edge_thresh=prep.edge_thresh,
+        n_iter=int(mapping_max_iter), k0=float(k0), cooling_rate=float(cooling_rate),
+        c_repulsion=float(c_repulsion), relative_epsilon=float(relative_epsilon),
+        convergence_window=int(convergence_counter),
+        convergence_check_freq=int(convergence_check_freq), verbose=bool(verbose),
+        names=names, order=order, reordered_matrix=m)
+
+
+def _device_prep_wanted(dissimilarity_matrix) -> bool:
+    forced = os.environ.get("TOPOLOW_DEVICE_PREP")
+    if forced == "0":
+        return False
+    if forced == "1":
+        return True
+    if _DEVICE_PREP_MIN_N is None:
+        return False
+    v = dissimilarity_matrix.values if isinstance(dissimilarity_matrix, (CodedMatrix, RMatrix)) else dissimilarity_matrix
+    shape = getattr(v, "shape", None)
+    return shape is not None and len(shape) == 2 and shape[0] >= _DEVICE_PREP_MIN_N
+
+
+def _prepare_layout_call_auto(dissimilarity_matrix, *args, **kw) -> LayoutCall:
+    """The pre-processing of euclidean_embedding(): on the device for matrices of at least _DEVICE_PREP_MIN_N points
+    (TOPOLOW_DEVICE_PREP forces the choice), on the host otherwise and wherever the device form answers
+    ERR_UNSUPPORTED or ERR_NO_DEVICE.  Both forms give the same LayoutCall."""
+    if _device_prep_wanted(dissimilarity_matrix):
+        from . import _native
+        try:
+            return prepare_layout_call_device(dissimilarity_matrix, *args, **kw)
+        except _native.NativeError as e:
+            if e.code not in (_native.ERR_UNSUPPORTED, _native.ERR_NO_DEVICE):
+                raise
+    return prepare_layout_call(dissimilarity_matrix, *args, **kw)
+
+
 def post_mae(reordered_matrix, est_distances: np.ndarray) -> float:
     """R/core.R:479-481: mean |as.numeric(D) - est| over every non-NA cell."""
     raw = coded_matrix(reordered_matrix).as_numeric()
@@ -471,15 +621,17 @@ def _finish(call: LayoutCall, native_result, ndim, k0, cooling_rate, c_repulsion
 def _embed_with(native_fn, pdist_fn, dissimilarity_matrix, ndim, mapping_max_iter, k0,
                 cooling_rate, c_repulsion, relative_epsilon, convergence_counter,
                 initial_positions, write_positions_to_csv, output_dir, verbose,
-                convergence_check_freq, preserve_order, rng=None, post_fn=None) -> Topolow:
-    """post_fn(call, positions) -> (est_distances, mae) replaces pdist_fn + post_mae when given."""
+                convergence_check_freq, preserve_order, rng=None, post_fn=None,
+                prepare_fn=prepare_layout_call) -> Topolow:
+    """post_fn(call, positions) -> (est_distances, mae) replaces pdist_fn + post_mae when given; prepare_fn has the
+    signature of prepare_layout_call and returns what it returns."""
     for nm, val in (("k0", k0), ("cooling_rate", cooling_rate), ("c_repulsion", c_repulsion)):
         if val is _MISSING:
             raise TypeError(f'argument "{nm}" is missing, with no default')
-    call = prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
-                               c_repulsion, relative_epsilon, convergence_counter,
-                               initial_positions, verbose, convergence_check_freq,
-                               preserve_order, rng)
+    call = prepare_fn(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
+                      c_repulsion, relative_epsilon, convergence_counter,
+                      initial_positions, verbose, convergence_check_freq,
+                      preserve_order, rng)
     if verbose:
         print("Starting C++ optimization...")
     import time
@@ -503,7 +655,8 @@ def euclidean_embedding(dissimilarity_matrix, ndim, mapping_max_iter=1000, k0=_M
                        dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
                        c_repulsion, relative_epsilon, convergence_counter, initial_positions,
                        write_positions_to_csv, output_dir, verbose, convergence_check_freq,
-                       preserve_order, _native.host_rng(), post_fn=device_post)
+                       preserve_order, _native.host_rng(), post_fn=device_post,
+                       prepare_fn=_prepare_layout_call_auto)
 
 
 def create_topolow_map(distance_matrix, ndim, mapping_max_iter=1000, k0=_MISSING,

@@ -1,0 +1,270 @@
+// topolow_amd/csrc/relax_prep.h -- the pre-processing kernels: ordering sums, degrees, dense fill, edge list
+// (reference R/core.R:269-436; host pipeline: topolow_layout_prep_* in topolow_relax.hip).
+//
+// Every kernel works in BUFFER coordinates: the caller's n x n buffer is read as B[a * n + b], a the slow index and
+// b the contiguous one.  For a column-major matrix a is the column, for a row-major one (transposed != 0) the row;
+// the host maps "slow"/"fast" to "row"/"column" and no transposed copy is made.
+#pragma once
+
+#include "relax_common.h"
+
+namespace topolow {
+
+constexpr int kPrepTile = 64;
+constexpr int kPrepThreads = 256;
+constexpr int kPrepWaves = kPrepThreads / 64;
+
+// Whole-matrix quantities.  Integer counts and a maximum: atomics do not make them depend on the grid.
+struct PrepTotals {
+  unsigned long long n_finite_nonzero, n_infinite, n_negative, n_inexact;
+  unsigned long long max_key;   // prep_order_key of the largest non-NA code-0 value; 0: there is none
+};
+
+// f64 -> u64, monotone over -Inf..+Inf; never 0 (the smallest image, that of -Inf, is 0x000f...).
+__device__ inline unsigned long long prep_order_key(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ inline unsigned long long prep_wave_sum(unsigned long long x) {
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+  return x;
+}
+
+// First pass: one workgroup per 64 x 64 tile (slow block ta = slow0 / 64 + blockIdx.y, fast block tb = blockIdx.x).
+// The tile goes to LDS once -- lanes along the contiguous index, 8-byte loads, consecutive lanes on consecutive
+// addresses -- with NA, the diagonal and cells past n as 0.0, and a flag per non-NA cell.  Then thread t < 64 adds
+// slow line t of the tile and thread 64 + t fast line t, both sequentially in index order from 0.0: the partial of
+// (point, block of 64 cells) is the same bits along either direction, whatever the layout and whatever the grid.
+//   part_slow_sum / part_slow_cnt   [tb * n + a]: slow line a over fast block tb
+//   part_fast_sum / part_fast_cnt   [ta * n + b]: fast line b over slow block ta
+//   diag_counts[a]                  1 iff the diagonal cell is not NA (the counts include it, the sums do not)
+__global__ __launch_bounds__(kPrepThreads) void prep_sums_kernel(
+    const double* __restrict__ vals, const int8_t* __restrict__ codes, int n, int slow0,
+    double* __restrict__ part_slow_sum, int32_t* __restrict__ part_slow_cnt, double* __restrict__ part_fast_sum,
+    int32_t* __restrict__ part_fast_cnt, uint8_t* __restrict__ diag_counts, PrepTotals* __restrict__ totals) {
+  __shared__ double tile[kPrepTile][kPrepTile + 1];
+  __shared__ uint8_t flag[kPrepTile][kPrepTile + 4];
+  const int tb = blockIdx.x, ta = slow0 / kPrepTile + blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = tb * kPrepTile + lane;
+  unsigned long long finite_nonzero = 0, infinite = 0, negative = 0, inexact = 0, max_key = 0;
+  for (int r = wave; r < kPrepTile; r += kPrepWaves) {
+    const int a = ta * kPrepTile + r;
+    double x = 0.0;
+    uint8_t f = 0;
+    if (a < n && b < n) {
+      const size_t cell = (size_t)a * (size_t)n + (size_t)b;
+      const double v = vals[cell];
+      const int c = codes != nullptr ? (int)codes[cell] : 0;
+      if (!__builtin_isnan(v)) {
+        f = 1;
+        if (a != b) x = v;
+        if (__builtin_isinf(v)) ++infinite;
+        if (v < 0.0) ++negative;
+        const double scaled = v * 1024.0;
+        if (!(v >= 0.0 && v < 1048576.0 && scaled == ::floor(scaled))) ++inexact;
+        if (c == 0) {
+          const unsigned long long key = prep_order_key(v);
+          max_key = key > max_key ? key : max_key;
+          if (__builtin_isfinite(v) && v != 0.0) ++finite_nonzero;
+        }
+      }
+      if (a == b) diag_counts[a] = f;
+    }
+    tile[r][lane] = x;
+    flag[r][lane] = f;
+  }
+  finite_nonzero = prep_wave_sum(finite_nonzero);
+  infinite = prep_wave_sum(infinite);
+  negative = prep_wave_sum(negative);
+  inexact = prep_wave_sum(inexact);
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long other = __shfl_down(max_key, off, 64);
+    max_key = other > max_key ? other : max_key;
+  }
+  if (lane == 0) {
+    if (finite_nonzero) atomicAdd(&totals->n_finite_nonzero, finite_nonzero);
+    if (infinite) atomicAdd(&totals->n_infinite, infinite);
+    if (negative) atomicAdd(&totals->n_negative, negative);
+    if (inexact) atomicAdd(&totals->n_inexact, inexact);
+    if (max_key) atomicMax(&totals->max_key, max_key);
+  }
+  __syncthreads();
+  if (threadIdx.x < kPrepTile) {
+    const int r = threadIdx.x, a = ta * kPrepTile + r;
+    if (a < n) {
+      double s = 0.0;
+      int32_t k = 0;
+      for (int q = 0; q < kPrepTile; ++q) { s += tile[r][q]; k += flag[r][q]; }
+      part_slow_sum[(size_t)tb * n + a] = s;
+      part_slow_cnt[(size_t)tb * n + a] = k;
+    }
+  } else if (threadIdx.x < 2 * kPrepTile) {
+    const int l = threadIdx.x - kPrepTile, bb = tb * kPrepTile + l;
+    if (bb < n) {
+      double s = 0.0;
+      int32_t k = 0;
+      for (int q = 0; q < kPrepTile; ++q) { s += tile[q][l]; k += flag[q][l]; }
+      part_fast_sum[(size_t)ta * n + bb] = s;
+      part_fast_cnt[(size_t)ta * n + bb] = k;
+    }
+  }
+}
+
+// One thread per point: its partials added in block order.  out_sum / out_cnt are 2 x n: slow lines, then fast lines.
+__global__ __launch_bounds__(kPrepThreads) void prep_finish_sums_kernel(
+    int n, int n_blocks, const double* __restrict__ part_slow_sum, const int32_t* __restrict__ part_slow_cnt,
+    const double* __restrict__ part_fast_sum, const int32_t* __restrict__ part_fast_cnt, double* __restrict__ out_sum,
+    int32_t* __restrict__ out_cnt) {
+  const int q = blockIdx.x * kPrepThreads + threadIdx.x;
+  if (q >= n) return;
+  double ss = 0.0, fs = 0.0;
+  int32_t sc = 0, fc = 0;
+  for (int blk = 0; blk < n_blocks; ++blk) {
+    const size_t at = (size_t)blk * n + q;
+    ss += part_slow_sum[at];
+    sc += part_slow_cnt[at];
+    fs += part_fast_sum[at];
+    fc += part_fast_cnt[at];
+  }
+  out_sum[q] = ss;
+  out_cnt[q] = sc;
+  out_sum[(size_t)n + q] = fs;
+  out_cnt[(size_t)n + q] = fc;
+}
+
+// Second pass, dense fill (R/core.R:340-374, 429-436) of the matrix gathered through ord: G[a][b] = B[ord[a]][ord[b]].
+// U = G with NA as +Inf, C = its code (0 where NA).  A cell of the matrix's upper triangle keeps U, the mirrored cell
+// takes the same U, so the result is symmetric bit for bit and reads the same in either layout.  One workgroup per
+// 64 x 64 tile that holds upper cells: the source line ord[a] is contiguous and the lanes gather within it; the
+// mirrored tile is written through LDS so that both stores have lanes on consecutive addresses.  Tiles wholly below
+// the diagonal return at once: their mirror writes them.
+//   upper_a_lt_b   != 0: the matrix's upper triangle is a < b (row-major buffer); 0: b < a (column-major)
+__global__ __launch_bounds__(kPrepThreads) void prep_dense_kernel(
+    const double* __restrict__ vals, const int8_t* __restrict__ codes, int n, const int32_t* __restrict__ ord,
+    int upper_a_lt_b, double* __restrict__ dense, int32_t* __restrict__ tdense) {
+  const int tb = blockIdx.x, ta = blockIdx.y;
+  const bool diag_tile = ta == tb;
+  if (!diag_tile && (upper_a_lt_b ? ta > tb : tb > ta)) return;
+  __shared__ double U[kPrepTile][kPrepTile + 1];
+  __shared__ int32_t Cd[kPrepTile][kPrepTile + 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = tb * kPrepTile + lane;
+  const size_t ob = b < n ? (size_t)ord[b] : 0;
+  for (int r = wave; r < kPrepTile; r += kPrepWaves) {
+    const int a = ta * kPrepTile + r;
+    double u = __builtin_inf();
+    int32_t c = 0;
+    if (a < n && b < n) {
+      const size_t cell = (size_t)ord[a] * (size_t)n + ob;
+      const double v = vals[cell];
+      if (!__builtin_isnan(v)) {
+        u = v;
+        c = codes != nullptr ? (int32_t)codes[cell] : 0;
+      }
+    }
+    U[r][lane] = u;
+    Cd[r][lane] = c;
+  }
+  __syncthreads();
+  if (diag_tile) {
+    for (int r = wave; r < kPrepTile; r += kPrepWaves) {
+      const int a = ta * kPrepTile + r;
+      if (a < n && b < n) {
+        const bool upper = upper_a_lt_b ? r <= lane : lane <= r;
+        const size_t at = (size_t)a * (size_t)n + (size_t)b;
+        dense[at] = upper ? U[r][lane] : U[lane][r];
+        tdense[at] = upper ? Cd[r][lane] : Cd[lane][r];
+      }
+    }
+    return;
+  }
+  const int a2 = ta * kPrepTile + lane;
+  for (int r = wave; r < kPrepTile; r += kPrepWaves) {
+    const int a = ta * kPrepTile + r;
+    if (a < n && b < n) {
+      const size_t at = (size_t)a * (size_t)n + (size_t)b;
+      dense[at] = U[r][lane];
+      tdense[at] = Cd[r][lane];
+    }
+    const int b2 = tb * kPrepTile + r;   // the mirrored tile: slow index from this tile's fast block
+    if (a2 < n && b2 < n) {
+      const size_t at = (size_t)b2 * (size_t)n + (size_t)a2;
+      dense[at] = U[lane][r];
+      tdense[at] = Cd[lane][r];
+    }
+  }
+}
+
+// Edges of column j: the cells i < j of the dense fill that are not +Inf.  The fill is symmetric, so column j is
+// line j of the buffer in either layout: contiguous reads.  One workgroup per column.
+__global__ __launch_bounds__(kPrepThreads) void prep_edge_count_kernel(const double* __restrict__ dense, int n,
+                                                                        int32_t* __restrict__ col_edges) {
+  __shared__ int32_t wave_cnt[kPrepWaves];
+  const int j = blockIdx.x;
+  const double* line = dense + (size_t)j * (size_t)n;
+  int32_t k = 0;
+  for (int i = threadIdx.x; i < j; i += kPrepThreads) k += line[i] != __builtin_inf() ? 1 : 0;
+  for (int off = 32; off > 0; off >>= 1) k += __shfl_down(k, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = k;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int32_t t = 0;
+    for (int w = 0; w < kPrepWaves; ++w) t += wave_cnt[w];
+    col_edges[j] = t;
+  }
+}
+
+// The stable compaction: column j's edges go to [edge_off[j], edge_off[j + 1]) in ascending i -- which(arr.ind = TRUE)
+// order (R/core.R:383-402).  256 cells at a time: a lane's rank is the set bits below it in its wave's ballot plus the
+// waves before it plus the chunks before this one.
+__global__ __launch_bounds__(kPrepThreads) void prep_edge_write_kernel(
+    const double* __restrict__ dense, const int32_t* __restrict__ tdense, int n, const int64_t* __restrict__ edge_off,
+    int32_t* __restrict__ edge_i, int32_t* __restrict__ edge_j, double* __restrict__ edge_dist,
+    int32_t* __restrict__ edge_thresh) {
+  __shared__ int32_t wave_cnt[kPrepWaves];
+  const int j = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t line = (size_t)j * (size_t)n;
+  int64_t base = edge_off[j];
+  for (int i0 = 0; i0 < j; i0 += kPrepThreads) {   // uniform over the workgroup
+    const int i = i0 + threadIdx.x;
+    double d = __builtin_inf();
+    if (i < j) d = dense[line + i];
+    const bool valid = d != __builtin_inf();
+    const unsigned long long mask = __ballot(valid);
+    if (lane == 0) wave_cnt[wave] = __popcll(mask);
+    __syncthreads();
+    int32_t before = 0, all = 0;
+    for (int w = 0; w < kPrepWaves; ++w) {
+      before += w < wave ? wave_cnt[w] : 0;
+      all += wave_cnt[w];
+    }
+    if (valid) {
+      const int64_t e = base + before + __popcll(mask & ((1ull << lane) - 1ull));
+      edge_i[e] = i;
+      edge_j[e] = j;
+      edge_dist[e] = d;
+      edge_thresh[e] = tdense[line + i];
+    }
+    base += all;
+    __syncthreads();
+  }
+}
+
+// The raw reordered matrix, CodedMatrix.reordered(order) in the buffer's own layout: out[a][b] = B[ord[a]][ord[b]].
+// One workgroup per line a; the source line ord[a] is read by all of it and stays in L2.
+__global__ __launch_bounds__(kPrepThreads) void prep_reorder_kernel(
+    const double* __restrict__ vals, const int8_t* __restrict__ codes, int n, const int32_t* __restrict__ ord,
+    double* __restrict__ out_vals, int8_t* __restrict__ out_codes) {
+  const int a = blockIdx.x;
+  const size_t src = (size_t)ord[a] * (size_t)n, dst = (size_t)a * (size_t)n;
+  for (int b = threadIdx.x; b < n; b += kPrepThreads) {
+    const size_t cell = src + (size_t)ord[b];
+    if (out_vals != nullptr) out_vals[dst + b] = vals[cell];
+    if (out_codes != nullptr) out_codes[dst + b] = codes[cell];
+  }
+}
+
+}  // namespace topolow

@@ -38,6 +38,7 @@
 #include "relax_symm_wide.h"
 #include "relax_cv.h"
 #include "relax_post.h"
+#include "relax_prep.h"
 
 using namespace topolow;
 
@@ -118,6 +119,18 @@ struct DevBuf {
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
 };
+
+// layout prep: an allocation that fails is "this problem is too large for the dense form", not a HIP error
+template <typename T>
+void prep_alloc(DevBuf<T>& buf, size_t count, const char* what) {
+  try {
+    buf.alloc(count);
+  } catch (const HipError& e) {
+    (void)hipGetLastError();
+    throw HipError{TOPOLOW_ERR_UNSUPPORTED, "layout prep: no device memory for " + std::string(what) + " (" +
+                                                std::to_string(count * sizeof(T)) + " bytes): " + e.msg};
+  }
+}
 
 double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch())
@@ -3099,6 +3112,320 @@ int topolow_post_metrics(const double* positions, int32_t n, int32_t ndim, const
                          int32_t device, char* errbuf, size_t errlen) {
   return topolow_post_metrics_ex(positions, n, ndim, values, codes, est_distances, sum_abs, count, device,
                                  TOPOLOW_POST_STAGING_DEFAULT, nullptr, errbuf, errlen);
+}
+
+// ---- layout prep: order, degrees, edge list and dense fill on the device (R/core.R:269-436) ----
+// create(): the matrix goes up in chunks of whole 64-line blocks through pinned staging while the first pass runs on
+// the chunks that have arrived; the host applies the ordering rule to the sums; the second pass fills the dense
+// matrices and counts the edges per column.  fetch(): the compaction, the reordered copy when asked for, and the
+// downloads, through the same pinned staging.  The matrix stays on the device between the two.
+struct topolow_layout_prep {
+  int n = 0, device = 0;
+  bool transposed = false, has_codes = false, declined = false;
+  DevBuf<double> vals, dense;
+  DevBuf<int8_t> codes;
+  DevBuf<int32_t> tdense, ord;
+  DevBuf<int64_t> edge_off;
+  std::vector<int32_t> order, degrees;   // order[0] == -1: the input order is kept
+  int64_t n_edges = 0;
+  double phase_seconds[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+};
+
+namespace {
+
+constexpr size_t kPrepChunkBytes = (size_t)32 << 20;
+constexpr int kPrepSlots = 3;
+
+// device -> pinned slot -> the caller's pageable memory, the slots going round: chunk t is on its way while the host
+// threads drain chunk t - 1.  Everything before it on `stream` has run when a chunk leaves.
+void prep_download(hipStream_t stream, hipEvent_t* done, PinBuf* pin, size_t slot_bytes, void* dst, const void* src,
+                   size_t bytes) {
+  if (bytes == 0) return;
+  const size_t n_chunks = (bytes + slot_bytes - 1) / slot_bytes;
+  auto drain = [&](size_t t) {
+    const size_t off = t * slot_bytes, len = std::min(slot_bytes, bytes - off);
+    HIP_TRY(hipEventSynchronize(done[t % kPrepSlots]));
+    post_host_copy(static_cast<char*>(dst) + off, pin[t % kPrepSlots].p, len);
+  };
+  for (size_t t = 0; t < n_chunks; ++t) {
+    const size_t off = t * slot_bytes, len = std::min(slot_bytes, bytes - off);
+    HIP_TRY(hipMemcpyAsync(pin[t % kPrepSlots].p, static_cast<const char*>(src) + off, len, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(done[t % kPrepSlots], stream));
+    if (t >= 1) drain(t - 1);
+  }
+  drain(n_chunks - 1);
+}
+
+bool prep_is_permutation(const int32_t* order, int n) {
+  std::vector<char> seen((size_t)n, 0);
+  for (int q = 0; q < n; ++q) {
+    if (order[q] < 0 || order[q] >= n || seen[(size_t)order[q]]) return false;
+    seen[(size_t)order[q]] = 1;
+  }
+  return true;
+}
+
+}  // namespace
+
+int32_t topolow_layout_order_from_sums(int32_t n, const double* row_sum, const int64_t* row_cnt,
+                                       const double* col_sum, const int64_t* col_cnt, int32_t exact_sums,
+                                       int32_t* order_out) {
+  if (order_out && n >= 1) order_out[0] = -1;
+  if (n < 1 || !row_sum || !row_cnt || !col_sum || !col_cnt || !order_out) return TOPOLOW_ORDER_DECLINED;
+  std::vector<double> key((size_t)n);
+  int64_t positive = 0;
+  for (int p = 0; p < n; ++p) {
+    const double rm = row_cnt[p] > 0 ? row_sum[p] / (double)row_cnt[p] : NAN;
+    const double cm = col_cnt[p] > 0 ? col_sum[p] / (double)col_cnt[p] : NAN;
+    double k = (rm + cm) / 2.0;
+    if (std::isnan(k)) k = 0.0;
+    key[(size_t)p] = k;
+    positive += k > 0.0 ? 1 : 0;
+  }
+  const bool exact = exact_sums > 0 && n <= (1 << 23);
+  if (!exact && exact_sums < 0) return TOPOLOW_ORDER_DECLINED;
+  std::vector<int32_t> idx((size_t)n);
+  for (int p = 0; p < n; ++p) idx[(size_t)p] = p;
+  std::stable_sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) { return key[(size_t)x] < key[(size_t)y]; });
+  if (!exact) {
+    // no negative and no infinite cell: either implementation's key is within (n + 2) * 2^-53 relative of the true
+    // one, so neighbours further apart than 8 n 2^-53 of the larger sort alike in both.  Two keys of exactly 0 are
+    // a tie in both (a sum of non-negative terms is 0 only when every term is).
+    const double rel = 8.0 * (double)n * 0x1p-53;
+    for (int q = 0; q + 1 < n; ++q) {
+      const double lo = key[(size_t)idx[(size_t)q]], hi = key[(size_t)idx[(size_t)q + 1]];
+      if (lo == 0.0 && hi == 0.0) continue;
+      if (!std::isfinite(hi) || lo < 0.0 || hi < 0x1p-1000 || !(hi - lo > rel * hi)) return TOPOLOW_ORDER_DECLINED;
+    }
+    if (n == 1 && !(key[0] == 0.0 || (std::isfinite(key[0]) && key[0] >= 0x1p-1000))) return TOPOLOW_ORDER_DECLINED;
+  }
+  if (positive > 1) std::copy(idx.begin(), idx.end(), order_out);
+  return exact ? TOPOLOW_ORDER_DEVICE_EXACT : TOPOLOW_ORDER_DEVICE_GAP;
+}
+
+int topolow_layout_prep_create(topolow_layout_prep** out, const double* values, const int8_t* codes, int32_t n,
+                               int32_t transposed, int32_t preserve_order, const int32_t* order_in, int32_t device,
+                               topolow_layout_prep_info* info, char* errbuf, size_t errlen) {
+  if (!out || !values || !info || n < 2) return TOPOLOW_ERR_BAD_ARGUMENT;
+  *out = nullptr;
+  const bool given = !preserve_order && order_in != nullptr;
+  if (given && order_in[0] != -1 && !prep_is_permutation(order_in, n)) {
+    set_err(errbuf, errlen, "order_in must be a permutation of 0..n-1, or start with -1");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  std::unique_ptr<topolow_layout_prep> p(new topolow_layout_prep());
+  const int rc = guarded(errbuf, errlen, [&] {
+    p->device = select_device(device);
+    p->n = n;
+    p->transposed = transposed != 0;
+    p->has_codes = codes != nullptr;
+    const size_t N = (size_t)n, cells = N * N;
+    const int nb = (n + kPrepTile - 1) / kPrepTile;
+    const double t0 = now_s();
+
+    // -- upload and first pass, overlapped
+    prep_alloc(p->vals, cells, "the matrix");
+    if (codes) prep_alloc(p->codes, cells, "the codes");
+    DevBuf<double> part_slow_sum, part_fast_sum, line_sum;
+    DevBuf<int32_t> part_slow_cnt, part_fast_cnt, line_cnt;
+    DevBuf<uint8_t> diag;
+    DevBuf<PrepTotals> totals;
+    prep_alloc(part_slow_sum, (size_t)nb * N, "the partial sums");
+    prep_alloc(part_fast_sum, (size_t)nb * N, "the partial sums");
+    prep_alloc(part_slow_cnt, (size_t)nb * N, "the partial counts");
+    prep_alloc(part_fast_cnt, (size_t)nb * N, "the partial counts");
+    prep_alloc(line_sum, 2 * N, "the sums");
+    prep_alloc(line_cnt, 2 * N, "the counts");
+    prep_alloc(diag, N, "the diagonal flags");
+    prep_alloc(totals, 1, "the totals");
+    const int chunk_lines = (int)std::min<size_t>(
+        (size_t)nb * kPrepTile, std::max<size_t>(kPrepTile, kPrepChunkBytes / (N * 8) / kPrepTile * kPrepTile));
+    const int n_chunks = (n + chunk_lines - 1) / chunk_lines, slots = std::min(kPrepSlots, n_chunks);
+    const size_t chunk_cells = (size_t)std::min(chunk_lines, n) * N;
+    PinBuf pvals[kPrepSlots], pcodes[kPrepSlots];
+    PostPipe P;
+    for (int b = 0; b < slots; ++b) {
+      pvals[b].alloc(chunk_cells * 8);
+      if (codes) pcodes[b].alloc(chunk_cells);
+    }
+    P.create(slots, 0);
+    HIP_TRY(hipMemsetAsync(totals.p, 0, sizeof(PrepTotals), P.run));
+    for (int t = 0; t < n_chunks; ++t) {
+      const int b = t % slots, a0 = t * chunk_lines, lines = std::min(chunk_lines, n - a0);
+      const size_t off = (size_t)a0 * N, len = (size_t)lines * N;
+      if (t >= slots) HIP_TRY(hipEventSynchronize(P.up_done[b]));   // chunk t - slots has left the staging buffers
+      post_host_copy(pvals[b].p, values + off, len * 8);
+      if (codes) post_host_copy(pcodes[b].p, codes + off, len);
+      HIP_TRY(hipMemcpyAsync(p->vals.p + off, pvals[b].p, len * 8, hipMemcpyHostToDevice, P.up));
+      if (codes) HIP_TRY(hipMemcpyAsync(p->codes.p + off, pcodes[b].p, len, hipMemcpyHostToDevice, P.up));
+      HIP_TRY(hipEventRecord(P.up_done[b], P.up));
+      HIP_TRY(hipStreamWaitEvent(P.run, P.up_done[b], 0));
+      hipLaunchKernelGGL(prep_sums_kernel, dim3(nb, (lines + kPrepTile - 1) / kPrepTile), dim3(kPrepThreads), 0, P.run,
+                         p->vals.p, codes ? p->codes.p : nullptr, n, a0, part_slow_sum.p, part_slow_cnt.p,
+                         part_fast_sum.p, part_fast_cnt.p, diag.p, totals.p);
+      HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(prep_finish_sums_kernel, dim3((n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, P.run,
+                       n, nb, part_slow_sum.p, part_slow_cnt.p, part_fast_sum.p, part_fast_cnt.p, line_sum.p, line_cnt.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> sums(2 * N);
+    std::vector<int32_t> cnts(2 * N);
+    std::vector<uint8_t> on_diag(N);
+    PrepTotals tot;
+    HIP_TRY(hipMemcpyAsync(sums.data(), line_sum.p, 2 * N * 8, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipMemcpyAsync(cnts.data(), line_cnt.p, 2 * N * 4, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipMemcpyAsync(on_diag.data(), diag.p, N, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipMemcpyAsync(&tot, totals.p, sizeof tot, hipMemcpyDeviceToHost, P.run));
+    P.sync();
+    const double t1 = now_s();
+
+    // -- the quantities of the info struct and the order
+    const size_t row_at = p->transposed ? 0 : N, col_at = p->transposed ? N : 0;   // slow lines are rows when transposed
+    std::vector<int64_t> row_cnt(N), col_cnt(N);
+    for (size_t q = 0; q < N; ++q) {
+      row_cnt[q] = (int64_t)cnts[row_at + q] - on_diag[q];
+      col_cnt[q] = (int64_t)cnts[col_at + q] - on_diag[q];
+    }
+    *info = topolow_layout_prep_info();
+    info->n_edges = -1;
+    info->n_finite_nonzero = (int64_t)tot.n_finite_nonzero;
+    info->n_infinite = (int64_t)tot.n_infinite;
+    info->n_negative = (int64_t)tot.n_negative;
+    info->exact_sums = tot.n_inexact == 0 ? 1 : 0;
+    if (tot.max_key == 0) {
+      info->numeric_max = NAN;
+    } else {
+      const uint64_t bits = (tot.max_key >> 63) ? (uint64_t)(tot.max_key & 0x7fffffffffffffffull) : (uint64_t)~tot.max_key;
+      memcpy(&info->numeric_max, &bits, 8);
+    }
+    p->order.assign(N, 0);
+    p->order[0] = -1;
+    if (preserve_order) {
+      info->order_route = TOPOLOW_ORDER_PRESERVED;
+    } else if (given) {
+      info->order_route = TOPOLOW_ORDER_DECLINED;
+      std::copy(order_in, order_in + (order_in[0] == -1 ? 1 : n), p->order.begin());
+    } else {
+      const int32_t flag = info->exact_sums ? 1 : (tot.n_negative + tot.n_infinite > 0 ? -1 : 0);
+      info->order_route = topolow_layout_order_from_sums(n, sums.data() + row_at, row_cnt.data(), sums.data() + col_at,
+                                                         col_cnt.data(), flag, p->order.data());
+      if (info->order_route == TOPOLOW_ORDER_DECLINED) {
+        p->declined = true;
+        p->phase_seconds[0] = t1 - t0;
+        return;
+      }
+    }
+    const bool reordered = p->order[0] != -1;
+    info->reordered = reordered ? 1 : 0;
+    std::vector<int32_t> ord(N);
+    for (size_t q = 0; q < N; ++q) ord[q] = reordered ? p->order[q] : (int32_t)q;
+    p->degrees.resize(N);
+    for (size_t q = 0; q < N; ++q) p->degrees[q] = cnts[row_at + (size_t)ord[q]];
+    const double t2 = now_s();
+
+    // -- second pass: dense fill, edges per column
+    prep_alloc(p->ord, N, "the order");
+    prep_alloc(p->dense, cells, "the dense distances");
+    prep_alloc(p->tdense, cells, "the dense thresholds");
+    prep_alloc(p->edge_off, N + 1, "the edge offsets");
+    DevBuf<int32_t> col_edges;
+    prep_alloc(col_edges, N, "the edge counts");
+    HIP_TRY(hipMemcpyAsync(p->ord.p, ord.data(), N * 4, hipMemcpyHostToDevice, P.run));
+    hipLaunchKernelGGL(prep_dense_kernel, dim3(nb, nb), dim3(kPrepThreads), 0, P.run, p->vals.p,
+                       codes ? p->codes.p : nullptr, n, p->ord.p, p->transposed ? 1 : 0, p->dense.p, p->tdense.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prep_edge_count_kernel, dim3(n), dim3(kPrepThreads), 0, P.run, p->dense.p, n, col_edges.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> per_col(N);
+    HIP_TRY(hipMemcpyAsync(per_col.data(), col_edges.p, N * 4, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipStreamSynchronize(P.run));
+    std::vector<int64_t> off(N + 1, 0);
+    for (size_t j = 0; j < N; ++j) off[j + 1] = off[j] + per_col[j];
+    HIP_TRY(hipMemcpy(p->edge_off.p, off.data(), (N + 1) * 8, hipMemcpyHostToDevice));
+    p->n_edges = off[N];
+    info->n_edges = p->n_edges;
+    p->phase_seconds[0] = t1 - t0;
+    p->phase_seconds[1] = t2 - t1;
+    p->phase_seconds[2] = now_s() - t2;
+  });
+  if (rc != TOPOLOW_OK) return rc;
+  *out = p.release();
+  return TOPOLOW_OK;
+}
+
+int topolow_layout_prep_fetch(topolow_layout_prep* p, int32_t* order, int32_t* degrees, int32_t* edge_i,
+                              int32_t* edge_j, double* edge_dist, int32_t* edge_thresh, double* dense, int32_t* tdense,
+                              double* values_reordered, int8_t* codes_reordered, char* errbuf, size_t errlen) {
+  if (!p || !order || !degrees || !edge_i || !edge_j || !edge_dist || !edge_thresh) return TOPOLOW_ERR_BAD_ARGUMENT;
+  if (p->declined) {
+    set_err(errbuf, errlen, "the ordering was declined (order_route 3): create again with order_in");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(p->device));
+    const double t0 = now_s();
+    const int n = p->n;
+    const size_t N = (size_t)n, cells = N * N, E = (size_t)p->n_edges;
+    std::copy(p->order.begin(), p->order.end(), order);
+    std::copy(p->degrees.begin(), p->degrees.end(), degrees);
+
+    const bool want_codes = codes_reordered != nullptr && p->has_codes;
+    size_t largest = std::max<size_t>(E * 8, 4096);
+    if (dense || values_reordered) largest = std::max(largest, cells * 8);
+    if (tdense) largest = std::max(largest, cells * 4);
+    if (want_codes) largest = std::max(largest, cells);
+    const size_t slot_bytes = std::min(kPrepChunkBytes, largest);
+    PinBuf pin[kPrepSlots];
+    PostPipe P;
+    for (int b = 0; b < kPrepSlots; ++b) pin[b].alloc(slot_bytes);
+    P.create(kPrepSlots, 0);
+
+    DevBuf<int32_t> dei, dej, det;
+    DevBuf<double> ded;
+    prep_alloc(dei, E, "the edge list");
+    prep_alloc(dej, E, "the edge list");
+    prep_alloc(det, E, "the edge list");
+    prep_alloc(ded, E, "the edge list");
+    hipLaunchKernelGGL(prep_edge_write_kernel, dim3(n), dim3(kPrepThreads), 0, P.down, p->dense.p, p->tdense.p, n,
+                       p->edge_off.p, dei.p, dej.p, ded.p, det.p);
+    HIP_TRY(hipGetLastError());
+    DevBuf<double> rvals;
+    DevBuf<int8_t> rcodes;
+    if (values_reordered || want_codes) {
+      if (values_reordered) prep_alloc(rvals, cells, "the reordered matrix");
+      if (want_codes) prep_alloc(rcodes, cells, "the reordered codes");
+      hipLaunchKernelGGL(prep_reorder_kernel, dim3(n), dim3(kPrepThreads), 0, P.down, p->vals.p,
+                         want_codes ? p->codes.p : nullptr, n, p->ord.p, values_reordered ? rvals.p : nullptr,
+                         want_codes ? rcodes.p : nullptr);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(P.down));   // the compaction and the gather end here, the downloads begin
+    const double t1 = now_s();
+    prep_download(P.down, P.down_done, pin, slot_bytes, edge_i, dei.p, E * 4);
+    prep_download(P.down, P.down_done, pin, slot_bytes, edge_j, dej.p, E * 4);
+    prep_download(P.down, P.down_done, pin, slot_bytes, edge_dist, ded.p, E * 8);
+    prep_download(P.down, P.down_done, pin, slot_bytes, edge_thresh, det.p, E * 4);
+    if (dense) prep_download(P.down, P.down_done, pin, slot_bytes, dense, p->dense.p, cells * 8);
+    if (tdense) prep_download(P.down, P.down_done, pin, slot_bytes, tdense, p->tdense.p, cells * 4);
+    if (values_reordered) prep_download(P.down, P.down_done, pin, slot_bytes, values_reordered, rvals.p, cells * 8);
+    if (want_codes) prep_download(P.down, P.down_done, pin, slot_bytes, codes_reordered, rcodes.p, cells);
+    else if (codes_reordered) memset(codes_reordered, 0, cells);   // no codes came in: all zero
+    P.sync();
+    p->phase_seconds[3] = t1 - t0;
+    p->phase_seconds[4] = now_s() - t1;
+  });
+}
+
+int topolow_layout_prep_phase_seconds(const topolow_layout_prep* p, double* seconds) {
+  if (!p || !seconds) return TOPOLOW_ERR_BAD_ARGUMENT;
+  for (int q = 0; q < 5; ++q) seconds[q] = p->phase_seconds[q];
+  return TOPOLOW_OK;
+}
+
+void topolow_layout_prep_destroy(topolow_layout_prep* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  delete p;
 }
 
 // ---- ONE embedding row-sharded over several sessions (one process, one host thread per block) ----
