@@ -382,8 +382,8 @@ int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, co
  * degrees[i] = row count of point order[i], dense / tdense as the 16-argument call takes them (unmeasured = +Inf,
  * the lower triangle the transpose of the upper, R/core.R:429-436), and the raw reordered matrix.
  * Memory: the matrix (9 n^2 bytes, 8 without codes) and the dense fill (12 n^2 bytes; the edge list is compacted from
- * it) stay on the device between create() and destroy(); fetch() adds the edge list and, when asked for, the
- * reordered matrix.  A failed device allocation: TOPOLOW_ERR_UNSUPPORTED with a message.
+ * it) stay on the device between create() and destroy(); the first fetch() (or session loaded from the handle that
+ * gathers an edge list) adds the edge list, which then stays too; fetch() adds, when asked for, the reordered matrix.  A failed device allocation: TOPOLOW_ERR_UNSUPPORTED with a message.
  * ------------------------------------------------------------------------------------- */
 typedef struct topolow_layout_prep topolow_layout_prep;
 
@@ -426,6 +426,69 @@ void topolow_layout_prep_destroy(topolow_layout_prep* p);
  * the ordering rule on the host, the second pass, fetch()'s compaction and reorder gather, fetch()'s downloads} of
  * this handle; 5 doubles out.  A handle that declined has the first figure only. */
 int topolow_layout_prep_phase_seconds(const topolow_layout_prep* p, double* seconds);
+
+/* ---------------------------------------------------------------------------------------
+ * Resident embedding: prepare, relax and score from ONE upload.  The three entries below read what a handle keeps on
+ * the device instead of the arrays fetch() would download and the caller upload again; each returns the bits the
+ * route over fetch() returns (tests/test_gpu_resident_embedding.py).  The handle is not consumed by any of them:
+ * fetch() afterwards returns what it returned before.
+ * Memory: between create() and destroy() the handle holds 21 n^2 bytes (the matrix 8 + its codes 1, the dense fill
+ * 8 + 4; 20 without codes), after the first compaction also its edge list (20 bytes per edge), beside the session's
+ * blocks (4 ld n bytes, 8 with f64_exact).  A failed device allocation: TOPOLOW_ERR_UNSUPPORTED with a message.
+ * ------------------------------------------------------------------------------------- */
+
+/* Loads a whole-problem session (row_begin = 0, row_end = n) from a handle that holds a second pass: what
+ * topolow_session_load_dense / _load_coo + topolow_session_set_edges do with the arrays fetch() returns, device to
+ * device -- the encoded block (and the deltas of an f64_exact session) from the resident dense fill through the
+ * session's relabelling, the degree terms, and the convergence edge list in session labels where the session gathers
+ * one (f64 sessions, ndim > 16, TOPOLOW_EDGE_MAE=1); otherwise the check reads the block, as after set_edges, and the
+ * handle's list is not even compacted.  A -DTOPOLOW_ENC_TILED=1 build is covered (the encoder addresses the block
+ * through enc_index).
+ * TOPOLOW_ERR_BAD_ARGUMENT with a message, before any device call: a NULL argument; a handle that declined; a handle
+ * of another n; a row-block session; a handle on another device than the session's. */
+struct topolow_session;   /* the session type: "Device-resident session" below */
+int topolow_session_load_prepared(struct topolow_session* s, topolow_layout_prep* p, char* errbuf, size_t errlen);
+
+/* topolow_optimize_layout_exact with the matrix, the degrees and the edges taken from the handle (n is the handle's):
+ * the same route for the same n, ndim and options, the same run, the same verbose lines, interrupt polls and stats.
+ * initial_positions: n x ndim, row q for the q-th point of the ORDERED matrix.  The slab and tile Gauss-Seidel routes
+ * load their session with topolow_session_load_prepared; the one-workgroup route (small n) fetches into temporaries
+ * inside the call.  opt->device: -1, or the handle's device.
+ * TOPOLOW_ERR_BAD_ARGUMENT before any device call: a NULL handle, initial_positions or output (stats may be NULL); a
+ * handle that declined; opt->device naming another device.  TOPOLOW_ERR_UNSUPPORTED: a sharded run (opt->n_devices > 1
+ * or opt->devices) -- the caller keeps the route over fetch(). */
+int topolow_layout_prep_optimize(topolow_layout_prep* p, const double* initial_positions, int32_t ndim,
+                                 int32_t n_iter, double k0, double cooling_rate, double c_repulsion,
+                                 double relative_epsilon, int32_t convergence_window, int32_t convergence_check_freq,
+                                 int32_t verbose, const topolow_options* opt, double* positions_out,
+                                 int32_t* converged, int32_t* iterations, double* final_mae, double* final_k,
+                                 topolow_run_stats* stats, char* errbuf, size_t errlen);
+
+/* topolow_post_metrics on the handle's resident matrix, gathered through its order: positions n x ndim f64
+ * column-major (host), row q for the q-th point of the ordered matrix; est_distances n x n f64 out (host) or NULL,
+ * bit-identical to topolow_est_distances, leaving through the same tiled, pinned, overlapped download
+ * (TOPOLOW_POST_TILE_COLS applies).  A cell counts iff its value is finite and its code is 0, the diagonal included.
+ * The sum: one partial per LINE of the handle's buffer, reduced on the device in topolow_post_metrics' fixed order,
+ * the lines added in index order on the host -- the same bits whatever the tile size and whether or not est_distances
+ * is asked for.  For a handle created with transposed = 1 a line is a row of the matrix: sum_abs has the bits
+ * topolow_post_metrics gives when it reads the C-ordered reordered matrix as its transpose (what
+ * euclidean_embedding() did before).  For transposed = 0 a line is a column: count and est_distances are identical,
+ * sum_abs / count agrees with that reading to 1e-12 relative (the same terms, grouped by columns instead of rows).
+ * TOPOLOW_ERR_BAD_ARGUMENT before any device call: NULL handle, positions, sum_abs or count; ndim < 1; a handle that
+ * declined. */
+int topolow_layout_prep_post_metrics(topolow_layout_prep* p, const double* positions, int32_t ndim,
+                                     double* est_distances, double* sum_abs, int64_t* count, char* errbuf,
+                                     size_t errlen);
+
+/* The n-sized outputs of fetch() alone, from the handle's host side (no device call, nothing of edge-list size moves):
+ * order (order[0] = -1: the input order is kept) and degrees, n entries each; either may be NULL, not both.
+ * TOPOLOW_ERR_BAD_ARGUMENT: a NULL or declined handle. */
+int topolow_layout_prep_order(const topolow_layout_prep* p, int32_t* order, int32_t* degrees);
+
+/* A study entry (tests/study/resident_embedding_timing.py): wall-clock seconds of this handle's last
+ * topolow_session_load_prepared, last topolow_layout_prep_optimize (the whole call) and last
+ * topolow_layout_prep_post_metrics; 3 doubles out, 0 where none ran. */
+int topolow_layout_prep_resident_seconds(const topolow_layout_prep* p, double* seconds);
 
 /* Host only: the ordering rule on given sums -- what create() runs after its first pass.
  * NOTE: exact_sums is three-valued here, unlike the 0 / 1 field of the info struct.  0 asserts that the data hold no

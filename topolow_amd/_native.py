@@ -341,6 +341,18 @@ def load() -> C.CDLL:
     lib.topolow_layout_prep_destroy.argtypes = [vp]
     lib.topolow_layout_prep_phase_seconds.restype = C.c_int
     lib.topolow_layout_prep_phase_seconds.argtypes = [vp, dp]
+    lib.topolow_session_load_prepared.restype = C.c_int
+    lib.topolow_session_load_prepared.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_optimize.restype = C.c_int
+    lib.topolow_layout_prep_optimize.argtypes = [
+        vp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+        C.POINTER(TopolowOptions), dp, ip, ip, dp, dp, C.POINTER(TopolowRunStats), C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_post_metrics.restype = C.c_int
+    lib.topolow_layout_prep_post_metrics.argtypes = [vp, dp, C.c_int32, dp, dp, i64p, C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_order.restype = C.c_int
+    lib.topolow_layout_prep_order.argtypes = [vp, ip, ip]
+    lib.topolow_layout_prep_resident_seconds.restype = C.c_int
+    lib.topolow_layout_prep_resident_seconds.argtypes = [vp, dp]
     lib.topolow_layout_order_from_sums.restype = C.c_int32
     lib.topolow_layout_order_from_sums.argtypes = [C.c_int32, dp, i64p, dp, i64p, C.c_int32, ip]
     _lib = lib
@@ -440,13 +452,16 @@ def optimize_layout_exact_arrays(initial_positions, dissimilarity_matrix, thresh
         int(bool(verbose)), C.byref(opt), _dp(out), C.byref(conv), C.byref(iters), C.byref(fmae),
         C.byref(fk), C.byref(stats), err, len(err))
     _check(rc, err)
-    info = dict(schedule={SCHEDULE_SLAB: "slab", SCHEDULE_GS: "gs"}.get(stats.schedule_used),
+    return NativeResult(np.ascontiguousarray(out), bool(conv.value), int(iters.value),
+                        float(fmae.value), float(fk.value), _run_info(stats, opt))
+
+
+def _run_info(stats: TopolowRunStats, opt: TopolowOptions) -> Dict[str, Any]:
+    return dict(schedule={SCHEDULE_SLAB: "slab", SCHEDULE_GS: "gs"}.get(stats.schedule_used),
                 precision=_PRECISION_NAMES.get(stats.precision_used),
                 iterations_run=stats.iterations_run, n_checks=stats.n_checks,
                 device_seconds=stats.device_seconds, total_seconds=stats.total_seconds,
                 setup_seconds=stats.setup_seconds, stage_launches=stats.stage_launches, seed=int(opt.seed))
-    return NativeResult(np.ascontiguousarray(out), bool(conv.value), int(iters.value),
-                        float(fmae.value), float(fk.value), info)
 
 
 def optimize_layout_exact(call) -> NativeResult:
@@ -901,6 +916,169 @@ def order_from_sums(row_sum, row_cnt, col_sum, col_cnt, exact_sums: int):
     return int(route), (None if order[0] == -1 else order[:n])
 
 
+class PreparedHandle:
+    """A prepared layout that stays on the device (topolow_layout_prep_*): a context manager around create / destroy.
+    `values` (f64, NaN = NA) and `codes` (int8 or None) are used where they lie: a C-contiguous matrix goes with
+    transposed=1, a Fortran-contiguous one with transposed=0 (`layout` = "C" / "F" forces the reading of a matrix that
+    is both).  `order`: the caller's order (an int array, or [-1] for "keep"), for data on which the device declines
+    to order.  `.info` holds the fields of topolow_layout_prep_info; on info["order_route"] == ORDER_DECLINED without an
+    `order` given the handle holds nothing else (`.declined`): the caller orders and creates again.
+
+        with PreparedHandle(values, codes) as h:
+            res = h.optimize(initial_positions, ndim, n_iter, k0, cooling_rate, c_repulsion)
+            est, sum_abs, count = h.post_metrics(res.positions)
+
+    The matrix goes up once; .optimize and .post_metrics read what the handle keeps on the device and return the bits
+    of optimize_layout_exact_arrays / post_metrics on the arrays .fetch() returns."""
+
+    def __init__(self, values, codes=None, preserve_order: bool = False, order=None, layout: Optional[str] = None,
+                 device: Optional[int] = None):
+        self.lib = load()
+        self._h = C.c_void_p(None)
+        vals = np.asarray(values)
+        if vals.ndim != 2 or vals.shape[0] != vals.shape[1]:
+            raise ValueError("values must be an n x n matrix")
+        n = vals.shape[0]
+        if layout is None:
+            layout = "F" if (vals.flags.f_contiguous and not vals.flags.c_contiguous) else "C"
+        need = [layout, "A"]
+        vals = np.require(vals, dtype=np.float64, requirements=need)
+        cds = None
+        if codes is not None:
+            cds = np.require(np.asarray(codes), dtype=np.int8, requirements=need)
+            if cds.shape != (n, n):
+                raise ValueError("codes must have the shape of values")
+        oin = None
+        if order is not None:
+            oin = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+            if oin.shape[0] != n and not (oin.shape[0] >= 1 and oin[0] == -1):
+                raise ValueError("order must have n entries")
+        self.n, self.layout, self.has_codes = int(n), layout, cds is not None
+        i8p = C.POINTER(C.c_int8)
+        info = TopolowLayoutPrepInfo()
+        self._err = C.create_string_buffer(512)
+        rc = self.lib.topolow_layout_prep_create(
+            C.byref(self._h), _dp(vals), cds.ctypes.data_as(i8p) if cds is not None else None, n,
+            1 if layout == "C" else 0, 1 if preserve_order else 0, _ip(oin) if oin is not None else None,
+            int(options.get("device", -1)) if device is None else int(device), C.byref(info), self._err, len(self._err))
+        _check(rc, self._err)
+        self.info = {k: getattr(info, k) for k, _ in TopolowLayoutPrepInfo._fields_ if k != "reserved"}
+        self._order = None
+
+    @property
+    def declined(self) -> bool:
+        return int(self.info["n_edges"]) < 0
+
+    @property
+    def order(self) -> Optional[np.ndarray]:
+        """The order applied (int32, 0-based), or None where the input order is kept.  n values from the handle's host
+        side: nothing of size n x n moves."""
+        if self.declined or not self.info["reordered"]:
+            return None
+        if self._order is None:
+            o = np.empty(self.n, dtype=np.int32)
+            if self.lib.topolow_layout_prep_order(self._h, _ip(o), None) != OK:
+                raise NativeError(ERR_BAD_ARGUMENT, "topolow_layout_prep_order refused the handle")
+            self._order = o
+        return self._order
+
+    def fetch(self, want_dense: bool = True, want_reordered: bool = True) -> PreparedLayout:
+        """topolow_layout_prep_fetch: the arrays of the 16-argument call as a PreparedLayout (see prepare_layout)."""
+        out = PreparedLayout(info=dict(self.info))
+        if self.declined:
+            return out
+        n, layout = self.n, self.layout
+        i8p = C.POINTER(C.c_int8)
+        E = int(self.info["n_edges"])
+        o = np.empty(n, dtype=np.int32)
+        out.degrees = np.empty(n, dtype=np.int32)
+        out.edge_i, out.edge_j = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
+        out.edge_dist, out.edge_thresh = np.empty(E, dtype=np.float64), np.empty(E, dtype=np.int32)
+        if want_dense:
+            out.dense = np.empty((n, n), dtype=np.float64, order=layout)
+            out.tdense = np.empty((n, n), dtype=np.int32, order=layout)
+        want_reordered = bool(want_reordered) and bool(self.info["reordered"])
+        if want_reordered:
+            out.values_reordered = np.empty((n, n), dtype=np.float64, order=layout)
+            out.codes_reordered = np.empty((n, n), dtype=np.int8, order=layout)
+        rc = self.lib.topolow_layout_prep_fetch(
+            self._h, _ip(o), _ip(out.degrees), _ip(out.edge_i), _ip(out.edge_j), _dp(out.edge_dist), _ip(out.edge_thresh),
+            _dp(out.dense) if want_dense else None, _ip(out.tdense) if want_dense else None,
+            _dp(out.values_reordered) if want_reordered else None,
+            out.codes_reordered.ctypes.data_as(i8p) if want_reordered else None, self._err, len(self._err))
+        _check(rc, self._err)
+        out.order = None if o[0] == -1 else o
+        out.phase_seconds = self.phase_seconds()
+        return out
+
+    def optimize(self, initial_positions, ndim: Optional[int] = None, n_iter: int = 1000, k0: float = 1.0,
+                 cooling_rate: float = 0.01, c_repulsion: float = 0.01, relative_epsilon: float = 1e-4,
+                 convergence_window: int = 5, convergence_check_freq: int = 3, verbose: bool = False,
+                 **opt_kw) -> NativeResult:
+        """topolow_layout_prep_optimize: optimize_layout_exact_arrays with the matrix, degrees and edges taken from the
+        handle.  initial_positions: n x ndim, row q for the q-th point of the ordered matrix."""
+        pos0 = _f64F(initial_positions)
+        n, dim = pos0.shape
+        if n != self.n or (ndim is not None and int(ndim) != dim):
+            raise ValueError("initial_positions must be n x ndim")
+        out = np.zeros((n, dim), dtype=np.float64, order="F")
+        conv, iters = C.c_int32(0), C.c_int32(0)
+        fmae, fk = C.c_double(0.0), C.c_double(0.0)
+        stats = TopolowRunStats()
+        opt = make_options(**opt_kw)
+        rc = self.lib.topolow_layout_prep_optimize(
+            self._h, _dp(pos0), dim, int(n_iter), float(k0), float(cooling_rate), float(c_repulsion),
+            float(relative_epsilon), int(convergence_window), int(convergence_check_freq), int(bool(verbose)),
+            C.byref(opt), _dp(out), C.byref(conv), C.byref(iters), C.byref(fmae), C.byref(fk), C.byref(stats),
+            self._err, len(self._err))
+        _check(rc, self._err)
+        return NativeResult(np.ascontiguousarray(out), bool(conv.value), int(iters.value), float(fmae.value),
+                            float(fk.value), _run_info(stats, opt))
+
+    def post_metrics(self, positions, want_est: bool = True):
+        """topolow_layout_prep_post_metrics: (est_distances or None, sum_abs, count) of the handle's resident matrix,
+        as post_metrics() gives them for the reordered matrix in the handle's layout."""
+        pos = _f64F(positions)
+        n, dim = pos.shape
+        if n != self.n:
+            raise ValueError("positions must have one row per point")
+        est = np.empty((n, n), dtype=np.float64) if want_est else None
+        s, c = C.c_double(0.0), C.c_int64(0)
+        rc = self.lib.topolow_layout_prep_post_metrics(self._h, _dp(pos), dim, _dp(est) if est is not None else None,
+                                                       C.byref(s), C.byref(c), self._err, len(self._err))
+        _check(rc, self._err)
+        return est, float(s.value), int(c.value)
+
+    def phase_seconds(self) -> list:
+        ph = (C.c_double * 5)()
+        self.lib.topolow_layout_prep_phase_seconds(self._h, ph)
+        return list(ph)
+
+    def resident_seconds(self) -> list:
+        """Seconds of the last Session.load_prepared, .optimize and .post_metrics on this handle."""
+        ph = (C.c_double * 3)()
+        self.lib.topolow_layout_prep_resident_seconds(self._h, ph)
+        return list(ph)
+
+    def close(self):
+        if self._h:
+            self.lib.topolow_layout_prep_destroy(self._h)
+            self._h = C.c_void_p(None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def prepare_layout(values, codes=None, preserve_order: bool = False, order=None, want_dense: bool = True,
                    want_reordered: bool = True, layout: Optional[str] = None) -> PreparedLayout:
     """The reference's pre-processing (R/core.R:269-436) on the GPU: see include/topolow_relax.h, "Prepared layout".
@@ -909,66 +1087,11 @@ def prepare_layout(values, codes=None, preserve_order: bool = False, order=None,
     is both); no n x n copy is made of a matrix that is contiguous and of the right dtype.  The n x n outputs come
     back in the layout of the input; values_reordered / codes_reordered stay None where the input order is kept (the
     input is then the reordered matrix).  `order`: the caller's order (an int array, or -1 / None-like [-1] for "keep"),
-    for data on which the device declines to order."""
-    lib = load()
-    vals = np.asarray(values)
-    if vals.ndim != 2 or vals.shape[0] != vals.shape[1]:
-        raise ValueError("values must be an n x n matrix")
-    n = vals.shape[0]
-    if layout is None:
-        layout = "F" if (vals.flags.f_contiguous and not vals.flags.c_contiguous) else "C"
-    need = [layout, "A"]
-    vals = np.require(vals, dtype=np.float64, requirements=need)
-    cds = None
-    if codes is not None:
-        cds = np.require(np.asarray(codes), dtype=np.int8, requirements=need)
-        if cds.shape != (n, n):
-            raise ValueError("codes must have the shape of values")
-    oin = None
-    if order is not None:
-        oin = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
-        if oin.shape[0] != n and not (oin.shape[0] >= 1 and oin[0] == -1):
-            raise ValueError("order must have n entries")
-    i8p = C.POINTER(C.c_int8)
-    info = TopolowLayoutPrepInfo()
-    handle = C.c_void_p()
-    err = C.create_string_buffer(512)
-    rc = lib.topolow_layout_prep_create(C.byref(handle), _dp(vals), cds.ctypes.data_as(i8p) if cds is not None else None,
-                                        n, 1 if layout == "C" else 0, 1 if preserve_order else 0,
-                                        _ip(oin) if oin is not None else None, int(options.get("device", -1)),
-                                        C.byref(info), err, len(err))
-    _check(rc, err)
-    out = None
-    try:
-        out = PreparedLayout(info={k: getattr(info, k) for k, _ in TopolowLayoutPrepInfo._fields_ if k != "reserved"})
-        if info.n_edges < 0:    # declined
-            return out
-        E = int(info.n_edges)
-        o = np.empty(n, dtype=np.int32)
-        out.degrees = np.empty(n, dtype=np.int32)
-        out.edge_i, out.edge_j = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
-        out.edge_dist, out.edge_thresh = np.empty(E, dtype=np.float64), np.empty(E, dtype=np.int32)
-        if want_dense:
-            out.dense = np.empty((n, n), dtype=np.float64, order=layout)
-            out.tdense = np.empty((n, n), dtype=np.int32, order=layout)
-        want_reordered = bool(want_reordered) and bool(info.reordered)
-        if want_reordered:
-            out.values_reordered = np.empty((n, n), dtype=np.float64, order=layout)
-            out.codes_reordered = np.empty((n, n), dtype=np.int8, order=layout)
-        rc = lib.topolow_layout_prep_fetch(
-            handle, _ip(o), _ip(out.degrees), _ip(out.edge_i), _ip(out.edge_j), _dp(out.edge_dist), _ip(out.edge_thresh),
-            _dp(out.dense) if want_dense else None, _ip(out.tdense) if want_dense else None,
-            _dp(out.values_reordered) if want_reordered else None,
-            out.codes_reordered.ctypes.data_as(i8p) if want_reordered else None, err, len(err))
-        _check(rc, err)
-        out.order = None if o[0] == -1 else o
+    for data on which the device declines to order.  (PreparedHandle, created, fetched and destroyed.)"""
+    with PreparedHandle(values, codes, preserve_order, order, layout) as h:
+        out = h.fetch(want_dense, want_reordered)
+        out.phase_seconds = h.phase_seconds()
         return out
-    finally:
-        if out is not None:
-            ph = (C.c_double * 5)()
-            lib.topolow_layout_prep_phase_seconds(handle, ph)
-            out.phase_seconds = list(ph)
-        lib.topolow_layout_prep_destroy(handle)
 
 
 # ---- host-side helpers (no GPU needed) ---------------------------------------------------
@@ -1076,6 +1199,12 @@ class Session:
         _check(self.lib.topolow_session_load_coo(self._h, _ip(ei), _ip(ej), _dp(ed), _ip(et),
                                                  int(ei.shape[0]), _ip(deg), self._err,
                                                  len(self._err)), self._err)
+
+    def load_prepared(self, handle: "PreparedHandle"):
+        """topolow_session_load_prepared: targets, degrees and the convergence edge list from a PreparedHandle, device
+        to device -- what load_dense + set_edges do with the arrays handle.fetch() returns."""
+        _check(self.lib.topolow_session_load_prepared(self._h, handle._h if handle is not None else None, self._err,
+                                                      len(self._err)), self._err)
 
     @property
     def encoded_ptr(self) -> int:

@@ -643,6 +643,169 @@ def _embed_with(native_fn, pdist_fn, dissimilarity_matrix, ndim, mapping_max_ite
                    output_dir, verbose, pdist_fn, post_fn)
 
 
+# Smallest matrix for which euclidean_embedding() runs resident -- prepare, relax and score from one upload
+# (_native.PreparedHandle) -- wherever it prepares on the device at all; None: only with TOPOLOW_RESIDENT=1.
+# TOPOLOW_RESIDENT=0 / =1 in the environment forces the choice, read per call.  The resident route returns the bits of
+# the present one (tests/test_gpu_resident_embedding.py), so the gate is a matter of time alone; it has not been
+# measured on the MI355X yet (tests/study/resident_embedding_timing.py is the measurement), hence None.
+_RESIDENT_MIN_N: Optional[int] = None
+
+
+def _resident_wanted(dissimilarity_matrix) -> bool:
+    if not _device_prep_wanted(dissimilarity_matrix):
+        return False
+    forced = os.environ.get("TOPOLOW_RESIDENT")
+    if forced == "0":
+        return False
+    if forced == "1":
+        return True
+    if _RESIDENT_MIN_N is None:
+        return False
+    v = dissimilarity_matrix.values if isinstance(dissimilarity_matrix, (CodedMatrix, RMatrix)) else dissimilarity_matrix
+    shape = getattr(v, "shape", None)
+    return shape is not None and len(shape) == 2 and shape[0] >= _RESIDENT_MIN_N
+
+
+@dataclass
+class _ResidentCall:
+    """What _finish reads of a LayoutCall, for a call whose arrays never left the device."""
+    names: Optional[List[str]] = None
+
+
+def _embed_resident(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
+                    convergence_counter, initial_positions, write_positions_to_csv, output_dir, verbose,
+                    convergence_check_freq, preserve_order, rng=None) -> Optional[Topolow]:
+    """euclidean_embedding() from one upload: the matrix goes to a _native.PreparedHandle, the relaxation and the
+    post-processing read it there; est_distances, the positions and n-sized vectors come back.  The same Topolow as
+    prepare_layout_call_device + optimize_layout_exact + device_post give, the same warnings, errors and verbose
+    lines, the same draws from `rng` and from the seed stream.
+
+    Returns None -- nothing has been uploaded, drawn or printed by then -- where the present route is to run instead:
+    a character matrix, a call that `_validate` rejects (the host form raises the reference's message), a run sharded
+    over devices, and a handle that answers ERR_UNSUPPORTED / ERR_NO_DEVICE.  If .optimize itself answers one of the
+    two, the present route runs with the start positions and the seed already chosen: nothing is drawn twice."""
+    from . import _native
+    for nm, val in (("k0", k0), ("cooling_rate", cooling_rate), ("c_repulsion", c_repulsion)):
+        if val is _MISSING:
+            raise TypeError(f'argument "{nm}" is missing, with no default')
+    if _native.options.get("devices") is not None:
+        return None
+    m, codes = None, None
+    if isinstance(dissimilarity_matrix, CodedMatrix):
+        m = dissimilarity_matrix
+        codes = m.codes if m.codes.any() else None
+    else:
+        r = _as_rmatrix(dissimilarity_matrix)
+        if r is not None and not _is_character(r.values):
+            vals = np.asarray(r.values, dtype=np.float64)
+            m = CodedMatrix(vals, np.zeros(vals.shape, dtype=np.int8), r.names, False)
+    ok = m is not None and m.values.ndim == 2 and m.values.shape[0] == m.values.shape[1] and m.values.shape[0] >= 2
+    if ok:   # the checks that do not need the matrix, before anything is uploaded
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
+                          convergence_counter, convergence_check_freq, initial_positions, n_finite_nonzero=1)
+        except Exception:
+            ok = False
+    if not ok:
+        return None
+    n = m.values.shape[0]
+    try:
+        handle = _native.PreparedHandle(m.values, codes, bool(preserve_order))
+        if handle.info["order_route"] == _native.ORDER_DECLINED:
+            handle.close()
+            host_order = spectral_order(m.values)
+            handle = _native.PreparedHandle(m.values, codes, False, order=host_order if host_order is not None else [-1])
+    except _native.NativeError as e:
+        if e.code not in (_native.ERR_UNSUPPORTED, _native.ERR_NO_DEVICE):
+            raise
+        return None
+    with handle:
+        info = handle.info
+        _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
+                  convergence_counter, convergence_check_freq, initial_positions,
+                  n_finite_nonzero=int(info["n_finite_nonzero"]))
+        names = m.names
+        ndim_i = int(ndim)
+
+        # -- reordering (R/core.R:269-322)
+        if not preserve_order:
+            order = handle.order
+            if order is not None:
+                names = [m.names[q] for q in order] if m.names is not None else None
+                if verbose:
+                    print("Matrix reordered for spectral pattern (largest values in corners)")
+            elif verbose:
+                print("Insufficient data for meaningful spectral ordering")
+        elif verbose:
+            print("Preserving original row/column order (preserve_order = TRUE)")
+
+        # -- initial positions follow the matrix only through row names (R/core.R:325-333)
+        init = None
+        if initial_positions is not None:
+            ip = _as_rmatrix(initial_positions)
+            init = np.asarray(ip.values, dtype=np.float64)
+            if ip.names is not None and names is not None and list(ip.names) != list(names):
+                lookup = {nm: q for q, nm in enumerate(ip.names)}
+                try:
+                    init = init[[lookup[nm] for nm in names], :]
+                except KeyError:
+                    raise IndexError("subscript out of bounds") from None
+        if int(info["n_edges"]) == 0:
+            _stop("No valid off-diagonal measurements found in dissimilarity matrix")
+
+        # -- initial positions (R/core.R:407-415): the maximum is the same before and after the reordering
+        if init is None:
+            init_step = np.float64(info["numeric_max"]) / n
+            gen = rng if rng is not None else np.random.default_rng()
+            steps = gen.uniform(0.0, 2.0 * init_step, size=(ndim_i, n - 1)).T
+            init = np.vstack([np.zeros((1, ndim_i)), np.cumsum(steps, axis=0)])
+        init = np.ascontiguousarray(init, dtype=np.float64)
+
+        if verbose:
+            print("Starting C++ optimization...")
+        import time
+        t0 = time.time()
+        seed = _native.options.get("seed")
+        if seed is None:   # make_options' own draw, made here so that a fallback below runs on the same seed
+            seed = int(_native.host_rng().integers(0, 2 ** 63 - 1))
+        try:
+            res = handle.optimize(init, ndim_i, int(mapping_max_iter), float(k0), float(cooling_rate), float(c_repulsion),
+                                  float(relative_epsilon), int(convergence_counter), int(convergence_check_freq),
+                                  bool(verbose), seed=seed)
+        except _native.NativeError as e:
+            if e.code not in (_native.ERR_UNSUPPORTED, _native.ERR_NO_DEVICE):
+                raise
+            res = None
+        if res is not None:
+            if verbose:
+                print("Optimization finished in %.2f seconds." % (time.time() - t0))
+
+            def post(_call, positions):
+                est, sum_abs, count = handle.post_metrics(positions)
+                return est, _native.mae_of(sum_abs, count)
+
+            return _finish(_ResidentCall(names), res, ndim, k0, cooling_rate, c_repulsion, write_positions_to_csv,
+                           output_dir, verbose, None, post)
+
+    # .optimize declined after the start positions and the seed were chosen: the present route with both, and with
+    # what has been said already -- warnings, the reordering line, the starting line -- not said again
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        call = _prepare_layout_call_auto(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion,
+                                         relative_epsilon, convergence_counter, init, False, convergence_check_freq,
+                                         preserve_order, rng)
+    res = _native.optimize_layout_exact_arrays(
+        call.initial_positions, call.dissimilarity_matrix, call.threshold_matrix, call.degrees, call.edge_i,
+        call.edge_j, call.edge_dist, call.edge_thresh, call.n_iter, call.k0, call.cooling_rate, call.c_repulsion,
+        call.relative_epsilon, call.convergence_window, call.convergence_check_freq, bool(verbose), seed=seed)
+    if verbose:
+        print("Optimization finished in %.2f seconds." % (time.time() - t0))
+    return _finish(call, res, ndim, k0, cooling_rate, c_repulsion, write_positions_to_csv, output_dir, verbose,
+                   _native.est_distances, device_post)
+
+
 def euclidean_embedding(dissimilarity_matrix, ndim, mapping_max_iter=1000, k0=_MISSING,
                         cooling_rate=_MISSING, c_repulsion=_MISSING, relative_epsilon=1e-4,
                         convergence_counter=5, initial_positions=None,
@@ -651,6 +814,12 @@ def euclidean_embedding(dissimilarity_matrix, ndim, mapping_max_iter=1000, k0=_M
     """Drop-in for the reference's `euclidean_embedding()` (R/core.R:184-197); the native
     relaxation runs on the MI355X through libtopolow_relax.so (no CPU fallback)."""
     from . import _native
+    if _resident_wanted(dissimilarity_matrix):
+        out = _embed_resident(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion,
+                              relative_epsilon, convergence_counter, initial_positions, write_positions_to_csv,
+                              output_dir, verbose, convergence_check_freq, preserve_order, _native.host_rng())
+        if out is not None:
+            return out
     return _embed_with(_native.optimize_layout_exact, _native.est_distances,
                        dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
                        c_repulsion, relative_epsilon, convergence_counter, initial_positions,

@@ -64,4 +64,63 @@ __global__ __launch_bounds__(kPostThreads) void post_metrics_kernel(
   }
 }
 
+// The same pass over a matrix that is resident on the device (topolow_layout_prep_post_metrics): one workgroup per
+// LINE of the handle's buffer -- line a holds B[a * n + b], b contiguous; a row of the matrix for a row-major handle,
+// a column for a column-major one -- of the matrix gathered through ord (nullable: the input order was kept):
+// cell (a, b) is B[ord[a] * n + ord[b]].  The source line ord[a] is contiguous and the lanes gather within it, as
+// prep_dense_kernel does; ord itself and the est tile are read and written with consecutive lanes on consecutive
+// addresses.
+//   vals / codes   n x n f64 / int8 (codes nullable: all zero)
+//   est            lines x n f64 out or nullptr: est[(a - line0) * n + b] = ||p_a - p_b||; the matrix is symmetric bit
+//                  for bit, so the caller's layout does not show
+//   line_sum / line_cnt   n entries each; this launch writes [line0, line0 + lines)
+// The distance, the counting rule and the order of the reduction are post_metrics_kernel's, line for column: the
+// partial of line a has the bits that kernel gives for column a of the matrix whose column a is this line.
+__global__ __launch_bounds__(kPostThreads) void post_metrics_resident_kernel(
+    const double* __restrict__ pos, int n, int dim, int line0, int lines, const double* __restrict__ vals,
+    const int8_t* __restrict__ codes, const int32_t* __restrict__ ord, double* __restrict__ est,
+    double* __restrict__ line_sum, uint32_t* __restrict__ line_cnt) {
+  __shared__ double wave_sum[kPostThreads / 64];
+  __shared__ uint32_t wave_cnt[kPostThreads / 64];
+  const int c = blockIdx.x;
+  if (c >= lines) return;
+  const int j = line0 + c;
+  const size_t base = (size_t)c * (size_t)n;
+  const size_t src = (size_t)(ord != nullptr ? ord[j] : j) * (size_t)n;
+  const double* pj = pos + (size_t)j * dim;
+  double sum = 0.0;
+  uint32_t cnt = 0;
+  for (int i = threadIdx.x; i < n; i += kPostThreads) {
+    const double* pi = pos + (size_t)i * dim;
+    double s = 0.0;
+    for (int d = 0; d < dim; ++d) {
+      const double dev = pj[d] - pi[d];
+      s += dev * dev;
+    }
+    const double r = ::sqrt(s);
+    if (est != nullptr) est[base + i] = r;
+    const size_t cell = src + (size_t)(ord != nullptr ? ord[i] : i);
+    const double v = vals[cell];
+    const bool counts = __builtin_isfinite(v) && (codes == nullptr || codes[cell] == 0);
+    if (counts) {
+      sum += ::fabs(v - r);
+      ++cnt;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_down(sum, off, 64);
+    cnt += __shfl_down(cnt, off, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { wave_sum[wave] = sum; wave_cnt[wave] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = wave_sum[0];
+    uint32_t k = wave_cnt[0];
+    for (int w = 1; w < kPostThreads / 64; ++w) { t += wave_sum[w]; k += wave_cnt[w]; }
+    line_sum[j] = t;
+    line_cnt[j] = k;
+  }
+}
+
 }  // namespace topolow

@@ -18,6 +18,7 @@
 #include <array>
 #include <atomic>
 #include <deque>
+#include <functional>
 #include <future>
 #include <mutex>
 #include <string>
@@ -1356,6 +1357,62 @@ int nonfinite_report(int first_nonfinite, int ran, bool stopped) {
 }
 
 // ---- a cross-validation fold on a resident session (relax_cv.h) ---------------------------
+// ---- the convergence edge list of a session: what topolow_session_set_edges (a host list) and
+// topolow_session_load_prepared (a device list) share ----
+
+// The sizes every check kernel reads and the partial buffers, for a list of n_edges; the flags start at "gather the list".
+void edges_begin(topolow_session* s, int64_t n_edges) {
+  s->n_edges = n_edges;
+  s->cv.list_compacted = false;
+  if (s->precision == TOPOLOW_PRECISION_F64) s->sym.invalidate();   // its delta tiles are made from this list: rebuilt on first use
+  s->n_parts = edge_error_blocks(n_edges);
+  // dense MAE pass: one workgroup per (column chunk, 64-row tile)
+  s->dense_grid_x = (((s->n + 3) & ~3) + ErrCfg::CHUNK - 1) / ErrCfg::CHUNK;
+  s->dense_grid_y = (s->rows() + kErrTileRows - 1) / kErrTileRows;
+  s->dense_blocks = s->dense_grid_x * s->dense_grid_y;
+  const int stage_blocks = (s->rows() + CfgProd::ROWS - 1) / CfgProd::ROWS;   // fused checks: one partial per workgroup
+  s->part_sum.alloc(std::max({s->n_parts, s->dense_blocks, stage_blocks}));
+  s->part_cnt.alloc(std::max({s->n_parts, s->dense_blocks, stage_blocks}));
+  s->dense_mae = false;
+  s->dense_parity = !(s->row_begin == 0 && s->row_end == s->n);
+  s->list_is_block = false;
+}
+
+// TOPOLOW_EDGE_MAE=1: always the edge-list pass
+bool edge_mae_forced() {
+  const char* force = getenv("TOPOLOW_EDGE_MAE");
+  return force && atoi(force) != 0;
+}
+
+// h[0]: the order-independent fingerprint, h[1]: the number of the measured cells the dense MAE pass would reduce.
+void block_fingerprint(topolow_session* s, unsigned long long h[2]) {
+  DevBuf<unsigned long long> d_fp;
+  d_fp.alloc(2);
+  // on the session's stream: it is non-blocking, a null-stream memset is not ordered with it
+  HIP_TRY(hipMemsetAsync(d_fp.p, 0, 16, s->stream));
+  hipLaunchKernelGGL(upper_fingerprint_kernel, dim3(s->rows()), dim3(kThreads), 0, s->stream,
+                     s->enc.p, s->n, s->row_begin, s->row_end, s->ld, s->dense_parity ? 1 : 0,
+                     d_fp.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpy(h, d_fp.p, 16, hipMemcpyDeviceToHost));
+}
+
+// The list is (or is not) exactly the block's measured cells.
+// (f64 sessions keep the exact edge-list pass: the block holds 4-byte targets; their symmetric sweep fuses the
+//  check through the delta tiles instead, relax_symm64.h)
+void edges_decide(topolow_session* s, bool list_is_block) {
+  s->list_is_block = list_is_block;
+  s->dense_mae = list_is_block && s->dim <= kMaxTunedDim && s->precision == TOPOLOW_PRECISION_F32;
+}
+
+// dense MAE: the gather fallback is not needed, the session keeps 1-element placeholders.  true: that was done.
+bool edges_placeholders(topolow_session* s) {
+  if (!s->dense_mae) return false;
+  s->ei.alloc(1); s->ej.alloc(1); s->ec.alloc(1); s->et.alloc(8);
+  return true;
+}
+
 template <typename T>
 void swap_buf(DevBuf<T>& a, DevBuf<T>& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); }
 
@@ -1713,28 +1770,14 @@ int topolow_session_set_edges(topolow_session* s, const int32_t* edge_i, const i
   if (!s || n_edges < 0) return TOPOLOW_ERR_BAD_ARGUMENT;
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
-    s->n_edges = n_edges;
-    s->cv.list_compacted = false;
-    if (s->precision == TOPOLOW_PRECISION_F64) s->sym.invalidate();   // its delta tiles are made from this list: rebuilt on first use
+    edges_begin(s, n_edges);
     const size_t m = (size_t)n_edges;
-    s->n_parts = edge_error_blocks(n_edges);
-    // dense MAE pass: one workgroup per (column chunk, 64-row tile)
-    s->dense_grid_x = (((s->n + 3) & ~3) + ErrCfg::CHUNK - 1) / ErrCfg::CHUNK;
-    s->dense_grid_y = (s->rows() + kErrTileRows - 1) / kErrTileRows;
-    s->dense_blocks = s->dense_grid_x * s->dense_grid_y;
-    const int stage_blocks = (s->rows() + CfgProd::ROWS - 1) / CfgProd::ROWS;   // fused checks: one partial per workgroup
-    s->part_sum.alloc(std::max({s->n_parts, s->dense_blocks, stage_blocks}));
-    s->part_cnt.alloc(std::max({s->n_parts, s->dense_blocks, stage_blocks}));
     // Can the MAE be reduced from the encoded block instead of gathering the edge list?  Only if
     // the list is exactly the set of measured cells the dense pass would visit -- checked with an
     // order-independent fingerprint BEFORE anything is uploaded: when it holds (it does for
     // everything the R driver builds), the list itself never travels to the device.
-    s->dense_mae = false;
-    s->dense_parity = !(s->row_begin == 0 && s->row_end == s->n);
     const int* inv = s->inv.empty() ? nullptr : s->inv.data();
-    const char* force = getenv("TOPOLOW_EDGE_MAE");
-    s->list_is_block = false;
-    if (s->gplus.p && !(force && atoi(force) != 0)) {
+    if (s->gplus.p && !edge_mae_forced()) {
       std::atomic<bool> owned{true};
       std::atomic<unsigned long long> fp_total{0};
       host_parallel(m, kEdgeGrain, [&](size_t lo_e, size_t hi_e) {
@@ -1754,27 +1797,12 @@ int topolow_session_set_edges(topolow_session* s, const int32_t* edge_i, const i
         fp_total.fetch_add(fp);
       });
       if (owned.load()) {
-        DevBuf<unsigned long long> d_fp;
-        d_fp.alloc(2);
-        // on the session's stream: it is non-blocking, a null-stream memset is not ordered with it
-        HIP_TRY(hipMemsetAsync(d_fp.p, 0, 16, s->stream));
-        hipLaunchKernelGGL(upper_fingerprint_kernel, dim3(s->rows()), dim3(kThreads), 0, s->stream,
-                           s->enc.p, s->n, s->row_begin, s->row_end, s->ld, s->dense_parity ? 1 : 0,
-                           d_fp.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s->stream));
         unsigned long long h[2];
-        HIP_TRY(hipMemcpy(h, d_fp.p, 16, hipMemcpyDeviceToHost));
-        s->list_is_block = (h[0] == fp_total.load()) && (h[1] == (unsigned long long)m);
-        // (f64 sessions keep the exact edge-list pass: the block holds 4-byte targets; their symmetric sweep fuses the
-        //  check through the delta tiles instead, relax_symm64.h)
-        s->dense_mae = s->list_is_block && s->dim <= kMaxTunedDim && s->precision == TOPOLOW_PRECISION_F32;
+        block_fingerprint(s, h);
+        edges_decide(s, (h[0] == fp_total.load()) && (h[1] == (unsigned long long)m));
       }
     }
-    if (s->dense_mae) {   // the gather fallback is not needed: keep 1-element placeholders
-      s->ei.alloc(1); s->ej.alloc(1); s->ec.alloc(1); s->et.alloc(8);
-      return;
-    }
+    if (edges_placeholders(s)) return;
     // edge-list MAE (parity sessions keep the exact f64 targets): upload the list in session labels
     s->ei.alloc(m); s->ej.alloc(m); s->ec.alloc(m);
     std::vector<int8_t> codes(m);
@@ -2983,17 +3011,21 @@ void post_host_copy(void* dst, const void* src, size_t bytes) {
   });
 }
 
-}  // namespace
+// The matrix of a post-metrics pass when it is resident on the device already (topolow_layout_prep_post_metrics): the
+// handle's buffers; a tile is then a run of the buffer's lines and nothing is uploaded.
+struct PostResident {
+  const double* vals;
+  const int8_t* codes;   // nullable
+  const int32_t* ord;    // nullable: the input order is kept
+};
 
-int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, const double* values,
-                            const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
-                            int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen) {
-  if (!positions || !values || !sum_abs || !count || n < 1 || ndim < 1 || staging < TOPOLOW_POST_STAGING_DEFAULT ||
-      staging > TOPOLOW_POST_STAGING_PAGEABLE)
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  if (staging == TOPOLOW_POST_STAGING_DEFAULT) staging = kPostDefaultStaging;
+// The pipeline of topolow_post_metrics_ex, and of topolow_layout_prep_post_metrics when `resident` is given (values
+// and codes are then NULL and the device is the current one).  The arguments are checked by the callers.
+int post_metrics_run(const double* positions, int32_t n, int32_t ndim, const double* values, const int32_t* codes,
+                     const PostResident* resident, double* est_distances, double* sum_abs, int64_t* count,
+                     int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen) {
   return guarded(errbuf, errlen, [&] {
-    select_device(device);
+    if (!resident) select_device(device);
     const bool pinned = staging == TOPOLOW_POST_STAGING_PINNED, want_est = est_distances != nullptr;
     int tile = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, kPostTileBytes / ((size_t)n * 8)));
     if (const char* e = getenv("TOPOLOW_POST_TILE_COLS")) {
@@ -3017,16 +3049,16 @@ int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, co
     dsum.alloc((size_t)n);
     dcnt.alloc((size_t)n);
     for (int b = 0; b < slots; ++b) {
-      dvals[b].alloc(tile_cells);
+      if (!resident) dvals[b].alloc(tile_cells);
       if (codes) dcodes[b].alloc(tile_cells);
       if (want_est) dest[b].alloc(tile_cells);
       if (pinned) {
-        pvals[b].alloc(tile_cells * 8);
+        if (!resident) pvals[b].alloc(tile_cells * 8);
         if (codes) pcodes[b].alloc(tile_cells * 4);
         if (want_est) pest[b].alloc(tile_cells * 8);
       }
     }
-    if (staging == TOPOLOW_POST_STAGING_REGISTER) {
+    if (staging == TOPOLOW_POST_STAGING_REGISTER && !resident) {
       const size_t cells = (size_t)n * n;
       reg_values.pin(values, cells * 8);
       if (codes) reg_codes.pin(codes, cells * 4);
@@ -3044,32 +3076,44 @@ int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, co
       const int b = t % slots, c0 = t * tile, cols = std::min(tile, n - c0);
       const size_t off = (size_t)c0 * n, cells = (size_t)cols * n;
       const bool reused = t >= slots;   // tile t - slots went through this slot
-      const double* src_v = values + off;
-      const int32_t* src_c = codes ? codes + off : nullptr;
-      if (pinned) {
-        if (reused) HIP_TRY(hipEventSynchronize(P.up_done[b]));   // its upload has left the staging buffers
-        post_host_copy(pvals[b].p, src_v, cells * 8);
-        src_v = static_cast<const double*>(pvals[b].p);
-        if (codes) {
-          post_host_copy(pcodes[b].p, src_c, cells * 4);
-          src_c = static_cast<const int32_t*>(pcodes[b].p);
+      if (resident) {   // nothing to upload: the kernel reads the handle's buffers
+        if (want_est && reused) HIP_TRY(hipStreamWaitEvent(P.run, P.down_done[b], 0));   // its est tile has left the device
+        P.mark(t, 0, P.run);
+        P.mark(t, 1, P.run);
+        P.mark(t, 2, P.run);
+        hipLaunchKernelGGL(post_metrics_resident_kernel, dim3(cols), dim3(kPostThreads), 0, P.run, dp.p, n, ndim, c0, cols,
+                           resident->vals, resident->codes, resident->ord, want_est ? dest[b].p : nullptr, dsum.p, dcnt.p);
+        HIP_TRY(hipGetLastError());
+        P.mark(t, 3, P.run);
+        HIP_TRY(hipEventRecord(P.run_done[b], P.run));
+      } else {
+        const double* src_v = values + off;
+        const int32_t* src_c = codes ? codes + off : nullptr;
+        if (pinned) {
+          if (reused) HIP_TRY(hipEventSynchronize(P.up_done[b]));   // its upload has left the staging buffers
+          post_host_copy(pvals[b].p, src_v, cells * 8);
+          src_v = static_cast<const double*>(pvals[b].p);
+          if (codes) {
+            post_host_copy(pcodes[b].p, src_c, cells * 4);
+            src_c = static_cast<const int32_t*>(pcodes[b].p);
+          }
         }
-      }
-      if (reused) HIP_TRY(hipStreamWaitEvent(P.up, P.run_done[b], 0));   // its kernel has read the device tile
-      P.mark(t, 0, P.up);
-      HIP_TRY(hipMemcpyAsync(dvals[b].p, src_v, cells * 8, hipMemcpyHostToDevice, P.up));
-      if (codes) HIP_TRY(hipMemcpyAsync(dcodes[b].p, src_c, cells * 4, hipMemcpyHostToDevice, P.up));
-      P.mark(t, 1, P.up);
-      HIP_TRY(hipEventRecord(P.up_done[b], P.up));
+        if (reused) HIP_TRY(hipStreamWaitEvent(P.up, P.run_done[b], 0));   // its kernel has read the device tile
+        P.mark(t, 0, P.up);
+        HIP_TRY(hipMemcpyAsync(dvals[b].p, src_v, cells * 8, hipMemcpyHostToDevice, P.up));
+        if (codes) HIP_TRY(hipMemcpyAsync(dcodes[b].p, src_c, cells * 4, hipMemcpyHostToDevice, P.up));
+        P.mark(t, 1, P.up);
+        HIP_TRY(hipEventRecord(P.up_done[b], P.up));
 
-      HIP_TRY(hipStreamWaitEvent(P.run, P.up_done[b], 0));
-      if (want_est && reused) HIP_TRY(hipStreamWaitEvent(P.run, P.down_done[b], 0));   // its est tile has left the device
-      P.mark(t, 2, P.run);
-      hipLaunchKernelGGL(post_metrics_kernel, dim3(cols), dim3(kPostThreads), 0, P.run, dp.p, n, ndim, c0, cols,
-                         dvals[b].p, codes ? dcodes[b].p : nullptr, want_est ? dest[b].p : nullptr, dsum.p, dcnt.p);
-      HIP_TRY(hipGetLastError());
-      P.mark(t, 3, P.run);
-      HIP_TRY(hipEventRecord(P.run_done[b], P.run));
+        HIP_TRY(hipStreamWaitEvent(P.run, P.up_done[b], 0));
+        if (want_est && reused) HIP_TRY(hipStreamWaitEvent(P.run, P.down_done[b], 0));   // its est tile has left the device
+        P.mark(t, 2, P.run);
+        hipLaunchKernelGGL(post_metrics_kernel, dim3(cols), dim3(kPostThreads), 0, P.run, dp.p, n, ndim, c0, cols,
+                           dvals[b].p, codes ? dcodes[b].p : nullptr, want_est ? dest[b].p : nullptr, dsum.p, dcnt.p);
+        HIP_TRY(hipGetLastError());
+        P.mark(t, 3, P.run);
+        HIP_TRY(hipEventRecord(P.run_done[b], P.run));
+      }
 
       if (want_est) {
         HIP_TRY(hipStreamWaitEvent(P.down, P.run_done[b], 0));
@@ -3107,6 +3151,19 @@ int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, co
   });
 }
 
+}  // namespace
+
+int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, const double* values,
+                            const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
+                            int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen) {
+  if (!positions || !values || !sum_abs || !count || n < 1 || ndim < 1 || staging < TOPOLOW_POST_STAGING_DEFAULT ||
+      staging > TOPOLOW_POST_STAGING_PAGEABLE)
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  if (staging == TOPOLOW_POST_STAGING_DEFAULT) staging = kPostDefaultStaging;
+  return post_metrics_run(positions, n, ndim, values, codes, nullptr, est_distances, sum_abs, count, device, staging,
+                          phase_seconds, errbuf, errlen);
+}
+
 int topolow_post_metrics(const double* positions, int32_t n, int32_t ndim, const double* values,
                          const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
                          int32_t device, char* errbuf, size_t errlen) {
@@ -3129,6 +3186,12 @@ struct topolow_layout_prep {
   std::vector<int32_t> order, degrees;   // order[0] == -1: the input order is kept
   int64_t n_edges = 0;
   double phase_seconds[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  // What the resident entries add (topolow_session_load_prepared, topolow_layout_prep_optimize, _post_metrics):
+  DevBuf<int32_t> ddeg;                  // `degrees` on the device: a session gathers its degree terms from it
+  bool compacted = false;                // the edge list below is written (prep_compact_edges: at most once per handle)
+  DevBuf<int32_t> edge_i, edge_j, edge_thresh;
+  DevBuf<double> edge_dist;
+  double resident_seconds[3] = {0.0, 0.0, 0.0};   // last load_prepared, last optimize (whole call), last post_metrics
 };
 
 namespace {
@@ -3154,6 +3217,23 @@ void prep_download(hipStream_t stream, hipEvent_t* done, PinBuf* pin, size_t slo
     if (t >= 1) drain(t - 1);
   }
   drain(n_chunks - 1);
+}
+
+// The stable compaction of the dense fill into the handle's edge list (relax_prep.h: prep_edge_write_kernel), on
+// `stream`; the caller orders its reads after it.  fetch() and topolow_session_load_prepared share it: it runs at most
+// once per handle, the list stays until destroy().
+void prep_compact_edges(topolow_layout_prep* p, hipStream_t stream) {
+  if (p->compacted) return;
+  const size_t E = (size_t)p->n_edges;
+  prep_alloc(p->edge_i, E, "the edge list");
+  prep_alloc(p->edge_j, E, "the edge list");
+  prep_alloc(p->edge_thresh, E, "the edge list");
+  prep_alloc(p->edge_dist, E, "the edge list");
+  hipLaunchKernelGGL(prep_edge_write_kernel, dim3(p->n), dim3(kPrepThreads), 0, stream, p->dense.p, p->tdense.p, p->n,
+                     p->edge_off.p, p->edge_i.p, p->edge_j.p, p->edge_dist.p, p->edge_thresh.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(stream));   // the list is complete before the flag says so
+  p->compacted = true;
 }
 
 bool prep_is_permutation(const int32_t* order, int n) {
@@ -3328,6 +3408,8 @@ int topolow_layout_prep_create(topolow_layout_prep** out, const double* values, 
     prep_alloc(p->dense, cells, "the dense distances");
     prep_alloc(p->tdense, cells, "the dense thresholds");
     prep_alloc(p->edge_off, N + 1, "the edge offsets");
+    prep_alloc(p->ddeg, N, "the degrees");
+    HIP_TRY(hipMemcpyAsync(p->ddeg.p, p->degrees.data(), N * 4, hipMemcpyHostToDevice, P.run));
     DevBuf<int32_t> col_edges;
     prep_alloc(col_edges, N, "the edge counts");
     HIP_TRY(hipMemcpyAsync(p->ord.p, ord.data(), N * 4, hipMemcpyHostToDevice, P.run));
@@ -3380,15 +3462,7 @@ int topolow_layout_prep_fetch(topolow_layout_prep* p, int32_t* order, int32_t* d
     for (int b = 0; b < kPrepSlots; ++b) pin[b].alloc(slot_bytes);
     P.create(kPrepSlots, 0);
 
-    DevBuf<int32_t> dei, dej, det;
-    DevBuf<double> ded;
-    prep_alloc(dei, E, "the edge list");
-    prep_alloc(dej, E, "the edge list");
-    prep_alloc(det, E, "the edge list");
-    prep_alloc(ded, E, "the edge list");
-    hipLaunchKernelGGL(prep_edge_write_kernel, dim3(n), dim3(kPrepThreads), 0, P.down, p->dense.p, p->tdense.p, n,
-                       p->edge_off.p, dei.p, dej.p, ded.p, det.p);
-    HIP_TRY(hipGetLastError());
+    prep_compact_edges(p, P.down);
     DevBuf<double> rvals;
     DevBuf<int8_t> rcodes;
     if (values_reordered || want_codes) {
@@ -3401,10 +3475,10 @@ int topolow_layout_prep_fetch(topolow_layout_prep* p, int32_t* order, int32_t* d
     }
     HIP_TRY(hipStreamSynchronize(P.down));   // the compaction and the gather end here, the downloads begin
     const double t1 = now_s();
-    prep_download(P.down, P.down_done, pin, slot_bytes, edge_i, dei.p, E * 4);
-    prep_download(P.down, P.down_done, pin, slot_bytes, edge_j, dej.p, E * 4);
-    prep_download(P.down, P.down_done, pin, slot_bytes, edge_dist, ded.p, E * 8);
-    prep_download(P.down, P.down_done, pin, slot_bytes, edge_thresh, det.p, E * 4);
+    prep_download(P.down, P.down_done, pin, slot_bytes, edge_i, p->edge_i.p, E * 4);
+    prep_download(P.down, P.down_done, pin, slot_bytes, edge_j, p->edge_j.p, E * 4);
+    prep_download(P.down, P.down_done, pin, slot_bytes, edge_dist, p->edge_dist.p, E * 8);
+    prep_download(P.down, P.down_done, pin, slot_bytes, edge_thresh, p->edge_thresh.p, E * 4);
     if (dense) prep_download(P.down, P.down_done, pin, slot_bytes, dense, p->dense.p, cells * 8);
     if (tdense) prep_download(P.down, P.down_done, pin, slot_bytes, tdense, p->tdense.p, cells * 4);
     if (values_reordered) prep_download(P.down, P.down_done, pin, slot_bytes, values_reordered, rvals.p, cells * 8);
@@ -3711,50 +3785,16 @@ int topolow_optimize_layout_exact_sharded(
   return rc;
 }
 
-// ---- the .Call payload -------------------------------------------------------------------
-int topolow_optimize_layout_exact(
-    const double* initial_positions, int32_t n, int32_t ndim,
-    const double* dissimilarity_matrix, const int32_t* threshold_matrix,
-    const int32_t* degrees, const int32_t* edge_i, const int32_t* edge_j,
-    const double* edge_dist, const int32_t* edge_thresh, int64_t n_edges, int32_t n_iter,
-    double k0, double cooling_rate, double c_repulsion, double relative_epsilon,
-    int32_t convergence_window, int32_t convergence_check_freq, int32_t verbose,
-    const topolow_options* opt_in, double* positions_out, int32_t* converged,
-    int32_t* iterations, double* final_mae, double* final_k, topolow_run_stats* stats,
-    char* errbuf, size_t errlen) {
-  if (n < 2) {  // reference :131
-    set_err(errbuf, errlen, "Need at least 2 points for embedding");
-    return TOPOLOW_ERR_TOO_FEW_POINTS;
-  }
-  if (!initial_positions || !dissimilarity_matrix || !threshold_matrix || !degrees ||
-      !positions_out || !converged || !iterations || !final_mae || !final_k ||
-      (n_edges > 0 && (!edge_i || !edge_j || !edge_dist || !edge_thresh)) || n_edges < 0) {
-    set_err(errbuf, errlen, "null argument");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
-  topolow_options opt;
-  if (opt_in) opt = *opt_in; else topolow_default_options(&opt);
-  const double t_start = now_s();
-  if (opt.n_devices > 1 || opt.devices != nullptr) {   // ONE embedding over several GPUs / row blocks
-    topolow_shard_stats sh;
-    const int rcs = topolow_optimize_layout_exact_sharded(
-        initial_positions, n, ndim, dissimilarity_matrix, threshold_matrix, degrees, edge_i, edge_j, edge_dist,
-        edge_thresh, n_edges, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon, convergence_window,
-        convergence_check_freq, verbose, &opt, positions_out, converged, iterations, final_mae, final_k,
-        stats ? &sh : nullptr, errbuf, errlen);
-    if (rcs == TOPOLOW_OK && stats) {
-      std::memset(stats, 0, sizeof *stats);
-      stats->schedule_used = TOPOLOW_SCHEDULE_SLAB;
-      stats->precision_used = opt.precision == TOPOLOW_PRECISION_F64 ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32;
-      stats->iterations_run = sh.iterations_run;
-      stats->n_checks = sh.n_checks;
-      stats->device_seconds = sh.loop_seconds;
-      stats->total_seconds = sh.total_seconds;
-      stats->stage_launches = sh.stage_launches;
-    }
-    return rcs;
-  }
+namespace {
 
+// Which device path an embedding of n points in ndim dimensions takes under `opt`: the decision of
+// topolow_optimize_layout_exact, shared with topolow_layout_prep_optimize.
+struct LayoutRoute {
+  int schedule = TOPOLOW_SCHEDULE_SLAB;   // AUTO resolved
+  bool tile_gs = false;                   // schedule gs beyond one workgroup: the session runs tile Gauss-Seidel
+};
+
+int layout_route(int n, int ndim, const topolow_options& opt, LayoutRoute* r, char* errbuf, size_t errlen) {
   int schedule = opt.schedule;
   const int gs_max_n = opt.gs_max_n > 0 ? opt.gs_max_n : kDefaultGsMaxN;
   if (schedule == TOPOLOW_SCHEDULE_AUTO)
@@ -3767,61 +3807,23 @@ int topolow_optimize_layout_exact(
   // exact GS: one workgroup while the problem fits its LDS, the tile schedule beyond that
   const bool gs_fits_lds =
       gs_lds_bytes(n, kernel_dim(ndim), (opt.precision == TOPOLOW_PRECISION_F32) ? 4 : 8) <= 150 * 1024 && n <= 2048;
-  const bool tile_gs = schedule == TOPOLOW_SCHEDULE_GS && !gs_fits_lds;
-  if (schedule == TOPOLOW_SCHEDULE_GS && !tile_gs) {
-    const int precision = opt.precision == TOPOLOW_PRECISION_AUTO ? TOPOLOW_PRECISION_F64 : opt.precision;
-    topolow_problem pb;
-    std::memset(&pb, 0, sizeof pb);
-    pb.initial_positions = initial_positions; pb.n = n; pb.ndim = ndim;
-    pb.dissimilarity_matrix = dissimilarity_matrix; pb.threshold_matrix = threshold_matrix; pb.degrees = degrees;
-    pb.edge_i = edge_i; pb.edge_j = edge_j; pb.edge_dist = edge_dist; pb.edge_thresh = edge_thresh;
-    pb.n_edges = n_edges; pb.n_iter = n_iter; pb.k0 = k0; pb.cooling_rate = cooling_rate;
-    pb.c_repulsion = c_repulsion; pb.relative_epsilon = relative_epsilon; pb.convergence_window = convergence_window;
-    pb.convergence_check_freq = convergence_check_freq; pb.seed = opt.seed;
-    topolow_result res;
-    std::memset(&res, 0, sizeof res);
-    res.positions_out = positions_out;
-    double dev_s = 0.0;
-    std::vector<double> trace;
-    if (verbose) emit_header(opt, "one-workgroup Gauss-Seidel", n, k0, cooling_rate, c_repulsion);
-    const int rc = guarded(errbuf, errlen, [&] {
-      select_device(opt.device);
-      std::vector<double>* trace_out = verbose ? &trace : nullptr;
-      if (precision == TOPOLOW_PRECISION_F32)
-        gs_relax<float>(&pb, &res, 1, &dev_s, opt.interrupt_cb, opt.interrupt_user, trace_out);
-      else
-        gs_relax<double>(&pb, &res, 1, &dev_s, opt.interrupt_cb, opt.interrupt_user, trace_out);
-    });
-    if (rc != TOPOLOW_OK) return rc;
-    if (res.error_code == TOPOLOW_ERR_NONFINITE)
-      set_err(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.", res.error_iteration);
-    if (res.error_code == TOPOLOW_ERR_INTERRUPTED) set_err(errbuf, errlen, "interrupted by the caller");
-    if (res.error_code != TOPOLOW_OK) return res.error_code;
-    *converged = res.converged; *iterations = res.iterations; *final_mae = res.final_mae;
-    *final_k = res.final_k;
-    if (stats) {
-      std::memset(stats, 0, sizeof *stats);
-      stats->schedule_used = TOPOLOW_SCHEDULE_GS;
-      stats->precision_used = precision;
-      stats->iterations_run = res.iterations_run;
-      stats->n_checks = res.n_checks;
-      stats->device_seconds = dev_s;
-      stats->total_seconds = now_s() - t_start;
-    }
-    if (verbose) {
-      const int nc = (int)(trace.size() / 3);
-      emit_checks(opt, trace.data(), 0, nc, n_iter);
-      if (res.converged) {
-        // the rule that stopped the run: the last `window` checks all lie inside the plateau band
-        // (plateau) or above it (worsening); the last check decides
-        const bool plateau = nc > 0 && trace[3 * (nc - 1) + 1] <= res.final_mae * (1.0 + relative_epsilon);
-        emit_converged(opt, plateau, res.iterations, res.final_mae);
-      }
-    }
-    return TOPOLOW_OK;
-  }
+  r->schedule = schedule;
+  r->tile_gs = schedule == TOPOLOW_SCHEDULE_GS && !gs_fits_lds;
+  return TOPOLOW_OK;
+}
 
-  // ---- slab schedule, or exact tile Gauss-Seidel (same session, different iteration body) ----
+// Targets, degrees and the convergence edge list into a fresh whole-problem session (relabelled already).
+using SessionLoader = std::function<int(topolow_session*, char*, size_t)>;
+
+// One embedding on a session, from session_create to session_finish: the slab schedule or tile Gauss-Seidel.  The
+// body of topolow_optimize_layout_exact (its loader: the 16 arguments) and of topolow_layout_prep_optimize (its
+// loader: the handle).  t_start: when the caller's entry began (stats->total_seconds, ->setup_seconds).
+int run_session_layout(int32_t n, int32_t ndim, bool tile_gs, const topolow_options& opt, const SessionLoader& load,
+                       const double* initial_positions, int32_t n_iter, double k0, double cooling_rate,
+                       double c_repulsion, double relative_epsilon, int32_t convergence_window,
+                       int32_t convergence_check_freq, int32_t verbose, double* positions_out, int32_t* converged,
+                       int32_t* iterations, double* final_mae, double* final_k, topolow_run_stats* stats,
+                       double t_start, char* errbuf, size_t errlen) {
   const int precision = opt.precision == TOPOLOW_PRECISION_AUTO
                             ? (tile_gs ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32)
                             : opt.precision;
@@ -3840,28 +3842,8 @@ int topolow_optimize_layout_exact(
       rc = topolow_session_set_relabel(s, mix64(opt.seed ^ 0x1abe15eedull) | 1ull, errbuf, errlen);
       if (rc) break;
     }
-    // The 16 arguments carry the matrix twice: dense (800 + 400 MB at config 3) and as the list of its
-    // measured upper-triangle cells (R/core.R:383-402 and :429-436 build both from one matrix).  When
-    // the list is verified to BE the matrix, the encoded block is built from the list -- a quarter of
-    // the bytes over PCIe -- and the dense arrays are only read on the host, once, to verify it.
-    bool from_edges = false;
-    if (precision == TOPOLOW_PRECISION_F32 && getenv("TOPOLOW_DENSE_UPLOAD") == nullptr &&
-        edges_are_the_matrix(dissimilarity_matrix, threshold_matrix, n, edge_i, edge_j, edge_dist, edge_thresh, n_edges,
-                             true)) {
-      rc = topolow_session_load_coo(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, degrees, errbuf, errlen);
-      if (rc) break;
-      rc = topolow_session_set_edges(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, errbuf, errlen);
-      if (rc) break;
-      // the device-side fingerprint (count and hash of the block's measured cells == the list) rules
-      // out what the host pass cannot see cheaply: a pair listed twice
-      from_edges = topolow_session_uses_dense_mae(s) != 0;
-    }
-    if (!from_edges) {
-      rc = topolow_session_load_dense(s, dissimilarity_matrix, threshold_matrix, degrees, errbuf, errlen);
-      if (rc) break;
-      rc = topolow_session_set_edges(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, errbuf, errlen);
-      if (rc) break;
-    }
+    rc = load(s, errbuf, errlen);
+    if (rc) break;
     rc = topolow_session_set_positions(s, initial_positions, errbuf, errlen);
     if (rc) break;
     rc = topolow_session_begin(s, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
@@ -3918,6 +3900,309 @@ int topolow_optimize_layout_exact(
   topolow_session_destroy(s);
   if (rc == TOPOLOW_OK && stats) stats->total_seconds = now_s() - t_start;
   return rc;
+}
+
+}  // namespace
+
+// ---- the .Call payload -------------------------------------------------------------------
+int topolow_optimize_layout_exact(
+    const double* initial_positions, int32_t n, int32_t ndim,
+    const double* dissimilarity_matrix, const int32_t* threshold_matrix,
+    const int32_t* degrees, const int32_t* edge_i, const int32_t* edge_j,
+    const double* edge_dist, const int32_t* edge_thresh, int64_t n_edges, int32_t n_iter,
+    double k0, double cooling_rate, double c_repulsion, double relative_epsilon,
+    int32_t convergence_window, int32_t convergence_check_freq, int32_t verbose,
+    const topolow_options* opt_in, double* positions_out, int32_t* converged,
+    int32_t* iterations, double* final_mae, double* final_k, topolow_run_stats* stats,
+    char* errbuf, size_t errlen) {
+  if (n < 2) {  // reference :131
+    set_err(errbuf, errlen, "Need at least 2 points for embedding");
+    return TOPOLOW_ERR_TOO_FEW_POINTS;
+  }
+  if (!initial_positions || !dissimilarity_matrix || !threshold_matrix || !degrees ||
+      !positions_out || !converged || !iterations || !final_mae || !final_k ||
+      (n_edges > 0 && (!edge_i || !edge_j || !edge_dist || !edge_thresh)) || n_edges < 0) {
+    set_err(errbuf, errlen, "null argument");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  topolow_options opt;
+  if (opt_in) opt = *opt_in; else topolow_default_options(&opt);
+  const double t_start = now_s();
+  if (opt.n_devices > 1 || opt.devices != nullptr) {   // ONE embedding over several GPUs / row blocks
+    topolow_shard_stats sh;
+    const int rcs = topolow_optimize_layout_exact_sharded(
+        initial_positions, n, ndim, dissimilarity_matrix, threshold_matrix, degrees, edge_i, edge_j, edge_dist,
+        edge_thresh, n_edges, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon, convergence_window,
+        convergence_check_freq, verbose, &opt, positions_out, converged, iterations, final_mae, final_k,
+        stats ? &sh : nullptr, errbuf, errlen);
+    if (rcs == TOPOLOW_OK && stats) {
+      std::memset(stats, 0, sizeof *stats);
+      stats->schedule_used = TOPOLOW_SCHEDULE_SLAB;
+      stats->precision_used = opt.precision == TOPOLOW_PRECISION_F64 ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32;
+      stats->iterations_run = sh.iterations_run;
+      stats->n_checks = sh.n_checks;
+      stats->device_seconds = sh.loop_seconds;
+      stats->total_seconds = sh.total_seconds;
+      stats->stage_launches = sh.stage_launches;
+    }
+    return rcs;
+  }
+
+  LayoutRoute route;
+  if (const int rcr = layout_route(n, ndim, opt, &route, errbuf, errlen)) return rcr;
+  const int schedule = route.schedule;
+  const bool tile_gs = route.tile_gs;
+  if (schedule == TOPOLOW_SCHEDULE_GS && !tile_gs) {
+    const int precision = opt.precision == TOPOLOW_PRECISION_AUTO ? TOPOLOW_PRECISION_F64 : opt.precision;
+    topolow_problem pb;
+    std::memset(&pb, 0, sizeof pb);
+    pb.initial_positions = initial_positions; pb.n = n; pb.ndim = ndim;
+    pb.dissimilarity_matrix = dissimilarity_matrix; pb.threshold_matrix = threshold_matrix; pb.degrees = degrees;
+    pb.edge_i = edge_i; pb.edge_j = edge_j; pb.edge_dist = edge_dist; pb.edge_thresh = edge_thresh;
+    pb.n_edges = n_edges; pb.n_iter = n_iter; pb.k0 = k0; pb.cooling_rate = cooling_rate;
+    pb.c_repulsion = c_repulsion; pb.relative_epsilon = relative_epsilon; pb.convergence_window = convergence_window;
+    pb.convergence_check_freq = convergence_check_freq; pb.seed = opt.seed;
+    topolow_result res;
+    std::memset(&res, 0, sizeof res);
+    res.positions_out = positions_out;
+    double dev_s = 0.0;
+    std::vector<double> trace;
+    if (verbose) emit_header(opt, "one-workgroup Gauss-Seidel", n, k0, cooling_rate, c_repulsion);
+    const int rc = guarded(errbuf, errlen, [&] {
+      select_device(opt.device);
+      std::vector<double>* trace_out = verbose ? &trace : nullptr;
+      if (precision == TOPOLOW_PRECISION_F32)
+        gs_relax<float>(&pb, &res, 1, &dev_s, opt.interrupt_cb, opt.interrupt_user, trace_out);
+      else
+        gs_relax<double>(&pb, &res, 1, &dev_s, opt.interrupt_cb, opt.interrupt_user, trace_out);
+    });
+    if (rc != TOPOLOW_OK) return rc;
+    if (res.error_code == TOPOLOW_ERR_NONFINITE)
+      set_err(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.", res.error_iteration);
+    if (res.error_code == TOPOLOW_ERR_INTERRUPTED) set_err(errbuf, errlen, "interrupted by the caller");
+    if (res.error_code != TOPOLOW_OK) return res.error_code;
+    *converged = res.converged; *iterations = res.iterations; *final_mae = res.final_mae;
+    *final_k = res.final_k;
+    if (stats) {
+      std::memset(stats, 0, sizeof *stats);
+      stats->schedule_used = TOPOLOW_SCHEDULE_GS;
+      stats->precision_used = precision;
+      stats->iterations_run = res.iterations_run;
+      stats->n_checks = res.n_checks;
+      stats->device_seconds = dev_s;
+      stats->total_seconds = now_s() - t_start;
+    }
+    if (verbose) {
+      const int nc = (int)(trace.size() / 3);
+      emit_checks(opt, trace.data(), 0, nc, n_iter);
+      if (res.converged) {
+        // the rule that stopped the run: the last `window` checks all lie inside the plateau band
+        // (plateau) or above it (worsening); the last check decides
+        const bool plateau = nc > 0 && trace[3 * (nc - 1) + 1] <= res.final_mae * (1.0 + relative_epsilon);
+        emit_converged(opt, plateau, res.iterations, res.final_mae);
+      }
+    }
+    return TOPOLOW_OK;
+  }
+
+  // ---- slab schedule, or exact tile Gauss-Seidel (same session, different iteration body) ----
+  return run_session_layout(n, ndim, tile_gs, opt, [&](topolow_session* s, char* eb, size_t el) -> int {
+    int rc = TOPOLOW_OK;
+    // The 16 arguments carry the matrix twice: dense (800 + 400 MB at config 3) and as the list of its
+    // measured upper-triangle cells (R/core.R:383-402 and :429-436 build both from one matrix).  When
+    // the list is verified to BE the matrix, the encoded block is built from the list -- a quarter of
+    // the bytes over PCIe -- and the dense arrays are only read on the host, once, to verify it.
+    bool from_edges = false;
+    if (s->precision == TOPOLOW_PRECISION_F32 && getenv("TOPOLOW_DENSE_UPLOAD") == nullptr &&
+        edges_are_the_matrix(dissimilarity_matrix, threshold_matrix, n, edge_i, edge_j, edge_dist, edge_thresh, n_edges,
+                             true)) {
+      rc = topolow_session_load_coo(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, degrees, eb, el);
+      if (rc) return rc;
+      rc = topolow_session_set_edges(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, eb, el);
+      if (rc) return rc;
+      // the device-side fingerprint (count and hash of the block's measured cells == the list) rules
+      // out what the host pass cannot see cheaply: a pair listed twice
+      from_edges = topolow_session_uses_dense_mae(s) != 0;
+    }
+    if (!from_edges) {
+      rc = topolow_session_load_dense(s, dissimilarity_matrix, threshold_matrix, degrees, eb, el);
+      if (rc) return rc;
+      rc = topolow_session_set_edges(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, eb, el);
+      if (rc) return rc;
+    }
+    return rc;
+  }, initial_positions, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon, convergence_window,
+  convergence_check_freq, verbose, positions_out, converged, iterations, final_mae, final_k, stats, t_start, errbuf, errlen);
+}
+
+// ---- the resident embedding: a session, the whole relaxation and the post-metrics from a prepared handle ----
+// The matrix went up once (topolow_layout_prep_create); these entries read what the handle keeps on the device.
+int topolow_session_load_prepared(topolow_session* s, topolow_layout_prep* p, char* errbuf, size_t errlen) {
+  if (!s || !p) {
+    set_err(errbuf, errlen, "null argument");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (p->declined) {
+    set_err(errbuf, errlen, "the ordering was declined (order_route 3): create the handle again with order_in");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (p->n != s->n) {
+    set_err(errbuf, errlen, "the handle holds %d points, the session %d", p->n, s->n);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (s->row_begin != 0 || s->row_end != s->n) {
+    set_err(errbuf, errlen, "whole-problem sessions only (rows [%d,%d) of %d): a row block loads from the caller's arrays",
+            s->row_begin, s->row_end, s->n);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (p->device != s->device) {
+    set_err(errbuf, errlen, "the handle lives on device %d, the session on device %d", p->device, s->device);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(s->device));
+    const double t0 = now_s();
+    const int n = s->n;
+    // -- the encoded block (and an f64_exact session's deltas) from the resident dense fill, through the session's
+    //    relabelling.  The fill is symmetric bit for bit, so the kernel's column-major reading of the upper triangle
+    //    holds for either layout of the handle; enc_index covers a -DTOPOLOW_ENC_TILED=1 build.
+    dim3 grid(s->rows(), (s->ld + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(encode_dense_kernel, grid, dim3(kThreads), 0, s->stream, p->dense.p, p->tdense.p, n,
+                       s->row_begin, s->row_end, s->ld, s->enc.p, s->perm.empty() ? nullptr : s->d_perm.p,
+                       s->exact ? s->denc.p : (float*)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    compute_row_flags(s);
+    // -- the degree terms: upload_degrees' arithmetic, gathered on the device
+    if (s->gplus.p == nullptr || s->gplus.n != (size_t)n) s->gplus.alloc(n);
+    hipLaunchKernelGGL(prep_degree_terms_kernel, dim3((n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0,
+                       s->stream, p->ddeg.p, n, s->perm.empty() ? nullptr : s->d_perm.p, s->gplus.p);
+    HIP_TRY(hipGetLastError());
+    // -- the convergence edge list
+    const int64_t E = p->n_edges;
+    edges_begin(s, E);
+    // Is the list the block's measured cells (topolow_session_set_edges' question)?  Both come from ONE dense fill:
+    // the list holds exactly the cells i < j of the fill that are not +Inf (prep_edge_count_kernel, which counted E,
+    // and prep_edge_write_kernel apply the same test to the same cells), each pair once, both ends in range, and the
+    // block holds encode_target of the same cells under the same relabelling.  So every measured cell of the block's
+    // upper triangle is an edge with the same word, and the two sets differ only where an edge's target encodes to
+    // the unmeasured word (NaN never reaches the fill; a -Inf cell would) -- then the block has fewer measured cells
+    // than the list has edges, which is what set_edges refuses a list for as well.  Hence: list_is_block iff the
+    // block's count equals E.  The count comes from the device (upper_fingerprint_kernel); no host pass reads an edge.
+    if (!edge_mae_forced()) {
+      unsigned long long h[2];
+      block_fingerprint(s, h);
+      edges_decide(s, h[1] == (unsigned long long)E);
+    }
+    if (!edges_placeholders(s)) {
+      // the list is gathered by the check: in session labels, from the handle's compacted list, device to device
+      prep_compact_edges(p, s->stream);
+      const size_t m = (size_t)E;
+      const bool f64 = s->precision == TOPOLOW_PRECISION_F64;
+      s->ei.alloc(m); s->ej.alloc(m); s->ec.alloc(m);
+      s->et.alloc(m * (f64 ? 8 : 4));
+      if (m) {
+        hipLaunchKernelGGL(prep_session_edges_kernel, dim3((unsigned)((m + kPrepThreads - 1) / kPrepThreads)),
+                           dim3(kPrepThreads), 0, s->stream, p->edge_i.p, p->edge_j.p, p->edge_dist.p, p->edge_thresh.p,
+                           (long long)E, s->inv.empty() ? nullptr : s->d_inv.p, s->ei.p, s->ej.p, s->ec.p,
+                           f64 ? reinterpret_cast<double*>(s->et.p) : nullptr,
+                           f64 ? nullptr : reinterpret_cast<float*>(s->et.p));
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    p->resident_seconds[0] = now_s() - t0;
+  });
+}
+
+int topolow_layout_prep_optimize(topolow_layout_prep* p, const double* initial_positions, int32_t ndim,
+                                 int32_t n_iter, double k0, double cooling_rate, double c_repulsion,
+                                 double relative_epsilon, int32_t convergence_window, int32_t convergence_check_freq,
+                                 int32_t verbose, const topolow_options* opt_in, double* positions_out,
+                                 int32_t* converged, int32_t* iterations, double* final_mae, double* final_k,
+                                 topolow_run_stats* stats, char* errbuf, size_t errlen) {
+  if (!p || !initial_positions || !positions_out || !converged || !iterations || !final_mae || !final_k) {
+    set_err(errbuf, errlen, "null argument");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (p->declined) {
+    set_err(errbuf, errlen, "the ordering was declined (order_route 3): create the handle again with order_in");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  topolow_options opt;
+  if (opt_in) opt = *opt_in; else topolow_default_options(&opt);
+  if (opt.n_devices > 1 || opt.devices != nullptr) {
+    set_err(errbuf, errlen, "a prepared handle lives on one device: a run sharded over devices takes the arrays "
+            "(topolow_layout_prep_fetch, then topolow_optimize_layout_exact)");
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
+  if (opt.device >= 0 && opt.device != p->device) {
+    set_err(errbuf, errlen, "the handle lives on device %d, the options ask for device %d", p->device, opt.device);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  opt.device = p->device;
+  const double t_start = now_s();
+  const int n = p->n;
+  LayoutRoute route;
+  if (const int rcr = layout_route(n, ndim, opt, &route, errbuf, errlen)) return rcr;
+  int rc = TOPOLOW_OK;
+  if (route.schedule == TOPOLOW_SCHEDULE_GS && !route.tile_gs) {
+    // one workgroup: the kernel reads the caller-form arrays.  These problems are small (n <= 2048): fetched into
+    // temporaries, and the 16-argument entry does the rest -- the same route, the same run.
+    const size_t N = (size_t)n, E = (size_t)std::max<int64_t>(p->n_edges, 0);
+    const size_t Ea = std::max<size_t>(E, 1);   // fetch() refuses NULL outputs
+    std::vector<int32_t> order(N), degrees(N), ei(Ea), ej(Ea), et(Ea), tdense(N * N);
+    std::vector<double> ed(Ea), dense(N * N);
+    rc = topolow_layout_prep_fetch(p, order.data(), degrees.data(), ei.data(), ej.data(), ed.data(), et.data(),
+                                   dense.data(), tdense.data(), nullptr, nullptr, errbuf, errlen);
+    if (rc == TOPOLOW_OK)
+      rc = topolow_optimize_layout_exact(initial_positions, n, ndim, dense.data(), tdense.data(), degrees.data(),
+                                         ei.data(), ej.data(), ed.data(), et.data(), (int64_t)E, n_iter, k0, cooling_rate,
+                                         c_repulsion, relative_epsilon, convergence_window, convergence_check_freq,
+                                         verbose, &opt, positions_out, converged, iterations, final_mae, final_k, stats,
+                                         errbuf, errlen);
+  } else {
+    rc = run_session_layout(n, ndim, route.tile_gs, opt, [&](topolow_session* s, char* eb, size_t el) -> int {
+      return topolow_session_load_prepared(s, p, eb, el);
+    }, initial_positions, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon, convergence_window,
+    convergence_check_freq, verbose, positions_out, converged, iterations, final_mae, final_k, stats, t_start, errbuf,
+    errlen);
+  }
+  p->resident_seconds[1] = now_s() - t_start;
+  return rc;
+}
+
+int topolow_layout_prep_post_metrics(topolow_layout_prep* p, const double* positions, int32_t ndim,
+                                     double* est_distances, double* sum_abs, int64_t* count, char* errbuf,
+                                     size_t errlen) {
+  if (!p || !positions || !sum_abs || !count || ndim < 1) {
+    set_err(errbuf, errlen, "null argument, or ndim < 1");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (p->declined) {
+    set_err(errbuf, errlen, "the ordering was declined (order_route 3): create the handle again with order_in");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  const double t0 = now_s();
+  (void)hipSetDevice(p->device);
+  const PostResident resident = {p->vals.p, p->has_codes ? p->codes.p : nullptr, p->order[0] != -1 ? p->ord.p : nullptr};
+  const int rc = post_metrics_run(positions, p->n, ndim, nullptr, nullptr, &resident, est_distances, sum_abs, count,
+                                  p->device, kPostDefaultStaging, nullptr, errbuf, errlen);
+  p->resident_seconds[2] = now_s() - t0;
+  return rc;
+}
+
+int topolow_layout_prep_order(const topolow_layout_prep* p, int32_t* order, int32_t* degrees) {
+  if (!p || p->declined || (!order && !degrees)) return TOPOLOW_ERR_BAD_ARGUMENT;
+  if (order) std::copy(p->order.begin(), p->order.end(), order);
+  if (degrees) std::copy(p->degrees.begin(), p->degrees.end(), degrees);
+  return TOPOLOW_OK;
+}
+
+int topolow_layout_prep_resident_seconds(const topolow_layout_prep* p, double* seconds) {
+  if (!p || !seconds) return TOPOLOW_ERR_BAD_ARGUMENT;
+  for (int q = 0; q < 3; ++q) seconds[q] = p->resident_seconds[q];
+  return TOPOLOW_OK;
 }
 
 }  // extern "C"

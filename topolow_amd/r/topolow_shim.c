@@ -15,6 +15,8 @@
  *     _topolow_est_distances                as.matrix(dist(positions))  (R/core.R:474)
  *     _topolow_est_distances_cols           a block of its columns, for n x n results too large to hold
  *     _topolow_post_metrics                 est_distances and mae in one fused pass  (R/core.R:474-481)
+ *     _topolow_euclidean_embedding_resident pre-processing, relaxation and post-processing from ONE upload of the
+ *                                           matrix (R/core.R:269-481)
  *
  * No logic lives here: unmarshal, call the library, marshal, and turn error codes into R errors
  * AFTER every native resource has been released (Rf_error longjmps).
@@ -575,6 +577,135 @@ SEXP _topolow_post_metrics(SEXP positionsSEXP, SEXP valuesSEXP, SEXP codesSEXP, 
   return out;
 }
 
+/* euclidean_embedding() from one upload (R/core.R:269-481): the matrix goes to the device once
+ * (topolow_layout_prep_create), the relaxation and the post-processing read it there (topolow_layout_prep_optimize,
+ * topolow_layout_prep_post_metrics); positions, est_distances and n-sized vectors come back.
+ *   values             numeric n x n, NA = not measured, any threshold prefix stripped
+ *   codes              integer n x n {0, 1 ">", -1 "<"}, or NULL: no thresholds
+ *   order              NULL, or the caller's order: 1-based integer vector of length n (after a declined call)
+ *   initial_positions  numeric n x ndim, row q for the q-th point OF THE ORDERED MATRIX (the reference's random walk,
+ *                      R/core.R:407-415, is laid along the ordered matrix; a caller with named start positions keeps
+ *                      the two-step route)
+ *   ndim ... convergence_check_freq, preserve_order, verbose   as euclidean_embedding's; want_est: logical
+ * Returns list(positions, est_distances (or NULL), sum_abs, count, order (1-based, or NULL: the input order is kept),
+ *              converged, iterations, final_mae, final_k, order_route, numeric_max); mae = sum_abs / count.
+ * Where the device declines to order (order_route = 3, see topolow_layout_order_from_sums) and no order was given,
+ * every field but order_route and numeric_max is NULL: the caller orders (R/core.R:269-319) and calls again with it.
+ * The handle is destroyed before any exit; every R object that outlives it is allocated before it is created. */
+SEXP _topolow_euclidean_embedding_resident(SEXP valuesSEXP, SEXP codesSEXP, SEXP orderSEXP, SEXP initial_positionsSEXP,
+                                           SEXP ndimSEXP, SEXP n_iterSEXP, SEXP k0SEXP, SEXP cooling_rateSEXP,
+                                           SEXP c_repulsionSEXP, SEXP relative_epsilonSEXP,
+                                           SEXP convergence_windowSEXP, SEXP convergence_check_freqSEXP,
+                                           SEXP preserve_orderSEXP, SEXP verboseSEXP, SEXP wantEstSEXP) {
+  if (!Rf_isReal(valuesSEXP) || !Rf_isMatrix(valuesSEXP) || Rf_nrows(valuesSEXP) != Rf_ncols(valuesSEXP))
+    Rf_error("values must be a numeric n x n matrix");
+  const int n = Rf_nrows(valuesSEXP);
+  if (n < 2) Rf_error("dissimilarity_matrix must have at least 2 rows/columns");
+  const int have_codes = codesSEXP != R_NilValue;
+  if (have_codes && (!Rf_isInteger(codesSEXP) || !Rf_isMatrix(codesSEXP) || Rf_nrows(codesSEXP) != n ||
+                     Rf_ncols(codesSEXP) != n))
+    Rf_error("codes must be NULL or an integer n x n matrix");
+  const int have_order = orderSEXP != R_NilValue;
+  if (have_order && (!Rf_isInteger(orderSEXP) || Rf_length(orderSEXP) != n))
+    Rf_error("order must be NULL or an integer vector of length n (1-based)");
+  const int ndim = Rf_asInteger(ndimSEXP);
+  if (!Rf_isReal(initial_positionsSEXP) || !Rf_isMatrix(initial_positionsSEXP) ||
+      Rf_nrows(initial_positionsSEXP) != n || Rf_ncols(initial_positionsSEXP) != ndim)
+    Rf_error("initial_positions must be a numeric n x ndim matrix");
+  const int want_est = Rf_asLogical(wantEstSEXP) != 0;
+  const size_t cells = (size_t)n * (size_t)n;
+
+  int8_t* codes = NULL;
+  if (have_codes) {
+    codes = (int8_t*)R_alloc(cells, sizeof(int8_t));
+    const int* c = INTEGER(codesSEXP);
+    for (size_t q = 0; q < cells; ++q) codes[q] = (int8_t)(c[q] == 1 ? 1 : (c[q] == -1 ? -1 : 0));
+  }
+  int32_t* order_in = NULL;
+  if (have_order) {
+    order_in = (int32_t*)R_alloc((size_t)n, sizeof(int32_t));
+    for (int q = 0; q < n; ++q) order_in[q] = INTEGER(orderSEXP)[q] - 1;   /* the library checks the permutation */
+  }
+  topolow_options opt;
+  int32_t devices[64];
+  fill_options(&opt, devices, 64);
+
+  /* everything R allocates that must outlive the handle, before the handle exists */
+  static const char* const names[] = {"positions", "est_distances", "sum_abs", "count", "order", "converged",
+                                      "iterations", "final_mae", "final_k", "order_route", "numeric_max"};
+  SEXP out = PROTECT(named_list(11, names));
+  SEXP positions = PROTECT(Rf_allocMatrix(REALSXP, n, ndim));
+  SEXP est = PROTECT(want_est ? Rf_allocMatrix(REALSXP, n, n) : R_NilValue);
+  SEXP order_out = PROTECT(Rf_allocVector(INTSXP, n));
+  SEXP scalars = PROTECT(Rf_allocVector(VECSXP, 8));
+  SET_VECTOR_ELT(scalars, 0, Rf_allocVector(REALSXP, 1));   /* sum_abs */
+  SET_VECTOR_ELT(scalars, 1, Rf_allocVector(REALSXP, 1));   /* count */
+  SET_VECTOR_ELT(scalars, 2, Rf_allocVector(LGLSXP, 1));    /* converged */
+  SET_VECTOR_ELT(scalars, 3, Rf_allocVector(INTSXP, 1));    /* iterations */
+  SET_VECTOR_ELT(scalars, 4, Rf_allocVector(REALSXP, 1));   /* final_mae */
+  SET_VECTOR_ELT(scalars, 5, Rf_allocVector(REALSXP, 1));   /* final_k */
+  SET_VECTOR_ELT(scalars, 6, Rf_allocVector(INTSXP, 1));    /* order_route */
+  SET_VECTOR_ELT(scalars, 7, Rf_allocVector(REALSXP, 1));   /* numeric_max */
+
+  char err[512];
+  err[0] = '\0';
+  topolow_layout_prep* h = NULL;
+  topolow_layout_prep_info info;
+  memset(&info, 0, sizeof info);
+  int rc = topolow_layout_prep_create(&h, REAL(valuesSEXP), codes, n, 0 /* column-major */,
+                                      Rf_asLogical(preserve_orderSEXP) != 0, order_in, opt.device, &info, err, sizeof err);
+  int declined = 0, converged = 0, iterations = 0;
+  double final_mae = 0.0, final_k = 0.0, sum_abs = 0.0;
+  int64_t count = 0;
+  if (rc == TOPOLOW_OK) {
+    declined = info.n_edges < 0;
+    if (!declined && info.n_edges == 0) {
+      snprintf(err, sizeof err, "No valid off-diagonal measurements found in dissimilarity matrix");
+      rc = TOPOLOW_ERR_BAD_ARGUMENT;
+    }
+    if (rc == TOPOLOW_OK && !declined)
+      rc = topolow_layout_prep_optimize(h, REAL(initial_positionsSEXP), ndim, Rf_asInteger(n_iterSEXP), Rf_asReal(k0SEXP),
+                                        Rf_asReal(cooling_rateSEXP), Rf_asReal(c_repulsionSEXP),
+                                        Rf_asReal(relative_epsilonSEXP), Rf_asInteger(convergence_windowSEXP),
+                                        Rf_asInteger(convergence_check_freqSEXP), Rf_asLogical(verboseSEXP), &opt,
+                                        REAL(positions), &converged, &iterations, &final_mae, &final_k, NULL, err,
+                                        sizeof err);
+    if (rc == TOPOLOW_OK && !declined)
+      rc = topolow_layout_prep_post_metrics(h, REAL(positions), ndim, want_est ? REAL(est) : NULL, &sum_abs, &count,
+                                            err, sizeof err);
+    if (rc == TOPOLOW_OK && !declined) rc = topolow_layout_prep_order(h, INTEGER(order_out), NULL);
+    topolow_layout_prep_destroy(h);   /* on every path: nothing below this line owns device memory */
+  }
+  if (rc != TOPOLOW_OK) {
+    UNPROTECT(5);
+    if (rc == TOPOLOW_ERR_INTERRUPTED) Rf_onintr();   /* re-raise the user's interrupt */
+    Rf_error("%s", err[0] ? err : "libtopolow_relax failed");
+  }
+  INTEGER(VECTOR_ELT(scalars, 6))[0] = info.order_route;
+  REAL(VECTOR_ELT(scalars, 7))[0] = info.numeric_max;
+  SET_VECTOR_ELT(out, 9, VECTOR_ELT(scalars, 6));
+  SET_VECTOR_ELT(out, 10, VECTOR_ELT(scalars, 7));
+  if (!declined) {
+    REAL(VECTOR_ELT(scalars, 0))[0] = sum_abs;
+    REAL(VECTOR_ELT(scalars, 1))[0] = (double)count;
+    LOGICAL(VECTOR_ELT(scalars, 2))[0] = converged != 0;
+    INTEGER(VECTOR_ELT(scalars, 3))[0] = iterations;
+    REAL(VECTOR_ELT(scalars, 4))[0] = final_mae;
+    REAL(VECTOR_ELT(scalars, 5))[0] = final_k;
+    SET_VECTOR_ELT(out, 0, positions);
+    SET_VECTOR_ELT(out, 1, est);
+    SET_VECTOR_ELT(out, 2, VECTOR_ELT(scalars, 0));
+    SET_VECTOR_ELT(out, 3, VECTOR_ELT(scalars, 1));
+    if (info.reordered) {
+      for (int q = 0; q < n; ++q) INTEGER(order_out)[q] += 1;
+      SET_VECTOR_ELT(out, 4, order_out);
+    }
+    for (int q = 0; q < 4; ++q) SET_VECTOR_ELT(out, 5 + q, VECTOR_ELT(scalars, 2 + q));
+  }
+  UNPROTECT(5);
+  return out;
+}
+
 static const R_CallMethodDef CallEntries[] = {
     {"_topolow_optimize_layout_exact_cpp", (DL_FUNC)&_topolow_optimize_layout_exact_cpp, 16},
     {"_topolow_optimize_layout_exact_batch", (DL_FUNC)&_topolow_optimize_layout_exact_batch, 1},
@@ -584,6 +715,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_topolow_est_distances", (DL_FUNC)&_topolow_est_distances, 1},
     {"_topolow_est_distances_cols", (DL_FUNC)&_topolow_est_distances_cols, 3},
     {"_topolow_post_metrics", (DL_FUNC)&_topolow_post_metrics, 4},
+    {"_topolow_euclidean_embedding_resident", (DL_FUNC)&_topolow_euclidean_embedding_resident, 15},
     {NULL, NULL, 0}};
 
 void R_init_topolow(DllInfo* dll) {
