@@ -118,6 +118,26 @@ def test_numeric_matrix_payload_and_init_walk():
     assert np.all(inc >= 0) and np.all(inc <= 2 * step)            # cumsum of U(0, 2*max/n)
 
 
+def test_start_walk_drawn_or_handed_in_is_the_same_walk():
+    """core._start_walk from `rng`, from the (ndim, n - 1) unit draw taken at the same point of an equally seeded
+    stream, and as prepare_layout_call's start positions: the same bits, and the streams left in the same place."""
+    n, ndim = 7, 3
+    D = _mat(n, seed=4).values * 3.7
+    numeric_max = D.max()
+    assert np.frexp(numeric_max)[0] != 0.5                            # not a power of two
+    a, b, c = (np.random.default_rng(12) for _ in range(3))
+    for g in (a, b, c):
+        g.random(5)                                                   # some way into the stream
+    drawn = core._start_walk(numeric_max, n, ndim, rng=a)
+    handed = core._start_walk(numeric_max, n, ndim, unit_draw=b.random((ndim, n - 1)))
+    assert drawn.shape == (n, ndim) and np.all(drawn[0] == 0) and np.all(np.diff(drawn, axis=0) > 0)
+    assert drawn.tobytes() == handed.tobytes()
+    assert a.bit_generator.state == b.bit_generator.state
+    call = core.prepare_layout_call(D, ndim, 5, 1.0, 0.1, 0.1, 1e-4, 5, None, False, 3, False, c)
+    assert call.initial_positions.tobytes() == drawn.tobytes()
+    assert c.bit_generator.state == a.bit_generator.state
+
+
 def test_post_mae_counts_diagonal_both_triangles_and_drops_threshold_strings():
     """G6: R/core.R:479-481."""
     m = np.array([["0", ">2", "3"], [">2", "0", None], ["3", None, "0"]], dtype=object)

@@ -289,6 +289,63 @@ def test_an_optimize_that_declines_hands_start_and_seed_to_the_present_route(mon
     assert out.mae == 0.75 and out.iter == 3
 
 
+def _fake_prepare_layout(values, codes=None, preserve_order=False, order=None, **kw):
+    """_native.prepare_layout's result over NumPy: the info and the order of a _FakeHandle on the same arguments."""
+    h = _FakeHandle(values, codes, preserve_order, order)
+    n, o = h.n, h.order
+    v = np.ascontiguousarray(values if o is None else values[np.ix_(o, o)])
+    ei, ej = np.triu_indices(n, 1)
+    return _native.PreparedLayout(
+        info=h.info, order=o, degrees=np.full(n, n, dtype=np.int32), edge_i=ei.astype(np.int32),
+        edge_j=ej.astype(np.int32), edge_dist=v[ei, ej], edge_thresh=np.zeros(ei.shape[0], dtype=np.int32), dense=v,
+        tdense=np.zeros((n, n), dtype=np.int32), values_reordered=None if o is None else v)
+
+
+def test_the_two_device_routes_say_draw_and_align_the_same(monkeypatch, capsys):
+    """prepare_layout_call_device over _native.prepare_layout and _embed_resident over _native.PreparedHandle, each
+    replaced by an object that reports the same info and order: the same verbose lines, the same numbers out of
+    identically seeded generators, and a named, permuted initial_positions lined up to the same rows."""
+    monkeypatch.setattr(_native, "prepare_layout", _fake_prepare_layout)
+    monkeypatch.setattr(_native, "PreparedHandle", _FakeHandle)
+    monkeypatch.setitem(_native.options, "seed", 4)     # the resident route draws no seed of its own
+    n = 6
+    names = ["v%d" % q for q in range(n)]
+    D = core.RMatrix(_matrix(n), names)
+    perm = (3, 1, 0, 5, 2, 4)
+    named_init = core.RMatrix(np.arange(2.0 * n).reshape(n, 2), [names[q] for q in perm])
+
+    def both(init, preserve_order):
+        ga, gb = np.random.default_rng(17), np.random.default_rng(17)
+        capsys.readouterr()
+        call = core.prepare_layout_call_device(D, 2, 10, 5.0, 0.01, 0.01, 1e-4, 5, init, True, 3, preserve_order, ga)
+        said_a = capsys.readouterr().out.splitlines()
+        out = core._embed_resident(D, 2, 10, 5.0, 0.01, 0.01, 1e-4, 5, init, False, None, True, 3, preserve_order, gb)
+        said_b = capsys.readouterr().out.splitlines()
+        assert len(said_a) == 1 and said_b[:said_b.index("Starting C++ optimization...")] == said_a
+        assert out.positions.tobytes() == call.initial_positions.tobytes()      # the fake "optimizes" to its start
+        assert out.names == call.names
+        assert ga.bit_generator.state == gb.bit_generator.state
+        return call, said_a[0], ga
+
+    call, said, gen = both(named_init, False)
+    assert said.startswith("Matrix reordered") and call.names == names[::-1]
+    assert np.array_equal(call.initial_positions, named_init.values[[perm.index(names.index(nm)) for nm in call.names]])
+    assert gen.bit_generator.state == np.random.default_rng(17).bit_generator.state       # nothing was drawn
+    call, said, gen = both(None, False)
+    assert said.startswith("Matrix reordered")
+    assert gen.bit_generator.state != np.random.default_rng(17).bit_generator.state       # the walk was
+    assert call.initial_positions.tobytes() == core._start_walk(np.nanmax(D.values), n, 2,
+                                                                np.random.default_rng(17)).tobytes()
+    call, said, _ = both(None, True)
+    assert said.startswith("Preserving original row/column order") and call.names == names
+    with pytest.raises(IndexError, match="subscript out of bounds"):
+        core.prepare_layout_call_device(D, 2, 10, 5.0, 0.01, 0.01, 1e-4, 5, core.RMatrix(named_init.values, list("abcdef")),
+                                        False, 3, False)
+    with pytest.raises(IndexError, match="subscript out of bounds"):
+        core._embed_resident(D, 2, 10, 5.0, 0.01, 0.01, 1e-4, 5, core.RMatrix(named_init.values, list("abcdef")),
+                             False, None, False, 3, False)
+
+
 # ---- the .Call entry on the test double of R's C API ------------------------------------------------------------------
 
 @pytest.fixture(scope="module")

@@ -579,13 +579,10 @@ def cv_fold(cells: CellList, picks, preserve_order: bool, named: bool):
             et[:e].copy(), hi[:h].copy(), hj[:h].copy(), ht[:h].copy(), float(vmax.value))
 
 
-def cv_sweep(cells: CellList, named: bool, preserve_order: bool, ndims, k0s, cooling_rates, c_repulsions, picks, unit_draws,
-             seeds, n_iter: int, relative_epsilon: float, convergence_window: int = 5, convergence_check_freq: int = 3,
-             precision: str = "f64", device: int = -1):
-    """All folds of a CV sweep in one library call (topolow_cv_sweep): fold f holds out the cells picks[f] and starts
-    from the random walk built from unit_draws[f] ((ndim, n - 1) uniform(0, 1) numbers).  Returns
-    (holdout_sum_abs, holdout_count, iterations, converged, error_code) arrays and the device seconds."""
-    lib = load()
+def _cv_sweep_call(symbol, cells: CellList, named, preserve_order, ndims, k0s, cooling_rates, c_repulsions, picks, unit_draws,
+                   seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq, precision, device, *extra):
+    """The marshalling of cv_sweep and cv_sweep_session: `symbol` is the bound library entry, `extra` what it takes
+    between `device` and the outputs."""
     nf = len(picks)
     nd = np.ascontiguousarray(ndims, dtype=np.int32)
     k0 = np.ascontiguousarray(k0s, dtype=np.float64)
@@ -604,14 +601,24 @@ def cv_sweep(cells: CellList, named: bool, preserve_order: bool, ndims, k0s, coo
     secs = C.c_double(0.0)
     err = C.create_string_buffer(512)
     i64 = C.POINTER(C.c_int64)
-    rc = lib.topolow_cv_sweep(C.byref(cells.c), int(bool(named)), int(bool(preserve_order)), nf, _ip(nd), _dp(k0), _dp(cr),
-                              _dp(cp), p_all.ctypes.data_as(i64), p_off.ctypes.data_as(i64), _dp(d_all),
-                              d_off.ctypes.data_as(i64), sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_iter),
-                              float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
-                              _PRECISIONS[precision], int(device), _dp(hsum), hcnt.ctypes.data_as(i64), _ip(its), _ip(conv),
-                              _ip(ec), C.byref(secs), err, len(err))
+    rc = symbol(C.byref(cells.c), int(bool(named)), int(bool(preserve_order)), nf, _ip(nd), _dp(k0), _dp(cr), _dp(cp),
+                p_all.ctypes.data_as(i64), p_off.ctypes.data_as(i64), _dp(d_all), d_off.ctypes.data_as(i64),
+                sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_iter), float(relative_epsilon), int(convergence_window),
+                int(convergence_check_freq), _PRECISIONS[precision], int(device), *extra, _dp(hsum),
+                hcnt.ctypes.data_as(i64), _ip(its), _ip(conv), _ip(ec), C.byref(secs), err, len(err))
     _check(rc, err)
     return hsum, hcnt, its, conv, ec, float(secs.value)
+
+
+def cv_sweep(cells: CellList, named: bool, preserve_order: bool, ndims, k0s, cooling_rates, c_repulsions, picks, unit_draws,
+             seeds, n_iter: int, relative_epsilon: float, convergence_window: int = 5, convergence_check_freq: int = 3,
+             precision: str = "f64", device: int = -1):
+    """All folds of a CV sweep in one library call (topolow_cv_sweep): fold f holds out the cells picks[f] and starts
+    from the random walk built from unit_draws[f] ((ndim, n - 1) uniform(0, 1) numbers).  Returns
+    (holdout_sum_abs, holdout_count, iterations, converged, error_code) arrays and the device seconds."""
+    return _cv_sweep_call(load().topolow_cv_sweep, cells, named, preserve_order, ndims, k0s, cooling_rates, c_repulsions,
+                          picks, unit_draws, seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq,
+                          precision, device)
 
 
 def cv_fold_pairs(cells: CellList, picks, preserve_order: bool, named: bool):
@@ -646,33 +653,9 @@ def cv_sweep_session(cells: CellList, named: bool, preserve_order: bool, ndims, 
     """`cv_sweep` on device-resident sessions (topolow_cv_sweep_session): one session per ndim holds the full matrix, a
     fold is held out of it, run, scored and put back.  schedule "auto" / "slab": the slab schedule, "gs": tile
     Gauss-Seidel; precision "auto": f32 for slab, f64 for gs.  Same returns as cv_sweep."""
-    lib = load()
-    nf = len(picks)
-    nd = np.ascontiguousarray(ndims, dtype=np.int32)
-    k0 = np.ascontiguousarray(k0s, dtype=np.float64)
-    cr = np.ascontiguousarray(cooling_rates, dtype=np.float64)
-    cp = np.ascontiguousarray(c_repulsions, dtype=np.float64)
-    p_off = np.zeros(nf + 1, dtype=np.int64)
-    d_off = np.zeros(nf + 1, dtype=np.int64)
-    if nf:
-        np.cumsum([len(p) for p in picks], out=p_off[1:])
-        np.cumsum([u.size for u in unit_draws], out=d_off[1:])
-    p_all = np.ascontiguousarray(np.concatenate(picks) if nf else np.zeros(0), dtype=np.int64)
-    d_all = np.ascontiguousarray(np.concatenate([np.ravel(u) for u in unit_draws]) if nf else np.zeros(0), dtype=np.float64)
-    sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
-    hsum, hcnt = np.zeros(nf, np.float64), np.zeros(nf, np.int64)
-    its, conv, ec = np.zeros(nf, np.int32), np.zeros(nf, np.int32), np.zeros(nf, np.int32)
-    secs = C.c_double(0.0)
-    err = C.create_string_buffer(512)
-    i64 = C.POINTER(C.c_int64)
-    rc = lib.topolow_cv_sweep_session(C.byref(cells.c), int(bool(named)), int(bool(preserve_order)), nf, _ip(nd), _dp(k0),
-                                      _dp(cr), _dp(cp), p_all.ctypes.data_as(i64), p_off.ctypes.data_as(i64), _dp(d_all),
-                                      d_off.ctypes.data_as(i64), sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_iter),
-                                      float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
-                                      _PRECISIONS[precision], int(device), _SCHEDULES[schedule], _dp(hsum),
-                                      hcnt.ctypes.data_as(i64), _ip(its), _ip(conv), _ip(ec), C.byref(secs), err, len(err))
-    _check(rc, err)
-    return hsum, hcnt, its, conv, ec, float(secs.value)
+    return _cv_sweep_call(load().topolow_cv_sweep_session, cells, named, preserve_order, ndims, k0s, cooling_rates,
+                          c_repulsions, picks, unit_draws, seeds, n_iter, relative_epsilon, convergence_window,
+                          convergence_check_freq, precision, device, _SCHEDULES[schedule])
 
 
 def symm_stage_bounds(n: int, stages: int):
@@ -1089,9 +1072,7 @@ def prepare_layout(values, codes=None, preserve_order: bool = False, order=None,
     input is then the reordered matrix).  `order`: the caller's order (an int array, or -1 / None-like [-1] for "keep"),
     for data on which the device declines to order.  (PreparedHandle, created, fetched and destroyed.)"""
     with PreparedHandle(values, codes, preserve_order, order, layout) as h:
-        out = h.fetch(want_dense, want_reordered)
-        out.phase_seconds = h.phase_seconds()
-        return out
+        return h.fetch(want_dense, want_reordered)
 
 
 # ---- host-side helpers (no GPU needed) ---------------------------------------------------

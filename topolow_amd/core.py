@@ -17,6 +17,7 @@ import math
 import os
 import re
 import warnings
+from contextlib import ExitStack
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Sequence
 
@@ -245,6 +246,9 @@ def _stop(msg: str):
     raise ValueError(msg)
 
 
+_NO_EDGES = "No valid off-diagonal measurements found in dissimilarity matrix"
+
+
 def _is_number(x: Any) -> bool:
     return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
 
@@ -319,6 +323,63 @@ def spectral_order(stripped: np.ndarray) -> Optional[np.ndarray]:
     return None
 
 
+def _announce_order(preserve_order, reordered: bool, verbose) -> None:
+    """The verbose line of the reordering step (R/core.R:269-322)."""
+    if not verbose:
+        return
+    if preserve_order:
+        print("Preserving original row/column order (preserve_order = TRUE)")
+    elif reordered:
+        print("Matrix reordered for spectral pattern (largest values in corners)")
+    else:
+        print("Insufficient data for meaningful spectral ordering")
+
+
+def _align_initial_positions(initial_positions, names) -> Optional[np.ndarray]:
+    """The caller's start positions in the order of `names` -- they follow the matrix only through row names
+    (R/core.R:325-333) -- or None where there are none."""
+    if initial_positions is None:
+        return None
+    ip = _as_rmatrix(initial_positions)
+    init = np.asarray(ip.values, dtype=np.float64)
+    if ip.names is not None and names is not None and list(ip.names) != list(names):
+        lookup = {nm: q for q, nm in enumerate(ip.names)}
+        try:
+            init = init[[lookup[nm] for nm in names], :]
+        except KeyError:
+            raise IndexError("subscript out of bounds") from None
+    return init
+
+
+def _start_walk(numeric_max, n: int, ndim: int, rng: Optional[np.random.Generator] = None,
+                unit_draw: Optional[np.ndarray] = None) -> np.ndarray:
+    """Start positions (R/core.R:407-415): a random walk from the origin with steps uniform(0, 2 numeric_max / n).
+    The numbers are drawn here (rng; None: a fresh generator) or handed in (unit_draw: the (ndim, n - 1) array
+    rng.random would have returned at this point of the stream -- uniform(0, 2a) is 2a * random(), bit for bit)."""
+    init_step = np.float64(numeric_max) / n
+    if unit_draw is None:
+        gen = rng if rng is not None else np.random.default_rng()
+        # runif fills the (n-1) x ndim matrix column by column
+        steps = gen.uniform(0.0, 2.0 * init_step, size=(ndim, n - 1)).T
+    else:
+        steps = (0.0 + (2.0 * init_step - 0.0) * unit_draw).T      # Generator.uniform's arithmetic
+    return np.vstack([np.zeros((1, ndim)), np.cumsum(steps, axis=0)])
+
+
+def _layout_call(init, dense, tdense, degrees, edge_i, edge_j, edge_dist, edge_thresh, mapping_max_iter, k0,
+                 cooling_rate, c_repulsion, relative_epsilon, convergence_counter, convergence_check_freq, verbose,
+                 names, order, reordered_matrix) -> LayoutCall:
+    return LayoutCall(
+        initial_positions=np.ascontiguousarray(init, dtype=np.float64),
+        dissimilarity_matrix=dense, threshold_matrix=tdense, degrees=degrees,
+        edge_i=edge_i, edge_j=edge_j, edge_dist=edge_dist, edge_thresh=edge_thresh,
+        n_iter=int(mapping_max_iter), k0=float(k0), cooling_rate=float(cooling_rate),
+        c_repulsion=float(c_repulsion), relative_epsilon=float(relative_epsilon),
+        convergence_window=int(convergence_counter),
+        convergence_check_freq=int(convergence_check_freq), verbose=bool(verbose),
+        names=names, order=order, reordered_matrix=reordered_matrix)
+
+
 def prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
                         c_repulsion, relative_epsilon, convergence_counter, initial_positions,
                         verbose, convergence_check_freq, preserve_order,
@@ -327,7 +388,6 @@ def prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, coolin
     m = coded_matrix(dissimilarity_matrix)
     _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
               convergence_counter, convergence_check_freq, initial_positions)
-    names = m.names
     n = m.values.shape[0]
     ndim = int(ndim)
 
@@ -337,26 +397,10 @@ def prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, coolin
         order = spectral_order(m.values)
         if order is not None:
             m = m.reordered(order)
-            names = m.names
-            if verbose:
-                print("Matrix reordered for spectral pattern (largest values in corners)")
-        elif verbose:
-            print("Insufficient data for meaningful spectral ordering")
-    elif preserve_order and verbose:
-        print("Preserving original row/column order (preserve_order = TRUE)")
-    v = m
-
-    # -- initial positions follow the matrix only through row names (R/core.R:325-333)
-    init = None
-    if initial_positions is not None:
-        ip = _as_rmatrix(initial_positions)
-        init = np.asarray(ip.values, dtype=np.float64)
-        if ip.names is not None and names is not None and list(ip.names) != list(names):
-            lookup = {nm: q for q, nm in enumerate(ip.names)}
-            try:
-                init = init[[lookup[nm] for nm in names], :]
-            except KeyError:
-                raise IndexError("subscript out of bounds") from None
+    if n > 1 or preserve_order:
+        _announce_order(preserve_order, order is not None, verbose)
+    names = m.names
+    init = _align_initial_positions(initial_positions, names)
 
     # -- degrees and parsing (R/core.R:340-374)
     non_na = ~np.isnan(m.values)
@@ -370,22 +414,15 @@ def prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, coolin
         valid = np.triu(np.ones((n, n), dtype=bool), k=1) & (distances != np.inf)
     cols, rows = np.nonzero(valid.T)  # column-major enumeration
     if rows.shape[0] == 0:
-        _stop("No valid off-diagonal measurements found in dissimilarity matrix")
-    edge_i = rows.astype(np.int32)
-    edge_j = cols.astype(np.int32)
+        _stop(_NO_EDGES)
     edge_dist = distances[rows, cols].astype(np.float64)
     edge_thresh = codes[rows, cols].astype(np.int32)
 
-    # -- initial positions (R/core.R:407-415)
     if init is None:
-        numeric = m.as_numeric()
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)
-            init_step = np.nanmax(numeric) / n
-        gen = rng if rng is not None else np.random.default_rng()
-        # runif fills the (n-1) x ndim matrix column by column
-        steps = gen.uniform(0.0, 2.0 * init_step, size=(ndim, n - 1)).T
-        init = np.vstack([np.zeros((1, ndim)), np.cumsum(steps, axis=0)])
+            numeric_max = np.nanmax(m.as_numeric())
+        init = _start_walk(numeric_max, n, ndim, rng)
 
     # -- symmetric dense fill: lower triangle <- transpose of upper (R/core.R:429-436)
     low = np.tril(np.ones((n, n), dtype=bool), k=-1)
@@ -394,15 +431,9 @@ def prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, coolin
     tdense = codes.copy()
     tdense[low] = codes.T[low]
 
-    return LayoutCall(
-        initial_positions=np.ascontiguousarray(init, dtype=np.float64),
-        dissimilarity_matrix=dense, threshold_matrix=tdense, degrees=degrees,
-        edge_i=edge_i, edge_j=edge_j, edge_dist=edge_dist, edge_thresh=edge_thresh,
-        n_iter=int(mapping_max_iter), k0=float(k0), cooling_rate=float(cooling_rate),
-        c_repulsion=float(c_repulsion), relative_epsilon=float(relative_epsilon),
-        convergence_window=int(convergence_counter),
-        convergence_check_freq=int(convergence_check_freq), verbose=bool(verbose),
-        names=names, order=order, reordered_matrix=v)
+    return _layout_call(init, dense, tdense, degrees, rows.astype(np.int32), cols.astype(np.int32), edge_dist,
+                        edge_thresh, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
+                        convergence_counter, convergence_check_freq, verbose, names, order, m)
 
 
 # Smallest matrix for which euclidean_embedding() prepares on the device; None: never by default.  Measured on the
@@ -410,6 +441,60 @@ def prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, coolin
 # n = 1 000 (10.9 ms against 26.8 ms) and from there on (106 ms against 3.59 s at n = 10 000).
 # TOPOLOW_DEVICE_PREP=0 / =1 in the environment forces the choice, read per call.
 _DEVICE_PREP_MIN_N: Optional[int] = 1000
+
+
+def _device_front(open_fn, dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion,
+                  relative_epsilon, convergence_counter, initial_positions, verbose, convergence_check_freq,
+                  preserve_order):
+    """What prepare_layout_call_device and _embed_resident do alike, up to the start positions: the matrix as a
+    CodedMatrix without a copy, the checks that need no upload, the matrix opened on the device, `_validate` with the
+    device's count, the order and its verbose line, the caller's start positions by row names, the stop for a matrix
+    without measurements.
+
+    open_fn(values, codes, preserve_order, order=...) opens the matrix (_native.prepare_layout, or a
+    _native.PreparedHandle); `.info` and `.order` are read of what it returns.  Where the device declines to order
+    (order_route 3) spectral_order runs here and open_fn is called a second time with its order.
+
+    Returns None -- nothing has been uploaded, printed or warned of by then -- where the call is not for the device: a
+    character matrix, or one that `_validate` rejects for its shape or a scalar argument.  Otherwise (m, codes, own,
+    opened, names, order, init, n): own, whether the caller handed a CodedMatrix in; names and order, those of the
+    ordered matrix (order None where the input order is kept); init, the aligned start positions or None."""
+    from . import _native
+    m, codes, own = None, None, False
+    if isinstance(dissimilarity_matrix, CodedMatrix):
+        m = dissimilarity_matrix
+        own = True
+        codes = m.codes if m.codes.any() else None
+    else:
+        r = _as_rmatrix(dissimilarity_matrix)
+        if r is not None and not _is_character(r.values):   # the matrix itself, not a copy: nothing here writes to it
+            vals = np.asarray(r.values, dtype=np.float64)
+            m = CodedMatrix(vals, np.zeros(vals.shape, dtype=np.int8), r.names, False)
+    if m is None or m.values.ndim != 2 or m.values.shape[0] != m.values.shape[1] or m.values.shape[0] < 2:
+        return None
+    try:   # the checks that do not need the matrix, before anything is uploaded
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
+                      convergence_counter, convergence_check_freq, initial_positions, n_finite_nonzero=1)
+    except Exception:
+        return None
+    opened = open_fn(m.values, codes, bool(preserve_order))
+    if opened.info["order_route"] == _native.ORDER_DECLINED:
+        host_order = spectral_order(m.values)
+        opened = open_fn(m.values, codes, False, order=host_order if host_order is not None else [-1])
+    _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
+              convergence_counter, convergence_check_freq, initial_positions,
+              n_finite_nonzero=int(opened.info["n_finite_nonzero"]))
+    names = m.names
+    order = None if preserve_order else opened.order
+    if order is not None and names is not None:
+        names = [names[q] for q in order]
+    _announce_order(preserve_order, order is not None, verbose)
+    init = _align_initial_positions(initial_positions, names)
+    if int(opened.info["n_edges"]) == 0:
+        _stop(_NO_EDGES)
+    return m, codes, own, opened, names, order, init, m.values.shape[0]
 
 
 def prepare_layout_call_device(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
@@ -434,108 +519,53 @@ def prepare_layout_call_device(dissimilarity_matrix, ndim, mapping_max_iter, k0,
     Where the device declines (route 3) the matrix is uploaded a second time with the host's order: twice the
     transfer and the first pass, on data that is rare in practice (tied inexact keys, negative or infinite cells)."""
     from . import _native
-    m, codes, own = None, None, False
-    if isinstance(dissimilarity_matrix, CodedMatrix):
-        m = dissimilarity_matrix
-        own = True
-        codes = m.codes if m.codes.any() else None
-    else:
-        r = _as_rmatrix(dissimilarity_matrix)
-        if r is not None and not _is_character(r.values):   # the matrix itself, not a copy: nothing here writes to it
-            vals = np.asarray(r.values, dtype=np.float64)
-            m = CodedMatrix(vals, np.zeros(vals.shape, dtype=np.int8), r.names, False)
-    ok = m is not None and m.values.ndim == 2 and m.values.shape[0] == m.values.shape[1] and m.values.shape[0] >= 2
-    if ok:   # the checks that do not need the matrix, before anything is uploaded
-        try:
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
-                          convergence_counter, convergence_check_freq, initial_positions, n_finite_nonzero=1)
-        except Exception:
-            ok = False
-    if not ok:
+    front = _device_front(_native.prepare_layout, dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
+                          c_repulsion, relative_epsilon, convergence_counter, initial_positions, verbose,
+                          convergence_check_freq, preserve_order)
+    if front is None:
         return prepare_layout_call(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion,
                                    relative_epsilon, convergence_counter, initial_positions, verbose,
                                    convergence_check_freq, preserve_order, rng)
-    n = m.values.shape[0]
-    prep = _native.prepare_layout(m.values, codes, bool(preserve_order))
-    if prep.info["order_route"] == _native.ORDER_DECLINED:
-        host_order = spectral_order(m.values)
-        prep = _native.prepare_layout(m.values, codes, False, order=host_order if host_order is not None else [-1])
+    m, codes, own, prep, names, order, init, n = front
     if route is not None:
         route[:] = [prep.info["order_route"]]
-    _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
-              convergence_counter, convergence_check_freq, initial_positions,
-              n_finite_nonzero=int(prep.info["n_finite_nonzero"]))
-    names = m.names
-    ndim = int(ndim)
-
-    # -- reordering (R/core.R:269-322)
-    order = None
-    if not preserve_order:
-        if prep.order is not None:
-            order = prep.order.astype(np.intp)
-            rcodes = prep.codes_reordered if codes is not None else np.zeros((n, n), dtype=np.int8)
-            m = CodedMatrix(np.ascontiguousarray(prep.values_reordered), np.ascontiguousarray(rcodes),
-                            [m.names[q] for q in order] if m.names is not None else None, m.character)
-            names = m.names
-            if verbose:
-                print("Matrix reordered for spectral pattern (largest values in corners)")
-        elif verbose:
-            print("Insufficient data for meaningful spectral ordering")
-    elif verbose:
-        print("Preserving original row/column order (preserve_order = TRUE)")
-
-    # -- initial positions follow the matrix only through row names (R/core.R:325-333)
-    init = None
-    if initial_positions is not None:
-        ip = _as_rmatrix(initial_positions)
-        init = np.asarray(ip.values, dtype=np.float64)
-        if ip.names is not None and names is not None and list(ip.names) != list(names):
-            lookup = {nm: q for q, nm in enumerate(ip.names)}
-            try:
-                init = init[[lookup[nm] for nm in names], :]
-            except KeyError:
-                raise IndexError("subscript out of bounds") from None
-
-    if int(prep.info["n_edges"]) == 0:
-        _stop("No valid off-diagonal measurements found in dissimilarity matrix")
-    if order is None and not own:
+    if order is not None:
+        order = order.astype(np.intp)
+        rcodes = prep.codes_reordered if codes is not None else np.zeros((n, n), dtype=np.int8)
+        m = CodedMatrix(np.ascontiguousarray(prep.values_reordered), np.ascontiguousarray(rcodes), names, m.character)
+    elif not own:
         m = CodedMatrix(np.array(m.values, dtype=np.float64), m.codes, m.names, False)
     # dense and tdense are symmetric bit for bit: the transpose of a Fortran-ordered one is the C-ordered one
     dense, tdense = prep.dense, prep.tdense
     if not dense.flags.c_contiguous:
         dense, tdense = dense.T, tdense.T
-
-    # -- initial positions (R/core.R:407-415): the maximum is the same before and after the reordering
-    if init is None:
-        init_step = np.float64(prep.info["numeric_max"]) / n
-        gen = rng if rng is not None else np.random.default_rng()
-        steps = gen.uniform(0.0, 2.0 * init_step, size=(ndim, n - 1)).T
-        init = np.vstack([np.zeros((1, ndim)), np.cumsum(steps, axis=0)])
-
-    return LayoutCall(
-        initial_positions=np.ascontiguousarray(init, dtype=np.float64),
-        dissimilarity_matrix=dense, threshold_matrix=tdense, degrees=prep.degrees,
-        edge_i=prep.edge_i, edge_j=prep.edge_j, edge_dist=prep.edge_dist, edge_thresh=prep.edge_thresh,
-        n_iter=int(mapping_max_iter), k0=float(k0), cooling_rate=float(cooling_rate),
-        c_repulsion=float(c_repulsion), relative_epsilon=float(relative_epsilon),
-        convergence_window=int(convergence_counter),
-        convergence_check_freq=int(convergence_check_freq), verbose=bool(verbose),
-        names=names, order=order, reordered_matrix=m)
+    if init is None:   # the maximum is the same before and after the reordering
+        init = _start_walk(prep.info["numeric_max"], n, int(ndim), rng)
+    return _layout_call(init, dense, tdense, prep.degrees, prep.edge_i, prep.edge_j, prep.edge_dist, prep.edge_thresh,
+                        mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon, convergence_counter,
+                        convergence_check_freq, verbose, names, order, m)
 
 
-def _device_prep_wanted(dissimilarity_matrix) -> bool:
-    forced = os.environ.get("TOPOLOW_DEVICE_PREP")
-    if forced == "0":
-        return False
-    if forced == "1":
-        return True
-    if _DEVICE_PREP_MIN_N is None:
+def _gate(env_name: str, min_n: Optional[int], dissimilarity_matrix) -> bool:
+    """The environment's "0" / "1" where it is set; otherwise: is the matrix of at least min_n points (None: never)?"""
+    forced = os.environ.get(env_name)
+    if forced in ("0", "1"):
+        return forced == "1"
+    if min_n is None:
         return False
     v = dissimilarity_matrix.values if isinstance(dissimilarity_matrix, (CodedMatrix, RMatrix)) else dissimilarity_matrix
     shape = getattr(v, "shape", None)
-    return shape is not None and len(shape) == 2 and shape[0] >= _DEVICE_PREP_MIN_N
+    return shape is not None and len(shape) == 2 and shape[0] >= min_n
+
+
+def _device_prep_wanted(dissimilarity_matrix) -> bool:
+    return _gate("TOPOLOW_DEVICE_PREP", _DEVICE_PREP_MIN_N, dissimilarity_matrix)
+
+
+def _declines(e) -> bool:
+    """Does this _native.NativeError say "not here", so that the host form, or the present route, is to run instead?"""
+    from . import _native
+    return e.code in (_native.ERR_UNSUPPORTED, _native.ERR_NO_DEVICE)
 
 
 def _prepare_layout_call_auto(dissimilarity_matrix, *args, **kw) -> LayoutCall:
@@ -547,7 +577,7 @@ def _prepare_layout_call_auto(dissimilarity_matrix, *args, **kw) -> LayoutCall:
         try:
             return prepare_layout_call_device(dissimilarity_matrix, *args, **kw)
         except _native.NativeError as e:
-            if e.code not in (_native.ERR_UNSUPPORTED, _native.ERR_NO_DEVICE):
+            if not _declines(e):
                 raise
     return prepare_layout_call(dissimilarity_matrix, *args, **kw)
 
@@ -618,6 +648,13 @@ def _finish(call: LayoutCall, native_result, ndim, k0, cooling_rate, c_repulsion
         names=call.names, native_info=dict(getattr(native_result, "info", {}) or {}))
 
 
+def _require(**arguments) -> None:
+    """R's error for an argument without a default that the caller left out."""
+    for nm, val in arguments.items():
+        if val is _MISSING:
+            raise TypeError(f'argument "{nm}" is missing, with no default')
+
+
 def _embed_with(native_fn, pdist_fn, dissimilarity_matrix, ndim, mapping_max_iter, k0,
                 cooling_rate, c_repulsion, relative_epsilon, convergence_counter,
                 initial_positions, write_positions_to_csv, output_dir, verbose,
@@ -625,9 +662,7 @@ def _embed_with(native_fn, pdist_fn, dissimilarity_matrix, ndim, mapping_max_ite
                 prepare_fn=prepare_layout_call) -> Topolow:
     """post_fn(call, positions) -> (est_distances, mae) replaces pdist_fn + post_mae when given; prepare_fn has the
     signature of prepare_layout_call and returns what it returns."""
-    for nm, val in (("k0", k0), ("cooling_rate", cooling_rate), ("c_repulsion", c_repulsion)):
-        if val is _MISSING:
-            raise TypeError(f'argument "{nm}" is missing, with no default')
+    _require(k0=k0, cooling_rate=cooling_rate, c_repulsion=c_repulsion)
     call = prepare_fn(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate,
                       c_repulsion, relative_epsilon, convergence_counter,
                       initial_positions, verbose, convergence_check_freq,
@@ -652,18 +687,7 @@ _RESIDENT_MIN_N: Optional[int] = None
 
 
 def _resident_wanted(dissimilarity_matrix) -> bool:
-    if not _device_prep_wanted(dissimilarity_matrix):
-        return False
-    forced = os.environ.get("TOPOLOW_RESIDENT")
-    if forced == "0":
-        return False
-    if forced == "1":
-        return True
-    if _RESIDENT_MIN_N is None:
-        return False
-    v = dissimilarity_matrix.values if isinstance(dissimilarity_matrix, (CodedMatrix, RMatrix)) else dissimilarity_matrix
-    shape = getattr(v, "shape", None)
-    return shape is not None and len(shape) == 2 and shape[0] >= _RESIDENT_MIN_N
+    return _device_prep_wanted(dissimilarity_matrix) and _gate("TOPOLOW_RESIDENT", _RESIDENT_MIN_N, dissimilarity_matrix)
 
 
 @dataclass
@@ -685,82 +709,28 @@ def _embed_resident(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_ra
     over devices, and a handle that answers ERR_UNSUPPORTED / ERR_NO_DEVICE.  If .optimize itself answers one of the
     two, the present route runs with the start positions and the seed already chosen: nothing is drawn twice."""
     from . import _native
-    for nm, val in (("k0", k0), ("cooling_rate", cooling_rate), ("c_repulsion", c_repulsion)):
-        if val is _MISSING:
-            raise TypeError(f'argument "{nm}" is missing, with no default')
+    _require(k0=k0, cooling_rate=cooling_rate, c_repulsion=c_repulsion)
     if _native.options.get("devices") is not None:
         return None
-    m, codes = None, None
-    if isinstance(dissimilarity_matrix, CodedMatrix):
-        m = dissimilarity_matrix
-        codes = m.codes if m.codes.any() else None
-    else:
-        r = _as_rmatrix(dissimilarity_matrix)
-        if r is not None and not _is_character(r.values):
-            vals = np.asarray(r.values, dtype=np.float64)
-            m = CodedMatrix(vals, np.zeros(vals.shape, dtype=np.int8), r.names, False)
-    ok = m is not None and m.values.ndim == 2 and m.values.shape[0] == m.values.shape[1] and m.values.shape[0] >= 2
-    if ok:   # the checks that do not need the matrix, before anything is uploaded
+    with ExitStack() as stack:
+        def open_handle(*a, **kw):
+            stack.close()   # a handle that declined to order is closed before the second one is created
+            return stack.enter_context(_native.PreparedHandle(*a, **kw))
+
         try:
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
-                          convergence_counter, convergence_check_freq, initial_positions, n_finite_nonzero=1)
-        except Exception:
-            ok = False
-    if not ok:
-        return None
-    n = m.values.shape[0]
-    try:
-        handle = _native.PreparedHandle(m.values, codes, bool(preserve_order))
-        if handle.info["order_route"] == _native.ORDER_DECLINED:
-            handle.close()
-            host_order = spectral_order(m.values)
-            handle = _native.PreparedHandle(m.values, codes, False, order=host_order if host_order is not None else [-1])
-    except _native.NativeError as e:
-        if e.code not in (_native.ERR_UNSUPPORTED, _native.ERR_NO_DEVICE):
-            raise
-        return None
-    with handle:
-        info = handle.info
-        _validate(m, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
-                  convergence_counter, convergence_check_freq, initial_positions,
-                  n_finite_nonzero=int(info["n_finite_nonzero"]))
-        names = m.names
+            front = _device_front(open_handle, dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_rate, c_repulsion,
+                                  relative_epsilon, convergence_counter, initial_positions, verbose,
+                                  convergence_check_freq, preserve_order)
+        except _native.NativeError as e:
+            if not _declines(e):
+                raise
+            return None
+        if front is None:
+            return None
+        _, _, _, handle, names, _, init, n = front
         ndim_i = int(ndim)
-
-        # -- reordering (R/core.R:269-322)
-        if not preserve_order:
-            order = handle.order
-            if order is not None:
-                names = [m.names[q] for q in order] if m.names is not None else None
-                if verbose:
-                    print("Matrix reordered for spectral pattern (largest values in corners)")
-            elif verbose:
-                print("Insufficient data for meaningful spectral ordering")
-        elif verbose:
-            print("Preserving original row/column order (preserve_order = TRUE)")
-
-        # -- initial positions follow the matrix only through row names (R/core.R:325-333)
-        init = None
-        if initial_positions is not None:
-            ip = _as_rmatrix(initial_positions)
-            init = np.asarray(ip.values, dtype=np.float64)
-            if ip.names is not None and names is not None and list(ip.names) != list(names):
-                lookup = {nm: q for q, nm in enumerate(ip.names)}
-                try:
-                    init = init[[lookup[nm] for nm in names], :]
-                except KeyError:
-                    raise IndexError("subscript out of bounds") from None
-        if int(info["n_edges"]) == 0:
-            _stop("No valid off-diagonal measurements found in dissimilarity matrix")
-
-        # -- initial positions (R/core.R:407-415): the maximum is the same before and after the reordering
-        if init is None:
-            init_step = np.float64(info["numeric_max"]) / n
-            gen = rng if rng is not None else np.random.default_rng()
-            steps = gen.uniform(0.0, 2.0 * init_step, size=(ndim_i, n - 1)).T
-            init = np.vstack([np.zeros((1, ndim_i)), np.cumsum(steps, axis=0)])
+        if init is None:   # the maximum is the same before and after the reordering
+            init = _start_walk(handle.info["numeric_max"], n, ndim_i, rng)
         init = np.ascontiguousarray(init, dtype=np.float64)
 
         if verbose:
@@ -775,7 +745,7 @@ def _embed_resident(dissimilarity_matrix, ndim, mapping_max_iter, k0, cooling_ra
                                   float(relative_epsilon), int(convergence_counter), int(convergence_check_freq),
                                   bool(verbose), seed=seed)
         except _native.NativeError as e:
-            if e.code not in (_native.ERR_UNSUPPORTED, _native.ERR_NO_DEVICE):
+            if not _declines(e):
                 raise
             res = None
         if res is not None:

@@ -253,4 +253,29 @@ inline int fold_pairs(const topolow_cell_list* L, const int64_t* picks, int64_t 
   return TOPOLOW_OK;
 }
 
+// What a sweep makes of a built fold (rc of fold_problem / fold_pairs): a fold without valid measurements, or whose
+// unit draws are not the (ndim, n - 1) numbers of its start walk, is left out with TOPOLOW_ERR_BAD_ARGUMENT.
+inline int fold_check(int rc, int64_t n_edges, double numeric_max, int ndim, int64_t n_draws, int n) {
+  if (rc != TOPOLOW_OK) return rc;
+  if (n_edges == 0 || !(numeric_max == numeric_max)) return TOPOLOW_ERR_BAD_ARGUMENT;   // no valid measurements
+  if (ndim < 1 || n_draws != (int64_t)ndim * (n - 1)) return TOPOLOW_ERR_BAD_ARGUMENT;
+  return TOPOLOW_OK;
+}
+
+// Start positions from the caller's unit draws ((ndim, n - 1), row-major) with NumPy's / R's arithmetic: a random walk
+// from the origin whose steps are uniform(0, 2 max / n), R/core.R:407-415.  out: n x ndim, column-major; point i of the
+// walk is row i, or row order[i] where an order is given (point i of a fold's order = the caller's point order[i]).
+inline void start_walk(const double* unit_draws, double vmax, int n, int ndim, const int32_t* order, std::vector<double>& out) {
+  const double step = vmax / (double)n;
+  out.assign((size_t)n * ndim, 0.0);
+  for (int d = 0; d < ndim; ++d) {
+    double acc = 0.0;
+    for (int i = 1; i < n; ++i) {
+      const double st_ = 0.0 + (2.0 * step - 0.0) * unit_draws[(size_t)d * (n - 1) + (i - 1)];   // Generator.uniform's arithmetic
+      acc = i == 1 ? st_ : acc + st_;                             // cumsum
+      out[(size_t)(order ? order[i] : i) + (size_t)d * n] = acc;
+    }
+  }
+}
+
 }  // namespace topolow

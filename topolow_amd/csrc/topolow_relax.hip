@@ -2449,6 +2449,21 @@ int topolow_cv_fold(const topolow_cell_list* cells, const int64_t* picks, int64_
   }
 }
 
+namespace {
+
+// The arguments both sweeps share: the cell list always, the per-fold arrays wherever there is a fold.
+bool cv_sweep_args_ok(const topolow_cell_list* cells, int32_t n_folds, const int32_t* ndim, const double* k0,
+                      const double* cooling_rate, const double* c_repulsion, const int64_t* picks_offset,
+                      const double* unit_draws, const int64_t* draws_offset, const uint64_t* seeds,
+                      const double* holdout_sum_abs, const int64_t* holdout_count, const int32_t* iterations,
+                      const int32_t* converged, const int32_t* error_code) {
+  if (!cells || n_folds < 0) return false;
+  return n_folds == 0 || (ndim && k0 && cooling_rate && c_repulsion && picks_offset && unit_draws && draws_offset && seeds &&
+                          holdout_sum_abs && holdout_count && iterations && converged && error_code);
+}
+
+}  // namespace
+
 // All folds of a cross-validation sweep in ONE call: the folds' problems are built side by side on host threads
 // (fold_problem; start positions from the caller's unit draws with NumPy's / R's arithmetic: a random walk whose
 // steps are uniform(0, 2 max / n), R/core.R:407-415) and relaxed as one batch; only the per-fold scores come back.
@@ -2459,9 +2474,8 @@ int topolow_cv_sweep(const topolow_cell_list* cells, int32_t named, int32_t pres
                      int32_t convergence_window, int32_t convergence_check_freq, int32_t precision, int32_t device,
                      double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations, int32_t* converged,
                      int32_t* error_code, double* device_seconds, char* errbuf, size_t errlen) {
-  if (!cells || n_folds < 0 || (n_folds > 0 && (!ndim || !k0 || !cooling_rate || !c_repulsion || !picks_offset ||
-      !unit_draws || !draws_offset || !seeds || !holdout_sum_abs || !holdout_count || !iterations || !converged ||
-      !error_code)))
+  if (!cv_sweep_args_ok(cells, n_folds, ndim, k0, cooling_rate, c_repulsion, picks_offset, unit_draws, draws_offset, seeds,
+                        holdout_sum_abs, holdout_count, iterations, converged, error_code))
     return TOPOLOW_ERR_BAD_ARGUMENT;
   if (device_seconds) *device_seconds = 0.0;
   if (n_folds == 0) return TOPOLOW_OK;
@@ -2486,22 +2500,10 @@ int topolow_cv_sweep(const topolow_cell_list* cells, int32_t named, int32_t pres
         x.rc = fold_problem(cells, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named,
                             x.order.data(), x.deg.data(), x.ei.data(), x.ej.data(), x.ed.data(), x.et.data(), &x.ne,
                             x.hi.data(), x.hj.data(), x.ht.data(), &x.nh, &vmax);
-        if (x.rc == TOPOLOW_OK && (x.ne == 0 || !(vmax == vmax))) x.rc = TOPOLOW_ERR_BAD_ARGUMENT;   // no valid measurements
+        x.rc = fold_check(x.rc, x.ne, vmax, ndim[f], draws_offset[f + 1] - draws_offset[f], n);
         if (x.rc != TOPOLOW_OK) continue;
-        const int d_ = ndim[f];
-        if (d_ < 1 || draws_offset[f + 1] - draws_offset[f] != (int64_t)d_ * (n - 1)) { x.rc = TOPOLOW_ERR_BAD_ARGUMENT; continue; }
-        const double* u = unit_draws + draws_offset[f];             // (ndim, n - 1), row-major
-        const double step = vmax / (double)n;
-        x.pos.assign((size_t)n * d_, 0.0);                          // column-major n x ndim
-        x.out.assign((size_t)n * d_, 0.0);
-        for (int d = 0; d < d_; ++d) {
-          double acc = 0.0;
-          for (int i = 1; i < n; ++i) {
-            const double st_ = 0.0 + (2.0 * step - 0.0) * u[(size_t)d * (n - 1) + (i - 1)];   // Generator.uniform's arithmetic
-            acc = i == 1 ? st_ : acc + st_;                         // cumsum
-            x.pos[(size_t)i + (size_t)d * n] = acc;
-          }
-        }
+        start_walk(unit_draws + draws_offset[f], vmax, n, ndim[f], nullptr, x.pos);
+        x.out.assign((size_t)n * ndim[f], 0.0);
       }
     });
   });
@@ -2745,6 +2747,56 @@ int topolow_cv_fold_pairs(const topolow_cell_list* cells, const int64_t* picks, 
   return rcg != TOPOLOW_OK ? rcg : rc;
 }
 
+namespace {
+
+// Schedule gs is tuned up to kMaxTunedDim dimensions: the one place that says so to a caller.
+int check_gs_dim(int ndim, char* errbuf, size_t errlen) {
+  if (ndim <= kMaxTunedDim) return TOPOLOW_OK;
+  set_err(errbuf, errlen, "schedule gs: ndim must be between 1 and %d (wider embeddings run the slab schedule)", kMaxTunedDim);
+  return TOPOLOW_ERR_UNSUPPORTED;
+}
+
+// Targets, degrees and the convergence edge list into a fresh whole-problem session (relabelled already).
+using SessionLoader = std::function<int(topolow_session*, char*, size_t)>;
+
+// A whole-problem session, opened: session_create, tile Gauss-Seidel where asked for, the labels shuffled by
+// relabel_seed (slabs / tiles of random points instead of index-contiguous ones; NULL: the caller's labels), then the
+// loader.  Where a step fails nothing stays open and *out is NULL.
+int open_session(topolow_session** out, int32_t n, int32_t ndim, bool tile_gs, int32_t precision, int32_t device,
+                 const uint64_t* relabel_seed, const SessionLoader& load, char* errbuf, size_t errlen) {
+  *out = nullptr;
+  topolow_session* s = nullptr;
+  int rc = topolow_session_create(&s, n, ndim, 0, n, precision, device, errbuf, errlen);
+  if (rc != TOPOLOW_OK) return rc;
+  if (tile_gs) {
+    rc = check_gs_dim(ndim, errbuf, errlen);
+    if (rc == TOPOLOW_OK) rc = topolow_session_set_schedule(s, TOPOLOW_SCHEDULE_GS);
+  }
+  if (rc == TOPOLOW_OK && relabel_seed)
+    rc = topolow_session_set_relabel(s, mix64(*relabel_seed ^ 0x1abe15eedull) | 1ull, errbuf, errlen);
+  if (rc == TOPOLOW_OK) rc = load(s, errbuf, errlen);
+  if (rc != TOPOLOW_OK) {
+    topolow_session_destroy(s);
+    return rc;
+  }
+  *out = s;
+  return TOPOLOW_OK;
+}
+
+// Every iteration of a begun run, enqueued 50 at a time: the reference's interrupt cadence (src/optimization.cpp:364).
+// after_chunk, where there is one, runs after each chunk that enqueued work; anything but TOPOLOW_OK from it ends the
+// run with that code.
+int enqueue_run(topolow_session* s, const std::function<int()>& after_chunk, char* errbuf, size_t errlen) {
+  for (;;) {
+    int enq = 0;
+    int rc = topolow_session_enqueue(s, 50, &enq, errbuf, errlen);
+    if (rc || enq == 0) return rc;
+    if (after_chunk && (rc = after_chunk()) != TOPOLOW_OK) return rc;
+  }
+}
+
+}  // namespace
+
 // The sweep of topolow_cv_sweep on resident sessions: one session per ndim, loaded once with the full matrix; a fold is
 // held out of it, run, scored on the device and put back.  The next fold is prepared on a host thread meanwhile.
 int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int32_t preserve_order, int32_t n_folds,
@@ -2754,9 +2806,8 @@ int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int3
                              int32_t convergence_window, int32_t convergence_check_freq, int32_t precision, int32_t device,
                              int32_t schedule, double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations,
                              int32_t* converged, int32_t* error_code, double* device_seconds, char* errbuf, size_t errlen) {
-  if (!cells || n_folds < 0 || (n_folds > 0 && (!ndim || !k0 || !cooling_rate || !c_repulsion || !picks_offset ||
-      !unit_draws || !draws_offset || !seeds || !holdout_sum_abs || !holdout_count || !iterations || !converged ||
-      !error_code)))
+  if (!cv_sweep_args_ok(cells, n_folds, ndim, k0, cooling_rate, c_repulsion, picks_offset, unit_draws, draws_offset, seeds,
+                        holdout_sum_abs, holdout_count, iterations, converged, error_code))
     return TOPOLOW_ERR_BAD_ARGUMENT;
   if (schedule != TOPOLOW_SCHEDULE_AUTO && schedule != TOPOLOW_SCHEDULE_SLAB && schedule != TOPOLOW_SCHEDULE_GS)
     return TOPOLOW_ERR_BAD_ARGUMENT;
@@ -2779,25 +2830,11 @@ int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int3
     auto p = std::make_unique<Prep>();
     try {
       p->rc = fold_pairs(cells, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named, p->fp);
-      const double vmax = p->fp.numeric_max;
-      if (p->rc == TOPOLOW_OK && (p->fp.n_edges == 0 || !(vmax == vmax))) p->rc = TOPOLOW_ERR_BAD_ARGUMENT;   // no valid measurements
-      const int d_ = ndim[f];
-      if (p->rc == TOPOLOW_OK && (d_ < 1 || draws_offset[f + 1] - draws_offset[f] != (int64_t)d_ * (n - 1)))
-        p->rc = TOPOLOW_ERR_BAD_ARGUMENT;
+      p->rc = fold_check(p->rc, p->fp.n_edges, p->fp.numeric_max, ndim[f], draws_offset[f + 1] - draws_offset[f], n);
       if (p->rc != TOPOLOW_OK) return p;
-      // the random walk of topolow_cv_sweep, point i of the fold's order = the caller's point order[i]
-      const double* u = unit_draws + draws_offset[f];             // (ndim, n - 1), row-major
-      const double step = vmax / (double)n;
-      const bool reordered = p->fp.order[0] >= 0;
-      p->pos.assign((size_t)n * d_, 0.0);
-      for (int d = 0; d < d_; ++d) {
-        double acc = 0.0;
-        for (int i = 1; i < n; ++i) {
-          const double st_ = 0.0 + (2.0 * step - 0.0) * u[(size_t)d * (n - 1) + (i - 1)];   // Generator.uniform's arithmetic
-          acc = i == 1 ? st_ : acc + st_;                         // cumsum
-          p->pos[(size_t)(reordered ? p->fp.order[i] : i) + (size_t)d * n] = acc;
-        }
-      }
+      // the random walk of topolow_cv_sweep in the caller's labels
+      start_walk(unit_draws + draws_offset[f], p->fp.numeric_max, n, ndim[f], p->fp.order[0] >= 0 ? p->fp.order.data() : nullptr,
+                 p->pos);
     } catch (const std::bad_alloc&) {
       p->rc = TOPOLOW_ERR_HIP;
     }
@@ -2830,70 +2867,52 @@ int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int3
       for (int f : members) error_code[f] = TOPOLOW_ERR_BAD_ARGUMENT;
       continue;
     }
-    topolow_session* s = nullptr;
-    int rc = topolow_session_create(&s, n, ndim[g0], 0, n, prec, device, errbuf, errlen);
-    if (rc != TOPOLOW_OK) return rc;
+    // the first fold is prepared while the session opens; the labels are shuffled by the first fold's seed
     std::future<std::unique_ptr<Prep>> next = std::async(std::launch::async, prepare, members[0]);
     bool next_valid = true;
-    do {
-      if (tile_gs) {
-        if (ndim[g0] > kMaxTunedDim) {
-          set_err(errbuf, errlen, "schedule gs: ndim must be between 1 and %d (wider embeddings run the slab schedule)", kMaxTunedDim);
-          rc = TOPOLOW_ERR_UNSUPPORTED;
-          break;
-        }
-        rc = topolow_session_set_schedule(s, TOPOLOW_SCHEDULE_GS);
-        if (rc) break;
+    topolow_session* s = nullptr;
+    int rc = open_session(&s, n, ndim[g0], tile_gs, prec, device, &seeds[members[0]], [&](topolow_session* t, char* eb, size_t el) -> int {
+      const int rcl = topolow_session_load_coo(t, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), fdeg.data(), eb, el);
+      return rcl ? rcl : topolow_session_set_edges(t, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), eb, el);
+    }, errbuf, errlen);
+    for (size_t q = 0; q < members.size() && rc == TOPOLOW_OK; ++q) {
+      const int f = members[q];
+      std::unique_ptr<Prep> p = next.get();
+      next_valid = false;
+      if (q + 1 < members.size()) { next = std::async(std::launch::async, prepare, members[q + 1]); next_valid = true; }
+      error_code[f] = p->rc;
+      if (p->rc != TOPOLOW_OK) continue;
+      const FoldPairs& fp = p->fp;
+      rc = topolow_session_hold_out(s, fp.pair_i.data(), fp.pair_j.data(), (int64_t)fp.pair_i.size(), fp.degrees.data(),
+                                    errbuf, errlen);
+      if (rc) break;
+      const double t0 = now_s();
+      int rcf = topolow_session_set_positions(s, p->pos.data(), errbuf, errlen);
+      if (rcf == TOPOLOW_OK)
+        rcf = topolow_session_begin(s, n_iter, k0[f], cooling_rate[f], c_repulsion[f], relative_epsilon, convergence_window,
+                                    convergence_check_freq, seeds[f], 0, errbuf, errlen);
+      if (rcf == TOPOLOW_OK) rcf = enqueue_run(s, nullptr, errbuf, errlen);
+      if (rcf == TOPOLOW_OK)
+        rcf = topolow_session_finish(s, nullptr, &converged[f], &iterations[f], nullptr, nullptr, errbuf, errlen);
+      else
+        (void)topolow_session_finish(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);   // the run is over either way
+      if (device_seconds) *device_seconds += now_s() - t0;
+      if (rcf == TOPOLOW_OK)
+        rcf = topolow_session_score_pairs(s, fp.score_i.data(), fp.score_j.data(), fp.score_truth.data(),
+                                          (int64_t)fp.score_i.size(), &holdout_sum_abs[f], &holdout_count[f], errbuf, errlen);
+      // the session is the full matrix again before the next fold starts, whatever this one did
+      char rerr[256] = "";
+      const int rcr = topolow_session_restore_held_out(s, fdeg.data(), rerr, sizeof rerr);
+      if (rcf == TOPOLOW_ERR_NONFINITE) {   // a diverged fold is this fold's result, not the call's
+        error_code[f] = TOPOLOW_ERR_NONFINITE;
+        iterations[f] = 0; converged[f] = 0;
+        rcf = TOPOLOW_OK;
       }
-      rc = topolow_session_set_relabel(s, mix64(seeds[members[0]] ^ 0x1abe15eedull) | 1ull, errbuf, errlen);
-      if (rc) break;
-      rc = topolow_session_load_coo(s, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), fdeg.data(), errbuf, errlen);
-      if (rc) break;
-      rc = topolow_session_set_edges(s, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), errbuf, errlen);
-      if (rc) break;
-      for (size_t q = 0; q < members.size() && rc == TOPOLOW_OK; ++q) {
-        const int f = members[q];
-        std::unique_ptr<Prep> p = next.get();
-        next_valid = false;
-        if (q + 1 < members.size()) { next = std::async(std::launch::async, prepare, members[q + 1]); next_valid = true; }
-        error_code[f] = p->rc;
-        if (p->rc != TOPOLOW_OK) continue;
-        const FoldPairs& fp = p->fp;
-        rc = topolow_session_hold_out(s, fp.pair_i.data(), fp.pair_j.data(), (int64_t)fp.pair_i.size(), fp.degrees.data(),
-                                      errbuf, errlen);
-        if (rc) break;
-        const double t0 = now_s();
-        int rcf = topolow_session_set_positions(s, p->pos.data(), errbuf, errlen);
-        if (rcf == TOPOLOW_OK)
-          rcf = topolow_session_begin(s, n_iter, k0[f], cooling_rate[f], c_repulsion[f], relative_epsilon, convergence_window,
-                                      convergence_check_freq, seeds[f], 0, errbuf, errlen);
-        while (rcf == TOPOLOW_OK) {   // 50 iterations at a time, the one-shot loop's cadence
-          int enq = 0;
-          rcf = topolow_session_enqueue(s, 50, &enq, errbuf, errlen);
-          if (rcf || enq == 0) break;
-        }
-        if (rcf == TOPOLOW_OK)
-          rcf = topolow_session_finish(s, nullptr, &converged[f], &iterations[f], nullptr, nullptr, errbuf, errlen);
-        else
-          (void)topolow_session_finish(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);   // the run is over either way
-        if (device_seconds) *device_seconds += now_s() - t0;
-        if (rcf == TOPOLOW_OK)
-          rcf = topolow_session_score_pairs(s, fp.score_i.data(), fp.score_j.data(), fp.score_truth.data(),
-                                            (int64_t)fp.score_i.size(), &holdout_sum_abs[f], &holdout_count[f], errbuf, errlen);
-        // the session is the full matrix again before the next fold starts, whatever this one did
-        char rerr[256] = "";
-        const int rcr = topolow_session_restore_held_out(s, fdeg.data(), rerr, sizeof rerr);
-        if (rcf == TOPOLOW_ERR_NONFINITE) {   // a diverged fold is this fold's result, not the call's
-          error_code[f] = TOPOLOW_ERR_NONFINITE;
-          iterations[f] = 0; converged[f] = 0;
-          rcf = TOPOLOW_OK;
-        }
-        if (rcf != TOPOLOW_OK) { rc = rcf; break; }
-        if (rcr != TOPOLOW_OK) { set_err(errbuf, errlen, "%s", rerr); rc = rcr; break; }
-      }
-    } while (0);
+      if (rcf != TOPOLOW_OK) { rc = rcf; break; }
+      if (rcr != TOPOLOW_OK) { set_err(errbuf, errlen, "%s", rerr); rc = rcr; break; }
+    }
     if (next_valid) (void)next.get();
-    topolow_session_destroy(s);
+    if (s) topolow_session_destroy(s);
     if (rc != TOPOLOW_OK) return rc;
   }
   return TOPOLOW_OK;
@@ -3799,9 +3818,8 @@ int layout_route(int n, int ndim, const topolow_options& opt, LayoutRoute* r, ch
   const int gs_max_n = opt.gs_max_n > 0 ? opt.gs_max_n : kDefaultGsMaxN;
   if (schedule == TOPOLOW_SCHEDULE_AUTO)
     schedule = (n <= gs_max_n && ndim <= kMaxTunedDim) ? TOPOLOW_SCHEDULE_GS : TOPOLOW_SCHEDULE_SLAB;
-  if (schedule == TOPOLOW_SCHEDULE_GS && ndim > kMaxTunedDim) {
-    set_err(errbuf, errlen, "schedule gs: ndim must be between 1 and %d (wider embeddings run the slab schedule)", kMaxTunedDim);
-    return TOPOLOW_ERR_UNSUPPORTED;
+  if (schedule == TOPOLOW_SCHEDULE_GS) {
+    if (const int rc = check_gs_dim(ndim, errbuf, errlen)) return rc;
   }
 
   // exact GS: one workgroup while the problem fits its LDS, the tile schedule beyond that
@@ -3811,9 +3829,6 @@ int layout_route(int n, int ndim, const topolow_options& opt, LayoutRoute* r, ch
   r->tile_gs = schedule == TOPOLOW_SCHEDULE_GS && !gs_fits_lds;
   return TOPOLOW_OK;
 }
-
-// Targets, degrees and the convergence edge list into a fresh whole-problem session (relabelled already).
-using SessionLoader = std::function<int(topolow_session*, char*, size_t)>;
 
 // One embedding on a session, from session_create to session_finish: the slab schedule or tile Gauss-Seidel.  The
 // body of topolow_optimize_layout_exact (its loader: the 16 arguments) and of topolow_layout_prep_optimize (its
@@ -3828,22 +3843,12 @@ int run_session_layout(int32_t n, int32_t ndim, bool tile_gs, const topolow_opti
                             ? (tile_gs ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32)
                             : opt.precision;
   topolow_session* s = nullptr;
-  int rc = topolow_session_create(&s, n, ndim, 0, n, precision, opt.device, errbuf, errlen);
+  int rc = open_session(&s, n, ndim, tile_gs, precision, opt.device, opt.keep_labels ? nullptr : &opt.seed, load, errbuf, errlen);
   if (rc != TOPOLOW_OK) return rc;
   double t_dev0 = 0.0, t_dev1 = 0.0;
   int iters_run = 0, stopped = 0;
   double t_setup = 0.0;
   do {
-    if (tile_gs) {
-      rc = topolow_session_set_schedule(s, TOPOLOW_SCHEDULE_GS);
-      if (rc) break;
-    }
-    if (!opt.keep_labels) {   // slabs / tiles of random points instead of index-contiguous ones
-      rc = topolow_session_set_relabel(s, mix64(opt.seed ^ 0x1abe15eedull) | 1ull, errbuf, errlen);
-      if (rc) break;
-    }
-    rc = load(s, errbuf, errlen);
-    if (rc) break;
     rc = topolow_session_set_positions(s, initial_positions, errbuf, errlen);
     if (rc) break;
     rc = topolow_session_begin(s, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
@@ -3864,18 +3869,14 @@ int run_session_layout(int32_t n, int32_t ndim, bool tile_gs, const topolow_opti
       emit_checks(opt, trace.data(), reported, nc, n_iter);
       reported = nc;
     };
-    for (;;) {
-      int enq = 0;
-      // 50 iterations at a time: the reference's interrupt cadence (src/optimization.cpp:364)
-      rc = topolow_session_enqueue(s, 50, &enq, errbuf, errlen);
-      if (rc || enq == 0) break;
+    rc = enqueue_run(s, [&]() -> int {
       if (opt.interrupt_cb && opt.interrupt_cb(opt.interrupt_user)) {
         set_err(errbuf, errlen, "interrupted by the caller");
-        rc = TOPOLOW_ERR_INTERRUPTED;
-        break;
+        return TOPOLOW_ERR_INTERRUPTED;
       }
       if (verbose) report();
-    }
+      return TOPOLOW_OK;
+    }, errbuf, errlen);
     if (rc == TOPOLOW_OK && verbose) report();
     if (rc) break;
     double last = 0.0;

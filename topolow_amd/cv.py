@@ -190,23 +190,24 @@ class FoldBuilder:
             self.cells(), picks, preserve_order, self.m.names is not None)
         if ei.shape[0] == 0:
             raise ValueError("No valid off-diagonal measurements found in dissimilarity matrix")
-        init_step = vmax / n
-        if unit_draw is None:
-            steps = rng.uniform(0.0, 2.0 * init_step, size=(int(ndim), n - 1)).T
-        else:
-            steps = (0.0 + (2.0 * init_step - 0.0) * unit_draw).T      # Generator.uniform's own arithmetic
-        init = np.vstack([np.zeros((1, int(ndim))), np.cumsum(steps, axis=0)])
+        init = core._start_walk(vmax, n, int(ndim), rng, unit_draw)
+        call = self._call(init, order, degrees, ei, ej, ed, et, mapping_max_iter, k0, cooling_rate, c_repulsion,
+                          relative_epsilon, convergence_counter, convergence_check_freq)
+        return call, (hi, hj, ht)
+
+    def _call(self, init, order, degrees, edge_i, edge_j, edge_dist, edge_thresh, mapping_max_iter, k0, cooling_rate,
+              c_repulsion, relative_epsilon, convergence_counter, convergence_check_freq) -> SparseCall:
+        """The SparseCall of a fold built in `order` (None: the input order), its names in that order."""
         names = self.m.names
         if names is not None and order is not None:
             names = [names[q] for q in order]
-        call = SparseCall(
+        return SparseCall(
             initial_positions=np.ascontiguousarray(init, dtype=np.float64), degrees=degrees,
-            edge_i=ei, edge_j=ej, edge_dist=ed, edge_thresh=et,
+            edge_i=edge_i, edge_j=edge_j, edge_dist=edge_dist, edge_thresh=edge_thresh,
             n_iter=int(mapping_max_iter), k0=float(k0), cooling_rate=float(cooling_rate),
             c_repulsion=float(c_repulsion), relative_epsilon=float(relative_epsilon),
             convergence_window=int(convergence_counter),
             convergence_check_freq=int(convergence_check_freq), names=names, order=order)
-        return call, (hi, hj, ht)
 
     def fold_numpy(self, picks: np.ndarray, ndim: int, mapping_max_iter, k0, cooling_rate, c_repulsion,
                    relative_epsilon, convergence_counter, convergence_check_freq, preserve_order, rng):
@@ -235,20 +236,10 @@ class FoldBuilder:
         er, ec, ev, ek = rows[up], cols[up], vals[up], codes[up]
         srt = np.lexsort((er, ec))                                   # column-major scan
         numeric = vals[codes == 0]
-        init_step = (numeric.max() if numeric.size else np.nan) / n
-        steps = rng.uniform(0.0, 2.0 * init_step, size=(int(ndim), n - 1)).T
-        init = np.vstack([np.zeros((1, int(ndim))), np.cumsum(steps, axis=0)])
-        names = self.m.names
-        if names is not None and order is not None:
-            names = [names[q] for q in order]
-        call = SparseCall(
-            initial_positions=np.ascontiguousarray(init, dtype=np.float64), degrees=degrees,
-            edge_i=er[srt].astype(np.int32), edge_j=ec[srt].astype(np.int32),
-            edge_dist=ev[srt].astype(np.float64), edge_thresh=ek[srt].astype(np.int32),
-            n_iter=int(mapping_max_iter), k0=float(k0), cooling_rate=float(cooling_rate),
-            c_repulsion=float(c_repulsion), relative_epsilon=float(relative_epsilon),
-            convergence_window=int(convergence_counter),
-            convergence_check_freq=int(convergence_check_freq), names=names, order=order)
+        init = core._start_walk(numeric.max() if numeric.size else np.nan, n, int(ndim), rng)
+        call = self._call(init, order, degrees, er[srt].astype(np.int32), ec[srt].astype(np.int32),
+                          ev[srt].astype(np.float64), ek[srt].astype(np.int32), mapping_max_iter, k0, cooling_rate,
+                          c_repulsion, relative_epsilon, convergence_counter, convergence_check_freq)
         # out-of-sample cells: held out AND numeric in the truth (as.numeric drops thresholds)
         numeric_truth = self.codes[at] == 0
         # error_calculator_comparison lines the prediction up with the truth BY NAME
