@@ -508,6 +508,63 @@ int32_t topolow_layout_order_from_sums(int32_t n, const double* row_sum, const i
                                        int32_t* order_out);
 
 /* ---------------------------------------------------------------------------------------
+ * Cross-validation folds from a prepared handle: a whole sweep from ONE upload of the matrix.  A fold is its picks
+ * (linear column-major indices r + c n, as topolow_cv_fold; their mirrors are held out too, the diagonal is eligible);
+ * the device marks them in a fold mask of n^2 bits that lives in the handle and is empty again when either entry
+ * returns, and derives from the masked matrix what topolow_cv_fold_pairs derives from the cell list.  Per fold the
+ * picks go up and O(n) numbers come down; nothing of size n x n or O(cells) is touched on the host.  vals and codes are
+ * never written: fetch(), optimize() and post_metrics() afterwards return what they returned before.
+ * Both entries want a handle created with preserve_order (the fold's labels are the caller's; a handle that declined
+ * or reordered: TOPOLOW_ERR_BAD_ARGUMENT, "create the handle with preserve_order") and a SYMMETRIC matrix -- every
+ * off-diagonal cell has a mirror with the same value bits, the same NA-ness and the same code, decided on the device
+ * at the first fold, once per handle; otherwise TOPOLOW_ERR_UNSUPPORTED with topolow_cv_fold_pairs' message.  A pick
+ * outside 0 .. n^2 - 1: TOPOLOW_ERR_BAD_ARGUMENT.  The first fold adds n^2 / 8 bytes (the mask) and 24 n^2 / 64 bytes
+ * (the partial sums) to what the handle holds.
+ * ------------------------------------------------------------------------------------- */
+
+/* topolow_cv_fold_pairs from the handle: the same outputs, computed on the device and downloaded.
+ *   order        as topolow_cv_fold_pairs, from topolow_layout_order_from_sums on the masked sums, judged with the
+ *                full matrix's exact_sums and negative / infinite counts (conservative for a subset of its cells).
+ *                *order_route says how (TOPOLOW_ORDER_*).  On TOPOLOW_ORDER_DECLINED the entry still returns
+ *                TOPOLOW_OK, order[0] = -1 and the scored cells are in the caller's numbering; degrees, numeric_max,
+ *                n_edges and the pairs are valid, the caller orders the fold on the host.
+ *   degrees, numeric_max, n_edges   equal to topolow_cv_fold_pairs'
+ *   pair_i/_j    the same SET of unique held-out pairs i < j, sorted by (j, i) (up to n_picks entries)
+ *   score_i/_j/_truth  equal to topolow_cv_fold_pairs' element for element: ascending column-major index of the
+ *                cell, the truth read from the resident matrix (up to 2 n_picks entries)
+ * TOPOLOW_ERR_BAD_ARGUMENT before any device call: a NULL argument (picks may be NULL when n_picks is 0), n_picks < 0. */
+int topolow_layout_prep_fold(topolow_layout_prep* p, const int64_t* picks, int64_t n_picks, int32_t preserve_order,
+                             int32_t named, int32_t* order, int32_t* degrees, double* numeric_max, int64_t* n_edges,
+                             int32_t* pair_i, int32_t* pair_j, int64_t* n_pairs, int32_t* score_i, int32_t* score_j,
+                             double* score_truth, int64_t* n_scored, int32_t* order_route, char* errbuf, size_t errlen);
+
+/* topolow_cv_sweep_session with the handle in place of the cell list (the device is the handle's): the same grouping
+ * by ndim, one session per group, relabelled from the group's first seed and loaded with
+ * topolow_session_load_prepared; the same numbers, bit for bit, for every fold it runs.  Per fold: mark, masked sums,
+ * order; the fold's checks and start positions along its order; compaction of the mask into held-out pairs and
+ * scored cells; the hold-out (the pairs mapped to session labels on the device), the run, the score (the scored cells
+ * gathered through the order and the session's labels on the device), restore with the handle's full degrees, the
+ * mask cleared.  order_route[f]: TOPOLOW_ORDER_* of fold f.  A fold whose order was declined is not run:
+ * error_code[f] = TOPOLOW_ERR_UNSUPPORTED, the session is not touched, the caller reruns that fold through
+ * topolow_cv_sweep_session.  Other error_code[f] as topolow_cv_sweep_session.  In every case -- errors included --
+ * the session is the full matrix again and the mask is empty before the next fold starts and when the call returns.
+ * TOPOLOW_ERR_BAD_ARGUMENT before any device call: a NULL argument, n_folds < 0, an unknown schedule; n_folds == 0
+ * is TOPOLOW_OK.  precision f64_exact: TOPOLOW_ERR_UNSUPPORTED, as topolow_cv_sweep_session. */
+int topolow_layout_prep_cv_sweep(topolow_layout_prep* p, int32_t named, int32_t preserve_order, int32_t n_folds,
+                                 const int32_t* ndim, const double* k0, const double* cooling_rate,
+                                 const double* c_repulsion, const int64_t* picks, const int64_t* picks_offset,
+                                 const double* unit_draws, const int64_t* draws_offset, const uint64_t* seeds,
+                                 int32_t n_iter, double relative_epsilon, int32_t convergence_window,
+                                 int32_t convergence_check_freq, int32_t precision, int32_t schedule,
+                                 double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations, int32_t* converged,
+                                 int32_t* error_code, int32_t* order_route, double* device_seconds, char* errbuf,
+                                 size_t errlen);
+
+/* A study entry (tests/study/cv_resident_cost.py): wall-clock seconds of this handle's last topolow_layout_prep_cv_sweep,
+ * summed over its folds: {fold preparation (mark, sums, order, compaction), hold-out, score, restore}; 4 doubles out. */
+int topolow_layout_prep_fold_seconds(const topolow_layout_prep* p, double* seconds);
+
+/* ---------------------------------------------------------------------------------------
  * Device-resident session: the same relaxation with inputs kept in HBM, for callers that
  * run many iterations / many embeddings on data they already hold on the GPU (bench.py, the
  * row-sharded multi-GPU driver).  Pointers named d_* are DEVICE pointers.

@@ -353,6 +353,15 @@ def load() -> C.CDLL:
     lib.topolow_layout_prep_order.argtypes = [vp, ip, ip]
     lib.topolow_layout_prep_resident_seconds.restype = C.c_int
     lib.topolow_layout_prep_resident_seconds.argtypes = [vp, dp]
+    lib.topolow_layout_prep_fold.restype = C.c_int
+    lib.topolow_layout_prep_fold.argtypes = [vp, i64p, C.c_int64, C.c_int32, C.c_int32, ip, ip, dp, i64p, ip, ip, i64p,
+                                             ip, ip, dp, i64p, ip, C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_cv_sweep.restype = C.c_int
+    lib.topolow_layout_prep_cv_sweep.argtypes = [
+        vp, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, i64p, i64p, dp, i64p, C.POINTER(C.c_uint64), C.c_int32,
+        C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, i64p, ip, ip, ip, ip, dp, C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_fold_seconds.restype = C.c_int
+    lib.topolow_layout_prep_fold_seconds.argtypes = [vp, dp]
     lib.topolow_layout_order_from_sums.restype = C.c_int32
     lib.topolow_layout_order_from_sums.argtypes = [C.c_int32, dp, i64p, dp, i64p, C.c_int32, ip]
     _lib = lib
@@ -581,8 +590,8 @@ def cv_fold(cells: CellList, picks, preserve_order: bool, named: bool):
 
 def _cv_sweep_call(symbol, cells: CellList, named, preserve_order, ndims, k0s, cooling_rates, c_repulsions, picks, unit_draws,
                    seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq, precision, device, *extra):
-    """The marshalling of cv_sweep and cv_sweep_session: `symbol` is the bound library entry, `extra` what it takes
-    between `device` and the outputs."""
+    """The marshalling of cv_sweep, cv_sweep_session and PreparedHandle.cv_sweep (cells None: the callable brings its
+    handle): `symbol` is the bound library entry, `extra` what it takes between `device` and the outputs."""
     nf = len(picks)
     nd = np.ascontiguousarray(ndims, dtype=np.int32)
     k0 = np.ascontiguousarray(k0s, dtype=np.float64)
@@ -601,7 +610,7 @@ def _cv_sweep_call(symbol, cells: CellList, named, preserve_order, ndims, k0s, c
     secs = C.c_double(0.0)
     err = C.create_string_buffer(512)
     i64 = C.POINTER(C.c_int64)
-    rc = symbol(C.byref(cells.c), int(bool(named)), int(bool(preserve_order)), nf, _ip(nd), _dp(k0), _dp(cr), _dp(cp),
+    rc = symbol(C.byref(cells.c) if cells is not None else None, int(bool(named)), int(bool(preserve_order)), nf, _ip(nd), _dp(k0), _dp(cr), _dp(cp),
                 p_all.ctypes.data_as(i64), p_off.ctypes.data_as(i64), _dp(d_all), d_off.ctypes.data_as(i64),
                 sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_iter), float(relative_epsilon), int(convergence_window),
                 int(convergence_check_freq), _PRECISIONS[precision], int(device), *extra, _dp(hsum),
@@ -1031,6 +1040,53 @@ class PreparedHandle:
                                                        C.byref(s), C.byref(c), self._err, len(self._err))
         _check(rc, self._err)
         return est, float(s.value), int(c.value)
+
+    def fold(self, picks, preserve_order: bool, named: bool):
+        """One cross-validation fold prepared on the device (topolow_layout_prep_fold): what cv_fold_pairs computes from
+        the cell list, from the resident matrix.  Returns (order or None, degrees, numeric_max, n_edges, (pair_i, pair_j),
+        (score_i, score_j, score_truth), order_route); the pairs are cv_fold_pairs' as a set (sorted by (j, i)), everything
+        else is equal to it.  order_route == ORDER_DECLINED: the order is the caller's to compute (None is returned)."""
+        picks = np.ascontiguousarray(picks, dtype=np.int64)
+        n, k = self.n, int(picks.shape[0])
+        order, deg = np.empty(n, np.int32), np.empty(n, np.int32)
+        pi, pj = np.empty(max(k, 1), np.int32), np.empty(max(k, 1), np.int32)
+        si, sj, st = np.empty(max(2 * k, 1), np.int32), np.empty(max(2 * k, 1), np.int32), np.empty(max(2 * k, 1), np.float64)
+        ne, npair, ns, vmax, route = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0), C.c_int32(0)
+        rc = self.lib.topolow_layout_prep_fold(
+            self._h, picks.ctypes.data_as(C.POINTER(C.c_int64)), k, int(bool(preserve_order)), int(bool(named)), _ip(order),
+            _ip(deg), C.byref(vmax), C.byref(ne), _ip(pi), _ip(pj), C.byref(npair), _ip(si), _ip(sj), _dp(st), C.byref(ns),
+            C.byref(route), self._err, len(self._err))
+        _check(rc, self._err)
+        p, q = int(npair.value), int(ns.value)
+        return (None if order[0] < 0 else order.astype(np.int64), deg, float(vmax.value), int(ne.value),
+                (pi[:p].copy(), pj[:p].copy()), (si[:q].copy(), sj[:q].copy(), st[:q].copy()), int(route.value))
+
+    def cv_sweep(self, named: bool, preserve_order: bool, ndims, k0s, cooling_rates, c_repulsions, picks, unit_draws, seeds,
+                 n_iter: int, relative_epsilon: float, convergence_window: int = 5, convergence_check_freq: int = 3,
+                 precision: str = "auto", schedule: str = "auto"):
+        """`cv_sweep_session` with this handle in place of the cell list (topolow_layout_prep_cv_sweep): the folds are
+        prepared on the device from the resident matrix.  Returns cv_sweep_session's (holdout_sum_abs, holdout_count,
+        iterations, converged, error_code, device seconds) -- the same bits for every fold that ran -- and, as a seventh
+        element, order_route per fold.  A fold with order_route == ORDER_DECLINED did not run (error_code
+        ERR_UNSUPPORTED): it is the caller's to rerun through cv_sweep_session."""
+        nf = len(picks)
+        route = np.zeros(nf, np.int32)
+
+        def symbol(cells, named_, preserve_, nf_, nd, k0, cr, cp, p_all, p_off, d_all, d_off, sd, n_iter_, eps, window, freq,
+                   prec, device, sched, *outs):
+            return self.lib.topolow_layout_prep_cv_sweep(self._h, named_, preserve_, nf_, nd, k0, cr, cp, p_all, p_off, d_all,
+                                                         d_off, sd, n_iter_, eps, window, freq, prec, sched, *outs[:5],
+                                                         _ip(route), *outs[5:])
+        out = _cv_sweep_call(symbol, None, named, preserve_order, ndims, k0s, cooling_rates, c_repulsions, picks, unit_draws,
+                             seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq, precision, -1,
+                             _SCHEDULES[schedule])
+        return out + (route,)
+
+    def fold_seconds(self) -> list:
+        """Seconds of the last .cv_sweep on this handle, summed over its folds: preparation, hold-out, score, restore."""
+        ph = (C.c_double * 4)()
+        self.lib.topolow_layout_prep_fold_seconds(self._h, ph)
+        return list(ph)
 
     def phase_seconds(self) -> list:
         ph = (C.c_double * 5)()

@@ -40,6 +40,7 @@
 #include "relax_cv.h"
 #include "relax_post.h"
 #include "relax_prep.h"
+#include "relax_prep_fold.h"
 
 using namespace topolow;
 
@@ -1482,6 +1483,89 @@ int cv_check_session(const topolow_session* s, char* errbuf, size_t errlen) {
   return TOPOLOW_OK;
 }
 
+// The device half of a hold-out, shared by topolow_session_hold_out and the folds prepared on the device
+// (topolow_layout_prep_cv_sweep).  fill(lo, hi) enqueues on s->stream whatever writes the n_pairs held-out pairs into
+// the two device arrays: session labels, lo < hi, every pair once, in ANY order -- the mask, tile and compaction
+// kernels of relax_cv.h need the pairs unique, not sorted.  degrees: the fold's, per caller's point (host).
+template <typename Fill>
+void cv_hold_out_pairs(topolow_session* s, long long np, const int32_t* degrees, Fill&& fill) {
+  auto& h = s->cv;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipStreamSynchronize(s->check_stream));
+  // the sweep's copy is built from the FULL block once and patched fold after fold
+  if (sym_eligible(s)) (void)sym_available(s);
+  grow_buf(h.lo, (size_t)np); grow_buf(h.hi, (size_t)np); grow_buf(h.words, 2 * (size_t)np); grow_buf(h.deltas, (size_t)np);
+  h.n_pairs = np;
+  h.tiles_patched = false;
+  h.list_compacted = false;
+  const bool gathers = !s->dense_mae;
+  if (np > 0) {
+    fill(h.lo.p, h.hi.p);
+    hipLaunchKernelGGL(cv_mask_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np, s->enc.p,
+                       s->ld, h.words.p, gathers ? kHeldMark : kInfWord);
+    HIP_TRY(hipGetLastError());
+  }
+  if (gathers) {
+    cv_compact_edges(s);
+    if (np > 0)
+      hipLaunchKernelGGL(cv_mask_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
+                         s->enc.p, s->ld, (uint32_t*)nullptr, kInfWord);
+    HIP_TRY(hipGetLastError());
+  }
+  if (s->sym.holds == SymHolds::kTriangle) {
+    if (np > 0)
+      hipLaunchKernelGGL(cv_tiles_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
+                         s->sym.tenc.p, s->sym.delta_ready ? s->sym.tdelta.p : (float*)nullptr, s->sym.npad / kSymCols,
+                         (const uint32_t*)nullptr, h.deltas.p);
+    HIP_TRY(hipGetLastError());
+    h.tiles_patched = true;
+    h.generation = s->sym.generation;
+  }
+  cv_refresh_flags(s, h.tiles_patched);
+  upload_degrees(s, degrees);
+  HIP_TRY(hipStreamSynchronize(s->stream));   // (whatever fill() read from the host may go out of scope)
+  h.active = true;
+}
+
+// What a session refuses a hold-out for, whoever brings the pairs.
+int cv_check_hold_out(const topolow_session* s, char* errbuf, size_t errlen) {
+  const int rc0 = cv_check_session(s, errbuf, errlen);
+  if (rc0 != TOPOLOW_OK) return rc0;
+  if (s->exact) {
+    set_err(errbuf, errlen, "precision f64_exact: folds cannot be held out of the session (the patch does not cover the delta block)");
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
+  if (s->cv.active) {
+    set_err(errbuf, errlen, "a fold is held out already: topolow_session_restore_held_out first");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  return TOPOLOW_OK;
+}
+
+// The device half of topolow_session_score_pairs: n_pairs > 0 pairs in SESSION labels with their truths, all three on
+// the device.  One partial per workgroup, the blocks fixed by n_pairs alone, summed by the host in index order: the
+// same pairs in the same order give the same bits wherever they came from.
+void cv_score_device(topolow_session* s, const int* d_i, const int* d_j, const double* d_truth, long long n_pairs,
+                     double* sum_abs, int64_t* count) {
+  auto& h = s->cv;
+  const int blocks = (int)std::min<long long>(1024, (n_pairs + kThreads - 1) / kThreads);   // fixed by n_pairs alone
+  grow_buf(h.sc_part, 1024);
+  if (s->precision == TOPOLOW_PRECISION_F64)
+    hipLaunchKernelGGL((cv_score_kernel<double>), dim3(blocks), dim3(kThreads), 0, s->stream, (const double*)s->best.p,
+                       s->dim, d_i, d_j, d_truth, n_pairs, h.sc_part.p);
+  else
+    hipLaunchKernelGGL((cv_score_kernel<float>), dim3(blocks), dim3(kThreads), 0, s->stream, (const float*)s->best.p,
+                       s->dim, d_i, d_j, d_truth, n_pairs, h.sc_part.p);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> part((size_t)blocks);
+  HIP_TRY(hipMemcpyAsync(part.data(), h.sc_part.p, (size_t)blocks * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  double total = 0.0;
+  for (int b = 0; b < blocks; ++b) total += part[(size_t)b];
+  if (sum_abs) *sum_abs = total;
+  if (count) *count = n_pairs;
+}
+
 #include "relax_sharded_engine.h"
 
 }  // namespace
@@ -2451,8 +2535,8 @@ int topolow_cv_fold(const topolow_cell_list* cells, const int64_t* picks, int64_
 
 namespace {
 
-// The arguments both sweeps share: the cell list always, the per-fold arrays wherever there is a fold.
-bool cv_sweep_args_ok(const topolow_cell_list* cells, int32_t n_folds, const int32_t* ndim, const double* k0,
+// The arguments the sweeps share: the cell list (or the prepared handle) always, the per-fold arrays wherever there is a fold.
+bool cv_sweep_args_ok(const void* cells, int32_t n_folds, const int32_t* ndim, const double* k0,
                       const double* cooling_rate, const double* c_repulsion, const int64_t* picks_offset,
                       const double* unit_draws, const int64_t* draws_offset, const uint64_t* seeds,
                       const double* holdout_sum_abs, const int64_t* holdout_count, const int32_t* iterations,
@@ -2548,16 +2632,8 @@ int topolow_cv_sweep(const topolow_cell_list* cells, int32_t named, int32_t pres
 int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const int32_t* pair_j, int64_t n_pairs,
                              const int32_t* degrees, char* errbuf, size_t errlen) {
   if (!s || !degrees || n_pairs < 0 || (n_pairs > 0 && (!pair_i || !pair_j))) return TOPOLOW_ERR_BAD_ARGUMENT;
-  const int rc0 = cv_check_session(s, errbuf, errlen);
+  const int rc0 = cv_check_hold_out(s, errbuf, errlen);
   if (rc0 != TOPOLOW_OK) return rc0;
-  if (s->exact) {
-    set_err(errbuf, errlen, "precision f64_exact: folds cannot be held out of the session (the patch does not cover the delta block)");
-    return TOPOLOW_ERR_UNSUPPORTED;
-  }
-  if (s->cv.active) {
-    set_err(errbuf, errlen, "a fold is held out already: topolow_session_restore_held_out first");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
   for (int64_t q = 0; q < n_pairs; ++q)
     if (pair_i[q] < 0 || pair_i[q] >= s->n || pair_j[q] < 0 || pair_j[q] >= s->n) {
       set_err(errbuf, errlen, "held-out pair %lld out of range", (long long)q);
@@ -2565,8 +2641,7 @@ int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const in
     }
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));
-    auto& h = s->cv;
-    // session labels, lo < hi, every pair once (i == j: nothing to hold out)
+    // the host front: session labels, lo < hi, every pair once (i == j: nothing to hold out)
     std::vector<long long> key;
     key.reserve((size_t)n_pairs);
     for (int64_t q = 0; q < n_pairs; ++q) {
@@ -2580,42 +2655,10 @@ int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const in
     const long long np = (long long)key.size();
     std::vector<int> lo((size_t)np), hi((size_t)np);
     for (long long q = 0; q < np; ++q) { lo[(size_t)q] = (int)(key[(size_t)q] / s->n); hi[(size_t)q] = (int)(key[(size_t)q] % s->n); }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipStreamSynchronize(s->check_stream));
-    // the sweep's copy is built from the FULL block once and patched fold after fold
-    if (sym_eligible(s)) (void)sym_available(s);
-    grow_buf(h.lo, (size_t)np); grow_buf(h.hi, (size_t)np); grow_buf(h.words, 2 * (size_t)np); grow_buf(h.deltas, (size_t)np);
-    h.n_pairs = np;
-    h.tiles_patched = false;
-    h.list_compacted = false;
-    const bool gathers = !s->dense_mae;
-    if (np > 0) {
-      HIP_TRY(hipMemcpyAsync(h.lo.p, lo.data(), (size_t)np * 4, hipMemcpyHostToDevice, s->stream));
-      HIP_TRY(hipMemcpyAsync(h.hi.p, hi.data(), (size_t)np * 4, hipMemcpyHostToDevice, s->stream));
-      hipLaunchKernelGGL(cv_mask_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np, s->enc.p,
-                         s->ld, h.words.p, gathers ? kHeldMark : kInfWord);
-      HIP_TRY(hipGetLastError());
-    }
-    if (gathers) {
-      cv_compact_edges(s);
-      if (np > 0)
-        hipLaunchKernelGGL(cv_mask_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
-                           s->enc.p, s->ld, (uint32_t*)nullptr, kInfWord);
-      HIP_TRY(hipGetLastError());
-    }
-    if (s->sym.holds == SymHolds::kTriangle) {
-      if (np > 0)
-        hipLaunchKernelGGL(cv_tiles_kernel, dim3(pair_grid(np)), dim3(kThreads), 0, s->stream, h.lo.p, h.hi.p, np,
-                           s->sym.tenc.p, s->sym.delta_ready ? s->sym.tdelta.p : (float*)nullptr, s->sym.npad / kSymCols,
-                           (const uint32_t*)nullptr, h.deltas.p);
-      HIP_TRY(hipGetLastError());
-      h.tiles_patched = true;
-      h.generation = s->sym.generation;
-    }
-    cv_refresh_flags(s, h.tiles_patched);
-    upload_degrees(s, degrees);
-    HIP_TRY(hipStreamSynchronize(s->stream));   // (the host arrays of the pairs go out of scope)
-    h.active = true;
+    cv_hold_out_pairs(s, np, degrees, [&](int* d_lo, int* d_hi) {
+      HIP_TRY(hipMemcpyAsync(d_lo, lo.data(), (size_t)np * 4, hipMemcpyHostToDevice, s->stream));
+      HIP_TRY(hipMemcpyAsync(d_hi, hi.data(), (size_t)np * 4, hipMemcpyHostToDevice, s->stream));
+    });
   });
 }
 
@@ -2679,8 +2722,7 @@ int topolow_session_score_pairs(topolow_session* s, const int32_t* pair_i, const
     HIP_TRY(hipSetDevice(s->device));
     auto& h = s->cv;
     const size_t np = (size_t)n_pairs;
-    const int blocks = (int)std::min<long long>(1024, (n_pairs + kThreads - 1) / kThreads);   // fixed by n_pairs alone
-    grow_buf(h.sc_i, np); grow_buf(h.sc_j, np); grow_buf(h.sc_t, np); grow_buf(h.sc_part, 1024);
+    grow_buf(h.sc_i, np); grow_buf(h.sc_j, np); grow_buf(h.sc_t, np);
     std::vector<int> si, sj;
     const int32_t* pi = pair_i;
     const int32_t* pj = pair_j;
@@ -2692,20 +2734,7 @@ int topolow_session_score_pairs(topolow_session* s, const int32_t* pair_i, const
     HIP_TRY(hipMemcpyAsync(h.sc_i.p, pi, np * 4, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(h.sc_j.p, pj, np * 4, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(h.sc_t.p, truth, np * 8, hipMemcpyHostToDevice, s->stream));
-    if (s->precision == TOPOLOW_PRECISION_F64)
-      hipLaunchKernelGGL((cv_score_kernel<double>), dim3(blocks), dim3(kThreads), 0, s->stream, (const double*)s->best.p,
-                         s->dim, h.sc_i.p, h.sc_j.p, h.sc_t.p, (long long)n_pairs, h.sc_part.p);
-    else
-      hipLaunchKernelGGL((cv_score_kernel<float>), dim3(blocks), dim3(kThreads), 0, s->stream, (const float*)s->best.p,
-                         s->dim, h.sc_i.p, h.sc_j.p, h.sc_t.p, (long long)n_pairs, h.sc_part.p);
-    HIP_TRY(hipGetLastError());
-    std::vector<double> part((size_t)blocks);
-    HIP_TRY(hipMemcpyAsync(part.data(), h.sc_part.p, (size_t)blocks * 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    double total = 0.0;
-    for (int b = 0; b < blocks; ++b) total += part[(size_t)b];
-    if (sum_abs) *sum_abs = total;
-    if (count) *count = n_pairs;
+    cv_score_device(s, h.sc_i.p, h.sc_j.p, h.sc_t.p, (long long)n_pairs, sum_abs, count);
   });
 }
 
@@ -3211,6 +3240,33 @@ struct topolow_layout_prep {
   DevBuf<int32_t> edge_i, edge_j, edge_thresh;
   DevBuf<double> edge_dist;
   double resident_seconds[3] = {0.0, 0.0, 0.0};   // last load_prepared, last optimize (whole call), last post_metrics
+  // What the ordering rule needs to know of the data (create()'s first pass): conservative for any subset of the cells,
+  // so a fold's masked sums are judged with them (topolow_layout_prep_fold).
+  bool exact_sums = false;
+  bool negative_or_infinite = false;
+  // Cross-validation folds prepared from the handle (relax_prep_fold.h), allocated by the first fold.
+  struct Fold {
+    bool ready = false;
+    bool symmetry_known = false, symmetric = false;   // fold_symmetry_kernel ran / what it found
+    hipStream_t stream = nullptr;          // topolow_layout_prep_fold's own; a sweep works on its session's stream
+    size_t mask_words = 0;
+    DevBuf<uint32_t> mask;                 // one bit per cell; all zero between folds
+    DevBuf<double> part_slow_sum, part_fast_sum, line_sum;
+    DevBuf<int32_t> part_slow_cnt, part_fast_cnt, line_cnt;
+    DevBuf<uint8_t> diag;
+    DevBuf<FoldTotals> totals;
+    DevBuf<int32_t> col_counts;            // 2 n: held-out pairs per column, then scored cells per column
+    DevBuf<int64_t> offsets;               // 2 (n + 1): their prefix sums
+    DevBuf<long long> picks;
+    DevBuf<int32_t> order;                 // the fold's order, where the scored cells are gathered through it
+    DevBuf<int32_t> pair_i, pair_j, score_r, score_c;   // caller's labels; the scored cells as (row, column)
+    DevBuf<int> score_i, score_j;          // the points the scored cells are scored against (topolow_layout_prep_fold)
+    DevBuf<double> score_truth;
+    double seconds[4] = {0.0, 0.0, 0.0, 0.0};   // last sweep, summed over its folds: prepare, hold out, score, restore
+  } fold;
+  ~topolow_layout_prep() {
+    if (fold.stream) (void)hipStreamDestroy(fold.stream);
+  }
 };
 
 namespace {
@@ -3391,6 +3447,8 @@ int topolow_layout_prep_create(topolow_layout_prep** out, const double* values, 
     info->n_infinite = (int64_t)tot.n_infinite;
     info->n_negative = (int64_t)tot.n_negative;
     info->exact_sums = tot.n_inexact == 0 ? 1 : 0;
+    p->exact_sums = tot.n_inexact == 0;
+    p->negative_or_infinite = tot.n_negative + tot.n_infinite > 0;
     if (tot.max_key == 0) {
       info->numeric_max = NAN;
     } else {
@@ -4203,6 +4261,367 @@ int topolow_layout_prep_order(const topolow_layout_prep* p, int32_t* order, int3
 int topolow_layout_prep_resident_seconds(const topolow_layout_prep* p, double* seconds) {
   if (!p || !seconds) return TOPOLOW_ERR_BAD_ARGUMENT;
   for (int q = 0; q < 3; ++q) seconds[q] = p->resident_seconds[q];
+  return TOPOLOW_OK;
+}
+
+// ---- cross-validation folds from a prepared handle (relax_prep_fold.h) -----------------------------------------------
+// The matrix is on the device already; a fold is its picks.  Per fold the host sees 2 n sums, 2 n counts, n diagonal
+// flags, 2 n column counts and the totals, and sends the picks, 2 (n + 1) offsets and, where one is applied, the order.
+namespace {
+
+// One fold as the device prepared it: the n-sized results on the host, the lists in the handle's device buffers.
+struct FoldPrepared {
+  std::vector<int32_t> order, degrees;   // order[0] = -1: input order kept; degrees per caller's point
+  int32_t route = TOPOLOW_ORDER_PRESERVED;
+  double numeric_max = NAN;
+  int64_t n_edges = 0, n_pairs = 0, n_scored = 0;
+  const int32_t* d_order = nullptr;      // on the device, where the scored cells are gathered through the order
+};
+
+int prep_fold_check_handle(const topolow_layout_prep* p, char* errbuf, size_t errlen) {
+  if (p->declined || p->order.empty() || p->order[0] != -1) {
+    set_err(errbuf, errlen, "a fold's labels are the caller's, the full matrix's order is of no use to it: create the "
+            "handle with preserve_order");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  return TOPOLOW_OK;
+}
+
+void prep_fold_alloc(topolow_layout_prep* p) {
+  auto& f = p->fold;
+  if (f.ready) return;
+  const size_t N = (size_t)p->n, nb = (N + kPrepTile - 1) / kPrepTile;
+  if (!f.stream) HIP_TRY(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
+  f.mask_words = (N * N + 31) / 32;
+  prep_alloc(f.mask, f.mask_words, "the fold mask");
+  prep_alloc(f.part_slow_sum, nb * N, "the partial sums");
+  prep_alloc(f.part_fast_sum, nb * N, "the partial sums");
+  prep_alloc(f.part_slow_cnt, nb * N, "the partial counts");
+  prep_alloc(f.part_fast_cnt, nb * N, "the partial counts");
+  prep_alloc(f.line_sum, 2 * N, "the sums");
+  prep_alloc(f.line_cnt, 2 * N, "the counts");
+  prep_alloc(f.diag, N, "the diagonal flags");
+  prep_alloc(f.totals, 1, "the totals");
+  prep_alloc(f.col_counts, 2 * N, "the column counts");
+  prep_alloc(f.offsets, 2 * (N + 1), "the column offsets");
+  prep_alloc(f.order, N, "the fold's order");
+  HIP_TRY(hipMemsetAsync(f.mask.p, 0, f.mask_words * 4, f.stream));
+  HIP_TRY(hipStreamSynchronize(f.stream));   // whichever stream the first fold works on finds the mask empty
+  f.ready = true;
+}
+
+// The mask is empty again when this leaves scope, whatever happened in between.
+struct FoldMaskGuard {
+  topolow_layout_prep* p;
+  hipStream_t stream;
+  ~FoldMaskGuard() {
+    if (!p->fold.ready) return;
+    (void)hipMemsetAsync(p->fold.mask.p, 0, p->fold.mask_words * 4, stream);
+    (void)hipStreamSynchronize(stream);
+  }
+};
+
+// Once per handle (the first fold): is the matrix symmetric?  Throws kAsymmetricCells where it is not.
+void prep_fold_symmetry(topolow_layout_prep* p) {
+  auto& f = p->fold;
+  if (!f.symmetry_known) {
+    const int nb = (p->n + kPrepTile - 1) / kPrepTile;
+    FoldTotals tot;
+    HIP_TRY(hipMemsetAsync(f.totals.p, 0, sizeof(FoldTotals), f.stream));
+    hipLaunchKernelGGL(fold_symmetry_kernel, dim3(nb, nb), dim3(kPrepThreads), 0, f.stream, p->vals.p,
+                       p->has_codes ? p->codes.p : nullptr, p->n, f.totals.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&tot, f.totals.p, sizeof tot, hipMemcpyDeviceToHost, f.stream));
+    HIP_TRY(hipStreamSynchronize(f.stream));
+    f.symmetric = tot.n_asymmetric == 0;
+    f.symmetry_known = true;
+  }
+  if (!f.symmetric) throw HipError{TOPOLOW_ERR_UNSUPPORTED, kAsymmetricCells};
+}
+
+// mark, masked sums, order, compaction -- on `stream`, which is idle when this returns.  The mask stays set: the caller
+// holds a FoldMaskGuard.
+void prep_fold_prepare(topolow_layout_prep* p, hipStream_t stream, const int64_t* picks, int64_t n_picks,
+                       int32_t preserve_order, int32_t named, FoldPrepared& out) {
+  auto& f = p->fold;
+  const int n = p->n;
+  const size_t N = (size_t)n;
+  const int nb = (n + kPrepTile - 1) / kPrepTile;
+  const int8_t* codes = p->has_codes ? p->codes.p : nullptr;
+  HIP_TRY(hipMemsetAsync(f.totals.p, 0, sizeof(FoldTotals), stream));
+  if (n_picks > 0) {
+    grow_buf(f.picks, (size_t)n_picks);
+    HIP_TRY(hipMemcpyAsync(f.picks.p, picks, (size_t)n_picks * 8, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(fold_mark_kernel, dim3((unsigned)((n_picks + kPrepThreads - 1) / kPrepThreads)), dim3(kPrepThreads),
+                       0, stream, f.picks.p, (long long)n_picks, n, f.mask.p, f.totals.p);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(fold_sums_kernel, dim3(nb, nb), dim3(kPrepThreads), 0, stream, p->vals.p, codes, f.mask.p, n,
+                     f.part_slow_sum.p, f.part_slow_cnt.p, f.part_fast_sum.p, f.part_fast_cnt.p, f.diag.p, f.totals.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(prep_finish_sums_kernel, dim3((n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, stream,
+                     n, nb, f.part_slow_sum.p, f.part_slow_cnt.p, f.part_fast_sum.p, f.part_fast_cnt.p, f.line_sum.p,
+                     f.line_cnt.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fold_compact_count_kernel, dim3(n), dim3(kPrepThreads), 0, stream, p->vals.p, codes, f.mask.p, n,
+                     f.col_counts.p, f.col_counts.p + N);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> sums(2 * N);
+  std::vector<int32_t> cnts(2 * N), per_col(2 * N);
+  std::vector<uint8_t> on_diag(N);
+  FoldTotals tot;
+  HIP_TRY(hipMemcpyAsync(sums.data(), f.line_sum.p, 2 * N * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(cnts.data(), f.line_cnt.p, 2 * N * 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(on_diag.data(), f.diag.p, N, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(per_col.data(), f.col_counts.p, 2 * N * 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(&tot, f.totals.p, sizeof tot, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (tot.n_bad_picks > 0)
+    throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, std::to_string(tot.n_bad_picks) + " of the fold's picks lie outside the matrix (linear column-major indices 0 .. n * n - 1)"};
+
+  // -- the n-sized results.  The buffer is read column-major (relax_prep_fold.h): slow lines are columns, fast lines rows.
+  const size_t row_at = N, col_at = 0;
+  out.order.assign(N, 0);
+  out.order[0] = -1;
+  out.route = TOPOLOW_ORDER_PRESERVED;
+  if (!preserve_order) {
+    std::vector<int64_t> row_cnt(N), col_cnt(N);
+    for (size_t q = 0; q < N; ++q) {
+      row_cnt[q] = (int64_t)cnts[row_at + q] - on_diag[q];
+      col_cnt[q] = (int64_t)cnts[col_at + q] - on_diag[q];
+    }
+    const int32_t flag = p->exact_sums ? 1 : (p->negative_or_infinite ? -1 : 0);
+    out.route = topolow_layout_order_from_sums(n, sums.data() + row_at, row_cnt.data(), sums.data() + col_at,
+                                               col_cnt.data(), flag, out.order.data());
+  }
+  out.degrees.resize(N);
+  for (size_t q = 0; q < N; ++q) out.degrees[q] = cnts[row_at + q];
+  out.n_edges = (int64_t)tot.n_upper;
+  out.numeric_max = NAN;
+  if (tot.max_key != 0) {
+    const uint64_t bits = (tot.max_key >> 63) ? (uint64_t)(tot.max_key & 0x7fffffffffffffffull) : (uint64_t)~tot.max_key;
+    memcpy(&out.numeric_max, &bits, 8);
+  }
+
+  // -- the stable compaction of the mask: held-out pairs and scored cells, column by column
+  std::vector<int64_t> off(2 * (N + 1), 0);
+  for (size_t j = 0; j < N; ++j) {
+    off[j + 1] = off[j] + per_col[j];
+    off[N + 1 + j + 1] = off[N + 1 + j] + per_col[N + j];
+  }
+  out.n_pairs = off[N];
+  out.n_scored = off[2 * N + 1];
+  out.d_order = nullptr;
+  if (out.n_pairs + out.n_scored > 0) {
+    grow_buf(f.pair_i, (size_t)out.n_pairs); grow_buf(f.pair_j, (size_t)out.n_pairs);
+    grow_buf(f.score_r, (size_t)out.n_scored); grow_buf(f.score_c, (size_t)out.n_scored);
+    grow_buf(f.score_truth, (size_t)out.n_scored);
+    HIP_TRY(hipMemcpyAsync(f.offsets.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(fold_compact_write_kernel, dim3(n), dim3(kPrepThreads), 0, stream, p->vals.p, codes, f.mask.p, n,
+                       f.offsets.p, f.offsets.p + N + 1, f.pair_i.p, f.pair_j.p, f.score_r.p, f.score_c.p,
+                       f.score_truth.p);
+    HIP_TRY(hipGetLastError());
+  }
+  if (!named && out.order[0] != -1 && out.n_scored > 0) {   // an unnamed matrix is scored in the returned numbering
+    HIP_TRY(hipMemcpyAsync(f.order.p, out.order.data(), N * 4, hipMemcpyHostToDevice, stream));
+    out.d_order = f.order.p;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));   // (the host arrays of the offsets go out of scope)
+}
+
+unsigned fold_grid(int64_t count) { return (unsigned)((count + kPrepThreads - 1) / kPrepThreads); }
+
+}  // namespace
+
+int topolow_layout_prep_fold(topolow_layout_prep* p, const int64_t* picks, int64_t n_picks, int32_t preserve_order,
+                             int32_t named, int32_t* order, int32_t* degrees, double* numeric_max, int64_t* n_edges,
+                             int32_t* pair_i, int32_t* pair_j, int64_t* n_pairs, int32_t* score_i, int32_t* score_j,
+                             double* score_truth, int64_t* n_scored, int32_t* order_route, char* errbuf, size_t errlen) {
+  if (!p || n_picks < 0 || (!picks && n_picks > 0) || !order || !degrees || !numeric_max || !n_edges || !pair_i ||
+      !pair_j || !n_pairs || !score_i || !score_j || !score_truth || !n_scored || !order_route) {
+    set_err(errbuf, errlen, "null argument, or n_picks < 0");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (const int rch = prep_fold_check_handle(p, errbuf, errlen)) return rch;
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(p->device));
+    prep_fold_alloc(p);
+    prep_fold_symmetry(p);
+    auto& f = p->fold;
+    FoldMaskGuard guard{p, f.stream};
+    FoldPrepared fp;
+    prep_fold_prepare(p, f.stream, picks, n_picks, preserve_order, named, fp);
+    std::copy(fp.order.begin(), fp.order.end(), order);
+    std::copy(fp.degrees.begin(), fp.degrees.end(), degrees);
+    *numeric_max = fp.numeric_max;
+    *n_edges = fp.n_edges;
+    *n_pairs = fp.n_pairs;
+    *n_scored = fp.n_scored;
+    *order_route = fp.route;
+    if (fp.n_pairs > 0) {
+      HIP_TRY(hipMemcpyAsync(pair_i, f.pair_i.p, (size_t)fp.n_pairs * 4, hipMemcpyDeviceToHost, f.stream));
+      HIP_TRY(hipMemcpyAsync(pair_j, f.pair_j.p, (size_t)fp.n_pairs * 4, hipMemcpyDeviceToHost, f.stream));
+    }
+    if (fp.n_scored > 0) {
+      grow_buf(f.score_i, (size_t)fp.n_scored); grow_buf(f.score_j, (size_t)fp.n_scored);
+      hipLaunchKernelGGL(fold_score_points_kernel, dim3(fold_grid(fp.n_scored)), dim3(kPrepThreads), 0, f.stream,
+                         f.score_r.p, f.score_c.p, (long long)fp.n_scored, fp.d_order, (const int*)nullptr, f.score_i.p,
+                         f.score_j.p);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(score_i, f.score_i.p, (size_t)fp.n_scored * 4, hipMemcpyDeviceToHost, f.stream));
+      HIP_TRY(hipMemcpyAsync(score_j, f.score_j.p, (size_t)fp.n_scored * 4, hipMemcpyDeviceToHost, f.stream));
+      HIP_TRY(hipMemcpyAsync(score_truth, f.score_truth.p, (size_t)fp.n_scored * 8, hipMemcpyDeviceToHost, f.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(f.stream));
+  });
+}
+
+int topolow_layout_prep_cv_sweep(topolow_layout_prep* p, int32_t named, int32_t preserve_order, int32_t n_folds,
+                                 const int32_t* ndim, const double* k0, const double* cooling_rate,
+                                 const double* c_repulsion, const int64_t* picks, const int64_t* picks_offset,
+                                 const double* unit_draws, const int64_t* draws_offset, const uint64_t* seeds,
+                                 int32_t n_iter, double relative_epsilon, int32_t convergence_window,
+                                 int32_t convergence_check_freq, int32_t precision, int32_t schedule,
+                                 double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations, int32_t* converged,
+                                 int32_t* error_code, int32_t* order_route, double* device_seconds, char* errbuf,
+                                 size_t errlen) {
+  if (!cv_sweep_args_ok(p, n_folds, ndim, k0, cooling_rate, c_repulsion, picks_offset, unit_draws, draws_offset, seeds,
+                        holdout_sum_abs, holdout_count, iterations, converged, error_code) ||
+      (n_folds > 0 && !order_route) ||
+      (schedule != TOPOLOW_SCHEDULE_AUTO && schedule != TOPOLOW_SCHEDULE_SLAB && schedule != TOPOLOW_SCHEDULE_GS)) {
+    set_err(errbuf, errlen, "null argument, n_folds < 0 or an unknown schedule");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (device_seconds) *device_seconds = 0.0;
+  if (precision == TOPOLOW_PRECISION_F64_EXACT) {
+    set_err(errbuf, errlen, "precision f64_exact: no cross-validation on resident sessions (holding a fold out does not "
+            "cover the delta block); topolow_cv_sweep runs it on the one-workgroup kernel");
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
+  if (n_folds == 0) return TOPOLOW_OK;
+  if (const int rch = prep_fold_check_handle(p, errbuf, errlen)) return rch;
+  const int n = p->n;
+  const int64_t cells = (int64_t)n * n;
+  for (int f = 0; f < n_folds; ++f)
+    for (int64_t q = picks_offset[f]; q < picks_offset[f + 1]; ++q)
+      if (!picks || picks[q] < 0 || picks[q] >= cells) {
+        set_err(errbuf, errlen, "fold %d: pick %lld lies outside the matrix (linear column-major indices 0 .. n * n - 1)",
+                f, (long long)(q - picks_offset[f]));
+        return TOPOLOW_ERR_BAD_ARGUMENT;
+      }
+  const bool tile_gs = schedule == TOPOLOW_SCHEDULE_GS;
+  const int prec = precision == TOPOLOW_PRECISION_AUTO ? (tile_gs ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32) : precision;
+  const int rc_sym = guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(p->device));
+    prep_fold_alloc(p);
+    prep_fold_symmetry(p);
+  });
+  if (rc_sym != TOPOLOW_OK) return rc_sym;
+  for (int f = 0; f < n_folds; ++f) {
+    holdout_sum_abs[f] = 0.0; holdout_count[f] = 0; iterations[f] = 0; converged[f] = 0;
+    error_code[f] = TOPOLOW_OK;
+    order_route[f] = TOPOLOW_ORDER_PRESERVED;
+  }
+  double* secs = p->fold.seconds;
+  secs[0] = secs[1] = secs[2] = secs[3] = 0.0;
+  std::vector<char> done((size_t)n_folds, 0);
+  for (int g0 = 0; g0 < n_folds; ++g0) {
+    if (done[(size_t)g0]) continue;
+    std::vector<int> members;   // the folds that share this ndim, in the caller's order
+    for (int f = g0; f < n_folds; ++f)
+      if (!done[(size_t)f] && ndim[f] == ndim[g0]) { members.push_back(f); done[(size_t)f] = 1; }
+    if (ndim[g0] < 1) {
+      for (int f : members) error_code[f] = TOPOLOW_ERR_BAD_ARGUMENT;
+      continue;
+    }
+    topolow_session* s = nullptr;
+    int rc = open_session(&s, n, ndim[g0], tile_gs, prec, p->device, &seeds[members[0]],
+                          [&](topolow_session* t, char* eb, size_t el) -> int { return topolow_session_load_prepared(t, p, eb, el); },
+                          errbuf, errlen);
+    for (size_t q = 0; q < members.size() && rc == TOPOLOW_OK; ++q) {
+      const int f = members[q];
+      auto& h = p->fold;
+      FoldMaskGuard guard{p, s->stream};   // the mask is empty before the next fold starts, whatever this one does
+      FoldPrepared fp;
+      std::vector<double> pos;   // start positions, n x ndim column-major, caller's labels
+      const double tp = now_s();
+      rc = guarded(errbuf, errlen, [&] {
+        HIP_TRY(hipSetDevice(p->device));
+        prep_fold_prepare(p, s->stream, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named, fp);
+        order_route[f] = fp.route;
+        if (fp.route == TOPOLOW_ORDER_DECLINED) {   // the caller reruns this fold with the host's ordering
+          error_code[f] = TOPOLOW_ERR_UNSUPPORTED;
+          return;
+        }
+        error_code[f] = fold_check(TOPOLOW_OK, fp.n_edges, fp.numeric_max, ndim[f], draws_offset[f + 1] - draws_offset[f], n);
+        if (error_code[f] == TOPOLOW_OK)
+          start_walk(unit_draws + draws_offset[f], fp.numeric_max, n, ndim[f], fp.order[0] >= 0 ? fp.order.data() : nullptr, pos);
+      });
+      secs[0] += now_s() - tp;
+      if (rc != TOPOLOW_OK) break;
+      if (error_code[f] != TOPOLOW_OK) continue;   // the session was not touched
+      // the shared hold-out, its pairs mapped to session labels on the device
+      const double th = now_s();
+      rc = cv_check_hold_out(s, errbuf, errlen);
+      if (rc == TOPOLOW_OK)
+        rc = guarded(errbuf, errlen, [&] {
+          cv_hold_out_pairs(s, (long long)fp.n_pairs, fp.degrees.data(), [&](int* d_lo, int* d_hi) {
+            hipLaunchKernelGGL(fold_pair_labels_kernel, dim3(fold_grid(fp.n_pairs)), dim3(kPrepThreads), 0, s->stream,
+                               h.pair_i.p, h.pair_j.p, (long long)fp.n_pairs, s->inv.empty() ? nullptr : s->d_inv.p, d_lo,
+                               d_hi);
+            HIP_TRY(hipGetLastError());
+          });
+        });
+      secs[1] += now_s() - th;
+      if (rc) break;
+      const double t0 = now_s();
+      int rcf = topolow_session_set_positions(s, pos.data(), errbuf, errlen);
+      if (rcf == TOPOLOW_OK)
+        rcf = topolow_session_begin(s, n_iter, k0[f], cooling_rate[f], c_repulsion[f], relative_epsilon, convergence_window,
+                                    convergence_check_freq, seeds[f], 0, errbuf, errlen);
+      if (rcf == TOPOLOW_OK) rcf = enqueue_run(s, nullptr, errbuf, errlen);
+      if (rcf == TOPOLOW_OK)
+        rcf = topolow_session_finish(s, nullptr, &converged[f], &iterations[f], nullptr, nullptr, errbuf, errlen);
+      else
+        (void)topolow_session_finish(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);   // the run is over either way
+      if (device_seconds) *device_seconds += now_s() - t0;
+      // the shared score: the scored cells' points gathered through the order and the session's labels on the device
+      const double ts = now_s();
+      if (rcf == TOPOLOW_OK && fp.n_scored > 0)
+        rcf = guarded(errbuf, errlen, [&] {
+          auto& c = s->cv;
+          grow_buf(c.sc_i, (size_t)fp.n_scored); grow_buf(c.sc_j, (size_t)fp.n_scored);
+          hipLaunchKernelGGL(fold_score_points_kernel, dim3(fold_grid(fp.n_scored)), dim3(kPrepThreads), 0, s->stream,
+                             h.score_r.p, h.score_c.p, (long long)fp.n_scored, fp.d_order,
+                             s->inv.empty() ? nullptr : s->d_inv.p, c.sc_i.p, c.sc_j.p);
+          HIP_TRY(hipGetLastError());
+          cv_score_device(s, c.sc_i.p, c.sc_j.p, h.score_truth.p, (long long)fp.n_scored, &holdout_sum_abs[f],
+                          &holdout_count[f]);
+        });
+      secs[2] += now_s() - ts;
+      // the session is the full matrix again before the next fold starts, whatever this one did
+      const double tr = now_s();
+      char rerr[256] = "";
+      const int rcr = topolow_session_restore_held_out(s, p->degrees.data(), rerr, sizeof rerr);
+      secs[3] += now_s() - tr;
+      if (rcf == TOPOLOW_ERR_NONFINITE) {   // a diverged fold is this fold's result, not the call's
+        error_code[f] = TOPOLOW_ERR_NONFINITE;
+        iterations[f] = 0; converged[f] = 0;
+        holdout_sum_abs[f] = 0.0; holdout_count[f] = 0;
+        rcf = TOPOLOW_OK;
+      }
+      if (rcf != TOPOLOW_OK) { rc = rcf; break; }
+      if (rcr != TOPOLOW_OK) { set_err(errbuf, errlen, "%s", rerr); rc = rcr; break; }
+    }
+    if (s) topolow_session_destroy(s);
+    if (rc != TOPOLOW_OK) return rc;
+  }
+  return TOPOLOW_OK;
+}
+
+int topolow_layout_prep_fold_seconds(const topolow_layout_prep* p, double* seconds) {
+  if (!p || !seconds) return TOPOLOW_ERR_BAD_ARGUMENT;
+  for (int q = 0; q < 4; ++q) seconds[q] = p->fold.seconds[q];
   return TOPOLOW_OK;
 }
 

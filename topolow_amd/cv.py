@@ -334,10 +334,11 @@ def _pooled(per_set):
 
 def _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon, preserve_order,
                           precision, convergence_counter: int = 5, session: Optional[bool] = None,
-                          schedule: str = "auto"):
+                          schedule: str = "auto", resident: bool = False):
     """The sweep as ONE library call: the batch (topolow_cv_sweep), or -- session = True, or None and a fold does not
     fit the batch kernel's one workgroup -- resident sessions (topolow_cv_sweep_session; a fold without valid
-    measurements is then left out instead of handing the sweep back).  Draws from `rng` exactly what the fold-by-fold loop draws when no fold fails
+    measurements is then left out instead of handing the sweep back); resident = True: the session sweep from a prepared
+    handle (_sweep_resident), which returns a fourth element, the number of folds rerouted to the session sweep.  Draws from `rng` exactly what the fold-by-fold loop draws when no fold fails
     (per set: the fold picks, then per fold its start positions' numbers; then one seed per fold); returns None --
     with the stream spent, the caller rewinds it -- when a fold has no valid measurements, because such a fold draws
     nothing in the reference's order."""
@@ -360,6 +361,11 @@ def _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, 
                 nd.append(int(ps["N"])); k0.append(float(ps["k0"])); cr.append(float(ps["cooling_rate"]))
                 cp.append(float(ps["c_repulsion"]))
     seeds = [int(rng.integers(0, 2 ** 63 - 1)) for _ in picks]
+    if resident:
+        hsum, hcnt, its, conv, ec, secs, rerouted = _sweep_resident(
+            m, builder, preserve_order, nd, k0, cr, cp, picks, draws, seeds, mapping_max_iter, relative_epsilon,
+            convergence_counter, precision or "auto", schedule)
+        return _pooled(_rows_per_set(param_sets, owners, hsum, hcnt, its, conv, ec)), secs, len(picks), rerouted
     if session is None:
         n_edges = int(np.sum(builder.rows < builder.cols))
         session = not all(_native.batch_problem_fits(n, d, precision or "f64", n_edges) for d in set(nd))
@@ -373,13 +379,43 @@ def _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, 
                                                            convergence_counter, 3, precision or "f64")
         if np.any(ec == _native.ERR_BAD_ARGUMENT):
             return None
+    return _pooled(_rows_per_set(param_sets, owners, hsum, hcnt, its, conv, ec)), secs, len(picks)
+
+
+def _rows_per_set(param_sets, owners, hsum, hcnt, its, conv, ec):
+    """The per-fold outputs of a library sweep as _pooled reads them: one list of rows per parameter set, the folds
+    that did not run left out."""
     per_set: List[List[dict]] = [[] for _ in param_sets]
     for f, owner in enumerate(owners):
         if ec[f] != _native.OK:
             continue
         per_set[owner].append(dict(n_samples=int(hcnt[f]), sum_abs_errors=float(hsum[f]), iter=int(its[f]),
                                    converged=int(conv[f])))
-    return _pooled(per_set), secs, len(picks)
+    return per_set
+
+
+def _sweep_resident(m, builder, preserve_order, nd, k0, cr, cp, picks, draws, seeds, mapping_max_iter, relative_epsilon,
+                    convergence_counter, precision, schedule):
+    """The session sweep from ONE upload of the matrix (PreparedHandle.cv_sweep): values and codes as
+    core._device_front hands them over, the handle opened with preserve_order=True (the folds' labels are the caller's).
+    Exactly the folds the device declined to order are rerun through cv_sweep_session -- the library's cell list is
+    built only then -- and merged in fold order.  Returns cv_sweep_session's six outputs and the number of rerouted
+    folds."""
+    codes = m.codes if m.codes.any() else None
+    with _native.PreparedHandle(m.values, codes, preserve_order=True) as handle:
+        hsum, hcnt, its, conv, ec, secs, route = handle.cv_sweep(
+            m.names is not None, preserve_order, nd, k0, cr, cp, picks, draws, seeds, mapping_max_iter, relative_epsilon,
+            convergence_counter, 3, precision, schedule=schedule)
+    again = [f for f in range(len(picks)) if route[f] == _native.ORDER_DECLINED]
+    if again:
+        pick = lambda xs: [xs[f] for f in again]
+        part = _native.cv_sweep_session(builder.cells(), m.names is not None, preserve_order, pick(nd), pick(k0), pick(cr),
+                                        pick(cp), pick(picks), pick(draws), pick(seeds), mapping_max_iter, relative_epsilon,
+                                        convergence_counter, 3, precision, schedule=schedule)
+        for out, sub in zip((hsum, hcnt, its, conv, ec), part[:5]):
+            out[again] = sub
+        secs += part[5]
+    return hsum, hcnt, its, conv, ec, secs, len(again)
 
 
 def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]], mapping_max_iter: int,
@@ -399,6 +435,11 @@ def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]
     per ndim holds the full matrix, a fold is held out of it on the device, run, scored there and put back; `schedule`
     "auto" / "slab": the slab schedule, "gs": tile Gauss-Seidel; the matrix must be symmetric).  It draws from `rng`
     exactly what "sparse" draws, so the stream is left in the same place;
+    path = "resident" is the session sweep from ONE upload of the matrix (topolow_layout_prep_cv_sweep: a prepared handle
+    holds the matrix, every fold's ordering, degrees, held-out pairs and scored cells are derived from it on the device);
+    same draws, same stream position, same numbers as "session".  A fold whose ordering the device cannot prove equal
+    to NumPy's is rerun through the session sweep; the return value gains a FOURTH element, the number of folds so
+    rerouted (0 on most data).  Opt-in: no other path routes to it;
     precision: None = "f64" on the batch paths and, on sessions, f32 for the slab schedule / f64 for "gs";
     path = "dense" runs the reference's own sequence per fold instead (masked n x n matrix ->
     prepare_layout_call -> est_distances -> error_calculator_comparison): same folds, same start
@@ -414,14 +455,17 @@ def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]
     m = core.coded_matrix(dissimilarity_matrix)   # strings are parsed once, not once per fold
     if m is None:
         raise ValueError("dissimilarity_matrix must be a matrix")
-    if path not in ("sparse", "sparse-calls", "dense", "session"):
-        raise ValueError("path must be 'sparse', 'sparse-calls', 'dense' or 'session'")
+    if path not in ("sparse", "sparse-calls", "dense", "session", "resident"):
+        raise ValueError("path must be 'sparse', 'sparse-calls', 'dense', 'session' or 'resident'")
     builder = FoldBuilder(m) if path != "dense" else None
     if builder is not None:      # the matrix half of R/core.R:202-264 once; per set only the parameters
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             core._validate(m, 2, 1, 1.0, 0.5, 1.0, 1.0, 1, 1, None)
     state0 = rng.bit_generator.state
+    if path == "resident":
+        return _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon,
+                                     preserve_order, precision, convergence_counter, schedule=schedule, resident=True)
     if path in ("sparse", "session"):
         fused = _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon,
                                       preserve_order, precision, convergence_counter,
