@@ -81,13 +81,30 @@ def assert_same_fold(got, want, what):
 
 # ---- 1. the fold preparation equals the host's -----------------------------------------------------------------------
 
+def crosses_a_pass(rows, cols, rows_per_pass=256):
+    """Some column lists rows of two different passes of the compaction kernels (kPrepThreads rows each)."""
+    first, last = {}, {}
+    for r, c in zip((np.asarray(rows) // rows_per_pass).tolist(), np.asarray(cols).tolist()):
+        first[c] = min(first.get(c, r), r)
+        last[c] = max(last.get(c, r), r)
+    return any(first[c] != last[c] for c in first)
+
+
 @pytest.mark.parametrize("form", ["exact", "generic"])
-@pytest.mark.parametrize("n", [2, 63, 64, 65, 130, 203])
+@pytest.mark.parametrize("n", [2, 63, 64, 65, 130, 203, 256, 257, 300, 513])
 def test_fold_from_the_handle_equals_the_fold_from_the_cell_list(n, form):
+    """fold_compact_count_kernel / fold_compact_write_kernel walk a column in passes of 256 rows with running bases.
+    Up to n = 256 a column is one pass; 257 is the smallest n with a second one (one row: the column's scored cells
+    only, a pair of column j lies in a row below j), 300 a ragged second pass that holds pairs too, 513 a third pass
+    of one row."""
     D, codes = fold_matrix(n, form)
     m, fb = cell_list(D, codes)
     every = fb.rows + fb.cols * n                               # holds out every measured cell
     folds = dict(mixed=fold_picks(D), empty=np.zeros(0, np.int64), everything=every)
+    if n > 256:         # the lists of the mixed fold do cross a pass: a change of fold_picks cannot quietly undo that
+        _, _, _, _, (w_pi, w_pj), (w_si, w_sj, _) = _native.cv_fold_pairs(fb.cells(), folds["mixed"], True, True)
+        assert crosses_a_pass(w_si, w_sj), n
+        assert n == 257 or crosses_a_pass(w_pi, w_pj), n
     for layout in ("C", "F"):
         Dl = np.asfortranarray(D) if layout == "F" else np.ascontiguousarray(D)
         cl = np.asfortranarray(codes) if layout == "F" else np.ascontiguousarray(codes)

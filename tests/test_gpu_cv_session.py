@@ -27,21 +27,26 @@ CASE_IDS = [f"{p}-{s}-ndim{d}{'-rowowner' if e is not FULL_SYMMETRIC else ''}" f
 HIV = dict(N=2, k0=3.550036, cooling_rate=0.04130713, c_repulsion=0.0007038619)   # tests/test_gpu_assays.py
 
 
-@functools.lru_cache(maxsize=1)
-def problem():
-    """203 synthetic points, 60 % missing, 10 % of the measured pairs '>' codes: the full edge list (upper triangle),
-    degrees, and two hold-out sets with what they leave."""
-    D = synthetic.make_problem(N, latent_dim=5, missing=0.6, seed=5).dissimilarity
+def problem(n=N, D=None, n_hold=280, always=(), which=("plain", "thresholds")):
+    """A matrix as a session's input: the full edge list (upper triangle in np.nonzero order, 10 % of the measured pairs
+    '>' codes), degrees, and hold-out sets with what they leave -- n_hold random edges, the edges at the list indices
+    `always`, ends in the last, partial tile of rows, and the oddities a caller may send.  Without arguments the cached
+    203 synthetic points, 60 % missing."""
+    if D is None:
+        assert (n, n_hold, tuple(always), tuple(which)) == (N, 280, (), ("plain", "thresholds"))
+        return _default_problem()
+    assert D.shape == (n, n)
     rng = np.random.default_rng(1)
     ei, ej = np.nonzero(np.triu(~np.isnan(D), 1))
     ed = D[ei, ej]
     et = (rng.uniform(size=ei.size) < 0.10).astype(np.int32)
     deg = (~np.isnan(D)).sum(axis=1).astype(np.int32)
     um_i, um_j = np.nonzero(np.triu(np.isnan(D), 1))
-    tail = np.flatnonzero(ej >= 192)                       # an end in the last, partial tile of rows
+    tail = np.flatnonzero(ej >= (n - 1) // 64 * 64)        # an end in the last, partial tile of rows
+    always = np.asarray(always, dtype=np.int64)
 
     def hold_set(extra):
-        take = np.unique(np.concatenate([rng.choice(ei.size, 280, replace=False), tail[:12], extra]))
+        take = np.unique(np.concatenate([rng.choice(ei.size, n_hold, replace=False), tail[:12], always, extra]))
         hi, hj = ei[take].tolist(), ej[take].tolist()
         hi += [hj[0], hi[1], 7, int(um_i[0])]              # a pair again the other way round, a pair twice, i == j,
         hj += [ei[take][0], hj[1], 7, int(um_j[0])]        # an unmeasured pair
@@ -52,14 +57,23 @@ def problem():
         np.subtract.at(fdeg, ej[take], 1)
         return dict(pi=np.array(hi, np.int32), pj=np.array(hj, np.int32), keep=keep, deg=fdeg.astype(np.int32),
                     truth=np.concatenate([ed[take], [ed[take][0], ed[take][1], 1.25, 2.5]]))
-    holds = dict(plain=hold_set(np.zeros(0, dtype=np.int64)), thresholds=hold_set(np.flatnonzero(et != 0)))
-    assert not holds["plain"]["keep"].all() and (et[holds["plain"]["keep"]] != 0).any()
-    assert not (et[holds["thresholds"]["keep"]] != 0).any()
-    return dict(ei=ei.astype(np.int32), ej=ej.astype(np.int32), ed=ed, et=et, deg=deg, holds=holds)
+    holds = {}
+    if "plain" in which:
+        holds["plain"] = hold_set(np.zeros(0, dtype=np.int64))
+        assert not holds["plain"]["keep"].all() and (et[holds["plain"]["keep"]] != 0).any()
+    if "thresholds" in which:
+        holds["thresholds"] = hold_set(np.flatnonzero(et != 0))
+        assert not (et[holds["thresholds"]["keep"]] != 0).any()
+    return dict(n=n, ei=ei.astype(np.int32), ej=ej.astype(np.int32), ed=ed, et=et, deg=deg, holds=holds)
+
+
+@functools.lru_cache(maxsize=1)
+def _default_problem():
+    return problem(N, synthetic.make_problem(N, latent_dim=5, missing=0.6, seed=5).dissimilarity)
 
 
 def make_session(monkeypatch, precision, schedule, ndim, env, edges=None, deg=None, n=N, **kw):
-    for k in ("TOPOLOW_SYMMETRIC", "TOPOLOW_SYMMETRIC_MIN_N", "TOPOLOW_SYMMETRIC_STAGE_MIN_TILES"):
+    for k in ("TOPOLOW_SYMMETRIC", "TOPOLOW_SYMMETRIC_MIN_N", "TOPOLOW_SYMMETRIC_STAGE_MIN_TILES", "TOPOLOW_EDGE_MAE"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -105,28 +119,32 @@ def same_run(a, b):
     assert (ra.converged, ra.iterations, ra.final_mae, ra.final_k) == (rb.converged, rb.iterations, rb.final_mae, rb.final_k)
 
 
-@pytest.mark.parametrize("which", ["plain", "thresholds"])
-@pytest.mark.parametrize("precision,schedule,ndim,env", CASES, ids=CASE_IDS)
-def test_held_out_session_is_the_fresh_session_of_the_fold(monkeypatch, precision, schedule, ndim, env, which):
-    """Block, flags and runs of a session with a fold held out equal, bit for bit, those of a fresh session loaded with
-    the fold's list; after the restore the session equals one that never held anything out; score_pairs is the NumPy
-    score of the positions finish() returns."""
-    p = problem()
-    h = p["holds"][which]
-    init = synthetic.initial_positions(np.full((N, N), 6.0), ndim, 3)
-    s = make_session(monkeypatch, precision, schedule, ndim, env, full_edges(p), p["deg"])
-    never = make_session(monkeypatch, precision, schedule, ndim, env, full_edges(p), p["deg"])
-    fresh = make_session(monkeypatch, precision, schedule, ndim, env, fold_edges(p, h), h["deg"])
+def check_held_out_session(monkeypatch, p, h, precision, schedule, ndim, env, thresholds_left, run_first, inspect=None):
+    """Block, flags and runs of a session of problem p with the set h held out equal, bit for bit, those of a fresh
+    session loaded with the fold's list; after the restore the session equals one that never held anything out;
+    score_pairs is the NumPy score of the positions finish() returns.  thresholds_left: whether the fold keeps a
+    threshold pair; run_first: the session runs before the fold arrives; inspect(session): the caller's own assertions
+    on each of the three sessions, once loaded, and on the held-out one again after its run."""
+    n = p["n"]
+    init = synthetic.initial_positions(np.full((n, n), 6.0), ndim, 3)
+    s = make_session(monkeypatch, precision, schedule, ndim, env, full_edges(p), p["deg"], n=n)
+    never = make_session(monkeypatch, precision, schedule, ndim, env, full_edges(p), p["deg"], n=n)
+    fresh = make_session(monkeypatch, precision, schedule, ndim, env, fold_edges(p, h), h["deg"], n=n)
     try:
+        for x in (s, never, fresh):
+            if inspect is not None:
+                inspect(x, False)
         original = block(s)
         assert s.has_thresholds
-        if which == "plain":      # the sweep's copy exists already when the fold arrives: it is patched, not rebuilt
+        if run_first:             # the sweep's copy exists already when the fold arrives: it is patched, not rebuilt
             same_run(run(s, init, ndim), run(never, init, ndim))
         s.hold_out(h["pi"], h["pj"], h["deg"])
         assert np.array_equal(block(s), block(fresh))
-        assert s.has_thresholds == fresh.has_thresholds == (which == "plain")
+        assert s.has_thresholds == fresh.has_thresholds == thresholds_left
         held = run(s, init, ndim)
         same_run(held, run(fresh, init, ndim))
+        if inspect is not None:
+            inspect(s, True)
         # the score, on the device: i == j and the unmeasured pair count like every other entry
         pos = held[0].positions
         want = np.abs(h["truth"] - np.linalg.norm(pos[h["pi"]] - pos[h["pj"]], axis=1)).sum()
@@ -146,6 +164,16 @@ def test_held_out_session_is_the_fresh_session_of_the_fold(monkeypatch, precisio
     finally:
         for x in (s, never, fresh):
             x.close()
+
+
+@pytest.mark.parametrize("which", ["plain", "thresholds"])
+@pytest.mark.parametrize("precision,schedule,ndim,env", CASES, ids=CASE_IDS)
+def test_held_out_session_is_the_fresh_session_of_the_fold(monkeypatch, precision, schedule, ndim, env, which):
+    """check_held_out_session on the 203-point problem: a fold that keeps threshold pairs, met by a session that has run
+    already, and one that holds out every threshold pair and flips the session's threshold bit."""
+    p = problem()
+    check_held_out_session(monkeypatch, p, p["holds"][which], precision, schedule, ndim, env,
+                           thresholds_left=which == "plain", run_first=which == "plain")
 
 
 def test_a_block_loaded_over_a_held_out_fold_is_a_fresh_session(monkeypatch):
