@@ -565,6 +565,46 @@ int topolow_layout_prep_cv_sweep(topolow_layout_prep* p, int32_t named, int32_t 
 int topolow_layout_prep_fold_seconds(const topolow_layout_prep* p, double* seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * Connected subsamples of a resident matrix (reference R/utils.R:199-253 check_matrix_connectivity over the adjacency
+ * of R/diagnostics.R:442-468, R/utils.R:321-463 subsample_dissimilarity_matrix): the components of the measurement
+ * graph of a handle's matrix or of any subset of its points, and a child handle for parent[subset, subset], both from
+ * what the parent keeps on the device.
+ * subset: NULL for all n points (m is then ignored), or m distinct indices into the matrix as it was given to create(),
+ * in any order.  Both entries take a handle that declined its ordering: it still holds the matrix.
+ * TOPOLOW_ERR_BAD_ARGUMENT with a message, before any device call: a NULL handle or output; m < 2 or m > n; an index
+ * out of range; a repeated index (and, for subsample, an order_in that is no permutation of 0..m-1).
+ * ------------------------------------------------------------------------------------- */
+
+/* The graph: the vertices are the points of the subset; {a, b}, a != b, is an edge iff cell (a, b) OR cell (b, a) is
+ * not NaN (!is.na; igraph's mode = "undirected").  Threshold-coded cells and +Inf count as measured, the diagonal
+ * never makes an edge; the same graph for either layout flag.
+ *   n_cells       the non-NaN off-diagonal cells of the induced submatrix over both triangles (sum(adjacency));
+ *                 n_measurements = n_cells / 2, completeness = n_cells / (m (m - 1))
+ *   labels        m entries or NULL; labels[q] = the smallest position q' in `subset` whose point lies in the component
+ *                 of subset[q] (canonical: any correct algorithm gives the same array)
+ *   n_components  the number of q with labels[q] == q
+ * One pass over the matrix leaves a packed bit adjacency of the subset (m^2 / 8 bytes) and n_cells; the component
+ * rounds run on the bits, driven from the host until one changes nothing, at most m + 1 of them (TOPOLOW_ERR_HIP with
+ * a message beyond that -- never a hang).  A failed device allocation: TOPOLOW_ERR_UNSUPPORTED with a message. */
+int topolow_layout_prep_connectivity(topolow_layout_prep* p, const int32_t* subset, int32_t m, int32_t* n_components,
+                                     int64_t* n_cells, int32_t* labels /* m, or NULL */, char* errbuf, size_t errlen);
+
+/* A handle for the matrix parent[subset, subset]: rows and columns in the subset's given order, the parent's layout
+ * flag, its codes if it has any, its device.  Values and codes are gathered device to device; then the child goes
+ * through exactly what create() does after its upload (first pass, ordering rule, second pass), so `info`, fetch(),
+ * order() and every other entry give, bit for bit, what a handle created from the host-gathered submatrix gives.
+ * preserve_order and order_in as for create(), relative to the child's own m points.  The child owns its buffers
+ * (21 m^2 bytes, as a fresh handle), outlives the parent and serves every handle entry, these two included; the parent
+ * is not touched.  A failed device allocation: TOPOLOW_ERR_UNSUPPORTED with a message. */
+int topolow_layout_prep_subsample(topolow_layout_prep* parent, const int32_t* subset, int32_t m,
+                                  int32_t preserve_order, const int32_t* order_in, topolow_layout_prep** out,
+                                  topolow_layout_prep_info* info, char* errbuf, size_t errlen);
+
+/* A study entry (tests/study/subsample_timing.py): of this handle's last topolow_layout_prep_connectivity, the rounds
+ * launched (the last one changed nothing) and the wall-clock seconds of {the bit pass, the rounds}; 2 doubles out. */
+int topolow_layout_prep_graph_stats(const topolow_layout_prep* p, int32_t* rounds, double* seconds);
+
+/* ---------------------------------------------------------------------------------------
  * Device-resident session: the same relaxation with inputs kept in HBM, for callers that
  * run many iterations / many embeddings on data they already hold on the GPU (bench.py, the
  * row-sharded multi-GPU driver).  Pointers named d_* are DEVICE pointers.

@@ -15,6 +15,8 @@ from .core import (  # noqa: F401
     summary_topolow,
 )
 from ._native import NativeError, options, set_seed  # noqa: F401
+from .subsample import check_matrix_connectivity, subsample_dissimilarity_matrix  # noqa: F401
 
 __all__ = ["euclidean_embedding", "create_topolow_map", "print_topolow", "summary_topolow",
-           "Topolow", "RMatrix", "options", "set_seed", "NativeError", "prepare_layout_call"]
+           "Topolow", "RMatrix", "options", "set_seed", "NativeError", "prepare_layout_call",
+           "check_matrix_connectivity", "subsample_dissimilarity_matrix"]

@@ -362,6 +362,13 @@ def load() -> C.CDLL:
         C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, i64p, ip, ip, ip, ip, dp, C.c_char_p, C.c_size_t]
     lib.topolow_layout_prep_fold_seconds.restype = C.c_int
     lib.topolow_layout_prep_fold_seconds.argtypes = [vp, dp]
+    lib.topolow_layout_prep_connectivity.restype = C.c_int
+    lib.topolow_layout_prep_connectivity.argtypes = [vp, ip, C.c_int32, ip, i64p, ip, C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_subsample.restype = C.c_int
+    lib.topolow_layout_prep_subsample.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.POINTER(vp),
+                                                  C.POINTER(TopolowLayoutPrepInfo), C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_graph_stats.restype = C.c_int
+    lib.topolow_layout_prep_graph_stats.argtypes = [vp, ip, dp]
     lib.topolow_layout_order_from_sums.restype = C.c_int32
     lib.topolow_layout_order_from_sums.argtypes = [C.c_int32, dp, i64p, dp, i64p, C.c_int32, ip]
     _lib = lib
@@ -1081,6 +1088,54 @@ class PreparedHandle:
                              seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq, precision, -1,
                              _SCHEDULES[schedule])
         return out + (route,)
+
+    def _subset(self, indices):
+        """`indices` as the C entries take a subset: (int32 array or None, m).  None: all n points."""
+        if indices is None:
+            return None, self.n
+        sub = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        return sub, int(sub.shape[0])
+
+    def connectivity(self, subset=None):
+        """topolow_layout_prep_connectivity: the components of the measurement graph of the resident matrix, or of the
+        points `subset` of it (distinct 0-based indices into the matrix as it was given, any order), on the device.
+        Returns (n_components, n_cells, labels): n_cells the non-NaN off-diagonal cells of the induced submatrix over
+        both triangles, labels[q] the smallest position in `subset` whose point lies in the component of subset[q]."""
+        sub, m = self._subset(subset)
+        labels = np.empty(m, dtype=np.int32)
+        nc, cells = C.c_int32(0), C.c_int64(0)
+        rc = self.lib.topolow_layout_prep_connectivity(self._h, _ip(sub) if sub is not None else None, m, C.byref(nc),
+                                                       C.byref(cells), _ip(labels), self._err, len(self._err))
+        _check(rc, self._err)
+        return int(nc.value), int(cells.value), labels
+
+    def subsample(self, indices, preserve_order: bool = False, order_in=None) -> "PreparedHandle":
+        """topolow_layout_prep_subsample: a PreparedHandle for values[indices][:, indices] (and the codes), gathered
+        device to device and prepared as a fresh handle is -- everything it reports equals, bit for bit, what
+        PreparedHandle(values[np.ix_(indices, indices)], ...) reports.  `preserve_order` and `order_in` (the `order` of
+        the constructor) are relative to the child's own points.  The child outlives this handle; close it as any."""
+        sub, m = self._subset(indices)
+        oin = None
+        if order_in is not None:
+            oin = np.ascontiguousarray(order_in, dtype=np.int32).reshape(-1)
+            if oin.shape[0] != m and not (oin.shape[0] >= 1 and oin[0] == -1):
+                raise ValueError("order must have one entry per selected point")
+        child = PreparedHandle.__new__(PreparedHandle)
+        child.lib, child._h, child._err, child._order = self.lib, C.c_void_p(None), C.create_string_buffer(512), None
+        child.n, child.layout, child.has_codes = m, self.layout, self.has_codes
+        info = TopolowLayoutPrepInfo()
+        rc = self.lib.topolow_layout_prep_subsample(
+            self._h, _ip(sub) if sub is not None else None, m, 1 if preserve_order else 0,
+            _ip(oin) if oin is not None else None, C.byref(child._h), C.byref(info), child._err, len(child._err))
+        _check(rc, child._err)
+        child.info = {k: getattr(info, k) for k, _ in TopolowLayoutPrepInfo._fields_ if k != "reserved"}
+        return child
+
+    def graph_stats(self):
+        """(rounds, [seconds of the bit pass, seconds of the rounds]) of the last .connectivity on this handle."""
+        rounds, ph = C.c_int32(0), (C.c_double * 2)()
+        self.lib.topolow_layout_prep_graph_stats(self._h, C.byref(rounds), ph)
+        return int(rounds.value), list(ph)
 
     def fold_seconds(self) -> list:
         """Seconds of the last .cv_sweep on this handle, summed over its folds: preparation, hold-out, score, restore."""

@@ -41,6 +41,7 @@
 #include "relax_post.h"
 #include "relax_prep.h"
 #include "relax_prep_fold.h"
+#include "relax_prep_graph.h"
 
 using namespace topolow;
 
@@ -3225,7 +3226,7 @@ int topolow_post_metrics(const double* positions, int32_t n, int32_t ndim, const
 // matrices and counts the edges per column.  fetch(): the compaction, the reordered copy when asked for, and the
 // downloads, through the same pinned staging.  The matrix stays on the device between the two.
 struct topolow_layout_prep {
-  int n = 0, device = 0;
+  int n = 0, device = 0;                 // n first: the subset checks of the graph entries read nothing else of a handle
   bool transposed = false, has_codes = false, declined = false;
   DevBuf<double> vals, dense;
   DevBuf<int8_t> codes;
@@ -3244,6 +3245,9 @@ struct topolow_layout_prep {
   // so a fold's masked sums are judged with them (topolow_layout_prep_fold).
   bool exact_sums = false;
   bool negative_or_infinite = false;
+  // The last topolow_layout_prep_connectivity (relax_prep_graph.h): rounds launched; seconds of the bit pass, the rounds.
+  int graph_rounds = 0;
+  double graph_seconds[2] = {0.0, 0.0};
   // Cross-validation folds prepared from the handle (relax_prep_fold.h), allocated by the first fold.
   struct Fold {
     bool ready = false;
@@ -3358,16 +3362,165 @@ int32_t topolow_layout_order_from_sums(int32_t n, const double* row_sum, const i
   return exact ? TOPOLOW_ORDER_DEVICE_EXACT : TOPOLOW_ORDER_DEVICE_GAP;
 }
 
+namespace {
+
+// How the lines of an n x n matrix arrive on the device: in chunks of whole 64-line blocks of about kPrepChunkBytes.
+struct PrepChunks {
+  int chunk_lines, n_chunks, slots;
+  size_t chunk_cells;
+  explicit PrepChunks(int n) {
+    const size_t N = (size_t)n;
+    const int nb = (n + kPrepTile - 1) / kPrepTile;
+    chunk_lines = (int)std::min<size_t>(
+        (size_t)nb * kPrepTile, std::max<size_t>(kPrepTile, kPrepChunkBytes / (N * 8) / kPrepTile * kPrepTile));
+    n_chunks = (n + chunk_lines - 1) / chunk_lines;
+    slots = std::min(kPrepSlots, n_chunks);
+    chunk_cells = (size_t)std::min(chunk_lines, n) * N;
+  }
+};
+
+bool prep_order_in_ok(int32_t preserve_order, const int32_t* order_in, int n, char* errbuf, size_t errlen) {
+  if (!preserve_order && order_in != nullptr && order_in[0] != -1 && !prep_is_permutation(order_in, n)) {
+    set_err(errbuf, errlen, "order_in must be a permutation of 0..n-1, or start with -1");
+    return false;
+  }
+  return true;
+}
+
+// Everything a handle goes through once its matrix is on the device -- the ONE copy of the passes, reached by
+// topolow_layout_prep_create (the matrix arrives by upload) and topolow_layout_prep_subsample (it arrives by a gather
+// from another handle).  p holds n, device, transposed, has_codes and the allocated vals / codes; arrive(P, t, a0,
+// lines) enqueues the arrival of lines [a0, a0 + lines) -- chunk t of `g` -- so that P.run is ordered after it.  The
+// first pass runs on each chunk as it arrives (the same bits whatever the chunking), then the ordering rule, then --
+// unless the rule declines -- the second pass.  t0: when the caller began (phase_seconds[0] counts from it).
+void prep_passes(topolow_layout_prep* p, int32_t preserve_order, const int32_t* order_in, topolow_layout_prep_info* info,
+                 double t0, const PrepChunks& g, const std::function<void(PostPipe&, int, int, int)>& arrive) {
+  const int n = p->n;
+  const bool given = !preserve_order && order_in != nullptr;
+  const int8_t* codes = p->has_codes ? p->codes.p : nullptr;
+  const size_t N = (size_t)n, cells = N * N;
+  const int nb = (n + kPrepTile - 1) / kPrepTile;
+
+  // -- arrival and first pass, overlapped
+  DevBuf<double> part_slow_sum, part_fast_sum, line_sum;
+  DevBuf<int32_t> part_slow_cnt, part_fast_cnt, line_cnt;
+  DevBuf<uint8_t> diag;
+  DevBuf<PrepTotals> totals;
+  prep_alloc(part_slow_sum, (size_t)nb * N, "the partial sums");
+  prep_alloc(part_fast_sum, (size_t)nb * N, "the partial sums");
+  prep_alloc(part_slow_cnt, (size_t)nb * N, "the partial counts");
+  prep_alloc(part_fast_cnt, (size_t)nb * N, "the partial counts");
+  prep_alloc(line_sum, 2 * N, "the sums");
+  prep_alloc(line_cnt, 2 * N, "the counts");
+  prep_alloc(diag, N, "the diagonal flags");
+  prep_alloc(totals, 1, "the totals");
+  PostPipe P;
+  P.create(g.slots, 0);
+  HIP_TRY(hipMemsetAsync(totals.p, 0, sizeof(PrepTotals), P.run));
+  for (int t = 0; t < g.n_chunks; ++t) {
+    const int a0 = t * g.chunk_lines, lines = std::min(g.chunk_lines, n - a0);
+    arrive(P, t, a0, lines);
+    hipLaunchKernelGGL(prep_sums_kernel, dim3(nb, (lines + kPrepTile - 1) / kPrepTile), dim3(kPrepThreads), 0, P.run,
+                       p->vals.p, codes, n, a0, part_slow_sum.p, part_slow_cnt.p, part_fast_sum.p, part_fast_cnt.p,
+                       diag.p, totals.p);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(prep_finish_sums_kernel, dim3((n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, P.run,
+                     n, nb, part_slow_sum.p, part_slow_cnt.p, part_fast_sum.p, part_fast_cnt.p, line_sum.p, line_cnt.p);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> sums(2 * N);
+  std::vector<int32_t> cnts(2 * N);
+  std::vector<uint8_t> on_diag(N);
+  PrepTotals tot;
+  HIP_TRY(hipMemcpyAsync(sums.data(), line_sum.p, 2 * N * 8, hipMemcpyDeviceToHost, P.run));
+  HIP_TRY(hipMemcpyAsync(cnts.data(), line_cnt.p, 2 * N * 4, hipMemcpyDeviceToHost, P.run));
+  HIP_TRY(hipMemcpyAsync(on_diag.data(), diag.p, N, hipMemcpyDeviceToHost, P.run));
+  HIP_TRY(hipMemcpyAsync(&tot, totals.p, sizeof tot, hipMemcpyDeviceToHost, P.run));
+  P.sync();
+  const double t1 = now_s();
+
+  // -- the quantities of the info struct and the order
+  const size_t row_at = p->transposed ? 0 : N, col_at = p->transposed ? N : 0;   // slow lines are rows when transposed
+  std::vector<int64_t> row_cnt(N), col_cnt(N);
+  for (size_t q = 0; q < N; ++q) {
+    row_cnt[q] = (int64_t)cnts[row_at + q] - on_diag[q];
+    col_cnt[q] = (int64_t)cnts[col_at + q] - on_diag[q];
+  }
+  *info = topolow_layout_prep_info();
+  info->n_edges = -1;
+  info->n_finite_nonzero = (int64_t)tot.n_finite_nonzero;
+  info->n_infinite = (int64_t)tot.n_infinite;
+  info->n_negative = (int64_t)tot.n_negative;
+  info->exact_sums = tot.n_inexact == 0 ? 1 : 0;
+  p->exact_sums = tot.n_inexact == 0;
+  p->negative_or_infinite = tot.n_negative + tot.n_infinite > 0;
+  if (tot.max_key == 0) {
+    info->numeric_max = NAN;
+  } else {
+    const uint64_t bits = (tot.max_key >> 63) ? (uint64_t)(tot.max_key & 0x7fffffffffffffffull) : (uint64_t)~tot.max_key;
+    memcpy(&info->numeric_max, &bits, 8);
+  }
+  p->order.assign(N, 0);
+  p->order[0] = -1;
+  if (preserve_order) {
+    info->order_route = TOPOLOW_ORDER_PRESERVED;
+  } else if (given) {
+    info->order_route = TOPOLOW_ORDER_DECLINED;
+    std::copy(order_in, order_in + (order_in[0] == -1 ? 1 : n), p->order.begin());
+  } else {
+    const int32_t flag = info->exact_sums ? 1 : (tot.n_negative + tot.n_infinite > 0 ? -1 : 0);
+    info->order_route = topolow_layout_order_from_sums(n, sums.data() + row_at, row_cnt.data(), sums.data() + col_at,
+                                                       col_cnt.data(), flag, p->order.data());
+    if (info->order_route == TOPOLOW_ORDER_DECLINED) {
+      p->declined = true;
+      p->phase_seconds[0] = t1 - t0;
+      return;
+    }
+  }
+  const bool reordered = p->order[0] != -1;
+  info->reordered = reordered ? 1 : 0;
+  std::vector<int32_t> ord(N);
+  for (size_t q = 0; q < N; ++q) ord[q] = reordered ? p->order[q] : (int32_t)q;
+  p->degrees.resize(N);
+  for (size_t q = 0; q < N; ++q) p->degrees[q] = cnts[row_at + (size_t)ord[q]];
+  const double t2 = now_s();
+
+  // -- second pass: dense fill, edges per column
+  prep_alloc(p->ord, N, "the order");
+  prep_alloc(p->dense, cells, "the dense distances");
+  prep_alloc(p->tdense, cells, "the dense thresholds");
+  prep_alloc(p->edge_off, N + 1, "the edge offsets");
+  prep_alloc(p->ddeg, N, "the degrees");
+  HIP_TRY(hipMemcpyAsync(p->ddeg.p, p->degrees.data(), N * 4, hipMemcpyHostToDevice, P.run));
+  DevBuf<int32_t> col_edges;
+  prep_alloc(col_edges, N, "the edge counts");
+  HIP_TRY(hipMemcpyAsync(p->ord.p, ord.data(), N * 4, hipMemcpyHostToDevice, P.run));
+  hipLaunchKernelGGL(prep_dense_kernel, dim3(nb, nb), dim3(kPrepThreads), 0, P.run, p->vals.p, codes, n, p->ord.p,
+                     p->transposed ? 1 : 0, p->dense.p, p->tdense.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(prep_edge_count_kernel, dim3(n), dim3(kPrepThreads), 0, P.run, p->dense.p, n, col_edges.p);
+  HIP_TRY(hipGetLastError());
+  std::vector<int32_t> per_col(N);
+  HIP_TRY(hipMemcpyAsync(per_col.data(), col_edges.p, N * 4, hipMemcpyDeviceToHost, P.run));
+  HIP_TRY(hipStreamSynchronize(P.run));
+  std::vector<int64_t> off(N + 1, 0);
+  for (size_t j = 0; j < N; ++j) off[j + 1] = off[j] + per_col[j];
+  HIP_TRY(hipMemcpy(p->edge_off.p, off.data(), (N + 1) * 8, hipMemcpyHostToDevice));
+  p->n_edges = off[N];
+  info->n_edges = p->n_edges;
+  p->phase_seconds[0] = t1 - t0;
+  p->phase_seconds[1] = t2 - t1;
+  p->phase_seconds[2] = now_s() - t2;
+}
+
+}  // namespace
+
 int topolow_layout_prep_create(topolow_layout_prep** out, const double* values, const int8_t* codes, int32_t n,
                                int32_t transposed, int32_t preserve_order, const int32_t* order_in, int32_t device,
                                topolow_layout_prep_info* info, char* errbuf, size_t errlen) {
   if (!out || !values || !info || n < 2) return TOPOLOW_ERR_BAD_ARGUMENT;
   *out = nullptr;
-  const bool given = !preserve_order && order_in != nullptr;
-  if (given && order_in[0] != -1 && !prep_is_permutation(order_in, n)) {
-    set_err(errbuf, errlen, "order_in must be a permutation of 0..n-1, or start with -1");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
+  if (!prep_order_in_ok(preserve_order, order_in, n, errbuf, errlen)) return TOPOLOW_ERR_BAD_ARGUMENT;
   std::unique_ptr<topolow_layout_prep> p(new topolow_layout_prep());
   const int rc = guarded(errbuf, errlen, [&] {
     p->device = select_device(device);
@@ -3375,137 +3528,27 @@ int topolow_layout_prep_create(topolow_layout_prep** out, const double* values, 
     p->transposed = transposed != 0;
     p->has_codes = codes != nullptr;
     const size_t N = (size_t)n, cells = N * N;
-    const int nb = (n + kPrepTile - 1) / kPrepTile;
     const double t0 = now_s();
-
-    // -- upload and first pass, overlapped
     prep_alloc(p->vals, cells, "the matrix");
     if (codes) prep_alloc(p->codes, cells, "the codes");
-    DevBuf<double> part_slow_sum, part_fast_sum, line_sum;
-    DevBuf<int32_t> part_slow_cnt, part_fast_cnt, line_cnt;
-    DevBuf<uint8_t> diag;
-    DevBuf<PrepTotals> totals;
-    prep_alloc(part_slow_sum, (size_t)nb * N, "the partial sums");
-    prep_alloc(part_fast_sum, (size_t)nb * N, "the partial sums");
-    prep_alloc(part_slow_cnt, (size_t)nb * N, "the partial counts");
-    prep_alloc(part_fast_cnt, (size_t)nb * N, "the partial counts");
-    prep_alloc(line_sum, 2 * N, "the sums");
-    prep_alloc(line_cnt, 2 * N, "the counts");
-    prep_alloc(diag, N, "the diagonal flags");
-    prep_alloc(totals, 1, "the totals");
-    const int chunk_lines = (int)std::min<size_t>(
-        (size_t)nb * kPrepTile, std::max<size_t>(kPrepTile, kPrepChunkBytes / (N * 8) / kPrepTile * kPrepTile));
-    const int n_chunks = (n + chunk_lines - 1) / chunk_lines, slots = std::min(kPrepSlots, n_chunks);
-    const size_t chunk_cells = (size_t)std::min(chunk_lines, n) * N;
+    // the matrix goes up in chunks through pinned staging, the slots going round
+    const PrepChunks g(n);
     PinBuf pvals[kPrepSlots], pcodes[kPrepSlots];
-    PostPipe P;
-    for (int b = 0; b < slots; ++b) {
-      pvals[b].alloc(chunk_cells * 8);
-      if (codes) pcodes[b].alloc(chunk_cells);
+    for (int b = 0; b < g.slots; ++b) {
+      pvals[b].alloc(g.chunk_cells * 8);
+      if (codes) pcodes[b].alloc(g.chunk_cells);
     }
-    P.create(slots, 0);
-    HIP_TRY(hipMemsetAsync(totals.p, 0, sizeof(PrepTotals), P.run));
-    for (int t = 0; t < n_chunks; ++t) {
-      const int b = t % slots, a0 = t * chunk_lines, lines = std::min(chunk_lines, n - a0);
+    prep_passes(p.get(), preserve_order, order_in, info, t0, g, [&](PostPipe& P, int t, int a0, int lines) {
+      const int b = t % g.slots;
       const size_t off = (size_t)a0 * N, len = (size_t)lines * N;
-      if (t >= slots) HIP_TRY(hipEventSynchronize(P.up_done[b]));   // chunk t - slots has left the staging buffers
+      if (t >= g.slots) HIP_TRY(hipEventSynchronize(P.up_done[b]));   // chunk t - slots has left the staging buffers
       post_host_copy(pvals[b].p, values + off, len * 8);
       if (codes) post_host_copy(pcodes[b].p, codes + off, len);
       HIP_TRY(hipMemcpyAsync(p->vals.p + off, pvals[b].p, len * 8, hipMemcpyHostToDevice, P.up));
       if (codes) HIP_TRY(hipMemcpyAsync(p->codes.p + off, pcodes[b].p, len, hipMemcpyHostToDevice, P.up));
       HIP_TRY(hipEventRecord(P.up_done[b], P.up));
       HIP_TRY(hipStreamWaitEvent(P.run, P.up_done[b], 0));
-      hipLaunchKernelGGL(prep_sums_kernel, dim3(nb, (lines + kPrepTile - 1) / kPrepTile), dim3(kPrepThreads), 0, P.run,
-                         p->vals.p, codes ? p->codes.p : nullptr, n, a0, part_slow_sum.p, part_slow_cnt.p,
-                         part_fast_sum.p, part_fast_cnt.p, diag.p, totals.p);
-      HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(prep_finish_sums_kernel, dim3((n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, P.run,
-                       n, nb, part_slow_sum.p, part_slow_cnt.p, part_fast_sum.p, part_fast_cnt.p, line_sum.p, line_cnt.p);
-    HIP_TRY(hipGetLastError());
-    std::vector<double> sums(2 * N);
-    std::vector<int32_t> cnts(2 * N);
-    std::vector<uint8_t> on_diag(N);
-    PrepTotals tot;
-    HIP_TRY(hipMemcpyAsync(sums.data(), line_sum.p, 2 * N * 8, hipMemcpyDeviceToHost, P.run));
-    HIP_TRY(hipMemcpyAsync(cnts.data(), line_cnt.p, 2 * N * 4, hipMemcpyDeviceToHost, P.run));
-    HIP_TRY(hipMemcpyAsync(on_diag.data(), diag.p, N, hipMemcpyDeviceToHost, P.run));
-    HIP_TRY(hipMemcpyAsync(&tot, totals.p, sizeof tot, hipMemcpyDeviceToHost, P.run));
-    P.sync();
-    const double t1 = now_s();
-
-    // -- the quantities of the info struct and the order
-    const size_t row_at = p->transposed ? 0 : N, col_at = p->transposed ? N : 0;   // slow lines are rows when transposed
-    std::vector<int64_t> row_cnt(N), col_cnt(N);
-    for (size_t q = 0; q < N; ++q) {
-      row_cnt[q] = (int64_t)cnts[row_at + q] - on_diag[q];
-      col_cnt[q] = (int64_t)cnts[col_at + q] - on_diag[q];
-    }
-    *info = topolow_layout_prep_info();
-    info->n_edges = -1;
-    info->n_finite_nonzero = (int64_t)tot.n_finite_nonzero;
-    info->n_infinite = (int64_t)tot.n_infinite;
-    info->n_negative = (int64_t)tot.n_negative;
-    info->exact_sums = tot.n_inexact == 0 ? 1 : 0;
-    p->exact_sums = tot.n_inexact == 0;
-    p->negative_or_infinite = tot.n_negative + tot.n_infinite > 0;
-    if (tot.max_key == 0) {
-      info->numeric_max = NAN;
-    } else {
-      const uint64_t bits = (tot.max_key >> 63) ? (uint64_t)(tot.max_key & 0x7fffffffffffffffull) : (uint64_t)~tot.max_key;
-      memcpy(&info->numeric_max, &bits, 8);
-    }
-    p->order.assign(N, 0);
-    p->order[0] = -1;
-    if (preserve_order) {
-      info->order_route = TOPOLOW_ORDER_PRESERVED;
-    } else if (given) {
-      info->order_route = TOPOLOW_ORDER_DECLINED;
-      std::copy(order_in, order_in + (order_in[0] == -1 ? 1 : n), p->order.begin());
-    } else {
-      const int32_t flag = info->exact_sums ? 1 : (tot.n_negative + tot.n_infinite > 0 ? -1 : 0);
-      info->order_route = topolow_layout_order_from_sums(n, sums.data() + row_at, row_cnt.data(), sums.data() + col_at,
-                                                         col_cnt.data(), flag, p->order.data());
-      if (info->order_route == TOPOLOW_ORDER_DECLINED) {
-        p->declined = true;
-        p->phase_seconds[0] = t1 - t0;
-        return;
-      }
-    }
-    const bool reordered = p->order[0] != -1;
-    info->reordered = reordered ? 1 : 0;
-    std::vector<int32_t> ord(N);
-    for (size_t q = 0; q < N; ++q) ord[q] = reordered ? p->order[q] : (int32_t)q;
-    p->degrees.resize(N);
-    for (size_t q = 0; q < N; ++q) p->degrees[q] = cnts[row_at + (size_t)ord[q]];
-    const double t2 = now_s();
-
-    // -- second pass: dense fill, edges per column
-    prep_alloc(p->ord, N, "the order");
-    prep_alloc(p->dense, cells, "the dense distances");
-    prep_alloc(p->tdense, cells, "the dense thresholds");
-    prep_alloc(p->edge_off, N + 1, "the edge offsets");
-    prep_alloc(p->ddeg, N, "the degrees");
-    HIP_TRY(hipMemcpyAsync(p->ddeg.p, p->degrees.data(), N * 4, hipMemcpyHostToDevice, P.run));
-    DevBuf<int32_t> col_edges;
-    prep_alloc(col_edges, N, "the edge counts");
-    HIP_TRY(hipMemcpyAsync(p->ord.p, ord.data(), N * 4, hipMemcpyHostToDevice, P.run));
-    hipLaunchKernelGGL(prep_dense_kernel, dim3(nb, nb), dim3(kPrepThreads), 0, P.run, p->vals.p,
-                       codes ? p->codes.p : nullptr, n, p->ord.p, p->transposed ? 1 : 0, p->dense.p, p->tdense.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(prep_edge_count_kernel, dim3(n), dim3(kPrepThreads), 0, P.run, p->dense.p, n, col_edges.p);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> per_col(N);
-    HIP_TRY(hipMemcpyAsync(per_col.data(), col_edges.p, N * 4, hipMemcpyDeviceToHost, P.run));
-    HIP_TRY(hipStreamSynchronize(P.run));
-    std::vector<int64_t> off(N + 1, 0);
-    for (size_t j = 0; j < N; ++j) off[j + 1] = off[j] + per_col[j];
-    HIP_TRY(hipMemcpy(p->edge_off.p, off.data(), (N + 1) * 8, hipMemcpyHostToDevice));
-    p->n_edges = off[N];
-    info->n_edges = p->n_edges;
-    p->phase_seconds[0] = t1 - t0;
-    p->phase_seconds[1] = t2 - t1;
-    p->phase_seconds[2] = now_s() - t2;
+    });
   });
   if (rc != TOPOLOW_OK) return rc;
   *out = p.release();
@@ -3577,6 +3620,147 @@ void topolow_layout_prep_destroy(topolow_layout_prep* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
   delete p;
+}
+
+// ---- the measurement graph of a handle and its sub-handles (relax_prep_graph.h) ----
+namespace {
+
+// The rules both graph entries share for `subset` (NULL: all n points); no device call.  n is the handle's.
+int prep_check_subset(int n, const int32_t* subset, int32_t m, char* errbuf, size_t errlen) {
+  if (subset == nullptr) return TOPOLOW_OK;
+  if (m < 2 || m > n) {
+    set_err(errbuf, errlen, "subset: m = %d must be between 2 and the handle's n = %d", (int)m, n);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  std::vector<char> seen((size_t)n, 0);
+  for (int q = 0; q < m; ++q) {
+    const int32_t x = subset[q];
+    if (x < 0 || x >= n) {
+      set_err(errbuf, errlen, "subset[%d] = %d is out of range (0 .. %d)", q, (int)x, n - 1);
+      return TOPOLOW_ERR_BAD_ARGUMENT;
+    }
+    if (seen[(size_t)x]) {
+      set_err(errbuf, errlen, "subset[%d] = %d is a repeated index", q, (int)x);
+      return TOPOLOW_ERR_BAD_ARGUMENT;
+    }
+    seen[(size_t)x] = 1;
+  }
+  return TOPOLOW_OK;
+}
+
+}  // namespace
+
+int topolow_layout_prep_connectivity(topolow_layout_prep* p, const int32_t* subset, int32_t m, int32_t* n_components,
+                                     int64_t* n_cells, int32_t* labels, char* errbuf, size_t errlen) {
+  if (!p || !n_components || !n_cells) {
+    set_err(errbuf, errlen, "topolow_layout_prep_connectivity: the handle, n_components and n_cells must not be NULL");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  const int rcs = prep_check_subset(p->n, subset, m, errbuf, errlen);
+  if (rcs != TOPOLOW_OK) return rcs;
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(p->device));
+    const double t0 = now_s();
+    const int M = subset != nullptr ? m : p->n;
+    const int words = (M + 63) / 64;
+    DevBuf<int32_t> sub, parent, changed;
+    DevBuf<unsigned long long> bits, cells;
+    if (subset != nullptr) prep_alloc(sub, (size_t)M, "the subset");
+    prep_alloc(parent, (size_t)M, "the component labels");
+    prep_alloc(changed, 1, "the round flag");
+    prep_alloc(bits, (size_t)M * (size_t)words, "the bit adjacency");
+    prep_alloc(cells, 1, "the cell count");
+    PostPipe P;
+    P.create(0, 0);
+    if (subset != nullptr) HIP_TRY(hipMemcpyAsync(sub.p, subset, (size_t)M * 4, hipMemcpyHostToDevice, P.run));
+    HIP_TRY(hipMemsetAsync(cells.p, 0, sizeof(unsigned long long), P.run));
+    hipLaunchKernelGGL(graph_bits_kernel, dim3(M), dim3(kGraphThreads), 0, P.run, p->vals.p, p->n,
+                       subset != nullptr ? sub.p : nullptr, M, words, bits.p, parent.p, cells.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long set_bits = 0;
+    HIP_TRY(hipMemcpyAsync(&set_bits, cells.p, sizeof set_bits, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipStreamSynchronize(P.run));
+    const double t1 = now_s();
+    // the rounds: flatten, hook, ask whether anything was hooked; the round that hooks nothing leaves the labels
+    int rounds = 0;
+    for (;;) {
+      if (rounds > M)   // a round that hooks lowers a label; this many cannot happen
+        throw HipError{TOPOLOW_ERR_HIP, "connectivity: the component rounds did not settle within m + 1 rounds"};
+      ++rounds;
+      int32_t any = 0;
+      HIP_TRY(hipMemsetAsync(changed.p, 0, sizeof(int32_t), P.run));
+      hipLaunchKernelGGL(graph_jump_kernel, dim3((M + kGraphThreads - 1) / kGraphThreads), dim3(kGraphThreads), 0, P.run,
+                         parent.p, M);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(graph_hook_kernel, dim3((M + kGraphWaves - 1) / kGraphWaves), dim3(kGraphThreads), 0, P.run,
+                         bits.p, M, words, parent.p, changed.p);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&any, changed.p, sizeof any, hipMemcpyDeviceToHost, P.run));
+      HIP_TRY(hipStreamSynchronize(P.run));
+      if (!any) break;
+    }
+    std::vector<int32_t> lab((size_t)M);
+    HIP_TRY(hipMemcpyAsync(lab.data(), parent.p, (size_t)M * 4, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipStreamSynchronize(P.run));
+    int32_t roots = 0;
+    for (int q = 0; q < M; ++q) roots += lab[(size_t)q] == q ? 1 : 0;
+    *n_components = roots;
+    *n_cells = (int64_t)set_bits;
+    if (labels != nullptr) std::copy(lab.begin(), lab.end(), labels);
+    p->graph_rounds = rounds;
+    p->graph_seconds[0] = t1 - t0;
+    p->graph_seconds[1] = now_s() - t1;
+  });
+}
+
+int topolow_layout_prep_subsample(topolow_layout_prep* parent, const int32_t* subset, int32_t m,
+                                  int32_t preserve_order, const int32_t* order_in, topolow_layout_prep** out,
+                                  topolow_layout_prep_info* info, char* errbuf, size_t errlen) {
+  if (!parent || !out || !info) {
+    set_err(errbuf, errlen, "topolow_layout_prep_subsample: the parent, out and info must not be NULL");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  *out = nullptr;
+  const int rcs = prep_check_subset(parent->n, subset, m, errbuf, errlen);
+  if (rcs != TOPOLOW_OK) return rcs;
+  const int M = subset != nullptr ? m : parent->n;
+  if (!prep_order_in_ok(preserve_order, order_in, M, errbuf, errlen)) return TOPOLOW_ERR_BAD_ARGUMENT;
+  std::unique_ptr<topolow_layout_prep> p(new topolow_layout_prep());
+  const int rc = guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(parent->device));
+    p->device = parent->device;
+    p->n = M;
+    p->transposed = parent->transposed;
+    p->has_codes = parent->has_codes;
+    const size_t cells = (size_t)M * (size_t)M;
+    const double t0 = now_s();
+    prep_alloc(p->vals, cells, "the matrix");
+    if (p->has_codes) prep_alloc(p->codes, cells, "the codes");
+    DevBuf<int32_t> sub;
+    if (subset != nullptr) {
+      prep_alloc(sub, (size_t)M, "the subset");
+      HIP_TRY(hipMemcpy(sub.p, subset, (size_t)M * 4, hipMemcpyHostToDevice));
+    }
+    // the matrix arrives from the parent, a chunk of lines per launch on the stream of the passes
+    const PrepChunks g(M);
+    prep_passes(p.get(), preserve_order, order_in, info, t0, g, [&](PostPipe& P, int, int a0, int lines) {
+      hipLaunchKernelGGL(graph_gather_kernel, dim3(lines), dim3(kGraphThreads), 0, P.run, parent->vals.p,
+                         parent->has_codes ? parent->codes.p : nullptr, parent->n, subset != nullptr ? sub.p : nullptr, M,
+                         a0, p->vals.p, p->has_codes ? p->codes.p : nullptr);
+      HIP_TRY(hipGetLastError());
+    });
+  });
+  if (rc != TOPOLOW_OK) return rc;
+  *out = p.release();
+  return TOPOLOW_OK;
+}
+
+int topolow_layout_prep_graph_stats(const topolow_layout_prep* p, int32_t* rounds, double* seconds) {
+  if (!p || !rounds || !seconds) return TOPOLOW_ERR_BAD_ARGUMENT;
+  *rounds = p->graph_rounds;
+  seconds[0] = p->graph_seconds[0];
+  seconds[1] = p->graph_seconds[1];
+  return TOPOLOW_OK;
 }
 
 // ---- ONE embedding row-sharded over several sessions (one process, one host thread per block) ----

@@ -12,6 +12,7 @@ import math
 import os
 import warnings
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import nullcontext
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -334,7 +335,7 @@ def _pooled(per_set):
 
 def _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon, preserve_order,
                           precision, convergence_counter: int = 5, session: Optional[bool] = None,
-                          schedule: str = "auto", resident: bool = False):
+                          schedule: str = "auto", resident: bool = False, handle=None):
     """The sweep as ONE library call: the batch (topolow_cv_sweep), or -- session = True, or None and a fold does not
     fit the batch kernel's one workgroup -- resident sessions (topolow_cv_sweep_session; a fold without valid
     measurements is then left out instead of handing the sweep back); resident = True: the session sweep from a prepared
@@ -364,7 +365,7 @@ def _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, 
     if resident:
         hsum, hcnt, its, conv, ec, secs, rerouted = _sweep_resident(
             m, builder, preserve_order, nd, k0, cr, cp, picks, draws, seeds, mapping_max_iter, relative_epsilon,
-            convergence_counter, precision or "auto", schedule)
+            convergence_counter, precision or "auto", schedule, handle=handle)
         return _pooled(_rows_per_set(param_sets, owners, hsum, hcnt, its, conv, ec)), secs, len(picks), rerouted
     if session is None:
         n_edges = int(np.sum(builder.rows < builder.cols))
@@ -395,14 +396,17 @@ def _rows_per_set(param_sets, owners, hsum, hcnt, its, conv, ec):
 
 
 def _sweep_resident(m, builder, preserve_order, nd, k0, cr, cp, picks, draws, seeds, mapping_max_iter, relative_epsilon,
-                    convergence_counter, precision, schedule):
+                    convergence_counter, precision, schedule, handle=None):
     """The session sweep from ONE upload of the matrix (PreparedHandle.cv_sweep): values and codes as
     core._device_front hands them over, the handle opened with preserve_order=True (the folds' labels are the caller's).
+    `handle`: an open PreparedHandle of this matrix, created with preserve_order=True (a subsample's child, say) -- it
+    is used as it is and left open; nothing is uploaded.
     Exactly the folds the device declined to order are rerun through cv_sweep_session -- the library's cell list is
     built only then -- and merged in fold order.  Returns cv_sweep_session's six outputs and the number of rerouted
     folds."""
     codes = m.codes if m.codes.any() else None
-    with _native.PreparedHandle(m.values, codes, preserve_order=True) as handle:
+    opened = _native.PreparedHandle(m.values, codes, preserve_order=True) if handle is None else nullcontext(handle)
+    with opened as handle:   # a given handle is left open
         hsum, hcnt, its, conv, ec, secs, route = handle.cv_sweep(
             m.names is not None, preserve_order, nd, k0, cr, cp, picks, draws, seeds, mapping_max_iter, relative_epsilon,
             convergence_counter, 3, precision, schedule=schedule)
@@ -421,7 +425,7 @@ def _sweep_resident(m, builder, preserve_order, nd, k0, cr, cp, picks, draws, se
 def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]], mapping_max_iter: int,
                      relative_epsilon: float, folds: int = 20, preserve_order: bool = False,
                      rng: Optional[np.random.Generator] = None, precision: Optional[str] = None,
-                     path: str = "sparse", convergence_counter: int = 5, schedule: str = "auto"):
+                     path: str = "sparse", convergence_counter: int = 5, schedule: str = "auto", handle=None):
     """`likelihood_function` for MANY parameter sets at once: all folds of all sets are relaxed
     in ONE batched launch, and the held-out cells are scored on the device (no est_distances, no
     n x n arrays).  param_sets: dicts with N (ndim), k0, cooling_rate, c_repulsion.
@@ -439,7 +443,10 @@ def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]
     holds the matrix, every fold's ordering, degrees, held-out pairs and scored cells are derived from it on the device);
     same draws, same stream position, same numbers as "session".  A fold whose ordering the device cannot prove equal
     to NumPy's is rerun through the session sweep; the return value gains a FOURTH element, the number of folds so
-    rerouted (0 on most data).  Opt-in: no other path routes to it;
+    rerouted (0 on most data).  Opt-in: no other path routes to it.  `handle`: an open _native.PreparedHandle of this
+    very matrix created with preserve_order=True -- the child that subsample_dissimilarity_matrix(..., handle=parent)
+    returns, say: the sweep reads it instead of uploading the matrix and leaves it open; with any other path a
+    `handle` is a ValueError;
     precision: None = "f64" on the batch paths and, on sessions, f32 for the slab schedule / f64 for "gs";
     path = "dense" runs the reference's own sequence per fold instead (masked n x n matrix ->
     prepare_layout_call -> est_distances -> error_calculator_comparison): same folds, same start
@@ -457,6 +464,13 @@ def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]
         raise ValueError("dissimilarity_matrix must be a matrix")
     if path not in ("sparse", "sparse-calls", "dense", "session", "resident"):
         raise ValueError("path must be 'sparse', 'sparse-calls', 'dense', 'session' or 'resident'")
+    if handle is not None:
+        if path != "resident":
+            raise ValueError("handle is taken by path = 'resident' only")
+        if not handle._h or handle.declined or handle.info["order_route"] != _native.ORDER_PRESERVED:
+            raise ValueError("handle must be an open PreparedHandle created with preserve_order=True")
+        if handle.n != m.values.shape[0]:
+            raise ValueError("handle holds a matrix of another size")
     builder = FoldBuilder(m) if path != "dense" else None
     if builder is not None:      # the matrix half of R/core.R:202-264 once; per set only the parameters
         with warnings.catch_warnings():
@@ -465,7 +479,8 @@ def likelihood_sweep(dissimilarity_matrix, param_sets: Sequence[Dict[str, float]
     state0 = rng.bit_generator.state
     if path == "resident":
         return _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon,
-                                     preserve_order, precision, convergence_counter, schedule=schedule, resident=True)
+                                     preserve_order, precision, convergence_counter, schedule=schedule, resident=True,
+                                     handle=handle)
     if path in ("sparse", "session"):
         fused = _sweep_in_the_library(m, builder, param_sets, folds, rng, mapping_max_iter, relative_epsilon,
                                       preserve_order, precision, convergence_counter,
