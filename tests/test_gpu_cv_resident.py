@@ -201,6 +201,36 @@ def test_two_ndim_groups_and_two_calls_on_one_handle_give_the_same_numbers():
     assert not got[4].any() and set(got[6].tolist()) == {_native.ORDER_DEVICE_GAP}
 
 
+def test_bad_folds_in_the_middle_of_a_group_leave_the_others_and_the_handle_alone():
+    """One ndim-2 group around a fold that fails its check (every measured cell picked), one that goes non-finite
+    (k0 = 1e30: the library's own NaN detection) and one of ndim < 1: both sweeps report the same five outputs, the
+    ordinary folds are what they are without the bad ones, and the mask is empty afterwards."""
+    D, codes, m, fb = sweep_problem(True)
+    ndims = [2, 2, 2, 0, 2, 2]
+    picks, draws, seeds = draw_folds(fb, ndims, 41)
+    picks = list(picks)
+    picks[1] = fb.rows + fb.cols * N
+    k0 = [5.0, 5.0, 1e30, 5.0, 5.0, 5.0]
+    good = [0, 4, 5]
+
+    def args(which):
+        return (True, False, [ndims[f] for f in which], [k0[f] for f in which], [0.02] * len(which),
+                [0.01] * len(which), [picks[f] for f in which], [draws[f] for f in which], [seeds[f] for f in which],
+                30, 1e-4, 5, 3)
+    with _native.PreparedHandle(D, codes, preserve_order=True) as h:
+        got = h.cv_sweep(*args(range(6)))
+        want = _native.cv_sweep_session(fb.cells(), *args(range(6)))
+        clean = h.cv_sweep(*args(good))
+        after = h.fold(picks[0], False, True)
+    assert_same_sweep(got, want, ("bad folds",))
+    assert got[4].tolist() == [_native.OK, _native.ERR_BAD_ARGUMENT, _native.ERR_NONFINITE, _native.ERR_BAD_ARGUMENT,
+                               _native.OK, _native.OK]
+    for name, a, b in zip(SWEEP_OUTPUTS, got[:5], clean[:5]):
+        assert rh.same_bits(a[good], b), (name, a, b)
+    assert got[1][good].min() > 0 and np.all(got[2][good] > 0)
+    assert_same_fold(after, _native.cv_fold_pairs(fb.cells(), picks[0], False, True), ("after the bad folds",))
+
+
 def test_the_handle_is_untouched_by_a_sweep():
     """The mask is cleared and vals / codes were never written: post_metrics and optimize on the handle give the bits
     they gave before the sweep, and a fold prepared afterwards is the fold prepared before."""

@@ -6,13 +6,11 @@
 // the host maps "slow"/"fast" to "row"/"column" and no transposed copy is made.
 #pragma once
 
-#include "relax_common.h"
+#include "relax_prep_rank.h"
 
 namespace topolow {
 
 constexpr int kPrepTile = 64;
-constexpr int kPrepThreads = 256;
-constexpr int kPrepWaves = kPrepThreads / 64;
 
 // Whole-matrix quantities.  Integer counts and a maximum: atomics do not make them depend on the grid.
 struct PrepTotals {
@@ -30,25 +28,34 @@ __device__ inline unsigned long long prep_wave_sum(unsigned long long x) {
   for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
   return x;
 }
+__device__ inline unsigned long long prep_wave_max(unsigned long long x) {
+  for (int off = 32; off > 0; off >>= 1) x = max(x, (unsigned long long)__shfl_down(x, off, 64));
+  return x;
+}
+// A wave's share x of a whole-matrix total: lane 0 adds it (kMax: takes the maximum with it) where it is not 0.
+template <bool kMax = false>
+__device__ inline void prep_flush(unsigned long long* total, unsigned long long x) {
+  x = kMax ? prep_wave_max(x) : prep_wave_sum(x);
+  if ((threadIdx.x & 63) == 0 && x) kMax ? atomicMax(total, x) : atomicAdd(total, x);
+}
 
-// First pass: one workgroup per 64 x 64 tile (slow block ta = slow0 / 64 + blockIdx.y, fast block tb = blockIdx.x).
-// The tile goes to LDS once -- lanes along the contiguous index, 8-byte loads, consecutive lanes on consecutive
-// addresses -- with NA, the diagonal and cells past n as 0.0, and a flag per non-NA cell.  Then thread t < 64 adds
-// slow line t of the tile and thread 64 + t fast line t, both sequentially in index order from 0.0: the partial of
-// (point, block of 64 cells) is the same bits along either direction, whatever the layout and whatever the grid.
-//   part_slow_sum / part_slow_cnt   [tb * n + a]: slow line a over fast block tb
-//   part_fast_sum / part_fast_cnt   [ta * n + b]: fast line b over slow block ta
-//   diag_counts[a]                  1 iff the diagonal cell is not NA (the counts include it, the sums do not)
-__global__ __launch_bounds__(kPrepThreads) void prep_sums_kernel(
-    const double* __restrict__ vals, const int8_t* __restrict__ codes, int n, int slow0,
-    double* __restrict__ part_slow_sum, int32_t* __restrict__ part_slow_cnt, double* __restrict__ part_fast_sum,
-    int32_t* __restrict__ part_fast_cnt, uint8_t* __restrict__ diag_counts, PrepTotals* __restrict__ totals) {
+// The sums pass of one 64 x 64 tile (slow block ta, fast block tb = blockIdx.x), shared with the masked sums of a fold
+// (relax_prep_fold.h).  The tile goes to LDS once -- lanes along the contiguous index, 8-byte loads, consecutive lanes
+// on consecutive addresses -- with cells that are not kept, the diagonal and cells past n as 0.0, and a flag per kept
+// cell.  Then thread t < 64 adds slow line t of the tile and thread 64 + t fast line t, both sequentially in index
+// order from 0.0: the partial of (point, block of 64 cells) is the same bits along either direction, whatever the
+// layout and whatever the grid.  part_slow_* [tb * n + a]: slow line a over fast block tb; part_fast_* [ta * n + b]:
+// fast line b over slow block ta; diag_counts[a]: is the diagonal cell kept (the counts include it, the sums do not).
+// Cells is the per-cell policy: kept(cell, v) -- does B[cell] = v count?; count(a, b, cell, v) -- a kept cell's share
+// of the caller's totals; flush() -- after the tile, the wave's totals to memory, one lane per wave.
+template <typename Cells>
+__device__ inline void prep_tile_sums(const double* __restrict__ vals, int n, int ta,
+                                      double* __restrict__ part_slow_sum, int32_t* __restrict__ part_slow_cnt,
+                                      double* __restrict__ part_fast_sum, int32_t* __restrict__ part_fast_cnt,
+                                      uint8_t* __restrict__ diag_counts, Cells cells) {
   __shared__ double tile[kPrepTile][kPrepTile + 1];
   __shared__ uint8_t flag[kPrepTile][kPrepTile + 4];
-  const int tb = blockIdx.x, ta = slow0 / kPrepTile + blockIdx.y;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int b = tb * kPrepTile + lane;
-  unsigned long long finite_nonzero = 0, infinite = 0, negative = 0, inexact = 0, max_key = 0;
+  const int tb = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = tb * kPrepTile + lane;
   for (int r = wave; r < kPrepTile; r += kPrepWaves) {
     const int a = ta * kPrepTile + r;
     double x = 0.0;
@@ -56,60 +63,68 @@ __global__ __launch_bounds__(kPrepThreads) void prep_sums_kernel(
     if (a < n && b < n) {
       const size_t cell = (size_t)a * (size_t)n + (size_t)b;
       const double v = vals[cell];
-      const int c = codes != nullptr ? (int)codes[cell] : 0;
-      if (!__builtin_isnan(v)) {
+      if (cells.kept(cell, v)) {
         f = 1;
         if (a != b) x = v;
-        if (__builtin_isinf(v)) ++infinite;
-        if (v < 0.0) ++negative;
-        const double scaled = v * 1024.0;
-        if (!(v >= 0.0 && v < 1048576.0 && scaled == ::floor(scaled))) ++inexact;
-        if (c == 0) {
-          const unsigned long long key = prep_order_key(v);
-          max_key = key > max_key ? key : max_key;
-          if (__builtin_isfinite(v) && v != 0.0) ++finite_nonzero;
-        }
+        cells.count(a, b, cell, v);
       }
       if (a == b) diag_counts[a] = f;
     }
     tile[r][lane] = x;
     flag[r][lane] = f;
   }
-  finite_nonzero = prep_wave_sum(finite_nonzero);
-  infinite = prep_wave_sum(infinite);
-  negative = prep_wave_sum(negative);
-  inexact = prep_wave_sum(inexact);
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long other = __shfl_down(max_key, off, 64);
-    max_key = other > max_key ? other : max_key;
-  }
-  if (lane == 0) {
-    if (finite_nonzero) atomicAdd(&totals->n_finite_nonzero, finite_nonzero);
-    if (infinite) atomicAdd(&totals->n_infinite, infinite);
-    if (negative) atomicAdd(&totals->n_negative, negative);
-    if (inexact) atomicAdd(&totals->n_inexact, inexact);
-    if (max_key) atomicMax(&totals->max_key, max_key);
-  }
+  cells.flush();
   __syncthreads();
-  if (threadIdx.x < kPrepTile) {
-    const int r = threadIdx.x, a = ta * kPrepTile + r;
-    if (a < n) {
-      double s = 0.0;
-      int32_t k = 0;
-      for (int q = 0; q < kPrepTile; ++q) { s += tile[r][q]; k += flag[r][q]; }
-      part_slow_sum[(size_t)tb * n + a] = s;
-      part_slow_cnt[(size_t)tb * n + a] = k;
+  auto add_line = [&](bool slow, int blk, int p, double* __restrict__ sum, int32_t* __restrict__ cnt) {
+    if (p >= n) return;   // point p's line `lane` of the tile, over block blk of the other index
+    double s = 0.0;
+    int32_t k = 0;
+    for (int q = 0; q < kPrepTile; ++q) {
+      s += slow ? tile[lane][q] : tile[q][lane];
+      k += slow ? flag[lane][q] : flag[q][lane];
     }
-  } else if (threadIdx.x < 2 * kPrepTile) {
-    const int l = threadIdx.x - kPrepTile, bb = tb * kPrepTile + l;
-    if (bb < n) {
-      double s = 0.0;
-      int32_t k = 0;
-      for (int q = 0; q < kPrepTile; ++q) { s += tile[q][l]; k += flag[q][l]; }
-      part_fast_sum[(size_t)ta * n + bb] = s;
-      part_fast_cnt[(size_t)ta * n + bb] = k;
-    }
+    sum[(size_t)blk * n + p] = s;
+    cnt[(size_t)blk * n + p] = k;
+  };
+  if (wave == 0) add_line(true, tb, ta * kPrepTile + lane, part_slow_sum, part_slow_cnt);
+  else if (wave == 1) add_line(false, ta, b, part_fast_sum, part_fast_cnt);
+}
+
+// The full matrix's cells: every non-NA cell is kept; c is its code, read beside the value whether it is kept or not.
+struct PrepSumsCells {
+  const int8_t* __restrict__ codes;
+  PrepTotals* __restrict__ totals;
+  int c = 0;
+  PrepTotals t = {};
+  __device__ bool kept(size_t cell, double v) {
+    c = codes != nullptr ? (int)codes[cell] : 0;
+    return !__builtin_isnan(v);
   }
+  __device__ void count(int, int, size_t, double v) {
+    const double scaled = v * 1024.0;
+    if (__builtin_isinf(v)) ++t.n_infinite;
+    if (v < 0.0) ++t.n_negative;
+    if (!(v >= 0.0 && v < 1048576.0 && scaled == ::floor(scaled))) ++t.n_inexact;
+    if (c != 0) return;
+    t.max_key = max(t.max_key, prep_order_key(v));
+    if (__builtin_isfinite(v) && v != 0.0) ++t.n_finite_nonzero;
+  }
+  __device__ void flush() {
+    prep_flush(&totals->n_finite_nonzero, t.n_finite_nonzero);
+    prep_flush(&totals->n_infinite, t.n_infinite);
+    prep_flush(&totals->n_negative, t.n_negative);
+    prep_flush(&totals->n_inexact, t.n_inexact);
+    prep_flush<true>(&totals->max_key, t.max_key);
+  }
+};
+
+// First pass: one workgroup per tile of the lines that begin at slow0 (a chunk of whole 64-line blocks).
+__global__ __launch_bounds__(kPrepThreads) void prep_sums_kernel(
+    const double* __restrict__ vals, const int8_t* __restrict__ codes, int n, int slow0,
+    double* __restrict__ part_slow_sum, int32_t* __restrict__ part_slow_cnt, double* __restrict__ part_fast_sum,
+    int32_t* __restrict__ part_fast_cnt, uint8_t* __restrict__ diag_counts, PrepTotals* __restrict__ totals) {
+  prep_tile_sums(vals, n, slow0 / kPrepTile + blockIdx.y, part_slow_sum, part_slow_cnt, part_fast_sum, part_fast_cnt,
+                 diag_counts, PrepSumsCells{codes, totals});
 }
 
 // One thread per point: its partials added in block order.  out_sum / out_cnt are 2 x n: slow lines, then fast lines.
@@ -198,58 +213,36 @@ __global__ __launch_bounds__(kPrepThreads) void prep_dense_kernel(
 }
 
 // Edges of column j: the cells i < j of the dense fill that are not +Inf.  The fill is symmetric, so column j is
-// line j of the buffer in either layout: contiguous reads.  One workgroup per column.
+// line j of the buffer in either layout: contiguous reads.
 __global__ __launch_bounds__(kPrepThreads) void prep_edge_count_kernel(const double* __restrict__ dense, int n,
                                                                         int32_t* __restrict__ col_edges) {
-  __shared__ int32_t wave_cnt[kPrepWaves];
   const int j = blockIdx.x;
   const double* line = dense + (size_t)j * (size_t)n;
-  int32_t k = 0;
-  for (int i = threadIdx.x; i < j; i += kPrepThreads) k += line[i] != __builtin_inf() ? 1 : 0;
-  for (int off = 32; off > 0; off >>= 1) k += __shfl_down(k, off, 64);
-  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = k;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t t = 0;
-    for (int w = 0; w < kPrepWaves; ++w) t += wave_cnt[w];
-    col_edges[j] = t;
-  }
+  int32_t k[1] = {0};
+  for (int i = threadIdx.x; i < j; i += kPrepThreads) k[0] += line[i] != __builtin_inf() ? 1 : 0;
+  prep_column_counts(k);
+  if (threadIdx.x == 0) col_edges[j] = k[0];
 }
 
-// The stable compaction: column j's edges go to [edge_off[j], edge_off[j + 1]) in ascending i -- which(arr.ind = TRUE)
-// order (R/core.R:383-402).  256 cells at a time: a lane's rank is the set bits below it in its wave's ballot plus the
-// waves before it plus the chunks before this one.
+// Column j's edges go to [edge_off[j], edge_off[j + 1]) in ascending i: which(arr.ind = TRUE) order (R/core.R:383-402).
 __global__ __launch_bounds__(kPrepThreads) void prep_edge_write_kernel(
     const double* __restrict__ dense, const int32_t* __restrict__ tdense, int n, const int64_t* __restrict__ edge_off,
     int32_t* __restrict__ edge_i, int32_t* __restrict__ edge_j, double* __restrict__ edge_dist,
     int32_t* __restrict__ edge_thresh) {
-  __shared__ int32_t wave_cnt[kPrepWaves];
   const int j = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t line = (size_t)j * (size_t)n;
-  int64_t base = edge_off[j];
+  int64_t base[1] = {edge_off[j]}, e[1];
   for (int i0 = 0; i0 < j; i0 += kPrepThreads) {   // uniform over the workgroup
     const int i = i0 + threadIdx.x;
-    double d = __builtin_inf();
-    if (i < j) d = dense[line + i];
-    const bool valid = d != __builtin_inf();
-    const unsigned long long mask = __ballot(valid);
-    if (lane == 0) wave_cnt[wave] = __popcll(mask);
-    __syncthreads();
-    int32_t before = 0, all = 0;
-    for (int w = 0; w < kPrepWaves; ++w) {
-      before += w < wave ? wave_cnt[w] : 0;
-      all += wave_cnt[w];
+    const double d = i < j ? dense[line + i] : __builtin_inf();
+    const bool valid[1] = {d != __builtin_inf()};
+    prep_rank_trip(valid, base, e);
+    if (valid[0]) {
+      edge_i[e[0]] = i;
+      edge_j[e[0]] = j;
+      edge_dist[e[0]] = d;
+      edge_thresh[e[0]] = tdense[line + i];
     }
-    if (valid) {
-      const int64_t e = base + before + __popcll(mask & ((1ull << lane) - 1ull));
-      edge_i[e] = i;
-      edge_j[e] = j;
-      edge_dist[e] = d;
-      edge_thresh[e] = tdense[line + i];
-    }
-    base += all;
-    __syncthreads();
   }
 }
 

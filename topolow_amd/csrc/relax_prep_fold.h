@@ -10,13 +10,16 @@
 // fold_cells_symmetric).  A symmetric matrix reads the same row- or column-major, so every kernel here treats the
 // handle's buffer as COLUMN-major whatever `transposed` says: the slow index a is the column, the contiguous index b
 // the row, and a pick IS its bit index.  Nothing here writes vals or codes.
+//
+// The masked sums are prep_tile_sums of relax_prep.h with this file's policy, the compaction prep_column_counts and
+// prep_rank_trip of relax_prep_rank.h with this file's cell test: only what a fold adds to them is written here.
 #pragma once
 
 #include "relax_prep.h"
 
 namespace topolow {
 
-// Integer counts and a maximum, as PrepTotals: atomics do not make them depend on the grid.
+// Integer counts and a maximum: atomics do not make them depend on the grid.
 struct FoldTotals {
   unsigned long long max_key;        // prep_order_key of the largest kept non-NA code-0 value; 0: there is none
   unsigned long long n_upper;        // kept non-NA cells strictly above the diagonal (row < column)
@@ -45,70 +48,32 @@ __global__ __launch_bounds__(kPrepThreads) void fold_mark_kernel(const long long
   atomicOr(&mask[y >> 5], 1u << (y & 31));
 }
 
-// The first pass of prep_sums_kernel on the masked matrix: a masked cell is NA.  Same 64 x 64 tiles through LDS, same
-// partial per (point, block of 64 cells) added in index order from 0.0, same diag_counts; of the totals the fold needs
-// the maximum (-> numeric_max) and the kept upper-triangle count (-> n_edges).  prep_finish_sums_kernel adds the
-// partials as it does for the full matrix.  Grid: (blocks of b, blocks of a).
+// The masked matrix's cells for prep_tile_sums: a masked cell is NA.  Of the totals the fold needs the maximum
+// (-> numeric_max) and the kept upper-triangle count (-> n_edges); the code is read where the cell is kept.
+struct FoldSumsCells {
+  const int8_t* __restrict__ codes;
+  const uint32_t* __restrict__ mask;
+  FoldTotals* __restrict__ totals;
+  unsigned long long upper = 0, max_key = 0;
+  __device__ bool kept(size_t cell, double v) const { return !__builtin_isnan(v) && !fold_bit(mask, cell); }
+  __device__ void count(int a, int b, size_t cell, double v) {
+    if (b < a) ++upper;
+    if (codes == nullptr || codes[cell] == 0) max_key = max(max_key, prep_order_key(v));
+  }
+  __device__ void flush() {
+    prep_flush(&totals->n_upper, upper);
+    prep_flush<true>(&totals->max_key, max_key);
+  }
+};
+
+// The first pass on the masked matrix; prep_finish_sums_kernel adds the partials as it does for the full matrix.
+// Grid: (blocks of b, blocks of a).
 __global__ __launch_bounds__(kPrepThreads) void fold_sums_kernel(
     const double* __restrict__ vals, const int8_t* __restrict__ codes, const uint32_t* __restrict__ mask, int n,
     double* __restrict__ part_slow_sum, int32_t* __restrict__ part_slow_cnt, double* __restrict__ part_fast_sum,
     int32_t* __restrict__ part_fast_cnt, uint8_t* __restrict__ diag_counts, FoldTotals* __restrict__ totals) {
-  __shared__ double tile[kPrepTile][kPrepTile + 1];
-  __shared__ uint8_t flag[kPrepTile][kPrepTile + 4];
-  const int tb = blockIdx.x, ta = blockIdx.y;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int b = tb * kPrepTile + lane;
-  unsigned long long upper = 0, max_key = 0;
-  for (int r = wave; r < kPrepTile; r += kPrepWaves) {
-    const int a = ta * kPrepTile + r;
-    double x = 0.0;
-    uint8_t f = 0;
-    if (a < n && b < n) {
-      const size_t cell = (size_t)a * (size_t)n + (size_t)b;
-      const double v = vals[cell];
-      if (!__builtin_isnan(v) && !fold_bit(mask, cell)) {
-        f = 1;
-        if (a != b) x = v;
-        if (b < a) ++upper;
-        if (codes == nullptr || codes[cell] == 0) {
-          const unsigned long long key = prep_order_key(v);
-          max_key = key > max_key ? key : max_key;
-        }
-      }
-      if (a == b) diag_counts[a] = f;
-    }
-    tile[r][lane] = x;
-    flag[r][lane] = f;
-  }
-  upper = prep_wave_sum(upper);
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long other = __shfl_down(max_key, off, 64);
-    max_key = other > max_key ? other : max_key;
-  }
-  if (lane == 0) {
-    if (upper) atomicAdd(&totals->n_upper, upper);
-    if (max_key) atomicMax(&totals->max_key, max_key);
-  }
-  __syncthreads();
-  if (threadIdx.x < kPrepTile) {
-    const int r = threadIdx.x, a = ta * kPrepTile + r;
-    if (a < n) {
-      double s = 0.0;
-      int32_t k = 0;
-      for (int q = 0; q < kPrepTile; ++q) { s += tile[r][q]; k += flag[r][q]; }
-      part_slow_sum[(size_t)tb * n + a] = s;
-      part_slow_cnt[(size_t)tb * n + a] = k;
-    }
-  } else if (threadIdx.x < 2 * kPrepTile) {
-    const int l = threadIdx.x - kPrepTile, bb = tb * kPrepTile + l;
-    if (bb < n) {
-      double s = 0.0;
-      int32_t k = 0;
-      for (int q = 0; q < kPrepTile; ++q) { s += tile[q][l]; k += flag[q][l]; }
-      part_fast_sum[(size_t)ta * n + bb] = s;
-      part_fast_cnt[(size_t)ta * n + bb] = k;
-    }
-  }
+  prep_tile_sums(vals, n, blockIdx.y, part_slow_sum, part_slow_cnt, part_fast_sum, part_fast_cnt, diag_counts,
+                 FoldSumsCells{codes, mask, totals});
 }
 
 // What the compaction lists of cell (row b, column a): a held-out PAIR when it is masked, not NA and b < a; a SCORED
@@ -128,80 +93,55 @@ __device__ inline void fold_cell_kind(const double* __restrict__ vals, const int
   *scored = codes == nullptr || codes[cell] == 0;
 }
 
-// Column a's held-out pairs and scored cells, counted.  One workgroup per column: line a of the buffer, contiguous.
+// Column a's held-out pairs and scored cells, counted (prep_column_counts).  One workgroup per column: line a of the
+// buffer, contiguous.
 __global__ __launch_bounds__(kPrepThreads) void fold_compact_count_kernel(
     const double* __restrict__ vals, const int8_t* __restrict__ codes, const uint32_t* __restrict__ mask, int n,
     int32_t* __restrict__ col_pairs, int32_t* __restrict__ col_scored) {
-  __shared__ int32_t wave_cnt[2][kPrepWaves];
   const int a = blockIdx.x;
   const size_t line = (size_t)a * (size_t)n;
-  int32_t kp = 0, ks = 0;
+  int32_t k[2] = {0, 0};
   for (int b = threadIdx.x; b < n; b += kPrepThreads) {
     bool pair, scored;
     double v;
     fold_cell_kind(vals, codes, mask, line + b, a, b, &pair, &scored, &v);
-    kp += pair ? 1 : 0;
-    ks += scored ? 1 : 0;
+    k[0] += pair ? 1 : 0;
+    k[1] += scored ? 1 : 0;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    kp += __shfl_down(kp, off, 64);
-    ks += __shfl_down(ks, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) { wave_cnt[0][threadIdx.x >> 6] = kp; wave_cnt[1][threadIdx.x >> 6] = ks; }
-  __syncthreads();
+  prep_column_counts(k);
   if (threadIdx.x == 0) {
-    int32_t tp = 0, ts = 0;
-    for (int w = 0; w < kPrepWaves; ++w) { tp += wave_cnt[0][w]; ts += wave_cnt[1][w]; }
-    col_pairs[a] = tp;
-    col_scored[a] = ts;
+    col_pairs[a] = k[0];
+    col_scored[a] = k[1];
   }
 }
 
-// The stable compaction, in the manner of prep_edge_write_kernel: column a's pairs go to [pair_off[a], pair_off[a + 1])
-// and its scored cells to [score_off[a], score_off[a + 1]), both in ascending row -- the pairs sorted by (j, i), the
-// scored cells in ascending column-major index with their truth from vals.  A cell's slot is its rank in that order,
-// never what an atomic returned: the lists do not depend on timing.
+// The stable compaction (prep_rank_trip, both lists at once): column a's pairs go to [pair_off[a], pair_off[a + 1]) and
+// its scored cells to [score_off[a], score_off[a + 1]), both in ascending row -- the pairs sorted by (j, i), the scored
+// cells in ascending column-major index with their truth from vals.
 __global__ __launch_bounds__(kPrepThreads) void fold_compact_write_kernel(
     const double* __restrict__ vals, const int8_t* __restrict__ codes, const uint32_t* __restrict__ mask, int n,
     const int64_t* __restrict__ pair_off, const int64_t* __restrict__ score_off, int32_t* __restrict__ pair_i,
     int32_t* __restrict__ pair_j, int32_t* __restrict__ score_r, int32_t* __restrict__ score_c,
     double* __restrict__ score_truth) {
-  __shared__ int32_t wave_cnt[2][kPrepWaves];
   const int a = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t line = (size_t)a * (size_t)n;
-  int64_t pbase = pair_off[a], sbase = score_off[a];
-  if (pair_off[a + 1] == pbase && score_off[a + 1] == sbase) return;   // uniform: nothing of this column is listed
+  int64_t base[2] = {pair_off[a], score_off[a]}, e[2];
+  if (pair_off[a + 1] == base[0] && score_off[a + 1] == base[1]) return;   // uniform: nothing of this column is listed
   for (int b0 = 0; b0 < n; b0 += kPrepThreads) {   // uniform over the workgroup
     const int b = b0 + threadIdx.x;
-    bool pair = false, scored = false;
+    bool in[2] = {false, false};   // a held-out pair, a scored cell
     double v = 0.0;
-    if (b < n) fold_cell_kind(vals, codes, mask, line + b, a, b, &pair, &scored, &v);
-    const unsigned long long pm = __ballot(pair), sm = __ballot(scored);
-    if (lane == 0) { wave_cnt[0][wave] = __popcll(pm); wave_cnt[1][wave] = __popcll(sm); }
-    __syncthreads();
-    int32_t pbefore = 0, pall = 0, sbefore = 0, sall = 0;
-    for (int w = 0; w < kPrepWaves; ++w) {
-      pbefore += w < wave ? wave_cnt[0][w] : 0;
-      pall += wave_cnt[0][w];
-      sbefore += w < wave ? wave_cnt[1][w] : 0;
-      sall += wave_cnt[1][w];
+    if (b < n) fold_cell_kind(vals, codes, mask, line + b, a, b, &in[0], &in[1], &v);
+    prep_rank_trip(in, base, e);
+    if (in[0]) {
+      pair_i[e[0]] = b;
+      pair_j[e[0]] = a;
     }
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (pair) {
-      const int64_t e = pbase + pbefore + __popcll(pm & below);
-      pair_i[e] = b;
-      pair_j[e] = a;
+    if (in[1]) {
+      score_r[e[1]] = b;
+      score_c[e[1]] = a;
+      score_truth[e[1]] = v;
     }
-    if (scored) {
-      const int64_t e = sbase + sbefore + __popcll(sm & below);
-      score_r[e] = b;
-      score_c[e] = a;
-      score_truth[e] = v;
-    }
-    pbase += pall;
-    sbase += sall;
-    __syncthreads();
   }
 }
 

@@ -2825,10 +2825,172 @@ int enqueue_run(topolow_session* s, const std::function<int()>& after_chunk, cha
   }
 }
 
+// What both resident sweeps take, in the ORDER of their signatures: an entry fills it with its own parameter list.
+struct SweepArgs {
+  int32_t named, preserve_order, n_folds;
+  const int32_t* ndim;
+  const double *k0, *cooling_rate, *c_repulsion;
+  const int64_t *picks, *picks_offset;
+  const double* unit_draws;
+  const int64_t* draws_offset;
+  const uint64_t* seeds;
+  int32_t n_iter;
+  double relative_epsilon;
+  int32_t convergence_window, convergence_check_freq, precision, schedule;
+  double* holdout_sum_abs;
+  int64_t* holdout_count;
+  int32_t *iterations, *converged, *error_code;
+  double* device_seconds;
+};
+
+// The sweep of topolow_cv_sweep on resident sessions, the loop of both entries: one session per ndim, loaded once with
+// the full matrix (`matrix`: NULL is refused); a fold is held out of it, run, scored on the device and put back.  Where
+// a fold comes from is its source's business (CellFolds: the host's cell list; HandleFolds: a prepared handle).  After
+// the shared refusals begin() checks what only the source checks and sets n, device, degrees (the full matrix's, for
+// the restore) and seconds (prepare, hold out, score, restore); load() fills a fresh session; prefetch(f) names the
+// fold that prepare() is asked for next; prepare() returns fold f with its `code` (not OK: reported, not run) and `pos`
+// (n x ndim start positions, column-major, caller's labels), or sets rc; drain() ends a group, in whichever way.
+extern "C++" template <typename Folds>
+int cv_sweep_resident(const void* matrix, Folds& src, const SweepArgs& a, char* errbuf, size_t errlen) {
+  if (!cv_sweep_args_ok(matrix, a.n_folds, a.ndim, a.k0, a.cooling_rate, a.c_repulsion, a.picks_offset, a.unit_draws,
+                        a.draws_offset, a.seeds, a.holdout_sum_abs, a.holdout_count, a.iterations, a.converged, a.error_code) ||
+      (a.schedule != TOPOLOW_SCHEDULE_AUTO && a.schedule != TOPOLOW_SCHEDULE_SLAB && a.schedule != TOPOLOW_SCHEDULE_GS)) {
+    set_err(errbuf, errlen, "null argument, n_folds < 0 or an unknown schedule");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (a.device_seconds) *a.device_seconds = 0.0;
+  if (a.precision == TOPOLOW_PRECISION_F64_EXACT) {
+    set_err(errbuf, errlen, "precision f64_exact: no cross-validation on resident sessions (holding a fold out does not "
+            "cover the delta block); topolow_cv_sweep runs it on the one-workgroup kernel");
+    return TOPOLOW_ERR_UNSUPPORTED;
+  }
+  if (a.n_folds == 0) return TOPOLOW_OK;
+  if (const int rcb = src.begin(errbuf, errlen)) return rcb;
+  const bool tile_gs = a.schedule == TOPOLOW_SCHEDULE_GS;
+  const int prec = a.precision == TOPOLOW_PRECISION_AUTO ? (tile_gs ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32) : a.precision;
+  auto nothing = [&](int f) { a.holdout_sum_abs[f] = 0.0; a.holdout_count[f] = 0; a.iterations[f] = 0; a.converged[f] = 0; };
+  for (int f = 0; f < a.n_folds; ++f) { nothing(f); a.error_code[f] = TOPOLOW_OK; }
+  double* secs = src.seconds;
+  secs[0] = secs[1] = secs[2] = secs[3] = 0.0;
+  std::vector<char> done((size_t)a.n_folds, 0);
+  for (int g0 = 0; g0 < a.n_folds; ++g0) {
+    if (done[(size_t)g0]) continue;
+    std::vector<int> members;   // the folds that share this ndim, in the caller's order
+    for (int f = g0; f < a.n_folds; ++f)
+      if (!done[(size_t)f] && a.ndim[f] == a.ndim[g0]) { members.push_back(f); done[(size_t)f] = 1; }
+    if (a.ndim[g0] < 1) {
+      for (int f : members) a.error_code[f] = TOPOLOW_ERR_BAD_ARGUMENT;
+      continue;
+    }
+    src.prefetch(members[0]);
+    topolow_session* s = nullptr;   // the labels are shuffled by the first fold's seed
+    int rc = open_session(&s, src.n, a.ndim[g0], tile_gs, prec, src.device, &a.seeds[members[0]],
+                          [&](topolow_session* t, char* eb, size_t el) -> int { return src.load(t, eb, el); }, errbuf, errlen);
+    for (size_t q = 0; q < members.size() && rc == TOPOLOW_OK; ++q) {
+      const int f = members[q];
+      const double tp = now_s();
+      auto fold = src.prepare(s, f, &rc, errbuf, errlen);
+      secs[0] += now_s() - tp;
+      if (q + 1 < members.size()) src.prefetch(members[q + 1]);
+      if (rc != TOPOLOW_OK) break;   // (error_code[f] stays TOPOLOW_OK: the call fails, not the fold)
+      a.error_code[f] = fold->code;
+      if (fold->code != TOPOLOW_OK) continue;   // the session was not touched
+      const double th = now_s();
+      rc = src.hold_out(s, *fold, errbuf, errlen);
+      secs[1] += now_s() - th;
+      if (rc) break;
+      const double t0 = now_s();
+      int rcf = topolow_session_set_positions(s, fold->pos.data(), errbuf, errlen);
+      if (rcf == TOPOLOW_OK)
+        rcf = topolow_session_begin(s, a.n_iter, a.k0[f], a.cooling_rate[f], a.c_repulsion[f], a.relative_epsilon,
+                                    a.convergence_window, a.convergence_check_freq, a.seeds[f], 0, errbuf, errlen);
+      if (rcf == TOPOLOW_OK) rcf = enqueue_run(s, nullptr, errbuf, errlen);
+      if (rcf == TOPOLOW_OK)
+        rcf = topolow_session_finish(s, nullptr, &a.converged[f], &a.iterations[f], nullptr, nullptr, errbuf, errlen);
+      else
+        (void)topolow_session_finish(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);   // the run is over either way
+      if (a.device_seconds) *a.device_seconds += now_s() - t0;
+      const double ts = now_s();
+      if (rcf == TOPOLOW_OK) rcf = src.score(s, *fold, &a.holdout_sum_abs[f], &a.holdout_count[f], errbuf, errlen);
+      secs[2] += now_s() - ts;
+      // the session is the full matrix again before the next fold starts, whatever this one did
+      const double tr = now_s();
+      char rerr[256] = "";
+      const int rcr = topolow_session_restore_held_out(s, src.degrees, rerr, sizeof rerr);
+      secs[3] += now_s() - tr;
+      if (rcf == TOPOLOW_ERR_NONFINITE) {   // a diverged fold is this fold's result, not the call's
+        a.error_code[f] = TOPOLOW_ERR_NONFINITE;
+        nothing(f);
+        rcf = TOPOLOW_OK;
+      }
+      if (rcf != TOPOLOW_OK) { rc = rcf; break; }
+      if (rcr != TOPOLOW_OK) { set_err(errbuf, errlen, "%s", rerr); rc = rcr; break; }
+    }
+    src.drain();
+    if (s) topolow_session_destroy(s);
+    if (rc != TOPOLOW_OK) return rc;
+  }
+  return TOPOLOW_OK;
+}
+
+// Folds from the host's cell list (fold_pairs), each prepared on a host thread while the fold before it runs.
+struct CellFolds {
+  const topolow_cell_list* cells;
+  const SweepArgs& a;
+  int32_t device, n = 0;
+  struct Fold { int code = TOPOLOW_OK; FoldPairs fp; std::vector<double> pos; };
+  std::vector<int32_t> fi, fj, ft, fdeg;   // what the sessions load: the (symmetric) list's upper triangle, degrees
+  std::vector<double> fd;
+  const int32_t* degrees = nullptr;
+  double untold[4], *seconds = untold;
+  std::future<std::unique_ptr<Fold>> next;
+  bool next_valid = false;
+  int begin(char* errbuf, size_t errlen) {
+    n = cells->n;
+    return guarded(errbuf, errlen, [&] {
+      if (n < 2) throw HipError{TOPOLOW_ERR_TOO_FEW_POINTS, "Need at least 2 points for embedding"};
+      if (!fold_cells_symmetric(cells)) throw HipError{TOPOLOW_ERR_UNSUPPORTED, kAsymmetricCells};
+      fdeg.resize((size_t)n); degrees = fdeg.data();
+      for (int i = 0; i < n; ++i) fdeg[(size_t)i] = (int32_t)(cells->row_ptr[i + 1] - cells->row_ptr[i]);
+      for (int64_t q = 0; q < cells->n_cells; ++q)
+        if (cells->row[q] < cells->col[q]) {
+          fi.push_back(cells->row[q]); fj.push_back(cells->col[q]); fd.push_back(cells->value[q]); ft.push_back(cells->code[q]);
+        }
+    });
+  }
+  int load(topolow_session* t, char* eb, size_t el) const {
+    const int rcl = topolow_session_load_coo(t, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), fdeg.data(), eb, el);
+    return rcl ? rcl : topolow_session_set_edges(t, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), eb, el);
+  }
+  std::unique_ptr<Fold> build(int f) const {
+    auto p = std::make_unique<Fold>();
+    try {
+      p->code = fold_pairs(cells, a.picks + a.picks_offset[f], a.picks_offset[f + 1] - a.picks_offset[f], a.preserve_order, a.named, p->fp);
+      p->code = fold_check(p->code, p->fp.n_edges, p->fp.numeric_max, a.ndim[f], a.draws_offset[f + 1] - a.draws_offset[f], n);
+      if (p->code != TOPOLOW_OK) return p;
+      // the random walk of topolow_cv_sweep in the caller's labels
+      start_walk(a.unit_draws + a.draws_offset[f], p->fp.numeric_max, n, a.ndim[f],
+                 p->fp.order[0] >= 0 ? p->fp.order.data() : nullptr, p->pos);
+    } catch (const std::bad_alloc&) {
+      p->code = TOPOLOW_ERR_HIP;
+    }
+    return p;
+  }
+  void prefetch(int f) { next = std::async(std::launch::async, [this, f] { return build(f); }); next_valid = true; }
+  std::unique_ptr<Fold> prepare(topolow_session*, int, int*, char*, size_t) { next_valid = false; return next.get(); }
+  void drain() { if (next_valid) (void)next.get(); next_valid = false; }
+  int hold_out(topolow_session* s, const Fold& p, char* errbuf, size_t errlen) const {
+    return topolow_session_hold_out(s, p.fp.pair_i.data(), p.fp.pair_j.data(), (int64_t)p.fp.pair_i.size(),
+                                    p.fp.degrees.data(), errbuf, errlen);
+  }
+  int score(topolow_session* s, const Fold& p, double* sum_abs, int64_t* count, char* errbuf, size_t errlen) const {
+    return topolow_session_score_pairs(s, p.fp.score_i.data(), p.fp.score_j.data(), p.fp.score_truth.data(),
+                                       (int64_t)p.fp.score_i.size(), sum_abs, count, errbuf, errlen);
+  }
+};
+
 }  // namespace
 
-// The sweep of topolow_cv_sweep on resident sessions: one session per ndim, loaded once with the full matrix; a fold is
-// held out of it, run, scored on the device and put back.  The next fold is prepared on a host thread meanwhile.
 int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int32_t preserve_order, int32_t n_folds,
                              const int32_t* ndim, const double* k0, const double* cooling_rate, const double* c_repulsion,
                              const int64_t* picks, const int64_t* picks_offset, const double* unit_draws,
@@ -2836,116 +2998,11 @@ int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int3
                              int32_t convergence_window, int32_t convergence_check_freq, int32_t precision, int32_t device,
                              int32_t schedule, double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations,
                              int32_t* converged, int32_t* error_code, double* device_seconds, char* errbuf, size_t errlen) {
-  if (!cv_sweep_args_ok(cells, n_folds, ndim, k0, cooling_rate, c_repulsion, picks_offset, unit_draws, draws_offset, seeds,
-                        holdout_sum_abs, holdout_count, iterations, converged, error_code))
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  if (schedule != TOPOLOW_SCHEDULE_AUTO && schedule != TOPOLOW_SCHEDULE_SLAB && schedule != TOPOLOW_SCHEDULE_GS)
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  if (device_seconds) *device_seconds = 0.0;
-  if (precision == TOPOLOW_PRECISION_F64_EXACT) {
-    set_err(errbuf, errlen, "precision f64_exact: no cross-validation on resident sessions (holding a fold out does not "
-            "cover the delta block); topolow_cv_sweep runs it on the one-workgroup kernel");
-    return TOPOLOW_ERR_UNSUPPORTED;
-  }
-  if (n_folds == 0) return TOPOLOW_OK;
-  const int n = cells->n;
-  const bool tile_gs = schedule == TOPOLOW_SCHEDULE_GS;
-  const int prec = precision == TOPOLOW_PRECISION_AUTO ? (tile_gs ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32) : precision;
-  struct Prep {
-    int rc = TOPOLOW_OK;
-    FoldPairs fp;
-    std::vector<double> pos;   // start positions, n x ndim column-major, caller's labels
-  };
-  auto prepare = [&](int f) {
-    auto p = std::make_unique<Prep>();
-    try {
-      p->rc = fold_pairs(cells, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named, p->fp);
-      p->rc = fold_check(p->rc, p->fp.n_edges, p->fp.numeric_max, ndim[f], draws_offset[f + 1] - draws_offset[f], n);
-      if (p->rc != TOPOLOW_OK) return p;
-      // the random walk of topolow_cv_sweep in the caller's labels
-      start_walk(unit_draws + draws_offset[f], p->fp.numeric_max, n, ndim[f], p->fp.order[0] >= 0 ? p->fp.order.data() : nullptr,
-                 p->pos);
-    } catch (const std::bad_alloc&) {
-      p->rc = TOPOLOW_ERR_HIP;
-    }
-    return p;
-  };
-  // the full matrix as the sessions load it: the upper triangle of the (symmetric) list, its degrees
-  std::vector<int32_t> fi, fj, ft, fdeg((size_t)n);
-  std::vector<double> fd;
-  const int rc_list = guarded(errbuf, errlen, [&] {
-    if (n < 2) throw HipError{TOPOLOW_ERR_TOO_FEW_POINTS, "Need at least 2 points for embedding"};
-    if (!fold_cells_symmetric(cells)) throw HipError{TOPOLOW_ERR_UNSUPPORTED, kAsymmetricCells};
-    for (int i = 0; i < n; ++i) fdeg[(size_t)i] = (int32_t)(cells->row_ptr[i + 1] - cells->row_ptr[i]);
-    for (int64_t q = 0; q < cells->n_cells; ++q)
-      if (cells->row[q] < cells->col[q]) {
-        fi.push_back(cells->row[q]); fj.push_back(cells->col[q]); fd.push_back(cells->value[q]); ft.push_back(cells->code[q]);
-      }
-  });
-  if (rc_list != TOPOLOW_OK) return rc_list;
-  for (int f = 0; f < n_folds; ++f) {
-    holdout_sum_abs[f] = 0.0; holdout_count[f] = 0; iterations[f] = 0; converged[f] = 0;
-    error_code[f] = TOPOLOW_OK;
-  }
-  std::vector<char> done((size_t)n_folds, 0);
-  for (int g0 = 0; g0 < n_folds; ++g0) {
-    if (done[(size_t)g0]) continue;
-    std::vector<int> members;   // the folds that share this ndim, in the caller's order
-    for (int f = g0; f < n_folds; ++f)
-      if (!done[(size_t)f] && ndim[f] == ndim[g0]) { members.push_back(f); done[(size_t)f] = 1; }
-    if (ndim[g0] < 1) {
-      for (int f : members) error_code[f] = TOPOLOW_ERR_BAD_ARGUMENT;
-      continue;
-    }
-    // the first fold is prepared while the session opens; the labels are shuffled by the first fold's seed
-    std::future<std::unique_ptr<Prep>> next = std::async(std::launch::async, prepare, members[0]);
-    bool next_valid = true;
-    topolow_session* s = nullptr;
-    int rc = open_session(&s, n, ndim[g0], tile_gs, prec, device, &seeds[members[0]], [&](topolow_session* t, char* eb, size_t el) -> int {
-      const int rcl = topolow_session_load_coo(t, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), fdeg.data(), eb, el);
-      return rcl ? rcl : topolow_session_set_edges(t, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), eb, el);
-    }, errbuf, errlen);
-    for (size_t q = 0; q < members.size() && rc == TOPOLOW_OK; ++q) {
-      const int f = members[q];
-      std::unique_ptr<Prep> p = next.get();
-      next_valid = false;
-      if (q + 1 < members.size()) { next = std::async(std::launch::async, prepare, members[q + 1]); next_valid = true; }
-      error_code[f] = p->rc;
-      if (p->rc != TOPOLOW_OK) continue;
-      const FoldPairs& fp = p->fp;
-      rc = topolow_session_hold_out(s, fp.pair_i.data(), fp.pair_j.data(), (int64_t)fp.pair_i.size(), fp.degrees.data(),
-                                    errbuf, errlen);
-      if (rc) break;
-      const double t0 = now_s();
-      int rcf = topolow_session_set_positions(s, p->pos.data(), errbuf, errlen);
-      if (rcf == TOPOLOW_OK)
-        rcf = topolow_session_begin(s, n_iter, k0[f], cooling_rate[f], c_repulsion[f], relative_epsilon, convergence_window,
-                                    convergence_check_freq, seeds[f], 0, errbuf, errlen);
-      if (rcf == TOPOLOW_OK) rcf = enqueue_run(s, nullptr, errbuf, errlen);
-      if (rcf == TOPOLOW_OK)
-        rcf = topolow_session_finish(s, nullptr, &converged[f], &iterations[f], nullptr, nullptr, errbuf, errlen);
-      else
-        (void)topolow_session_finish(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);   // the run is over either way
-      if (device_seconds) *device_seconds += now_s() - t0;
-      if (rcf == TOPOLOW_OK)
-        rcf = topolow_session_score_pairs(s, fp.score_i.data(), fp.score_j.data(), fp.score_truth.data(),
-                                          (int64_t)fp.score_i.size(), &holdout_sum_abs[f], &holdout_count[f], errbuf, errlen);
-      // the session is the full matrix again before the next fold starts, whatever this one did
-      char rerr[256] = "";
-      const int rcr = topolow_session_restore_held_out(s, fdeg.data(), rerr, sizeof rerr);
-      if (rcf == TOPOLOW_ERR_NONFINITE) {   // a diverged fold is this fold's result, not the call's
-        error_code[f] = TOPOLOW_ERR_NONFINITE;
-        iterations[f] = 0; converged[f] = 0;
-        rcf = TOPOLOW_OK;
-      }
-      if (rcf != TOPOLOW_OK) { rc = rcf; break; }
-      if (rcr != TOPOLOW_OK) { set_err(errbuf, errlen, "%s", rerr); rc = rcr; break; }
-    }
-    if (next_valid) (void)next.get();
-    if (s) topolow_session_destroy(s);
-    if (rc != TOPOLOW_OK) return rc;
-  }
-  return TOPOLOW_OK;
+  const SweepArgs a{named, preserve_order, n_folds, ndim, k0, cooling_rate, c_repulsion, picks, picks_offset, unit_draws,
+                    draws_offset, seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq, precision,
+                    schedule, holdout_sum_abs, holdout_count, iterations, converged, error_code, device_seconds};
+  CellFolds src{cells, a, device};
+  return cv_sweep_resident(cells, src, a, errbuf, errlen);
 }
 
 // rows [row_begin, row_end) of as.matrix(dist(positions)): out is (row_end - row_begin) x n, row-major.
@@ -3220,6 +3277,69 @@ int topolow_post_metrics(const double* positions, int32_t n, int32_t ndim, const
                                  TOPOLOW_POST_STAGING_DEFAULT, nullptr, errbuf, errlen);
 }
 
+namespace {
+
+// The host's side of a sums pass (prep_tile_sums), of the full matrix (prep_passes) or a fold's masked one
+// (prep_fold_prepare): the buffers the tile kernels write, and what the host reads of them.
+extern "C++" template <typename Totals>
+struct PrepSums {
+  DevBuf<double> part_slow_sum, part_fast_sum, line_sum;
+  DevBuf<int32_t> part_slow_cnt, part_fast_cnt, line_cnt;
+  DevBuf<uint8_t> diag;
+  DevBuf<Totals> totals;
+  std::vector<double> sums;      // after fetch(), 2 n each: the slow lines, then the fast lines
+  std::vector<int32_t> cnts;
+  std::vector<uint8_t> on_diag;  // n: is the diagonal cell counted?
+  Totals tot;
+  void alloc(int n) {
+    const size_t N = (size_t)n, nb = (N + kPrepTile - 1) / kPrepTile;
+    for (auto* b : {&part_slow_sum, &part_fast_sum}) prep_alloc(*b, nb * N, "the partial sums");
+    for (auto* b : {&part_slow_cnt, &part_fast_cnt}) prep_alloc(*b, nb * N, "the partial counts");
+    prep_alloc(line_sum, 2 * N, "the sums");
+    prep_alloc(line_cnt, 2 * N, "the counts");
+    prep_alloc(diag, N, "the diagonal flags");
+    prep_alloc(totals, 1, "the totals");
+  }
+  // Behind the tile kernels on `stream`: the partials added per point, all of it sent down; the caller synchronises.
+  void fetch(int n, hipStream_t stream) {
+    const size_t N = (size_t)n;
+    hipLaunchKernelGGL(prep_finish_sums_kernel, dim3((n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, stream,
+                       n, (n + kPrepTile - 1) / kPrepTile, part_slow_sum.p, part_slow_cnt.p, part_fast_sum.p,
+                       part_fast_cnt.p, line_sum.p, line_cnt.p);
+    HIP_TRY(hipGetLastError());
+    sums.resize(2 * N); cnts.resize(2 * N); on_diag.resize(N);
+    HIP_TRY(hipMemcpyAsync(sums.data(), line_sum.p, 2 * N * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(cnts.data(), line_cnt.p, 2 * N * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(on_diag.data(), diag.p, N, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&tot, totals.p, sizeof tot, hipMemcpyDeviceToHost, stream));
+  }
+  // topolow_layout_order_from_sums on the fetched sums, the counts less the diagonal; rows at row_at, columns at col_at.
+  int32_t order(int n, size_t row_at, size_t col_at, bool exact_sums, bool negative_or_infinite, int32_t* order_out) const {
+    std::vector<int64_t> row_cnt((size_t)n), col_cnt((size_t)n);
+    for (size_t q = 0; q < (size_t)n; ++q) {
+      row_cnt[q] = (int64_t)cnts[row_at + q] - on_diag[q];
+      col_cnt[q] = (int64_t)cnts[col_at + q] - on_diag[q];
+    }
+    return topolow_layout_order_from_sums(n, sums.data() + row_at, row_cnt.data(), sums.data() + col_at, col_cnt.data(),
+                                          exact_sums ? 1 : (negative_or_infinite ? -1 : 0), order_out);
+  }
+  double numeric_max() const {   // from the totals' max_key (prep_order_key); NaN: there is no non-NA code-0 value
+    const uint64_t key = tot.max_key, bits = (key >> 63) ? key & 0x7fffffffffffffffull : ~key;
+    double v = NAN;
+    if (key != 0) memcpy(&v, &bits, 8);
+    return v;
+  }
+};
+
+// Counts per column -> exclusive offsets, off[0 .. n]; returns the total.
+int64_t prep_offsets(const int32_t* per_col, size_t n, int64_t* off) {
+  off[0] = 0;
+  for (size_t j = 0; j < n; ++j) off[j + 1] = off[j] + per_col[j];
+  return off[n];
+}
+
+}  // namespace
+
 // ---- layout prep: order, degrees, edge list and dense fill on the device (R/core.R:269-436) ----
 // create(): the matrix goes up in chunks of whole 64-line blocks through pinned staging while the first pass runs on
 // the chunks that have arrived; the host applies the ordering rule to the sums; the second pass fills the dense
@@ -3255,10 +3375,7 @@ struct topolow_layout_prep {
     hipStream_t stream = nullptr;          // topolow_layout_prep_fold's own; a sweep works on its session's stream
     size_t mask_words = 0;
     DevBuf<uint32_t> mask;                 // one bit per cell; all zero between folds
-    DevBuf<double> part_slow_sum, part_fast_sum, line_sum;
-    DevBuf<int32_t> part_slow_cnt, part_fast_cnt, line_cnt;
-    DevBuf<uint8_t> diag;
-    DevBuf<FoldTotals> totals;
+    PrepSums<FoldTotals> sums;             // of the masked matrix; its totals serve fold_symmetry_kernel too
     DevBuf<int32_t> col_counts;            // 2 n: held-out pairs per column, then scored cells per column
     DevBuf<int64_t> offsets;               // 2 (n + 1): their prefix sums
     DevBuf<long long> picks;
@@ -3313,6 +3430,13 @@ void prep_compact_edges(topolow_layout_prep* p, hipStream_t stream) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(stream));   // the list is complete before the flag says so
   p->compacted = true;
+}
+
+// A handle whose ordering was declined went through no second pass: every entry that reads one refuses it here.
+int prep_check_usable(const topolow_layout_prep* p, char* errbuf, size_t errlen) {
+  if (!p->declined) return TOPOLOW_OK;
+  set_err(errbuf, errlen, "the ordering was declined (order_route 3): create the handle again with order_in");
+  return TOPOLOW_ERR_BAD_ARGUMENT;
 }
 
 bool prep_is_permutation(const int32_t* order, int n) {
@@ -3402,50 +3526,26 @@ void prep_passes(topolow_layout_prep* p, int32_t preserve_order, const int32_t* 
   const int nb = (n + kPrepTile - 1) / kPrepTile;
 
   // -- arrival and first pass, overlapped
-  DevBuf<double> part_slow_sum, part_fast_sum, line_sum;
-  DevBuf<int32_t> part_slow_cnt, part_fast_cnt, line_cnt;
-  DevBuf<uint8_t> diag;
-  DevBuf<PrepTotals> totals;
-  prep_alloc(part_slow_sum, (size_t)nb * N, "the partial sums");
-  prep_alloc(part_fast_sum, (size_t)nb * N, "the partial sums");
-  prep_alloc(part_slow_cnt, (size_t)nb * N, "the partial counts");
-  prep_alloc(part_fast_cnt, (size_t)nb * N, "the partial counts");
-  prep_alloc(line_sum, 2 * N, "the sums");
-  prep_alloc(line_cnt, 2 * N, "the counts");
-  prep_alloc(diag, N, "the diagonal flags");
-  prep_alloc(totals, 1, "the totals");
+  PrepSums<PrepTotals> S;
+  S.alloc(n);
   PostPipe P;
   P.create(g.slots, 0);
-  HIP_TRY(hipMemsetAsync(totals.p, 0, sizeof(PrepTotals), P.run));
+  HIP_TRY(hipMemsetAsync(S.totals.p, 0, sizeof(PrepTotals), P.run));
   for (int t = 0; t < g.n_chunks; ++t) {
     const int a0 = t * g.chunk_lines, lines = std::min(g.chunk_lines, n - a0);
     arrive(P, t, a0, lines);
     hipLaunchKernelGGL(prep_sums_kernel, dim3(nb, (lines + kPrepTile - 1) / kPrepTile), dim3(kPrepThreads), 0, P.run,
-                       p->vals.p, codes, n, a0, part_slow_sum.p, part_slow_cnt.p, part_fast_sum.p, part_fast_cnt.p,
-                       diag.p, totals.p);
+                       p->vals.p, codes, n, a0, S.part_slow_sum.p, S.part_slow_cnt.p, S.part_fast_sum.p,
+                       S.part_fast_cnt.p, S.diag.p, S.totals.p);
     HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(prep_finish_sums_kernel, dim3((n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, P.run,
-                     n, nb, part_slow_sum.p, part_slow_cnt.p, part_fast_sum.p, part_fast_cnt.p, line_sum.p, line_cnt.p);
-  HIP_TRY(hipGetLastError());
-  std::vector<double> sums(2 * N);
-  std::vector<int32_t> cnts(2 * N);
-  std::vector<uint8_t> on_diag(N);
-  PrepTotals tot;
-  HIP_TRY(hipMemcpyAsync(sums.data(), line_sum.p, 2 * N * 8, hipMemcpyDeviceToHost, P.run));
-  HIP_TRY(hipMemcpyAsync(cnts.data(), line_cnt.p, 2 * N * 4, hipMemcpyDeviceToHost, P.run));
-  HIP_TRY(hipMemcpyAsync(on_diag.data(), diag.p, N, hipMemcpyDeviceToHost, P.run));
-  HIP_TRY(hipMemcpyAsync(&tot, totals.p, sizeof tot, hipMemcpyDeviceToHost, P.run));
+  S.fetch(n, P.run);
   P.sync();
+  const PrepTotals& tot = S.tot;
   const double t1 = now_s();
 
   // -- the quantities of the info struct and the order
   const size_t row_at = p->transposed ? 0 : N, col_at = p->transposed ? N : 0;   // slow lines are rows when transposed
-  std::vector<int64_t> row_cnt(N), col_cnt(N);
-  for (size_t q = 0; q < N; ++q) {
-    row_cnt[q] = (int64_t)cnts[row_at + q] - on_diag[q];
-    col_cnt[q] = (int64_t)cnts[col_at + q] - on_diag[q];
-  }
   *info = topolow_layout_prep_info();
   info->n_edges = -1;
   info->n_finite_nonzero = (int64_t)tot.n_finite_nonzero;
@@ -3454,12 +3554,7 @@ void prep_passes(topolow_layout_prep* p, int32_t preserve_order, const int32_t* 
   info->exact_sums = tot.n_inexact == 0 ? 1 : 0;
   p->exact_sums = tot.n_inexact == 0;
   p->negative_or_infinite = tot.n_negative + tot.n_infinite > 0;
-  if (tot.max_key == 0) {
-    info->numeric_max = NAN;
-  } else {
-    const uint64_t bits = (tot.max_key >> 63) ? (uint64_t)(tot.max_key & 0x7fffffffffffffffull) : (uint64_t)~tot.max_key;
-    memcpy(&info->numeric_max, &bits, 8);
-  }
+  info->numeric_max = S.numeric_max();
   p->order.assign(N, 0);
   p->order[0] = -1;
   if (preserve_order) {
@@ -3468,9 +3563,7 @@ void prep_passes(topolow_layout_prep* p, int32_t preserve_order, const int32_t* 
     info->order_route = TOPOLOW_ORDER_DECLINED;
     std::copy(order_in, order_in + (order_in[0] == -1 ? 1 : n), p->order.begin());
   } else {
-    const int32_t flag = info->exact_sums ? 1 : (tot.n_negative + tot.n_infinite > 0 ? -1 : 0);
-    info->order_route = topolow_layout_order_from_sums(n, sums.data() + row_at, row_cnt.data(), sums.data() + col_at,
-                                                       col_cnt.data(), flag, p->order.data());
+    info->order_route = S.order(n, row_at, col_at, p->exact_sums, p->negative_or_infinite, p->order.data());
     if (info->order_route == TOPOLOW_ORDER_DECLINED) {
       p->declined = true;
       p->phase_seconds[0] = t1 - t0;
@@ -3482,7 +3575,7 @@ void prep_passes(topolow_layout_prep* p, int32_t preserve_order, const int32_t* 
   std::vector<int32_t> ord(N);
   for (size_t q = 0; q < N; ++q) ord[q] = reordered ? p->order[q] : (int32_t)q;
   p->degrees.resize(N);
-  for (size_t q = 0; q < N; ++q) p->degrees[q] = cnts[row_at + (size_t)ord[q]];
+  for (size_t q = 0; q < N; ++q) p->degrees[q] = S.cnts[row_at + (size_t)ord[q]];
   const double t2 = now_s();
 
   // -- second pass: dense fill, edges per column
@@ -3503,10 +3596,9 @@ void prep_passes(topolow_layout_prep* p, int32_t preserve_order, const int32_t* 
   std::vector<int32_t> per_col(N);
   HIP_TRY(hipMemcpyAsync(per_col.data(), col_edges.p, N * 4, hipMemcpyDeviceToHost, P.run));
   HIP_TRY(hipStreamSynchronize(P.run));
-  std::vector<int64_t> off(N + 1, 0);
-  for (size_t j = 0; j < N; ++j) off[j + 1] = off[j] + per_col[j];
+  std::vector<int64_t> off(N + 1);
+  p->n_edges = prep_offsets(per_col.data(), N, off.data());
   HIP_TRY(hipMemcpy(p->edge_off.p, off.data(), (N + 1) * 8, hipMemcpyHostToDevice));
-  p->n_edges = off[N];
   info->n_edges = p->n_edges;
   p->phase_seconds[0] = t1 - t0;
   p->phase_seconds[1] = t2 - t1;
@@ -3559,10 +3651,7 @@ int topolow_layout_prep_fetch(topolow_layout_prep* p, int32_t* order, int32_t* d
                               int32_t* edge_j, double* edge_dist, int32_t* edge_thresh, double* dense, int32_t* tdense,
                               double* values_reordered, int8_t* codes_reordered, char* errbuf, size_t errlen) {
   if (!p || !order || !degrees || !edge_i || !edge_j || !edge_dist || !edge_thresh) return TOPOLOW_ERR_BAD_ARGUMENT;
-  if (p->declined) {
-    set_err(errbuf, errlen, "the ordering was declined (order_route 3): create again with order_in");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
+  if (const int rcu = prep_check_usable(p, errbuf, errlen)) return rcu;
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(p->device));
     const double t0 = now_s();
@@ -4285,10 +4374,7 @@ int topolow_session_load_prepared(topolow_session* s, topolow_layout_prep* p, ch
     set_err(errbuf, errlen, "null argument");
     return TOPOLOW_ERR_BAD_ARGUMENT;
   }
-  if (p->declined) {
-    set_err(errbuf, errlen, "the ordering was declined (order_route 3): create the handle again with order_in");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
+  if (const int rcu = prep_check_usable(p, errbuf, errlen)) return rcu;
   if (p->n != s->n) {
     set_err(errbuf, errlen, "the handle holds %d points, the session %d", p->n, s->n);
     return TOPOLOW_ERR_BAD_ARGUMENT;
@@ -4368,10 +4454,7 @@ int topolow_layout_prep_optimize(topolow_layout_prep* p, const double* initial_p
     set_err(errbuf, errlen, "null argument");
     return TOPOLOW_ERR_BAD_ARGUMENT;
   }
-  if (p->declined) {
-    set_err(errbuf, errlen, "the ordering was declined (order_route 3): create the handle again with order_in");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
+  if (const int rcu = prep_check_usable(p, errbuf, errlen)) return rcu;
   topolow_options opt;
   if (opt_in) opt = *opt_in; else topolow_default_options(&opt);
   if (opt.n_devices > 1 || opt.devices != nullptr) {
@@ -4422,10 +4505,7 @@ int topolow_layout_prep_post_metrics(topolow_layout_prep* p, const double* posit
     set_err(errbuf, errlen, "null argument, or ndim < 1");
     return TOPOLOW_ERR_BAD_ARGUMENT;
   }
-  if (p->declined) {
-    set_err(errbuf, errlen, "the ordering was declined (order_route 3): create the handle again with order_in");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
+  if (const int rcu = prep_check_usable(p, errbuf, errlen)) return rcu;
   const double t0 = now_s();
   (void)hipSetDevice(p->device);
   const PostResident resident = {p->vals.p, p->has_codes ? p->codes.p : nullptr, p->order[0] != -1 ? p->ord.p : nullptr};
@@ -4463,29 +4543,21 @@ struct FoldPrepared {
 };
 
 int prep_fold_check_handle(const topolow_layout_prep* p, char* errbuf, size_t errlen) {
-  if (p->declined || p->order.empty() || p->order[0] != -1) {
-    set_err(errbuf, errlen, "a fold's labels are the caller's, the full matrix's order is of no use to it: create the "
-            "handle with preserve_order");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
-  return TOPOLOW_OK;
+  if (!p->declined && !p->order.empty() && p->order[0] == -1) return TOPOLOW_OK;
+  set_err(errbuf, errlen, "a fold's labels are the caller's, the full matrix's order is of no use to it: create the "
+          "handle with preserve_order");
+  return TOPOLOW_ERR_BAD_ARGUMENT;
 }
 
-void prep_fold_alloc(topolow_layout_prep* p) {
+void prep_fold_alloc(topolow_layout_prep* p) {   // on the handle's device, which it makes the current one
   auto& f = p->fold;
+  HIP_TRY(hipSetDevice(p->device));
   if (f.ready) return;
-  const size_t N = (size_t)p->n, nb = (N + kPrepTile - 1) / kPrepTile;
+  const size_t N = (size_t)p->n;
   if (!f.stream) HIP_TRY(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
   f.mask_words = (N * N + 31) / 32;
   prep_alloc(f.mask, f.mask_words, "the fold mask");
-  prep_alloc(f.part_slow_sum, nb * N, "the partial sums");
-  prep_alloc(f.part_fast_sum, nb * N, "the partial sums");
-  prep_alloc(f.part_slow_cnt, nb * N, "the partial counts");
-  prep_alloc(f.part_fast_cnt, nb * N, "the partial counts");
-  prep_alloc(f.line_sum, 2 * N, "the sums");
-  prep_alloc(f.line_cnt, 2 * N, "the counts");
-  prep_alloc(f.diag, N, "the diagonal flags");
-  prep_alloc(f.totals, 1, "the totals");
+  f.sums.alloc(p->n);
   prep_alloc(f.col_counts, 2 * N, "the column counts");
   prep_alloc(f.offsets, 2 * (N + 1), "the column offsets");
   prep_alloc(f.order, N, "the fold's order");
@@ -4511,11 +4583,11 @@ void prep_fold_symmetry(topolow_layout_prep* p) {
   if (!f.symmetry_known) {
     const int nb = (p->n + kPrepTile - 1) / kPrepTile;
     FoldTotals tot;
-    HIP_TRY(hipMemsetAsync(f.totals.p, 0, sizeof(FoldTotals), f.stream));
+    HIP_TRY(hipMemsetAsync(f.sums.totals.p, 0, sizeof(FoldTotals), f.stream));
     hipLaunchKernelGGL(fold_symmetry_kernel, dim3(nb, nb), dim3(kPrepThreads), 0, f.stream, p->vals.p,
-                       p->has_codes ? p->codes.p : nullptr, p->n, f.totals.p);
+                       p->has_codes ? p->codes.p : nullptr, p->n, f.sums.totals.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&tot, f.totals.p, sizeof tot, hipMemcpyDeviceToHost, f.stream));
+    HIP_TRY(hipMemcpyAsync(&tot, f.sums.totals.p, sizeof tot, hipMemcpyDeviceToHost, f.stream));
     HIP_TRY(hipStreamSynchronize(f.stream));
     f.symmetric = tot.n_asymmetric == 0;
     f.symmetry_known = true;
@@ -4532,69 +4604,42 @@ void prep_fold_prepare(topolow_layout_prep* p, hipStream_t stream, const int64_t
   const size_t N = (size_t)n;
   const int nb = (n + kPrepTile - 1) / kPrepTile;
   const int8_t* codes = p->has_codes ? p->codes.p : nullptr;
-  HIP_TRY(hipMemsetAsync(f.totals.p, 0, sizeof(FoldTotals), stream));
+  auto& S = f.sums;
+  HIP_TRY(hipMemsetAsync(S.totals.p, 0, sizeof(FoldTotals), stream));
   if (n_picks > 0) {
     grow_buf(f.picks, (size_t)n_picks);
     HIP_TRY(hipMemcpyAsync(f.picks.p, picks, (size_t)n_picks * 8, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(fold_mark_kernel, dim3((unsigned)((n_picks + kPrepThreads - 1) / kPrepThreads)), dim3(kPrepThreads),
-                       0, stream, f.picks.p, (long long)n_picks, n, f.mask.p, f.totals.p);
+                       0, stream, f.picks.p, (long long)n_picks, n, f.mask.p, S.totals.p);
     HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(fold_sums_kernel, dim3(nb, nb), dim3(kPrepThreads), 0, stream, p->vals.p, codes, f.mask.p, n,
-                     f.part_slow_sum.p, f.part_slow_cnt.p, f.part_fast_sum.p, f.part_fast_cnt.p, f.diag.p, f.totals.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(prep_finish_sums_kernel, dim3((n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, stream,
-                     n, nb, f.part_slow_sum.p, f.part_slow_cnt.p, f.part_fast_sum.p, f.part_fast_cnt.p, f.line_sum.p,
-                     f.line_cnt.p);
+                     S.part_slow_sum.p, S.part_slow_cnt.p, S.part_fast_sum.p, S.part_fast_cnt.p, S.diag.p, S.totals.p);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(fold_compact_count_kernel, dim3(n), dim3(kPrepThreads), 0, stream, p->vals.p, codes, f.mask.p, n,
                      f.col_counts.p, f.col_counts.p + N);
   HIP_TRY(hipGetLastError());
-  std::vector<double> sums(2 * N);
-  std::vector<int32_t> cnts(2 * N), per_col(2 * N);
-  std::vector<uint8_t> on_diag(N);
-  FoldTotals tot;
-  HIP_TRY(hipMemcpyAsync(sums.data(), f.line_sum.p, 2 * N * 8, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(cnts.data(), f.line_cnt.p, 2 * N * 4, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(on_diag.data(), f.diag.p, N, hipMemcpyDeviceToHost, stream));
+  std::vector<int32_t> per_col(2 * N);
+  S.fetch(n, stream);
   HIP_TRY(hipMemcpyAsync(per_col.data(), f.col_counts.p, 2 * N * 4, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(&tot, f.totals.p, sizeof tot, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  if (tot.n_bad_picks > 0)
-    throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, std::to_string(tot.n_bad_picks) + " of the fold's picks lie outside the matrix (linear column-major indices 0 .. n * n - 1)"};
+  if (S.tot.n_bad_picks > 0)
+    throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, std::to_string(S.tot.n_bad_picks) + " of the fold's picks lie outside the matrix (linear column-major indices 0 .. n * n - 1)"};
 
   // -- the n-sized results.  The buffer is read column-major (relax_prep_fold.h): slow lines are columns, fast lines rows.
   const size_t row_at = N, col_at = 0;
   out.order.assign(N, 0);
   out.order[0] = -1;
-  out.route = TOPOLOW_ORDER_PRESERVED;
-  if (!preserve_order) {
-    std::vector<int64_t> row_cnt(N), col_cnt(N);
-    for (size_t q = 0; q < N; ++q) {
-      row_cnt[q] = (int64_t)cnts[row_at + q] - on_diag[q];
-      col_cnt[q] = (int64_t)cnts[col_at + q] - on_diag[q];
-    }
-    const int32_t flag = p->exact_sums ? 1 : (p->negative_or_infinite ? -1 : 0);
-    out.route = topolow_layout_order_from_sums(n, sums.data() + row_at, row_cnt.data(), sums.data() + col_at,
-                                               col_cnt.data(), flag, out.order.data());
-  }
-  out.degrees.resize(N);
-  for (size_t q = 0; q < N; ++q) out.degrees[q] = cnts[row_at + q];
-  out.n_edges = (int64_t)tot.n_upper;
-  out.numeric_max = NAN;
-  if (tot.max_key != 0) {
-    const uint64_t bits = (tot.max_key >> 63) ? (uint64_t)(tot.max_key & 0x7fffffffffffffffull) : (uint64_t)~tot.max_key;
-    memcpy(&out.numeric_max, &bits, 8);
-  }
+  out.route = preserve_order ? TOPOLOW_ORDER_PRESERVED
+                             : S.order(n, row_at, col_at, p->exact_sums, p->negative_or_infinite, out.order.data());
+  out.degrees.assign(S.cnts.begin() + row_at, S.cnts.begin() + row_at + N);
+  out.n_edges = (int64_t)S.tot.n_upper;
+  out.numeric_max = S.numeric_max();
 
   // -- the stable compaction of the mask: held-out pairs and scored cells, column by column
-  std::vector<int64_t> off(2 * (N + 1), 0);
-  for (size_t j = 0; j < N; ++j) {
-    off[j + 1] = off[j] + per_col[j];
-    off[N + 1 + j + 1] = off[N + 1 + j] + per_col[N + j];
-  }
-  out.n_pairs = off[N];
-  out.n_scored = off[2 * N + 1];
+  std::vector<int64_t> off(2 * (N + 1));
+  out.n_pairs = prep_offsets(per_col.data(), N, off.data());
+  out.n_scored = prep_offsets(per_col.data() + N, N, off.data() + N + 1);
   out.d_order = nullptr;
   if (out.n_pairs + out.n_scored > 0) {
     grow_buf(f.pair_i, (size_t)out.n_pairs); grow_buf(f.pair_j, (size_t)out.n_pairs);
@@ -4628,7 +4673,6 @@ int topolow_layout_prep_fold(topolow_layout_prep* p, const int64_t* picks, int64
   }
   if (const int rch = prep_fold_check_handle(p, errbuf, errlen)) return rch;
   return guarded(errbuf, errlen, [&] {
-    HIP_TRY(hipSetDevice(p->device));
     prep_fold_alloc(p);
     prep_fold_symmetry(p);
     auto& f = p->fold;
@@ -4660,6 +4704,84 @@ int topolow_layout_prep_fold(topolow_layout_prep* p, const int64_t* picks, int64
   });
 }
 
+namespace {
+
+// Folds prepared from a handle on the session's stream (prep_fold_prepare); a fold's guard empties the mask after it.
+struct HandleFolds {
+  topolow_layout_prep* p;
+  const SweepArgs& a;
+  int32_t* order_route;
+  struct Fold { FoldMaskGuard guard; int code = TOPOLOW_OK; FoldPrepared fp; std::vector<double> pos; };
+  int n = 0, device = 0;
+  const int32_t* degrees = nullptr;
+  double* seconds = nullptr;
+  int begin(char* errbuf, size_t errlen) {
+    if (const int rch = prep_fold_check_handle(p, errbuf, errlen)) return rch;
+    n = p->n; device = p->device; degrees = p->degrees.data(); seconds = p->fold.seconds;
+    const int64_t cells = (int64_t)n * n;
+    for (int f = 0; f < a.n_folds; ++f)
+      for (int64_t q = a.picks_offset[f]; q < a.picks_offset[f + 1]; ++q)
+        if (!a.picks || a.picks[q] < 0 || a.picks[q] >= cells) {
+          set_err(errbuf, errlen, "fold %d: pick %lld lies outside the matrix (linear column-major indices 0 .. n * n - 1)",
+                  f, (long long)(q - a.picks_offset[f]));
+          return TOPOLOW_ERR_BAD_ARGUMENT;
+        }
+    const int rc = guarded(errbuf, errlen, [&] { prep_fold_alloc(p); prep_fold_symmetry(p); });
+    for (int f = 0; f < a.n_folds && rc == TOPOLOW_OK; ++f) order_route[f] = TOPOLOW_ORDER_PRESERVED;
+    return rc;
+  }
+  int load(topolow_session* t, char* eb, size_t el) const { return topolow_session_load_prepared(t, p, eb, el); }
+  void prefetch(int) {}   // (nothing is prepared ahead, so drain() has nothing to wait for)
+  void drain() {}
+  std::unique_ptr<Fold> prepare(topolow_session* s, int f, int* rc, char* errbuf, size_t errlen) {
+    std::unique_ptr<Fold> o;
+    *rc = guarded(errbuf, errlen, [&] {
+      o.reset(new Fold{FoldMaskGuard{p, s->stream}});
+      HIP_TRY(hipSetDevice(p->device));
+      prep_fold_prepare(p, s->stream, a.picks + a.picks_offset[f], a.picks_offset[f + 1] - a.picks_offset[f],
+                        a.preserve_order, a.named, o->fp);
+      order_route[f] = o->fp.route;
+      if (o->fp.route == TOPOLOW_ORDER_DECLINED) {   // the caller reruns this fold with the host's ordering
+        o->code = TOPOLOW_ERR_UNSUPPORTED;
+        return;
+      }
+      o->code = fold_check(TOPOLOW_OK, o->fp.n_edges, o->fp.numeric_max, a.ndim[f], a.draws_offset[f + 1] - a.draws_offset[f], p->n);
+      if (o->code == TOPOLOW_OK)
+        start_walk(a.unit_draws + a.draws_offset[f], o->fp.numeric_max, p->n, a.ndim[f],
+                   o->fp.order[0] >= 0 ? o->fp.order.data() : nullptr, o->pos);
+    });
+    return o;
+  }
+  // the shared hold-out, its pairs mapped to session labels on the device
+  int hold_out(topolow_session* s, const Fold& o, char* errbuf, size_t errlen) const {
+    if (const int rc = cv_check_hold_out(s, errbuf, errlen)) return rc;
+    return guarded(errbuf, errlen, [&] {
+      cv_hold_out_pairs(s, (long long)o.fp.n_pairs, o.fp.degrees.data(), [&](int* d_lo, int* d_hi) {
+        hipLaunchKernelGGL(fold_pair_labels_kernel, dim3(fold_grid(o.fp.n_pairs)), dim3(kPrepThreads), 0, s->stream,
+                           p->fold.pair_i.p, p->fold.pair_j.p, (long long)o.fp.n_pairs,
+                           s->inv.empty() ? nullptr : s->d_inv.p, d_lo, d_hi);
+        HIP_TRY(hipGetLastError());
+      });
+    });
+  }
+  // the shared score: the scored cells' points gathered through the order and the session's labels on the device
+  int score(topolow_session* s, const Fold& o, double* sum_abs, int64_t* count, char* errbuf, size_t errlen) const {
+    if (o.fp.n_scored == 0) return TOPOLOW_OK;
+    return guarded(errbuf, errlen, [&] {
+      auto& c = s->cv;
+      const auto& h = p->fold;
+      grow_buf(c.sc_i, (size_t)o.fp.n_scored); grow_buf(c.sc_j, (size_t)o.fp.n_scored);
+      hipLaunchKernelGGL(fold_score_points_kernel, dim3(fold_grid(o.fp.n_scored)), dim3(kPrepThreads), 0, s->stream,
+                         h.score_r.p, h.score_c.p, (long long)o.fp.n_scored, o.fp.d_order,
+                         s->inv.empty() ? nullptr : s->d_inv.p, c.sc_i.p, c.sc_j.p);
+      HIP_TRY(hipGetLastError());
+      cv_score_device(s, c.sc_i.p, c.sc_j.p, h.score_truth.p, (long long)o.fp.n_scored, sum_abs, count);
+    });
+  }
+};
+
+}  // namespace
+
 int topolow_layout_prep_cv_sweep(topolow_layout_prep* p, int32_t named, int32_t preserve_order, int32_t n_folds,
                                  const int32_t* ndim, const double* k0, const double* cooling_rate,
                                  const double* c_repulsion, const int64_t* picks, const int64_t* picks_offset,
@@ -4669,138 +4791,15 @@ int topolow_layout_prep_cv_sweep(topolow_layout_prep* p, int32_t named, int32_t 
                                  double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations, int32_t* converged,
                                  int32_t* error_code, int32_t* order_route, double* device_seconds, char* errbuf,
                                  size_t errlen) {
-  if (!cv_sweep_args_ok(p, n_folds, ndim, k0, cooling_rate, c_repulsion, picks_offset, unit_draws, draws_offset, seeds,
-                        holdout_sum_abs, holdout_count, iterations, converged, error_code) ||
-      (n_folds > 0 && !order_route) ||
-      (schedule != TOPOLOW_SCHEDULE_AUTO && schedule != TOPOLOW_SCHEDULE_SLAB && schedule != TOPOLOW_SCHEDULE_GS)) {
-    set_err(errbuf, errlen, "null argument, n_folds < 0 or an unknown schedule");
+  const SweepArgs a{named, preserve_order, n_folds, ndim, k0, cooling_rate, c_repulsion, picks, picks_offset, unit_draws,
+                    draws_offset, seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq, precision,
+                    schedule, holdout_sum_abs, holdout_count, iterations, converged, error_code, device_seconds};
+  if (n_folds > 0 && !order_route) {
+    set_err(errbuf, errlen, "null argument: order_route");
     return TOPOLOW_ERR_BAD_ARGUMENT;
   }
-  if (device_seconds) *device_seconds = 0.0;
-  if (precision == TOPOLOW_PRECISION_F64_EXACT) {
-    set_err(errbuf, errlen, "precision f64_exact: no cross-validation on resident sessions (holding a fold out does not "
-            "cover the delta block); topolow_cv_sweep runs it on the one-workgroup kernel");
-    return TOPOLOW_ERR_UNSUPPORTED;
-  }
-  if (n_folds == 0) return TOPOLOW_OK;
-  if (const int rch = prep_fold_check_handle(p, errbuf, errlen)) return rch;
-  const int n = p->n;
-  const int64_t cells = (int64_t)n * n;
-  for (int f = 0; f < n_folds; ++f)
-    for (int64_t q = picks_offset[f]; q < picks_offset[f + 1]; ++q)
-      if (!picks || picks[q] < 0 || picks[q] >= cells) {
-        set_err(errbuf, errlen, "fold %d: pick %lld lies outside the matrix (linear column-major indices 0 .. n * n - 1)",
-                f, (long long)(q - picks_offset[f]));
-        return TOPOLOW_ERR_BAD_ARGUMENT;
-      }
-  const bool tile_gs = schedule == TOPOLOW_SCHEDULE_GS;
-  const int prec = precision == TOPOLOW_PRECISION_AUTO ? (tile_gs ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32) : precision;
-  const int rc_sym = guarded(errbuf, errlen, [&] {
-    HIP_TRY(hipSetDevice(p->device));
-    prep_fold_alloc(p);
-    prep_fold_symmetry(p);
-  });
-  if (rc_sym != TOPOLOW_OK) return rc_sym;
-  for (int f = 0; f < n_folds; ++f) {
-    holdout_sum_abs[f] = 0.0; holdout_count[f] = 0; iterations[f] = 0; converged[f] = 0;
-    error_code[f] = TOPOLOW_OK;
-    order_route[f] = TOPOLOW_ORDER_PRESERVED;
-  }
-  double* secs = p->fold.seconds;
-  secs[0] = secs[1] = secs[2] = secs[3] = 0.0;
-  std::vector<char> done((size_t)n_folds, 0);
-  for (int g0 = 0; g0 < n_folds; ++g0) {
-    if (done[(size_t)g0]) continue;
-    std::vector<int> members;   // the folds that share this ndim, in the caller's order
-    for (int f = g0; f < n_folds; ++f)
-      if (!done[(size_t)f] && ndim[f] == ndim[g0]) { members.push_back(f); done[(size_t)f] = 1; }
-    if (ndim[g0] < 1) {
-      for (int f : members) error_code[f] = TOPOLOW_ERR_BAD_ARGUMENT;
-      continue;
-    }
-    topolow_session* s = nullptr;
-    int rc = open_session(&s, n, ndim[g0], tile_gs, prec, p->device, &seeds[members[0]],
-                          [&](topolow_session* t, char* eb, size_t el) -> int { return topolow_session_load_prepared(t, p, eb, el); },
-                          errbuf, errlen);
-    for (size_t q = 0; q < members.size() && rc == TOPOLOW_OK; ++q) {
-      const int f = members[q];
-      auto& h = p->fold;
-      FoldMaskGuard guard{p, s->stream};   // the mask is empty before the next fold starts, whatever this one does
-      FoldPrepared fp;
-      std::vector<double> pos;   // start positions, n x ndim column-major, caller's labels
-      const double tp = now_s();
-      rc = guarded(errbuf, errlen, [&] {
-        HIP_TRY(hipSetDevice(p->device));
-        prep_fold_prepare(p, s->stream, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named, fp);
-        order_route[f] = fp.route;
-        if (fp.route == TOPOLOW_ORDER_DECLINED) {   // the caller reruns this fold with the host's ordering
-          error_code[f] = TOPOLOW_ERR_UNSUPPORTED;
-          return;
-        }
-        error_code[f] = fold_check(TOPOLOW_OK, fp.n_edges, fp.numeric_max, ndim[f], draws_offset[f + 1] - draws_offset[f], n);
-        if (error_code[f] == TOPOLOW_OK)
-          start_walk(unit_draws + draws_offset[f], fp.numeric_max, n, ndim[f], fp.order[0] >= 0 ? fp.order.data() : nullptr, pos);
-      });
-      secs[0] += now_s() - tp;
-      if (rc != TOPOLOW_OK) break;
-      if (error_code[f] != TOPOLOW_OK) continue;   // the session was not touched
-      // the shared hold-out, its pairs mapped to session labels on the device
-      const double th = now_s();
-      rc = cv_check_hold_out(s, errbuf, errlen);
-      if (rc == TOPOLOW_OK)
-        rc = guarded(errbuf, errlen, [&] {
-          cv_hold_out_pairs(s, (long long)fp.n_pairs, fp.degrees.data(), [&](int* d_lo, int* d_hi) {
-            hipLaunchKernelGGL(fold_pair_labels_kernel, dim3(fold_grid(fp.n_pairs)), dim3(kPrepThreads), 0, s->stream,
-                               h.pair_i.p, h.pair_j.p, (long long)fp.n_pairs, s->inv.empty() ? nullptr : s->d_inv.p, d_lo,
-                               d_hi);
-            HIP_TRY(hipGetLastError());
-          });
-        });
-      secs[1] += now_s() - th;
-      if (rc) break;
-      const double t0 = now_s();
-      int rcf = topolow_session_set_positions(s, pos.data(), errbuf, errlen);
-      if (rcf == TOPOLOW_OK)
-        rcf = topolow_session_begin(s, n_iter, k0[f], cooling_rate[f], c_repulsion[f], relative_epsilon, convergence_window,
-                                    convergence_check_freq, seeds[f], 0, errbuf, errlen);
-      if (rcf == TOPOLOW_OK) rcf = enqueue_run(s, nullptr, errbuf, errlen);
-      if (rcf == TOPOLOW_OK)
-        rcf = topolow_session_finish(s, nullptr, &converged[f], &iterations[f], nullptr, nullptr, errbuf, errlen);
-      else
-        (void)topolow_session_finish(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);   // the run is over either way
-      if (device_seconds) *device_seconds += now_s() - t0;
-      // the shared score: the scored cells' points gathered through the order and the session's labels on the device
-      const double ts = now_s();
-      if (rcf == TOPOLOW_OK && fp.n_scored > 0)
-        rcf = guarded(errbuf, errlen, [&] {
-          auto& c = s->cv;
-          grow_buf(c.sc_i, (size_t)fp.n_scored); grow_buf(c.sc_j, (size_t)fp.n_scored);
-          hipLaunchKernelGGL(fold_score_points_kernel, dim3(fold_grid(fp.n_scored)), dim3(kPrepThreads), 0, s->stream,
-                             h.score_r.p, h.score_c.p, (long long)fp.n_scored, fp.d_order,
-                             s->inv.empty() ? nullptr : s->d_inv.p, c.sc_i.p, c.sc_j.p);
-          HIP_TRY(hipGetLastError());
-          cv_score_device(s, c.sc_i.p, c.sc_j.p, h.score_truth.p, (long long)fp.n_scored, &holdout_sum_abs[f],
-                          &holdout_count[f]);
-        });
-      secs[2] += now_s() - ts;
-      // the session is the full matrix again before the next fold starts, whatever this one did
-      const double tr = now_s();
-      char rerr[256] = "";
-      const int rcr = topolow_session_restore_held_out(s, p->degrees.data(), rerr, sizeof rerr);
-      secs[3] += now_s() - tr;
-      if (rcf == TOPOLOW_ERR_NONFINITE) {   // a diverged fold is this fold's result, not the call's
-        error_code[f] = TOPOLOW_ERR_NONFINITE;
-        iterations[f] = 0; converged[f] = 0;
-        holdout_sum_abs[f] = 0.0; holdout_count[f] = 0;
-        rcf = TOPOLOW_OK;
-      }
-      if (rcf != TOPOLOW_OK) { rc = rcf; break; }
-      if (rcr != TOPOLOW_OK) { set_err(errbuf, errlen, "%s", rerr); rc = rcr; break; }
-    }
-    if (s) topolow_session_destroy(s);
-    if (rc != TOPOLOW_OK) return rc;
-  }
-  return TOPOLOW_OK;
+  HandleFolds src{p, a, order_route};
+  return cv_sweep_resident(p, src, a, errbuf, errlen);
 }
 
 int topolow_layout_prep_fold_seconds(const topolow_layout_prep* p, double* seconds) {
