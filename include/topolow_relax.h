@@ -605,6 +605,73 @@ int topolow_layout_prep_subsample(topolow_layout_prep* parent, const int32_t* su
 int topolow_layout_prep_graph_stats(const topolow_layout_prep* p, int32_t* rounds, double* seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * Spectrum of a resident matrix: step 1 of the reference's Euclidify(), "Assessing data characteristics"
+ * (R/core.R:983-1007) -- as.numeric, median fill, square, double-centre, all eigenvalues, deviation_score and
+ * dims_90_percent -- and the symmetric eigenvalue path under it.  All f64, one GPU, no solver library.
+ *   Householder tridiagonalisation, unblocked, one reflection per column applied as a rank-2 update of the trailing
+ *   matrix: three launches per step on one stream (a one-workgroup step kernel; one streaming kernel that applies the
+ *   pending update and accumulates the next A v in the same read, one partial per column and block of 64 lines; one
+ *   kernel that adds the partials in block order), no grid barrier.  The matrix is held in full
+ *   (both triangles, kept symmetric bit for bit): 8 n^2 bytes, read and written once per step.
+ *   Eigenvalues of the tridiagonal by Sturm bisection on the Gershgorin interval, one index per thread, with LAPACK
+ *   dstebz's pivmin guard; an interval ends at a width of 2 u max(|lo|, |hi|) + pivmin, u = 2^-52.  Descending order.
+ *   No floating-point atomics: every reduction has fixed partitions added in fixed order, so two calls on the same
+ *   input return the same bits.  The entries assume values whose squares stay inside the f64 range.
+ * ------------------------------------------------------------------------------------- */
+
+/* All eigenvalues of the symmetric tridiagonal matrix with diagonal d (n) and off-diagonal e (n - 1; not read when
+ * n == 1), descending, into eigenvalues_out (n).  A zero in e needs no special treatment.
+ * TOPOLOW_ERR_BAD_ARGUMENT with a message, before any device call: NULL d or eigenvalues_out; n < 1; NULL e with
+ * n >= 2; an entry of d or e that is not finite. */
+int topolow_tridiagonal_eigenvalues(const double* d, const double* e, int32_t n, int32_t device,
+                                    double* eigenvalues_out, char* errbuf, size_t errlen);
+
+/* a: host, n x n f64 column-major; only its lower triangle (row >= column) is read.  Each output may be NULL (not
+ * wanted): d_out (n) and e_out (n - 1), the tridiagonal form Q^T A Q, and eigenvalues_out (n), descending.
+ * Memory: the matrix on the device (8 n^2 bytes) and O(n) beside it; a failed allocation: TOPOLOW_ERR_UNSUPPORTED.
+ * TOPOLOW_ERR_BAD_ARGUMENT with a message, before any device call: NULL a; n < 1; a cell of the lower triangle that
+ * is not finite. */
+int topolow_symmetric_eigenvalues(const double* a, int32_t n, int32_t device, double* d_out, double* e_out,
+                                  double* eigenvalues_out, char* errbuf, size_t errlen);
+
+typedef struct topolow_spectrum_info {
+  double  median;             /* of the numeric cells (code 0, not NaN), diagonal and both triangles: np.median's value */
+  int64_t n_numeric;          /* how many of them there are */
+  int64_t n_filled;           /* n^2 - n_numeric: the cells that took the median (NaN, or a threshold code) */
+  double  trace;              /* of the centred matrix B, its diagonal added in index order */
+  int64_t n_positive, n_negative;       /* eigenvalues > 1e-12, < -1e-12 */
+  double  sum_positive, sum_negative;   /* their sums, the negative ones by absolute value */
+  double  deviation_score;    /* sum_negative / sum_positive; 1.0 when nothing is positive */
+  int32_t dims_90;            /* max(1, first count of leading positive eigenvalues with >= 0.90 of sum_positive) */
+  int32_t reserved32;
+  double  seconds[4];         /* wall clock: median, centring, tridiagonalisation, bisection */
+  int64_t reserved[4];
+} topolow_spectrum_info;
+
+/* The assessment of the handle's matrix, defined on the matrix in its INPUT order whatever the handle's ordering (a
+ * handle that declined its ordering serves: only the matrix and the codes are read).  The matrix need not be symmetric.
+ *   median   over every cell with code 0 that is not NaN, by a radix select over the order-preserving 64-bit key of
+ *            the double, both middle ranks in the same 8 passes, integer atomics only; an even count gives
+ *            (a + b) / 2 of the two middle values.  Equal to np.median of those cells (the sign of a zero aside).
+ *   x_ij     the cell where it is numeric, otherwise the median (threshold-coded cells too: as.numeric makes them NA)
+ *   B_ij     -0.5 (x_ij^2 - r_i - c_j + g), r / c / g the row / column / grand means of x^2.  The sums follow the first
+ *            pass's rule ("Prepared layout" above: one partial per point and block of 64 cells added in index order, a
+ *            point's partials in block order), g comes from the row sums in index order: the same bits whatever the
+ *            grid and the layout flag.
+ *   eigenvalues   of the symmetric matrix whose lower triangle (row >= column) is B's, as R's eigen(symmetric = TRUE)
+ *            and NumPy's eigvalsh read it; descending
+ *   info     deviation_score and dims_90 from the downloaded eigenvalues on the host, as R/core.R:994-1007
+ * eigenvalues_out: n, or NULL.  centered_out: host, n x n laid out as the handle's inputs are, or NULL: B itself, both
+ * triangles as computed.  The handle is neither consumed nor altered: fetch(), optimize() and the fold entries return
+ * afterwards what they returned before.  B is 8 n^2 bytes of transient device memory, freed before return; a failed
+ * allocation: TOPOLOW_ERR_UNSUPPORTED with a message.
+ * TOPOLOW_ERR_BAD_ARGUMENT with a message: a NULL handle or info (before any device call); no numeric cell; a code-0
+ * cell that is +-Inf ("infinite or missing values in 'x'", R's eigen). */
+int topolow_layout_prep_spectrum(topolow_layout_prep* p, double* eigenvalues_out /* n, or NULL */,
+                                 double* centered_out /* n x n, or NULL */, topolow_spectrum_info* info, char* errbuf,
+                                 size_t errlen);
+
+/* ---------------------------------------------------------------------------------------
  * Device-resident session: the same relaxation with inputs kept in HBM, for callers that
  * run many iterations / many embeddings on data they already hold on the GPU (bench.py, the
  * row-sharded multi-GPU driver).  Pointers named d_* are DEVICE pointers.

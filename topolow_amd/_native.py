@@ -88,6 +88,13 @@ class TopolowLayoutPrepInfo(C.Structure):
                 ("order_route", C.c_int32), ("exact_sums", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class TopolowSpectrumInfo(C.Structure):
+    _fields_ = [("median", C.c_double), ("n_numeric", C.c_int64), ("n_filled", C.c_int64), ("trace", C.c_double),
+                ("n_positive", C.c_int64), ("n_negative", C.c_int64), ("sum_positive", C.c_double),
+                ("sum_negative", C.c_double), ("deviation_score", C.c_double), ("dims_90", C.c_int32),
+                ("reserved32", C.c_int32), ("seconds", C.c_double * 4), ("reserved", C.c_int64 * 4)]
+
+
 class TopolowResult(C.Structure):
     _fields_ = [("positions_out", C.POINTER(C.c_double)), ("final_mae", C.c_double),
                 ("final_k", C.c_double), ("converged", C.c_int32), ("iterations", C.c_int32),
@@ -369,6 +376,12 @@ def load() -> C.CDLL:
                                                   C.POINTER(TopolowLayoutPrepInfo), C.c_char_p, C.c_size_t]
     lib.topolow_layout_prep_graph_stats.restype = C.c_int
     lib.topolow_layout_prep_graph_stats.argtypes = [vp, ip, dp]
+    lib.topolow_tridiagonal_eigenvalues.restype = C.c_int
+    lib.topolow_tridiagonal_eigenvalues.argtypes = [dp, dp, C.c_int32, C.c_int32, dp, C.c_char_p, C.c_size_t]
+    lib.topolow_symmetric_eigenvalues.restype = C.c_int
+    lib.topolow_symmetric_eigenvalues.argtypes = [dp, C.c_int32, C.c_int32, dp, dp, dp, C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_spectrum.restype = C.c_int
+    lib.topolow_layout_prep_spectrum.argtypes = [vp, dp, dp, C.POINTER(TopolowSpectrumInfo), C.c_char_p, C.c_size_t]
     lib.topolow_layout_order_from_sums.restype = C.c_int32
     lib.topolow_layout_order_from_sums.argtypes = [C.c_int32, dp, i64p, dp, i64p, C.c_int32, ip]
     _lib = lib
@@ -1131,6 +1144,24 @@ class PreparedHandle:
         child.info = {k: getattr(info, k) for k, _ in TopolowLayoutPrepInfo._fields_ if k != "reserved"}
         return child
 
+    def spectrum(self, want_eigenvalues: bool = True, want_centered: bool = False):
+        """topolow_layout_prep_spectrum: the data assessment of the reference's Euclidify() (R/core.R:983-1007) of the
+        resident matrix in its input order.  Returns (info, eigenvalues or None, centered or None): info the fields of
+        topolow_spectrum_info as a dict (`seconds`: median, centring, tridiagonalisation, bisection), the eigenvalues
+        descending, centered the matrix B = -0.5 J D^2 J in the handle's layout.  Serves a handle that declined its
+        ordering; the handle is not altered.  No numeric cell, or an infinite one: NativeError(ERR_BAD_ARGUMENT)."""
+        n = self.n
+        eig = np.empty(n, dtype=np.float64) if want_eigenvalues else None
+        cen = np.empty((n, n), dtype=np.float64, order=self.layout) if want_centered else None
+        info = TopolowSpectrumInfo()
+        rc = self.lib.topolow_layout_prep_spectrum(self._h, _dp(eig) if eig is not None else None,
+                                                   _dp(cen) if cen is not None else None, C.byref(info), self._err,
+                                                   len(self._err))
+        _check(rc, self._err)
+        out = {k: getattr(info, k) for k, _ in TopolowSpectrumInfo._fields_ if not k.startswith("reserved")}
+        out["seconds"] = list(info.seconds)
+        return out, eig, cen
+
     def graph_stats(self):
         """(rounds, [seconds of the bit pass, seconds of the rounds]) of the last .connectivity on this handle."""
         rounds, ph = C.c_int32(0), (C.c_double * 2)()
@@ -1171,6 +1202,46 @@ class PreparedHandle:
             self.close()
         except Exception:
             pass
+
+
+def tridiagonal_eigenvalues(d, e, device: Optional[int] = None) -> np.ndarray:
+    """topolow_tridiagonal_eigenvalues: all eigenvalues of the symmetric tridiagonal matrix (diagonal d, off-diagonal
+    e), descending, by Sturm bisection on the device."""
+    lib = load()
+    d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+    e = np.ascontiguousarray(e, dtype=np.float64).reshape(-1)
+    n = int(d.shape[0])
+    if e.shape[0] != max(n - 1, 0):
+        raise ValueError("e must have n - 1 entries")
+    out = np.empty(max(n, 1), dtype=np.float64)
+    err = C.create_string_buffer(512)
+    rc = lib.topolow_tridiagonal_eigenvalues(_dp(d), _dp(e) if n >= 2 else None, n,
+                                             int(options.get("device", -1)) if device is None else int(device), _dp(out),
+                                             err, len(err))
+    _check(rc, err)
+    return out[:n]
+
+
+def symmetric_eigenvalues(a, want_tridiagonal: bool = False, want_eigenvalues: bool = True, device: Optional[int] = None):
+    """topolow_symmetric_eigenvalues: the eigenvalues (descending) of the symmetric matrix whose lower triangle is
+    a's, by Householder tridiagonalisation and bisection on the device.  Returns the eigenvalues, or with
+    want_tridiagonal (eigenvalues or None, d, e): the tridiagonal form."""
+    lib = load()
+    a = np.asarray(a)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError("a must be an n x n matrix")
+    a = _f64F(a)
+    n = int(a.shape[0])
+    eig = np.empty(max(n, 1), dtype=np.float64) if want_eigenvalues else None
+    d = np.empty(max(n, 1), dtype=np.float64) if want_tridiagonal else None
+    e = np.empty(max(n, 1), dtype=np.float64) if want_tridiagonal else None
+    err = C.create_string_buffer(512)
+    rc = lib.topolow_symmetric_eigenvalues(_dp(a), n, int(options.get("device", -1)) if device is None else int(device),
+                                           _dp(d) if d is not None else None, _dp(e) if e is not None else None,
+                                           _dp(eig) if eig is not None else None, err, len(err))
+    _check(rc, err)
+    eig = eig[:n] if eig is not None else None
+    return (eig, d[:n], e[:max(n - 1, 0)]) if want_tridiagonal else eig
 
 
 def prepare_layout(values, codes=None, preserve_order: bool = False, order=None, want_dense: bool = True,
