@@ -805,6 +805,9 @@ int32_t topolow_session_uses_dense_mae(const topolow_session* s);
 /* Number of slab-stage kernel launches so far, and the algorithmic bytes one iteration
  * moves (4*rows*n + 8*n*ndim + 4*n). */
 int64_t topolow_session_stage_launches(const topolow_session* s);
+/* Convergence checks of the current run whose controller step went out in a symmetric apply's launch instead of a
+ * controller launch of its own (one-stage symmetric iterations; 0 under TOPOLOW_CHECK_IN_APPLY=0). */
+int64_t topolow_session_checks_in_apply(const topolow_session* s);
 int64_t topolow_session_bytes_per_iteration(const topolow_session* s);
 
 /* ---------------------------------------------------------------------------------------

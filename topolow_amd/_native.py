@@ -315,6 +315,8 @@ def load() -> C.CDLL:
     lib.topolow_session_uses_dense_mae.argtypes = [vp]
     lib.topolow_session_stage_launches.restype = C.c_int64
     lib.topolow_session_stage_launches.argtypes = [vp]
+    lib.topolow_session_checks_in_apply.restype = C.c_int64
+    lib.topolow_session_checks_in_apply.argtypes = [vp]
     lib.topolow_session_bytes_per_iteration.restype = C.c_int64
     lib.topolow_session_bytes_per_iteration.argtypes = [vp]
     lib.topolow_session_stage.restype = C.c_int
@@ -1542,6 +1544,11 @@ class Session:
     @property
     def stage_launches(self) -> int:
         return int(self.lib.topolow_session_stage_launches(self._h))
+
+    @property
+    def checks_in_apply(self) -> int:
+        """Checks of the current run whose controller step rode in a symmetric apply's launch."""
+        return int(self.lib.topolow_session_checks_in_apply(self._h))
 
     @property
     def symm_grid(self) -> int:

@@ -992,32 +992,51 @@ __global__ __launch_bounds__(1024) void reduce_total_kernel(
   if (threadIdx.x == 0) { out2[0] = sh_s[0]; out2[1] = (double)sh_c[0]; }
 }
 
-// Single-block controller step: reduces the partials in a fixed order, runs the reference's
+// Controller step of one workgroup: reduces the partials in a fixed order, runs the reference's
 // three-way classification, snapshots positions when the error improved, advances the run
 // state and mirrors it to the pinned host mailbox.
+//
+// The order of the reduction is part of the result: kCtlThreads strided partial sums (virtual
+// thread v sums the partials v, v + 1024, ...) followed by a halving tree over them.  A workgroup
+// of THREADS < kCtlThreads threads gives thread t the virtual threads t, t + THREADS, ... and
+// folds them exactly as the tree's first levels do (v with v + 512, then with v + 256, ...)
+// before it runs the remaining levels: the same additions on the same operands.
 constexpr int kCtlThreads = 1024;
 
-template <typename real>
-__global__ __launch_bounds__(kCtlThreads) void controller_kernel(
+template <int THREADS, typename real>
+__device__ __forceinline__ void controller_step(
     RunState* st, RunState* mailbox, const double* __restrict__ part_sum,
     const unsigned long long* __restrict__ part_cnt, int n_parts, const real* __restrict__ pos,
     real* __restrict__ best_pos, long long n_values, int iter1, double k_after,
     double* __restrict__ trace, int trace_cap, const double* __restrict__ total2) {
+  static_assert(THREADS >= 64 && THREADS <= kCtlThreads && kCtlThreads % THREADS == 0 && (THREADS & (THREADS - 1)) == 0,
+                "controller_step: a power-of-two workgroup of at most kCtlThreads threads");
+  constexpr int V = kCtlThreads / THREADS;   // virtual threads per thread
   // total2 != nullptr: the error sum and count arrive already reduced (two doubles: the row-sharded
   // multi-process driver all-reduces them over RCCL); the partial arrays are ignored
   if (st->stopped) return;
-  __shared__ double sh_s[kCtlThreads];
-  __shared__ unsigned long long sh_c[kCtlThreads];
+  __shared__ double sh_s[THREADS];
+  __shared__ unsigned long long sh_c[THREADS];
   __shared__ int sh_action;
-  double s = 0.0;
-  unsigned long long c = 0;
-  if (total2 == nullptr)
-    for (int p = threadIdx.x; p < n_parts; p += kCtlThreads) { s += part_sum[p]; c += part_cnt[p]; }
-  else if (threadIdx.x == 0) { s = total2[0]; c = (unsigned long long)total2[1]; }
-  sh_s[threadIdx.x] = s;
-  sh_c[threadIdx.x] = c;
+  double s[V];
+  unsigned long long c[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    s[j] = 0.0;
+    c[j] = 0;
+    if (total2 == nullptr)
+      for (int p = threadIdx.x + j * THREADS; p < n_parts; p += kCtlThreads) { s[j] += part_sum[p]; c[j] += part_cnt[p]; }
+  }
+  if (total2 != nullptr && threadIdx.x == 0) { s[0] = total2[0]; c[0] = (unsigned long long)total2[1]; }
+#pragma unroll
+  for (int h = V / 2; h >= 1; h >>= 1) {   // the tree's levels above THREADS
+#pragma unroll
+    for (int j = 0; j < h; ++j) { s[j] += s[j + h]; c[j] += c[j + h]; }
+  }
+  sh_s[threadIdx.x] = s[0];
+  sh_c[threadIdx.x] = c[0];
   __syncthreads();
-  for (int half = kCtlThreads / 2; half >= 1; half >>= 1) {
+  for (int half = THREADS / 2; half >= 1; half >>= 1) {
     if (threadIdx.x < half) {
       sh_s[threadIdx.x] += sh_s[threadIdx.x + half];
       sh_c[threadIdx.x] += sh_c[threadIdx.x + half];
@@ -1046,8 +1065,8 @@ __global__ __launch_bounds__(kCtlThreads) void controller_kernel(
     const long long n16 = bytes / 16;
     const uint4* src = reinterpret_cast<const uint4*>(pos);
     uint4* dst = reinterpret_cast<uint4*>(best_pos);
-    for (long long q = threadIdx.x; q < n16; q += kCtlThreads) dst[q] = src[q];
-    for (long long q = n16 * 16 / (long long)sizeof(real) + threadIdx.x; q < n_values; q += kCtlThreads)
+    for (long long q = threadIdx.x; q < n16; q += THREADS) dst[q] = src[q];
+    for (long long q = n16 * 16 / (long long)sizeof(real) + threadIdx.x; q < n_values; q += THREADS)
       best_pos[q] = pos[q];
   }
   __syncthreads();
@@ -1055,6 +1074,20 @@ __global__ __launch_bounds__(kCtlThreads) void controller_kernel(
     *mailbox = *st;
     __threadfence_system();
   }
+}
+
+// The controller step as a launch of its own: one workgroup of kCtlThreads threads.  The checks that do not ride on a
+// symmetric sweep use it (separate error passes, the row-owner ERR launches, the sharded engines and their total2 form,
+// the GS schedule, TOPOLOW_CHECK_IN_APPLY=0); a check that rode on a one-stage symmetric sweep runs the same step in one
+// more workgroup of that iteration's symm_apply_kernel (relax_symm.h).
+template <typename real>
+__global__ __launch_bounds__(kCtlThreads) void controller_kernel(
+    RunState* st, RunState* mailbox, const double* __restrict__ part_sum,
+    const unsigned long long* __restrict__ part_cnt, int n_parts, const real* __restrict__ pos,
+    real* __restrict__ best_pos, long long n_values, int iter1, double k_after,
+    double* __restrict__ trace, int trace_cap, const double* __restrict__ total2) {
+  controller_step<kCtlThreads, real>(st, mailbox, part_sum, part_cnt, n_parts, pos, best_pos, n_values, iter1, k_after,
+                                     trace, trace_cap, total2);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@
 #include <type_traits>
 #include <vector>
 #include "relax_common.h"
+#include "relax_kernels.h"
 
 namespace topolow {
 
@@ -589,12 +590,39 @@ template <int DIM> struct SymReal<DIM, float> {
   __device__ static float far(int) { return kFarF32; }
 };
 
+// A convergence check that rides in the apply's launch (part_sum == nullptr: none): the ERR sweep in front of this apply
+// left the MAE partials of the positions it read -- this iteration's input, `pos`, which nothing writes before this
+// launch has finished -- and one more workgroup behind the column blocks' runs the controller step on them.
+struct SymApplyCheck {
+  const double* part_sum = nullptr;
+  const unsigned long long* part_cnt = nullptr;
+  int n_parts = 0;
+  const void* pos = nullptr;   // the check's positions and the snapshot's buffer (the session's precision), n_values of them
+  void* best = nullptr;
+  long long n_values = 0;
+  int iter1 = 0;
+  double k_after = 0.0;
+  double* trace = nullptr;
+  int trace_cap = 0;
+  RunState* mailbox = nullptr;
+};
+
 // Sums the partials of one column block's 32 points in a fixed order and moves the points:
 //   p_i(new) = p_i - (row sums of i's units) + (column sums of the tile-rows above i's)
 // (relax_kernels.h: p_i(new) = p_i - sum over ALL c of (p_c - p_i) coef_i; for c in a tile-row above, the stored
 // column sum is sum (p_i - p_c)... with dx = p_c' - p_i' taken row-side, hence the sign).
 // Writes the positions (row-major n4 x DIM, as every other kernel reads them) and the records of the NEXT
 // iteration (k_next).
+//
+// With a check (chk.part_sum != nullptr) the grid is npad / 32 + 1 workgroups and the last one is the controller
+// (relax_kernels.h: controller_step on this kernel's 512 threads, the same sums in the same order as controller_kernel's
+// 1 024): it needs nothing from its siblings -- the partials are the sweep's, a launch earlier -- and they nothing from
+// it, so there is no synchronisation between workgroups.  The branch is on blockIdx.x and npad alone, wave-uniform, and sits
+// behind the opening all workgroups share (the check's workgroup reads row_units[0] for nothing: row_units ends at the
+// last tile-row).  The controller may set st->stopped
+// while its siblings are starting: one that sees the flag returns without storing, the others store, and pos_out and
+// rec_next come out mixed.  That is the race a controller beside running stage kernels has always had: after a stop every
+// later kernel is a no-op and the caller receives the snapshot (`best`), the run state and the trace, never pos_out.
 #ifndef TL_APPLY_PARTS
 #define TL_APPLY_PARTS 16
 #endif
@@ -603,17 +631,27 @@ template <int DIM, typename real>
 __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
     const real* __restrict__ rec, real* __restrict__ rec_next, real* __restrict__ pos_out, const float* __restrict__ gplus,
     const real* __restrict__ rowpart, const real* __restrict__ colpart, const int2* __restrict__ row_units, int n,
-    int npad, double k_next, double c_rep, int iter1, RunState* st, int rr_stages = 0, int rr_stage = 0) {
-  const int R = blockIdx.x >> 1;                   // the tile-row of this column block's points
+    int npad, double k_next, double c_rep, int iter1, RunState* st, int rr_stages = 0, int rr_stage = 0,
+    SymApplyCheck chk = SymApplyCheck{}) {
+  const bool check_wg = (int)blockIdx.x * kSymCols >= npad;   // the workgroup behind the last column block: the check
+  const int R = check_wg ? 0 : blockIdx.x >> 1;    // the tile-row of this column block's points (the check's: any valid one)
   // the tile-row's units are requested together with the stop flag, and what the first strips need is pinned in scalar
   // registers in front of the branch, as in the sweep: kernel arguments, then these two, where the optimiser left to
   // itself waits for the flag's pointer, the flag, the other arguments and row_units[R] one after the other
-  // (st is never null here)
+  // (st is never null here).  Both loads stand in front of the check's branch: behind it, on a path the controller
+  // step's stores to *st might reach as far as the optimiser can tell, the flag would no longer be a scalar load.
   const int2 ru = row_units[R];
   int stopped = st->stopped;
   asm("" : "+s"(stopped) : "s"(ru.x), "s"(ru.y), "s"(rec), "s"(rowpart), "s"(colpart), "s"(n), "s"(npad), "s"(rr_stages), "s"(rr_stage),
       "s"(rec_next), "s"(pos_out), "s"(gplus), "s"(k_next), "s"(c_rep));
   if (stopped) return;
+  if (check_wg) {                                  // (wave-uniform: blockIdx.x and a kernel argument)
+    if (chk.part_sum != nullptr)
+      controller_step<32 * kSymApplyParts, real>(st, chk.mailbox, chk.part_sum, chk.part_cnt, chk.n_parts,
+                                                 (const real*)chk.pos, (real*)chk.best, chk.n_values, chk.iter1,
+                                                 chk.k_after, chk.trace, chk.trace_cap, nullptr);
+    return;
+  }
   using T = SymReal<DIM, real>;
   constexpr int W = T::W;
   constexpr int kWavesA = kSymApplyParts / 2;

@@ -151,7 +151,11 @@ double now_s() {
 // stage, that stage's kernel reduces the MAE of the positions it reads (exactly this check's positions)
 // on its way (slab_stage_pipe_kernel<..., ERR = true>) and the separate 2 N^2-byte pass is dropped.
 // beside: the session's own loop runs it on the check stream (launch_check).
-struct PendingCheck { bool active = false; int iter1 = 0; double k_after = 0.0; int buf = -1; bool beside = false; };
+// in_apply: the check rides on a one-stage symmetric sweep and its controller step runs in that iteration's apply launch
+// (relax_symm.h: SymApplyCheck): no check stream, no stream marker, no held buffer.
+struct PendingCheck {
+  bool active = false; int iter1 = 0; double k_after = 0.0; int buf = -1; bool beside = false; bool in_apply = false;
+};
 
 struct topolow_session {
   int n = 0, dim = 0, udim = 0, row_begin = 0, row_end = 0, ld = 0;   // dim: coordinates the kernels carry, udim: the caller's ndim
@@ -169,6 +173,9 @@ struct topolow_session {
   PendingCheck pcheck;
   bool fuse_checks = true;      // TOPOLOW_FUSE_CHECKS=0: always the separate pass
   bool serial_checks = false;   // TOPOLOW_SERIAL_CHECKS=1: keep every check on the main stream
+  bool check_in_apply = true;   // TOPOLOW_CHECK_IN_APPLY=0: a check fused into a symmetric sweep keeps the separate controller
+  int checks_launched = 0;      // checks of the current run enqueued so far (the mailbox's n_checks counts those that ran)
+  long long checks_in_apply = 0;   // ... those of them whose controller step went out in an apply's launch
 
   // Session labels.  With a relabelling (topolow_session_set_relabel) the session stores point
   // perm[q] of the caller as its point q, so that a slab -- a run of consecutive session labels -- is
@@ -1025,17 +1032,34 @@ bool sym_fused_ok(const topolow_session* s) {
 }
 
 // The apply of the whole triangle (rr_stages = 0) or of stage rr_stage of an rr_stages-stage iteration: positions into
-// `pout`, the records of k_next into `rec_next`.
+// `pout`, the records of k_next into `rec_next`.  chk (nullable): the check whose MAE partials the sweep in front of
+// this apply wrote (n_parts of them, of the positions `pin`): one more workgroup runs its controller step.
 template <int DIM>
 void sym_apply(topolow_session* s, const SymPlanDev& plan, const void* rec, void* rec_next, void* pout, double k_next,
-               int iter, int rr_stages, int rr_stage) {
+               int iter, int rr_stages, int rr_stage, const PendingCheck* chk = nullptr, const void* pin = nullptr,
+               int n_parts = 0) {
   auto& y = s->sym;
+  SymApplyCheck ac;
+  if (chk != nullptr) {
+    ac.part_sum = s->part_sum.p;
+    ac.part_cnt = s->part_cnt.p;
+    ac.n_parts = n_parts;
+    ac.pos = pin;
+    ac.best = s->best.p;
+    ac.n_values = (long long)s->n * s->dim;
+    ac.iter1 = chk->iter1;
+    ac.k_after = chk->k_after;
+    ac.trace = s->trace_dev;
+    ac.trace_cap = s->trace_cap;
+    ac.mailbox = s->mailbox_dev;
+  }
   sym_real<DIM>(s, [&](auto r) {
     using real = decltype(r);
-    hipLaunchKernelGGL((symm_apply_kernel<DIM, real>), dim3(y.npad / kSymCols), dim3(32 * kSymApplyParts), 0, s->stream,
+    hipLaunchKernelGGL((symm_apply_kernel<DIM, real>), dim3(y.npad / kSymCols + (chk != nullptr ? 1 : 0)),
+                       dim3(32 * kSymApplyParts), 0, s->stream,
                        (const real*)rec, (real*)rec_next, (real*)pout, s->gplus.p, (const real*)y.rowpart.p,
                        (const real*)y.colpart.p, plan.row_units.p, s->n, y.npad, k_next, s->c_rep, iter + 1, s->state.p,
-                       rr_stages, rr_stage);
+                       rr_stages, rr_stage, ac);
   });
 }
 
@@ -1079,10 +1103,11 @@ bool sym_rr_available(topolow_session* s, int S) {
 // One symmetric sweep + apply from `pin` into `pout`: a whole one-stage iteration (S = 0), or stage st of an S-stage
 // iteration (the tiles of rr[log2 S][st]).  The records of this iteration are built from `pin` unless the previous apply
 // left them; the apply leaves the next sweep's: this iteration's, or after the iteration's last sweep (`last`) the next
-// one's.  err: the sweep also reduces the pending check's MAE (positions read = that check's positions).
+// one's.  err: the sweep also reduces the pending check's MAE (positions read = that check's positions).  in_apply
+// (nullable, with err on a whole sweep only): that check, whose controller step then runs in the apply's launch.
 template <int DIM>
 void sym_iteration(topolow_session* s, const void* pin, void* pout, int iter, double k, bool err, int S = 0, int st = 0,
-                   bool last = true) {
+                   bool last = true, const PendingCheck* in_apply = nullptr) {
   auto& y = s->sym;
   const SymPlanDev& plan = S == 0 ? y.plan : y.rr[sym_rr_log2(S)][st];
   ProfScope prof(s, S > 0 ? &s->prof_stage : err ? &s->prof_sym_err : &s->prof_sym);
@@ -1094,7 +1119,10 @@ void sym_iteration(topolow_session* s, const void* pin, void* pout, int iter, do
     y.rec_cur = 0;
   }
   sym_sweep<DIM>(s, plan, y.rec[y.rec_cur].p, s->any_threshold, err, S == 0 ? s->block_cells : 0ull, 0, true);
-  sym_apply<DIM>(s, plan, y.rec[y.rec_cur].p, y.rec[y.rec_cur ^ 1].p, pout, last ? k * (1.0 - s->cooling) : k, iter, S, st);
+  if (in_apply != nullptr && !(err && S == 0))
+    throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, "symmetric sweep: a check in the apply needs the ERR sweep of a one-stage iteration"};
+  sym_apply<DIM>(s, plan, y.rec[y.rec_cur].p, y.rec[y.rec_cur ^ 1].p, pout, last ? k * (1.0 - s->cooling) : k, iter, S, st,
+                 in_apply, pin, plan.n_units);
   HIP_TRY(hipGetLastError());
   y.rec_cur ^= 1;
   y.rec_iter = last ? iter + 1 : iter;
@@ -1138,15 +1166,18 @@ IterPlan plan_iteration(topolow_session* s, int iter, double k) {
 
 // Enqueues stage t of iteration `iter` in the form p names, from pin into pout: the whole sweep, stage t's sweep, or the
 // row-owner slab t (push: the other blocks' copies of pout, n_push of them).  err: the launch also reduces the pending
-// check's MAE of pin.  Returns the error partials it wrote (0 without err).
+// check's MAE of pin; in_apply (nullable, SymForm::kSweep with err only): that check, run in the sweep's apply launch.
+// Returns the error partials it wrote (0 without err).
 int enqueue_stage(topolow_session* s, const IterPlan& p, int t, const void* pin, void* pout, int iter, double k,
-                  const void* push, int n_push, bool err) {
+                  const void* push, int n_push, bool err, const PendingCheck* in_apply = nullptr) {
+  if (in_apply != nullptr && p.form != SymForm::kSweep)
+    throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, "a check in the apply needs a one-stage symmetric sweep"};
   if (p.form == SymForm::kRowOwner) {
     TL_DISPATCH_DIM(s->dim, launch_stage, s, pin, pout, s->state.p, slab_ranges(p.geo, s->seed, iter, t), iter + 1, k,
                     push, n_push, err);
     if (err) s->fused_parts = (s->rows() + CfgProd::ROWS - 1) / CfgProd::ROWS;
   } else if (p.form == SymForm::kSweep) {   // one sweep over the upper triangle moves both ends of every pair
-    TL_DISPATCH_SYM(s->dim, sym_iteration, s, pin, pout, iter, k, err);
+    TL_DISPATCH_SYM(s->dim, sym_iteration, s, pin, pout, iter, k, err, 0, 0, true, in_apply);
   } else {   // S symmetric sweeps over the tiles of one stage each, in random order
     const int S = p.geo.n_stages;
     TL_DISPATCH_SYM(s->dim, sym_iteration, s, pin, pout, iter, k, err, S, p.order[t], t == S - 1);
@@ -1341,8 +1372,31 @@ void launch_check(topolow_session* s, PendingCheck& pc, bool error_pass) {
   hipEvent_t e = take_event(s);
   HIP_TRY(hipEventRecord(e, check_on));
   s->pending.push_back(e);
+  s->checks_launched += 1;
   poll_checks(s, 3);
   pc.active = false;
+}
+
+// The host side of a check whose controller step went out in an apply's launch (sym_apply): nothing is put on a stream
+// for it.  The host still has to see a stop and to stay at most three checks ahead, and reads both from the pinned
+// mailbox, which every controller step mirrors the run state to (n_checks counts the steps that ran, whichever kernel
+// ran them; after a stop they no longer count, and `stopped` ends the wait).  No event is recorded behind the apply: a
+// marker between an apply and the next sweep is part of what this path removes.  The wait is
+// bounded: a check completes every few hundred microseconds, and once per millisecond of waiting the stream is queried --
+// idle (the mailbox is final) or failed (the next HIP call reports it) ends the wait.
+void check_went_in_apply(topolow_session* s, PendingCheck& pc) {
+  s->checks_launched += 1;
+  s->checks_in_apply += 1;
+  pc.active = false;
+  const volatile RunState* mb = s->mailbox;
+  double asked = now_s();
+  while (!mb->stopped && s->checks_launched - mb->n_checks > 3) {
+    if (now_s() - asked < 1e-3) continue;
+    if (hipStreamQuery(s->stream) != hipErrorNotReady) break;
+    (void)hipGetLastError();   // "not ready" is no error of a launch
+    asked = now_s();
+  }
+  if (mb->stopped) s->host_seen_stop = true;
 }
 
 // A check that was waiting for the next iteration's kernel and will not get one (the caller stopped
@@ -1698,6 +1752,8 @@ int topolow_session_create(topolow_session** out, int32_t n, int32_t ndim, int32
     s->serial_checks = serial != nullptr && serial[0] == '1';
     const char* fuse = getenv("TOPOLOW_FUSE_CHECKS");
     s->fuse_checks = !(fuse != nullptr && fuse[0] == '0');
+    const char* in_apply = getenv("TOPOLOW_CHECK_IN_APPLY");
+    s->check_in_apply = !(in_apply != nullptr && in_apply[0] == '0');
     const char* symm = getenv("TOPOLOW_SYMMETRIC");
     s->sym.allowed = !(symm != nullptr && symm[0] == '0');   // TOPOLOW_SYMMETRIC=0: row-owner sweeps only
     s->sym.forced = symm != nullptr && symm[0] == '1';       // TOPOLOW_SYMMETRIC=1: also at an ndim that is off by default
@@ -1987,6 +2043,8 @@ int topolow_session_begin(topolow_session* s, int32_t n_iter, double k0, double 
     s->host_seen_stop = false;
     s->held = -1;
     s->pcheck.active = false;
+    s->checks_launched = 0;
+    s->checks_in_apply = 0;
     s->sym.rec_iter = -1;
     s->began = true;
     s->in_run = true;
@@ -2022,13 +2080,17 @@ int topolow_session_enqueue(topolow_session* s, int32_t max_iters, int32_t* enqu
         const IterPlan plan = plan_iteration(s, iter, s->k_host);
         const bool fuse_now = s->pcheck.active && check_fusable(s, plan.geo.n_stages);
         if (s->pcheck.active && !fuse_now) flush_pending_check(s);
+        // the check rides on this iteration's one sweep and its controller step goes out in the sweep's apply launch
+        const bool in_apply = fuse_now && s->pcheck.in_apply && plan.form == SymForm::kSweep;
         for (int t = 0; t < plan.geo.n_stages; ++t) {
           int out = 0;   // a buffer that is neither the input nor the one a running check reads
           while (out == s->cur || out == s->held) ++out;
-          enqueue_stage(s, plan, t, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host, nullptr, 0, fuse_now);
+          enqueue_stage(s, plan, t, s->pos[s->cur].p, s->pos[out].p, iter, s->k_host, nullptr, 0, fuse_now,
+                        in_apply ? &s->pcheck : nullptr);
           s->cur = out;
         }
-        if (fuse_now) launch_check(s, s->pcheck, /*error_pass=*/false);
+        if (in_apply) check_went_in_apply(s, s->pcheck);
+        else if (fuse_now) launch_check(s, s->pcheck, /*error_pass=*/false);
       }
       s->iters_enqueued = iter + 1;
       s->k_host *= (1.0 - s->cooling);  // reference :289
@@ -2037,12 +2099,16 @@ int topolow_session_enqueue(topolow_session* s, int32_t max_iters, int32_t* enqu
         PendingCheck pc{true, iter + 1, s->k_host, s->cur};
         pc.beside = s->schedule == TOPOLOW_SCHEDULE_SLAB && s->stream == s->own_stream &&
                     !s->profiling && !s->serial_checks;
+        // The run's last check has no next iteration to run beside.  With the fused checks in the applies the check
+        // stream has by then been idle for the whole one-stage phase, and its queue would have to be woken for this one
+        // check while everything waits for it: the check goes to the main stream.  (TOPOLOW_CHECK_IN_APPLY=0 keeps it
+        // where it was.)
+        if (s->check_in_apply && iter + 1 == s->n_iter) pc.beside = false;
         // The check reads this iteration's positions while the next iteration's stages run.  Its
         // verdict (stop / snapshot) is the same as in the serial order: the buffer it reads is
         // not written until the next check has waited for it; stage kernels that start after a
         // stop are no-ops and those already running write buffers nobody returns.
         if (s->held >= 0) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_check_done, 0));
-        s->held = pc.beside ? s->cur : -1;
         // one stage next iteration: its kernel reduces this check's MAE (the positions it reads ARE this
         // check's positions) and the separate pass over the block is dropped
         // (fp32: the row-owner ERR instance or the symmetric sweep's, when the MAE comes from the block; f64: the
@@ -2050,6 +2116,15 @@ int topolow_session_enqueue(topolow_session* s, int32_t max_iters, int32_t* enqu
         const bool fuse = s->fuse_checks && s->schedule == TOPOLOW_SCHEDULE_SLAB && iter + 1 < s->n_iter &&
                           (s->dense_mae || s->precision == TOPOLOW_PRECISION_F64) &&
                           check_fusable(s, iteration_stages(s, iter + 1, s->k_host));
+        // ... and when that kernel is the symmetric sweep, the controller step rides in the sweep's apply launch on the
+        // main stream: the check's positions are that iteration's input, read-only until the apply has finished, so
+        // no buffer is held and nothing goes to the check stream.  (Should the check be flushed instead -- the caller
+        // asks for results first -- it runs as a separate pass on the main stream.)
+        if (pc.beside && fuse && s->check_in_apply && sym_form(s, 1) == SymForm::kSweep) {
+          pc.in_apply = true;
+          pc.beside = false;
+        }
+        s->held = pc.beside ? s->cur : -1;
         if (fuse) s->pcheck = pc;
         else launch_check(s, pc, /*error_pass=*/true);
       }
@@ -2244,6 +2319,10 @@ int32_t topolow_session_uses_dense_mae(const topolow_session* s) {
 
 int64_t topolow_session_stage_launches(const topolow_session* s) {
   return s ? s->stage_launches : 0;
+}
+
+int64_t topolow_session_checks_in_apply(const topolow_session* s) {
+  return s ? s->checks_in_apply : 0;
 }
 
 int64_t topolow_session_bytes_per_iteration(const topolow_session* s) {
