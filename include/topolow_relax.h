@@ -605,6 +605,69 @@ int topolow_layout_prep_subsample(topolow_layout_prep* parent, const int32_t* su
 int topolow_layout_prep_graph_stats(const topolow_layout_prep* p, int32_t* rounds, double* seconds);
 
 /* ---------------------------------------------------------------------------------------
+ * Degrees and pruning of a resident matrix (reference R/diagnostics.R:434-475 analyze_network_structure,
+ * R/data_preprocessing.R:1225-1503 prune_sparse_matrix).  Both entries count along MATRIX ROWS for either layout flag
+ * -- cell (r, c) counts for point r -- and the matrix need not be symmetric.  A cell is measured when it is not NaN:
+ * threshold-coded cells and +-Inf count, the diagonal never does.  Both serve a handle that declined its ordering, and
+ * neither alters the handle.  One pass over the matrix leaves a packed bit adjacency (n^2 / 8 bytes; twice that while
+ * the bits of a column-line layout are turned round, 64 x 64 bits at a time); everything after it reads the bits.
+ * Transient device memory: those bits and O(n), freed before return; a failed allocation: TOPOLOW_ERR_UNSUPPORTED with
+ * a message.
+ * ------------------------------------------------------------------------------------- */
+
+/* degrees[q] = the measured cells (subset[q], subset[c]), c != q, along the matrix row; *n_cells their sum (the n_cells
+ * of topolow_layout_prep_connectivity).  subset as for that entry (NULL: all n points, m ignored).
+ * TOPOLOW_ERR_BAD_ARGUMENT with a message, before any device call: a NULL handle, degrees or n_cells; the subset errors
+ * of the connectivity entry. */
+int topolow_layout_prep_degrees(topolow_layout_prep* p, const int32_t* subset, int32_t m, int32_t* degrees /* m */,
+                                int64_t* n_cells, char* errbuf, size_t errlen);
+
+#define TOPOLOW_PRUNE_CONVERGED 1       /* a round found every kept point at or above the threshold */
+#define TOPOLOW_PRUNE_MIN_POINTS 2      /* removing the round's candidates would leave fewer than min_points: they stay */
+#define TOPOLOW_PRUNE_MAX_ITERATIONS 3  /* max_iterations rounds, the last of which still removed points */
+#define TOPOLOW_PRUNE_ALL_REMOVED 4     /* a round removed the last points ("All points removed during pruning") */
+#define TOPOLOW_PRUNE_MAX_ATTEMPTS 10
+
+typedef struct topolow_prune_info {
+  int32_t original_size, final_size;
+  int32_t iterations;            /* rounds of the last attempt, counted before the test: a run that converges reports the
+                                  * round that found nothing to remove */
+  int32_t min_connections_used;  /* the threshold of the last attempt */
+  int32_t attempts;              /* 1 without a target */
+  int32_t stop_reason;           /* TOPOLOW_PRUNE_* of the last attempt */
+  int32_t target_reached;        /* 0 / 1; -1 when no target was given */
+  int32_t last_remove;           /* the points the last decided round of the last attempt found below the threshold */
+  int64_t original_cells, final_cells;   /* measured off-diagonal cells over both triangles, of the matrix / of kept x kept */
+  double  seconds[3];            /* wall clock: the bit pass, the rounds, the rest */
+  /* per attempt a (0-based), for the callers that repeat the reference's warnings: */
+  int32_t attempt_iterations[TOPOLOW_PRUNE_MAX_ATTEMPTS], attempt_stop_reason[TOPOLOW_PRUNE_MAX_ATTEMPTS];
+  int32_t attempt_last_remove[TOPOLOW_PRUNE_MAX_ATTEMPTS], attempt_final_size[TOPOLOW_PRUNE_MAX_ATTEMPTS];
+  int64_t attempt_final_cells[TOPOLOW_PRUNE_MAX_ATTEMPTS];
+  int64_t reserved[4];
+} topolow_prune_info;
+
+/* prune_sparse_matrix on the resident matrix: rounds that remove every kept point with fewer than min_connections
+ * measured cells among the kept points of its row, until a round removes nothing (the reference's loop,
+ * R/data_preprocessing.R:1371-1415, with the count its documentation describes: the measured off-diagonal cells).
+ *   target_completeness NaN   one attempt at min_connections.
+ *   target_completeness t     the reference's search as its code has it (:1288-1355): thresholds 4, 6, 8, ... for at
+ *                             most TOPOLOW_PRUNE_MAX_ATTEMPTS attempts, each from the whole matrix, all inside this call
+ *                             on one bit pass; min_connections is not used.  An attempt ends the search when
+ *                             final_cells / (s (s - 1)) >= t in double, s its final_size (target_reached = 1), when
+ *                             s <= min_points, or when it removed every point; running out of attempts is TOPOLOW_OK
+ *                             with target_reached = 0 and attempts = TOPOLOW_PRUNE_MAX_ATTEMPTS.
+ *   kept                      n flags of the last attempt: 1 where the point stays.
+ * A round is two launches (count, decide); the host launches them in batches behind a device stop flag and reads one
+ * small record per batch; at most min(max_iterations, n) + 1 count launches per attempt.
+ * TOPOLOW_ERR_BAD_ARGUMENT with a message, before any device call: a NULL handle, kept or info; min_connections < 1;
+ * a target that is not NaN and lies outside (0, 1]; n < min_points.  max_iterations <= 0 runs no round, as the
+ * reference's loop does. */
+int topolow_layout_prep_prune(topolow_layout_prep* p, int32_t min_connections,
+                              double target_completeness /* NaN: fixed threshold */, int32_t max_iterations,
+                              int32_t min_points, uint8_t* kept /* n flags */, topolow_prune_info* info, char* errbuf,
+                              size_t errlen);
+
+/* ---------------------------------------------------------------------------------------
  * Spectrum of a resident matrix: step 1 of the reference's Euclidify(), "Assessing data characteristics"
  * (R/core.R:983-1007) -- as.numeric, median fill, square, double-centre, all eigenvalues, deviation_score and
  * dims_90_percent -- and the symmetric eigenvalue path under it.  All f64, one GPU, no solver library.

@@ -7,6 +7,7 @@ NO fallback: if the library is missing or no HIP device is usable, calls raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, Optional
@@ -82,6 +83,9 @@ class TopolowCellList(C.Structure):
                 ("row_ptr", C.POINTER(C.c_int64))]
 
 
+PRUNE_MAX_ATTEMPTS = 10   # TOPOLOW_PRUNE_MAX_ATTEMPTS
+
+
 class TopolowLayoutPrepInfo(C.Structure):
     _fields_ = [("n_edges", C.c_int64), ("n_finite_nonzero", C.c_int64), ("n_infinite", C.c_int64),
                 ("n_negative", C.c_int64), ("numeric_max", C.c_double), ("reordered", C.c_int32),
@@ -93,6 +97,16 @@ class TopolowSpectrumInfo(C.Structure):
                 ("n_positive", C.c_int64), ("n_negative", C.c_int64), ("sum_positive", C.c_double),
                 ("sum_negative", C.c_double), ("deviation_score", C.c_double), ("dims_90", C.c_int32),
                 ("reserved32", C.c_int32), ("seconds", C.c_double * 4), ("reserved", C.c_int64 * 4)]
+
+
+class TopolowPruneInfo(C.Structure):
+    _fields_ = [("original_size", C.c_int32), ("final_size", C.c_int32), ("iterations", C.c_int32),
+                ("min_connections_used", C.c_int32), ("attempts", C.c_int32), ("stop_reason", C.c_int32),
+                ("target_reached", C.c_int32), ("last_remove", C.c_int32), ("original_cells", C.c_int64),
+                ("final_cells", C.c_int64), ("seconds", C.c_double * 3),
+                ("attempt_iterations", C.c_int32 * PRUNE_MAX_ATTEMPTS), ("attempt_stop_reason", C.c_int32 * PRUNE_MAX_ATTEMPTS),
+                ("attempt_last_remove", C.c_int32 * PRUNE_MAX_ATTEMPTS), ("attempt_final_size", C.c_int32 * PRUNE_MAX_ATTEMPTS),
+                ("attempt_final_cells", C.c_int64 * PRUNE_MAX_ATTEMPTS), ("reserved", C.c_int64 * 4)]
 
 
 class TopolowResult(C.Structure):
@@ -378,6 +392,11 @@ def load() -> C.CDLL:
                                                   C.POINTER(TopolowLayoutPrepInfo), C.c_char_p, C.c_size_t]
     lib.topolow_layout_prep_graph_stats.restype = C.c_int
     lib.topolow_layout_prep_graph_stats.argtypes = [vp, ip, dp]
+    lib.topolow_layout_prep_degrees.restype = C.c_int
+    lib.topolow_layout_prep_degrees.argtypes = [vp, ip, C.c_int32, ip, i64p, C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_prune.restype = C.c_int
+    lib.topolow_layout_prep_prune.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
+                                              C.POINTER(TopolowPruneInfo), C.c_char_p, C.c_size_t]
     lib.topolow_tridiagonal_eigenvalues.restype = C.c_int
     lib.topolow_tridiagonal_eigenvalues.argtypes = [dp, dp, C.c_int32, C.c_int32, dp, C.c_char_p, C.c_size_t]
     lib.topolow_symmetric_eigenvalues.restype = C.c_int
@@ -1145,6 +1164,41 @@ class PreparedHandle:
         _check(rc, child._err)
         child.info = {k: getattr(info, k) for k, _ in TopolowLayoutPrepInfo._fields_ if k != "reserved"}
         return child
+
+    def degrees(self, subset=None):
+        """topolow_layout_prep_degrees: (degrees, n_cells) of the resident matrix or of the points `subset` of it (as
+        .connectivity takes them): degrees[q] the measured cells (subset[q], subset[c]), c != q, along the matrix ROW
+        (int32), n_cells their sum."""
+        sub, m = self._subset(subset)
+        deg = np.empty(m, dtype=np.int32)
+        cells = C.c_int64(0)
+        rc = self.lib.topolow_layout_prep_degrees(self._h, _ip(sub) if sub is not None else None, m, _ip(deg),
+                                                  C.byref(cells), self._err, len(self._err))
+        _check(rc, self._err)
+        return deg, int(cells.value)
+
+    def prune(self, min_connections=4, target_completeness=None, max_iterations=100, min_points=10):
+        """topolow_layout_prep_prune: the rounds of prune.prune_sparse_matrix on the resident matrix, the whole
+        `target_completeness` search included.  Returns (kept, info): kept a bool array over the n points, info the
+        fields of topolow_prune_info as a dict (the per-attempt arrays as lists of `attempts` entries, `seconds`: bit
+        pass, rounds, the rest).  Non-integer thresholds are rounded up, which decides every `count <` test alike."""
+        def as_i32(x):
+            return int(min(max(math.ceil(x), -(2 ** 31 - 1)), 2 ** 31 - 1))
+
+        kept = np.zeros(self.n, dtype=np.uint8)
+        info = TopolowPruneInfo()
+        rc = self.lib.topolow_layout_prep_prune(
+            self._h, as_i32(min_connections), float("nan") if target_completeness is None else float(target_completeness),
+            as_i32(max_iterations), as_i32(min_points), kept.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info),
+            self._err, len(self._err))
+        _check(rc, self._err)
+        out = {}
+        for k, _ in TopolowPruneInfo._fields_:
+            v = getattr(info, k)
+            if k == "reserved":
+                continue
+            out[k] = list(v)[:info.attempts] if k.startswith("attempt_") else (list(v) if k == "seconds" else v)
+        return kept.astype(bool), out
 
     def spectrum(self, want_eigenvalues: bool = True, want_centered: bool = False):
         """topolow_layout_prep_spectrum: the data assessment of the reference's Euclidify() (R/core.R:983-1007) of the

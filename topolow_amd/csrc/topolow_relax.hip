@@ -43,6 +43,7 @@
 #include "relax_prep.h"
 #include "relax_prep_fold.h"
 #include "relax_prep_graph.h"
+#include "relax_prep_prune.h"
 #include "relax_spectrum.h"
 
 using namespace topolow;
@@ -3931,6 +3932,199 @@ int topolow_layout_prep_graph_stats(const topolow_layout_prep* p, int32_t* round
   seconds[0] = p->graph_seconds[0];
   seconds[1] = p->graph_seconds[1];
   return TOPOLOW_OK;
+}
+
+// ---- degrees and pruning of a resident matrix (relax_prep_prune.h) ----
+namespace {
+
+static_assert(kPruneConverged == TOPOLOW_PRUNE_CONVERGED && kPruneMinPoints == TOPOLOW_PRUNE_MIN_POINTS &&
+                  kPruneMaxIterations == TOPOLOW_PRUNE_MAX_ITERATIONS && kPruneAllRemoved == TOPOLOW_PRUNE_ALL_REMOVED,
+              "the kernels' stop reasons are the header's");
+
+constexpr int kPruneBatch = 8;   // rounds launched between two reads of the state
+
+// The row-oriented bits of parent[subset, subset] (M x words; bit (r, c): cell (r, c) is measured) into `bits`, on
+// `stream`; returns the set bits.  Where a buffer line is a matrix column the line bits are turned round and freed.
+unsigned long long prune_row_bits(const topolow_layout_prep* p, const int32_t* subset, int M, int words, hipStream_t stream,
+                                  DevBuf<unsigned long long>& bits) {
+  DevBuf<int32_t> sub, first;
+  DevBuf<unsigned long long> cells, line_bits;
+  const size_t count = (size_t)M * (size_t)words;
+  if (subset != nullptr) prep_alloc(sub, (size_t)M, "the subset");
+  prep_alloc(first, (size_t)M, "the first neighbours");
+  prep_alloc(cells, 1, "the cell count");
+  DevBuf<unsigned long long>& by_line = p->transposed ? bits : line_bits;
+  prep_alloc(by_line, count, "the bit adjacency");
+  if (subset != nullptr) HIP_TRY(hipMemcpyAsync(sub.p, subset, (size_t)M * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetAsync(cells.p, 0, sizeof(unsigned long long), stream));
+  hipLaunchKernelGGL(graph_bits_kernel, dim3(M), dim3(kGraphThreads), 0, stream, p->vals.p, p->n,
+                     subset != nullptr ? sub.p : nullptr, M, words, by_line.p, first.p, cells.p);
+  HIP_TRY(hipGetLastError());
+  if (!p->transposed) {
+    prep_alloc(bits, count, "the transposed bit adjacency");
+    const long long tiles = (long long)words * (long long)words;
+    hipLaunchKernelGGL(prune_bits_transpose_kernel, dim3((unsigned)((tiles + kGraphWaves - 1) / kGraphWaves)),
+                       dim3(kGraphThreads), 0, stream, line_bits.p, M, words, bits.p);
+    HIP_TRY(hipGetLastError());
+  }
+  unsigned long long set_bits = 0;
+  HIP_TRY(hipMemcpyAsync(&set_bits, cells.p, sizeof set_bits, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return set_bits;
+}
+
+// `words` words with the bits 0 .. M - 1 set: every point alive.
+void prune_all_alive(int M, int words, std::vector<unsigned long long>& all) {
+  all.assign((size_t)words, ~0ull);
+  if (M & 63) all[(size_t)words - 1] = (1ull << (M & 63)) - 1ull;
+}
+
+void prune_launch_count(hipStream_t stream, const unsigned long long* bits, int M, int words, const unsigned long long* alive,
+                        int min_connections, uint8_t* flag, int32_t* counts, PruneState* st) {
+  hipLaunchKernelGGL(prune_count_kernel, dim3((M + kGraphWaves - 1) / kGraphWaves), dim3(kGraphThreads), 0, stream, bits, M,
+                     words, alive, min_connections, flag, counts, st);
+  HIP_TRY(hipGetLastError());
+}
+
+}  // namespace
+
+int topolow_layout_prep_degrees(topolow_layout_prep* p, const int32_t* subset, int32_t m, int32_t* degrees,
+                                int64_t* n_cells, char* errbuf, size_t errlen) {
+  if (!p || !degrees || !n_cells) {
+    set_err(errbuf, errlen, "topolow_layout_prep_degrees: the handle, degrees and n_cells must not be NULL");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  const int rcs = prep_check_subset(p->n, subset, m, errbuf, errlen);
+  if (rcs != TOPOLOW_OK) return rcs;
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(p->device));
+    const int M = subset != nullptr ? m : p->n;
+    const int words = (M + 63) / 64;
+    DevBuf<unsigned long long> bits, alive;
+    DevBuf<uint8_t> flag;
+    DevBuf<int32_t> counts;
+    DevBuf<PruneState> st;
+    PostPipe P;
+    P.create(0, 0);
+    prune_row_bits(p, subset, M, words, P.run, bits);
+    prep_alloc(alive, (size_t)words, "the mask of kept points");
+    prep_alloc(flag, (size_t)M, "the round's flags");
+    prep_alloc(counts, (size_t)M, "the degrees");
+    prep_alloc(st, 1, "the pruning state");
+    std::vector<unsigned long long> all;
+    prune_all_alive(M, words, all);
+    PruneState state = PruneState();
+    state.size = M;
+    HIP_TRY(hipMemcpy(alive.p, all.data(), (size_t)words * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(st.p, &state, sizeof state, hipMemcpyHostToDevice));
+    prune_launch_count(P.run, bits.p, M, words, alive.p, 0, flag.p, counts.p, st.p);
+    HIP_TRY(hipMemcpyAsync(degrees, counts.p, (size_t)M * 4, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipMemcpyAsync(&state, st.p, sizeof state, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipStreamSynchronize(P.run));
+    *n_cells = (int64_t)state.cells;
+  });
+}
+
+int topolow_layout_prep_prune(topolow_layout_prep* p, int32_t min_connections, double target_completeness,
+                              int32_t max_iterations, int32_t min_points, uint8_t* kept, topolow_prune_info* info,
+                              char* errbuf, size_t errlen) {
+  if (!p || !kept || !info) {
+    set_err(errbuf, errlen, "topolow_layout_prep_prune: the handle, kept and info must not be NULL");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  const bool search = !std::isnan(target_completeness);
+  if (p->n < min_points) {
+    set_err(errbuf, errlen, "Matrix size (%d) is smaller than min_points (%d)", p->n, (int)min_points);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (min_connections < 1) {
+    set_err(errbuf, errlen, "min_connections must be a positive integer");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (search && !(target_completeness > 0.0 && target_completeness <= 1.0)) {
+    set_err(errbuf, errlen, "target_completeness must be between 0 and 1");
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(p->device));
+    const double t0 = now_s();
+    const int n = p->n, words = (n + 63) / 64;
+    const int rounds_asked = std::max<int32_t>(max_iterations, 0), limit = std::min(rounds_asked, n);
+    DevBuf<unsigned long long> bits, alive;
+    DevBuf<uint8_t> flag;
+    DevBuf<PruneState> st;
+    PostPipe P;
+    P.create(0, 0);
+    const unsigned long long set_bits = prune_row_bits(p, nullptr, n, words, P.run, bits);
+    const double t1 = now_s();
+    prep_alloc(alive, (size_t)words, "the mask of kept points");
+    prep_alloc(flag, (size_t)n, "the round's flags");
+    prep_alloc(st, 1, "the pruning state");
+    std::vector<unsigned long long> all;
+    prune_all_alive(n, words, all);
+    PruneState fresh = PruneState();
+    fresh.size = n;
+    *info = topolow_prune_info();
+    info->original_size = n;
+    info->original_cells = (int64_t)set_bits;
+    info->target_reached = search ? 0 : -1;
+    for (int a = 0; a < (search ? TOPOLOW_PRUNE_MAX_ATTEMPTS : 1); ++a) {
+      const int threshold = search ? 4 + 2 * a : (int)min_connections;
+      // every attempt starts from the whole matrix; `all` and `fresh` stay as they are while the copies are under way
+      HIP_TRY(hipMemcpyAsync(alive.p, all.data(), (size_t)words * 8, hipMemcpyHostToDevice, P.run));
+      HIP_TRY(hipMemcpyAsync(st.p, &fresh, sizeof fresh, hipMemcpyHostToDevice, P.run));
+      PruneState state = fresh;
+      int launched = 0;
+      while (launched < limit && state.stopped == 0) {
+        const int batch = std::min(kPruneBatch, limit - launched);
+        for (int b = 0; b < batch; ++b) {
+          prune_launch_count(P.run, bits.p, n, words, alive.p, threshold, flag.p, nullptr, st.p);
+          hipLaunchKernelGGL(prune_decide_kernel, dim3(1), dim3(kGraphThreads), 0, P.run, n, words, (int)min_points, flag.p,
+                             alive.p, st.p);
+          HIP_TRY(hipGetLastError());
+        }
+        launched += batch;
+        HIP_TRY(hipMemcpyAsync(&state, st.p, sizeof state, hipMemcpyDeviceToHost, P.run));
+        HIP_TRY(hipStreamSynchronize(P.run));
+      }
+      int reason = state.stopped;
+      unsigned long long final_cells = state.final_cells;
+      if (reason == 0) {
+        // no round stopped: max_iterations rounds each removed points.  (Fewer than that cannot be: a round that does
+        // not stop removes a point, so n of them leave none.)  One more count gives the cells of what is left.
+        if (launched < rounds_asked)
+          throw HipError{TOPOLOW_ERR_HIP, "prune: the rounds did not stop within n rounds"};
+        prune_launch_count(P.run, bits.p, n, words, alive.p, threshold, flag.p, nullptr, st.p);
+        HIP_TRY(hipMemcpyAsync(&state, st.p, sizeof state, hipMemcpyDeviceToHost, P.run));
+        HIP_TRY(hipStreamSynchronize(P.run));
+        reason = kPruneMaxIterations;
+        final_cells = state.cells;
+      }
+      info->attempts = a + 1;
+      info->min_connections_used = threshold;
+      info->iterations = info->attempt_iterations[a] = state.iteration;
+      info->stop_reason = info->attempt_stop_reason[a] = reason;
+      info->last_remove = info->attempt_last_remove[a] = state.last_remove;
+      info->final_size = info->attempt_final_size[a] = state.size;
+      info->final_cells = info->attempt_final_cells[a] = (int64_t)final_cells;
+      if (!search || reason == kPruneAllRemoved) break;
+      const double s = (double)state.size;
+      const double completeness = state.size >= 2 ? (double)final_cells / (s * (s - 1.0)) : NAN;
+      if (completeness >= target_completeness) {
+        info->target_reached = 1;
+        break;
+      }
+      if (state.size <= min_points) break;
+    }
+    const double t2 = now_s();
+    std::vector<unsigned long long> mask((size_t)words);
+    HIP_TRY(hipMemcpyAsync(mask.data(), alive.p, (size_t)words * 8, hipMemcpyDeviceToHost, P.run));
+    HIP_TRY(hipStreamSynchronize(P.run));
+    for (int q = 0; q < n; ++q) kept[q] = (uint8_t)((mask[(size_t)q >> 6] >> (q & 63)) & 1ull);
+    info->seconds[0] = t1 - t0;
+    info->seconds[1] = t2 - t1;
+    info->seconds[2] = now_s() - t2;
+  });
 }
 
 // ---- spectrum of a resident matrix (relax_spectrum.h; reference R/core.R:983-1007) ----
