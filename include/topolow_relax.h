@@ -735,6 +735,83 @@ int topolow_layout_prep_spectrum(topolow_layout_prep* p, double* eigenvalues_out
                                  size_t errlen);
 
 /* ---------------------------------------------------------------------------------------
+ * Fit report of a resident embedding (reference R/error_metrics.R:55-202 error_calculator_comparison and
+ * calculate_prediction_interval, R/visualization.R:2626-2648): the signed errors e = v - r of the handle's matrix
+ * against a set of positions -- v the cell's value, r the distance of the two points with the bits of
+ * topolow_est_distances -- their moments per series and their exact order statistics, from what the handle keeps on
+ * the device.  Nothing of size n x n is allocated, downloaded or touched on the host; no buffer of errors exists.
+ *   positions   n x ndim f64 column-major (host), row q for the q-th point of the ordered matrix, exactly as
+ *               topolow_layout_prep_post_metrics; they must be finite
+ *   picks       the held-out cells as linear column-major indices r + c n in the CALLER's numbering, as
+ *               topolow_layout_prep_fold; their mirrors are held out too; NULL when n_picks is 0.  They are marked in
+ *               the handle's fold mask, which is empty again on every return, errors included.  A pick outside
+ *               0 .. n^2 - 1: TOPOLOW_ERR_BAD_ARGUMENT with the fold entries' message.
+ * A cell belongs to zero or more of three series:
+ *   TOPOLOW_FIT_IN    its value is finite, its code is 0 and it is not held out
+ *   TOPOLOW_FIT_OUT   its value is finite, its code is 0 and it is held out
+ *   TOPOLOW_FIT_ALL   its value is finite, whatever its code and whether held out or not (extract_numeric_values)
+ * The diagonal counts, as in post-metrics.  DEVIATION from the reference: +-Inf cells are left out of every series, as
+ * post-metrics leaves them out; in the reference they would turn every statistic into Inf or NaN.
+ * Unlike the fold entries these need neither preserve_order nor a symmetric matrix: any handle that holds a second pass
+ * serves (a handle that declined its ordering: TOPOLOW_ERR_BAD_ARGUMENT).  The handle is not altered: fetch(),
+ * optimize(), post_metrics() and the fold entries return afterwards what they returned before.  The first call with
+ * picks adds what the first fold adds (the mask, n^2 / 8 bytes, and the fold's O(n^2 / 64) partials).
+ * Both entries: TOPOLOW_ERR_BAD_ARGUMENT with a message before any device call for a NULL handle, positions or output,
+ * ndim < 1, n_picks < 0, picks NULL with n_picks > 0 (and, for the order statistics, an unknown series, n_ranks outside
+ * 1 .. TOPOLOW_FIT_MAX_RANKS, a malformed negative rank).  A failed device allocation: TOPOLOW_ERR_UNSUPPORTED with
+ * the handle as it was.
+ * ------------------------------------------------------------------------------------- */
+#define TOPOLOW_FIT_IN 0
+#define TOPOLOW_FIT_OUT 1
+#define TOPOLOW_FIT_ALL 2
+#define TOPOLOW_FIT_MAX_RANKS 8
+#define TOPOLOW_FIT_RANK_UPPER ((int64_t)1 << 32) /* see topolow_layout_prep_fit_order_stats: ranks */
+
+typedef struct topolow_fit_series {
+  int64_t count;              /* m: the cells of the series */
+  double  sum_e, sum_abs_e;   /* sum of e, of |e| */
+  double  min_e, max_e;       /* the bits of the smallest / largest e; NaN when count is 0 */
+  int64_t pct_count;          /* IN, OUT: the cells of the series with v > 0 (R/error_metrics.R:116); ALL: 0 */
+  double  sum_pct, sum_abs_pct;   /* IN, OUT: sum of p = e / v * 100 over them, of |p|; ALL: 0 */
+  double  sum_v, sum_r;       /* ALL: sum of v, of r; IN, OUT: 0 */
+  double  css_e;              /* sum of (e - mean e)^2, mean e = sum_e / count formed on the host between the passes */
+  double  css_v, css_r, css_vr;   /* ALL: sum of (v - mean v)^2, (r - mean r)^2, (v - mean v)(r - mean r); IN, OUT: 0 */
+} topolow_fit_series;
+
+typedef struct topolow_fit_report {
+  topolow_fit_series series[3];   /* [TOPOLOW_FIT_IN], [TOPOLOW_FIT_OUT], [TOPOLOW_FIT_ALL] */
+  double  seconds[3];         /* wall clock: pass 1 (with the upload and the marking), pass 2, the whole call */
+  int64_t reserved[4];
+} topolow_fit_report;
+
+/* Two passes over the resident matrix.  Every sum is reduced in topolow_post_metrics' fixed order -- each lane over its
+ * indices in ascending order, the 64 lanes by a shuffle tree, the four waves in wave order, one partial per line of the
+ * handle's buffer, the lines added in index order on the host -- with no floating-point atomic anywhere: the same bits
+ * on every call.  The second pass takes the means the host formed from the first pass's totals. */
+int topolow_layout_prep_fit_report(topolow_layout_prep* p, const double* positions, int32_t ndim,
+                                   const int64_t* picks, int64_t n_picks, topolow_fit_report* out, char* errbuf,
+                                   size_t errlen);
+
+/* Exact order statistics of the signed errors of one series: a radix select over the order-preserving 64-bit key of the
+ * double, one 8-bit digit per pass, all ranks at once -- exactly eight passes over the resident matrix whatever the
+ * data, the errors recomputed in every pass; integer atomics only.
+ *   series       TOPOLOW_FIT_IN, _OUT or _ALL
+ *   ranks        n_ranks of them, 1 <= n_ranks <= TOPOLOW_FIT_MAX_RANKS.  A rank >= 0 is a 0-based rank of the ascending
+ *                errors.  A negative rank -1 - q, q in 0 .. 1000000, is the rank floor((m - 1) q / 10^6): the lower
+ *                neighbour of R's type-7 quantile at q / 10^6, for a caller that does not know m yet;
+ *                -1 - (q + TOPOLOW_FIT_RANK_UPPER) is ceil((m - 1) q / 10^6), the upper neighbour.  (A caller that has
+ *                the report knows m and passes plain ranks; topolow_amd.error_metrics does.)
+ *   values_out   n_ranks doubles: values_out[k] has the bits of the ranks[k]-th smallest error (-0.0 sorts before 0.0)
+ *   count_out    m
+ * An empty series: TOPOLOW_OK, m = 0 and NaN values.  A rank >= m: TOPOLOW_ERR_BAD_ARGUMENT, reported after the first
+ * pass (which counts m).  A rank whose key the eighth pass does not find: TOPOLOW_ERR_HIP with a message -- no pass is
+ * ever added. */
+int topolow_layout_prep_fit_order_stats(topolow_layout_prep* p, const double* positions, int32_t ndim,
+                                        const int64_t* picks, int64_t n_picks, int32_t series,
+                                        const int64_t* ranks, int32_t n_ranks, double* values_out, int64_t* count_out,
+                                        char* errbuf, size_t errlen);
+
+/* ---------------------------------------------------------------------------------------
  * Device-resident session: the same relaxation with inputs kept in HBM, for callers that
  * run many iterations / many embeddings on data they already hold on the GPU (bench.py, the
  * row-sharded multi-GPU driver).  Pointers named d_* are DEVICE pointers.

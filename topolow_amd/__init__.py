@@ -18,8 +18,15 @@ from ._native import NativeError, options, set_seed  # noqa: F401
 from .subsample import check_matrix_connectivity, subsample_dissimilarity_matrix  # noqa: F401
 from .prune import analyze_network_structure, prune_sparse_matrix  # noqa: F401
 from .spectrum import adjust_ndim_range, data_characteristics  # noqa: F401
+from .error_metrics import (  # noqa: F401
+    FitStatistics,
+    calculate_prediction_interval,
+    error_calculator_comparison,
+    fit_statistics,
+)
 
 __all__ = ["euclidean_embedding", "create_topolow_map", "print_topolow", "summary_topolow",
            "Topolow", "RMatrix", "options", "set_seed", "NativeError", "prepare_layout_call",
            "check_matrix_connectivity", "subsample_dissimilarity_matrix", "data_characteristics",
-           "adjust_ndim_range", "analyze_network_structure", "prune_sparse_matrix"]
+           "adjust_ndim_range", "analyze_network_structure", "prune_sparse_matrix", "error_calculator_comparison",
+           "calculate_prediction_interval", "fit_statistics", "FitStatistics"]

@@ -99,6 +99,23 @@ class TopolowSpectrumInfo(C.Structure):
                 ("reserved32", C.c_int32), ("seconds", C.c_double * 4), ("reserved", C.c_int64 * 4)]
 
 
+FIT_IN, FIT_OUT, FIT_ALL = 0, 1, 2   # TOPOLOW_FIT_*
+FIT_MAX_RANKS = 8                     # TOPOLOW_FIT_MAX_RANKS
+FIT_RANK_UPPER = 1 << 32              # TOPOLOW_FIT_RANK_UPPER
+_FIT_SERIES = {"in": FIT_IN, "out": FIT_OUT, "all": FIT_ALL, FIT_IN: FIT_IN, FIT_OUT: FIT_OUT, FIT_ALL: FIT_ALL}
+
+
+class TopolowFitSeries(C.Structure):
+    _fields_ = [("count", C.c_int64), ("sum_e", C.c_double), ("sum_abs_e", C.c_double), ("min_e", C.c_double),
+                ("max_e", C.c_double), ("pct_count", C.c_int64), ("sum_pct", C.c_double), ("sum_abs_pct", C.c_double),
+                ("sum_v", C.c_double), ("sum_r", C.c_double), ("css_e", C.c_double), ("css_v", C.c_double),
+                ("css_r", C.c_double), ("css_vr", C.c_double)]
+
+
+class TopolowFitReport(C.Structure):
+    _fields_ = [("series", TopolowFitSeries * 3), ("seconds", C.c_double * 3), ("reserved", C.c_int64 * 4)]
+
+
 class TopolowPruneInfo(C.Structure):
     _fields_ = [("original_size", C.c_int32), ("final_size", C.c_int32), ("iterations", C.c_int32),
                 ("min_connections_used", C.c_int32), ("attempts", C.c_int32), ("stop_reason", C.c_int32),
@@ -403,6 +420,12 @@ def load() -> C.CDLL:
     lib.topolow_symmetric_eigenvalues.argtypes = [dp, C.c_int32, C.c_int32, dp, dp, dp, C.c_char_p, C.c_size_t]
     lib.topolow_layout_prep_spectrum.restype = C.c_int
     lib.topolow_layout_prep_spectrum.argtypes = [vp, dp, dp, C.POINTER(TopolowSpectrumInfo), C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_fit_report.restype = C.c_int
+    lib.topolow_layout_prep_fit_report.argtypes = [vp, dp, C.c_int32, i64p, C.c_int64, C.POINTER(TopolowFitReport),
+                                                   C.c_char_p, C.c_size_t]
+    lib.topolow_layout_prep_fit_order_stats.restype = C.c_int
+    lib.topolow_layout_prep_fit_order_stats.argtypes = [vp, dp, C.c_int32, i64p, C.c_int64, C.c_int32, i64p, C.c_int32, dp,
+                                                        i64p, C.c_char_p, C.c_size_t]
     lib.topolow_layout_order_from_sums.restype = C.c_int32
     lib.topolow_layout_order_from_sums.argtypes = [C.c_int32, dp, i64p, dp, i64p, C.c_int32, ip]
     _lib = lib
@@ -1217,6 +1240,47 @@ class PreparedHandle:
         out = {k: getattr(info, k) for k, _ in TopolowSpectrumInfo._fields_ if not k.startswith("reserved")}
         out["seconds"] = list(info.seconds)
         return out, eig, cen
+
+    def _fit_inputs(self, positions, picks):
+        pos = _f64F(positions)
+        if pos.ndim != 2 or pos.shape[0] != self.n:
+            raise ValueError("positions must have one row per point")
+        pk = np.ascontiguousarray(picks if picks is not None else [], dtype=np.int64).reshape(-1)
+        return pos, pk, (pk.ctypes.data_as(C.POINTER(C.c_int64)) if pk.size else None)
+
+    def fit_report(self, positions, picks=None):
+        """topolow_layout_prep_fit_report: the moments of the signed errors value - distance of the handle's resident
+        matrix against `positions` (n x ndim, row q for the q-th point of the ordered matrix, as post_metrics), per
+        series "in" / "out" / "all".  `picks`: the held-out cells as linear column-major indices r + c * n in the
+        caller's numbering (their mirrors are held out too), or None.  +-Inf cells are in no series (a deviation from
+        the reference, as post_metrics).  Returns {"in": {...}, "out": {...}, "all": {...}, "seconds": [pass 1, pass 2,
+        total]}, each series with the fields of topolow_fit_series."""
+        pos, pk, pkp = self._fit_inputs(positions, picks)
+        rep = TopolowFitReport()
+        rc = self.lib.topolow_layout_prep_fit_report(self._h, _dp(pos), pos.shape[1], pkp, int(pk.size), C.byref(rep),
+                                                     self._err, len(self._err))
+        _check(rc, self._err)
+        out = {name: {k: getattr(rep.series[s], k) for k, _ in TopolowFitSeries._fields_}
+               for name, s in (("in", FIT_IN), ("out", FIT_OUT), ("all", FIT_ALL))}
+        out["seconds"] = list(rep.seconds)
+        return out
+
+    def fit_order_stats(self, positions, series, ranks, picks=None):
+        """topolow_layout_prep_fit_order_stats: (values, m) -- values[k] has the bits of the ranks[k]-th smallest signed
+        error of `series` ("in", "out", "all" or FIT_*), m is the series' count; 1 .. FIT_MAX_RANKS ranks, eight passes
+        over the resident matrix whatever their number.  An empty series gives NaN values and m = 0; a rank >= m raises
+        NativeError(ERR_BAD_ARGUMENT).  Negative ranks: see include/topolow_relax.h."""
+        if series not in _FIT_SERIES:
+            raise ValueError('series must be "in", "out" or "all"')
+        pos, pk, pkp = self._fit_inputs(positions, picks)
+        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        vals = np.full(max(int(rk.size), 1), np.nan)
+        m = C.c_int64(0)
+        rc = self.lib.topolow_layout_prep_fit_order_stats(
+            self._h, _dp(pos), pos.shape[1], pkp, int(pk.size), _FIT_SERIES[series],
+            rk.ctypes.data_as(C.POINTER(C.c_int64)), int(rk.size), _dp(vals), C.byref(m), self._err, len(self._err))
+        _check(rc, self._err)
+        return vals[:rk.size].copy(), int(m.value)
 
     def graph_stats(self):
         """(rounds, [seconds of the bit pass, seconds of the rounds]) of the last .connectivity on this handle."""

@@ -8,6 +8,18 @@ namespace topolow {
 
 constexpr int kPostThreads = 256;
 
+// ||pj - pi||: pdist_kernel's own arithmetic -- a sequential s += dev * dev over the coordinates, then ::sqrt -- so the
+// result is bit-identical to topolow_est_distances.  The one copy every kernel that scores a cell calls (this file,
+// relax_fit.h).
+__device__ inline double post_distance(const double* __restrict__ pj, const double* __restrict__ pi, int dim) {
+  double s = 0.0;
+  for (int d = 0; d < dim; ++d) {
+    const double dev = pj[d] - pi[d];
+    s += dev * dev;
+  }
+  return ::sqrt(s);
+}
+
 // One workgroup per column of a tile of columns [col0, col0 + cols) of the caller's column-major n x n matrices.
 //   vals   cols x n f64: the tile of `values`, column after column (the caller's own layout)
 //   codes  cols x n i32 or nullptr
@@ -33,13 +45,7 @@ __global__ __launch_bounds__(kPostThreads) void post_metrics_kernel(
   double sum = 0.0;
   uint32_t cnt = 0;
   for (int i = threadIdx.x; i < n; i += kPostThreads) {
-    const double* pi = pos + (size_t)i * dim;
-    double s = 0.0;
-    for (int d = 0; d < dim; ++d) {
-      const double dev = pj[d] - pi[d];
-      s += dev * dev;
-    }
-    const double r = ::sqrt(s);
+    const double r = post_distance(pj, pos + (size_t)i * dim, dim);
     if (est != nullptr) est[base + i] = r;
     const double v = vals[base + i];
     const bool counts = __builtin_isfinite(v) && (codes == nullptr || codes[base + i] == 0);
@@ -91,13 +97,7 @@ __global__ __launch_bounds__(kPostThreads) void post_metrics_resident_kernel(
   double sum = 0.0;
   uint32_t cnt = 0;
   for (int i = threadIdx.x; i < n; i += kPostThreads) {
-    const double* pi = pos + (size_t)i * dim;
-    double s = 0.0;
-    for (int d = 0; d < dim; ++d) {
-      const double dev = pj[d] - pi[d];
-      s += dev * dev;
-    }
-    const double r = ::sqrt(s);
+    const double r = post_distance(pj, pos + (size_t)i * dim, dim);
     if (est != nullptr) est[base + i] = r;
     const size_t cell = src + (size_t)(ord != nullptr ? ord[i] : i);
     const double v = vals[cell];

@@ -45,6 +45,7 @@
 #include "relax_prep_graph.h"
 #include "relax_prep_prune.h"
 #include "relax_spectrum.h"
+#include "relax_fit.h"
 
 using namespace topolow;
 
@@ -5358,6 +5359,234 @@ int topolow_layout_prep_fold_seconds(const topolow_layout_prep* p, double* secon
   if (!p || !seconds) return TOPOLOW_ERR_BAD_ARGUMENT;
   for (int q = 0; q < 4; ++q) seconds[q] = p->fold.seconds[q];
   return TOPOLOW_OK;
+}
+
+// ---- the fit report of a resident embedding (relax_fit.h) ---------------------------------------------------------------
+namespace {
+
+static_assert(kFitMaxRanks == TOPOLOW_FIT_MAX_RANKS, "relax_fit.h and the header disagree");
+
+// What the fit kernels read: the handle's buffers, the positions one row per point, the fold mask where picks were given.
+struct FitInputs {
+  const double* pos;
+  const double* vals;
+  const int8_t* codes;
+  const int32_t* ord;
+  const uint32_t* mask;
+  hipStream_t stream;
+};
+
+int fit_check_arguments(const char* entry, const topolow_layout_prep* p, const double* positions, int32_t ndim,
+                        const int64_t* picks, int64_t n_picks, const void* out, char* errbuf, size_t errlen) {
+  if (!p || !positions || !out) {
+    set_err(errbuf, errlen, "%s: the handle, positions and the outputs must not be NULL", entry);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (ndim < 1) {
+    set_err(errbuf, errlen, "%s: ndim >= 1 is required (got %d)", entry, ndim);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (n_picks < 0 || (!picks && n_picks > 0)) {
+    set_err(errbuf, errlen, "%s: n_picks >= 0 is required, and picks must not be NULL when it is > 0", entry);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  return TOPOLOW_OK;
+}
+
+// The positions go up, the picks are marked in the handle's fold mask, body(inputs) runs, and the mask is empty again
+// when this returns, whatever body threw.  No picks: no mask is allocated and none is read.
+int fit_run(topolow_layout_prep* p, const double* positions, int32_t ndim, const int64_t* picks, int64_t n_picks,
+            char* errbuf, size_t errlen, const std::function<void(const FitInputs&)>& body) {
+  return guarded(errbuf, errlen, [&] {
+    HIP_TRY(hipSetDevice(p->device));
+    const int n = p->n;
+    std::vector<double> rowmajor((size_t)n * ndim);
+    for (int i = 0; i < n; ++i)
+      for (int d = 0; d < ndim; ++d) rowmajor[(size_t)i * ndim + d] = positions[i + (size_t)d * n];
+    DevBuf<double> dpos;
+    PostPipe P;   // destroyed before dpos
+    prep_alloc(dpos, rowmajor.size(), "the positions");
+    P.create(0, 0);
+    std::unique_ptr<FoldMaskGuard> guard;   // destroyed before the stream it clears the mask on
+    FitInputs in = {dpos.p, p->vals.p, p->has_codes ? p->codes.p : nullptr, p->order[0] != -1 ? p->ord.p : nullptr, nullptr,
+                    P.run};
+    HIP_TRY(hipMemcpyAsync(dpos.p, rowmajor.data(), rowmajor.size() * 8, hipMemcpyHostToDevice, P.run));
+    if (n_picks > 0) {
+      auto& f = p->fold;
+      prep_fold_alloc(p);
+      guard.reset(new FoldMaskGuard{p, P.run});
+      FoldTotals tot;
+      if (f.picks.p == nullptr || f.picks.n < (size_t)n_picks) prep_alloc(f.picks, (size_t)n_picks, "the picks");
+      HIP_TRY(hipMemsetAsync(f.sums.totals.p, 0, sizeof(FoldTotals), P.run));
+      HIP_TRY(hipMemcpyAsync(f.picks.p, picks, (size_t)n_picks * 8, hipMemcpyHostToDevice, P.run));
+      hipLaunchKernelGGL(fold_mark_kernel, dim3((unsigned)((n_picks + kPrepThreads - 1) / kPrepThreads)), dim3(kPrepThreads),
+                         0, P.run, f.picks.p, (long long)n_picks, n, f.mask.p, f.sums.totals.p);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&tot, f.sums.totals.p, sizeof tot, hipMemcpyDeviceToHost, P.run));
+      HIP_TRY(hipStreamSynchronize(P.run));
+      if (tot.n_bad_picks > 0)
+        throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, std::to_string(tot.n_bad_picks) + " of the fold's picks lie outside the matrix (linear column-major indices 0 .. n * n - 1)"};
+      in.mask = f.mask.p;
+    }
+    HIP_TRY(hipStreamSynchronize(P.run));   // rowmajor is pageable
+    body(in);
+  });
+}
+
+}  // namespace
+
+int topolow_layout_prep_fit_report(topolow_layout_prep* p, const double* positions, int32_t ndim,
+                                   const int64_t* picks, int64_t n_picks, topolow_fit_report* out, char* errbuf,
+                                   size_t errlen) {
+  if (const int rca = fit_check_arguments("topolow_layout_prep_fit_report", p, positions, ndim, picks, n_picks, out, errbuf,
+                                          errlen))
+    return rca;
+  if (const int rcu = prep_check_usable(p, errbuf, errlen)) return rcu;
+  const double t0 = now_s();
+  return fit_run(p, positions, ndim, picks, n_picks, errbuf, errlen, [&](const FitInputs& in) {
+    const int n = p->n;
+    const size_t N = (size_t)n;
+    *out = topolow_fit_report();
+    // -- pass 1: one partial per line, the lines added in index order
+    DevBuf<FitLineSums> dsums;
+    DevBuf<FitLineCentred> dcss;
+    prep_alloc(dsums, N, "the lines' sums");
+    prep_alloc(dcss, N, "the lines' centred sums");
+    std::vector<FitLineSums> ls(N);
+    std::vector<FitLineCentred> lc(N);
+    hipLaunchKernelGGL(fit_sums_kernel, dim3(n), dim3(kFitThreads), 0, in.stream, in.pos, n, ndim, in.vals, in.codes, in.ord,
+                       in.mask, dsums.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ls.data(), dsums.p, N * sizeof(FitLineSums), hipMemcpyDeviceToHost, in.stream));
+    HIP_TRY(hipStreamSynchronize(in.stream));
+    double sum[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < kFitSeries; ++s) {
+      out->series[s].min_e = INFINITY;
+      out->series[s].max_e = -INFINITY;
+    }
+    for (size_t a = 0; a < N; ++a) {
+      for (int k = 0; k < 12; ++k) sum[k] += ls[a].sum[k];
+      for (int s = 0; s < kFitSeries; ++s) {
+        topolow_fit_series& o = out->series[s];
+        o.count += ls[a].count[s];
+        o.min_e = std::fmin(o.min_e, ls[a].min_e[s]);
+        o.max_e = std::fmax(o.max_e, ls[a].max_e[s]);
+        if (s < 2) o.pct_count += ls[a].pct_count[s];
+      }
+    }
+    FitMeans means = {{0.0, 0.0, 0.0}, 0.0, 0.0};
+    for (int s = 0; s < kFitSeries; ++s) {
+      topolow_fit_series& o = out->series[s];
+      o.sum_e = sum[s];
+      o.sum_abs_e = sum[3 + s];
+      if (s < 2) { o.sum_pct = sum[6 + s]; o.sum_abs_pct = sum[8 + s]; }
+      if (o.count == 0) o.min_e = o.max_e = NAN;
+      else means.e[s] = o.sum_e / (double)o.count;
+    }
+    topolow_fit_series& all = out->series[TOPOLOW_FIT_ALL];
+    all.sum_v = sum[10];
+    all.sum_r = sum[11];
+    if (all.count > 0) {
+      means.v = all.sum_v / (double)all.count;
+      means.r = all.sum_r / (double)all.count;
+    }
+    const double t1 = now_s();
+    // -- pass 2: about the means
+    hipLaunchKernelGGL(fit_centred_kernel, dim3(n), dim3(kFitThreads), 0, in.stream, in.pos, n, ndim, in.vals, in.codes,
+                       in.ord, in.mask, means, dcss.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(lc.data(), dcss.p, N * sizeof(FitLineCentred), hipMemcpyDeviceToHost, in.stream));
+    HIP_TRY(hipStreamSynchronize(in.stream));
+    double css[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (size_t a = 0; a < N; ++a)
+      for (int k = 0; k < 6; ++k) css[k] += lc[a].css[k];
+    for (int s = 0; s < kFitSeries; ++s) out->series[s].css_e = css[s];
+    all.css_v = css[3];
+    all.css_r = css[4];
+    all.css_vr = css[5];
+    const double t2 = now_s();
+    out->seconds[0] = t1 - t0;
+    out->seconds[1] = t2 - t1;
+    out->seconds[2] = t2 - t0;
+  });
+}
+
+int topolow_layout_prep_fit_order_stats(topolow_layout_prep* p, const double* positions, int32_t ndim,
+                                        const int64_t* picks, int64_t n_picks, int32_t series,
+                                        const int64_t* ranks, int32_t n_ranks, double* values_out, int64_t* count_out,
+                                        char* errbuf, size_t errlen) {
+  const char* entry = "topolow_layout_prep_fit_order_stats";
+  if (const int rca = fit_check_arguments(entry, p, positions, ndim, picks, n_picks,
+                                          ranks && values_out && count_out ? (const void*)values_out : nullptr, errbuf,
+                                          errlen))
+    return rca;
+  if (series != TOPOLOW_FIT_IN && series != TOPOLOW_FIT_OUT && series != TOPOLOW_FIT_ALL) {
+    set_err(errbuf, errlen, "%s: unknown series %d (TOPOLOW_FIT_IN, _OUT or _ALL)", entry, series);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (n_ranks < 1 || n_ranks > TOPOLOW_FIT_MAX_RANKS) {
+    set_err(errbuf, errlen, "%s: 1 <= n_ranks <= %d is required (got %d)", entry, TOPOLOW_FIT_MAX_RANKS, n_ranks);
+    return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  for (int k = 0; k < n_ranks; ++k) {
+    if (ranks[k] >= 0) continue;
+    const int64_t code = -1 - ranks[k], q = code >= TOPOLOW_FIT_RANK_UPPER ? code - TOPOLOW_FIT_RANK_UPPER : code;
+    if (q > 1000000) {
+      set_err(errbuf, errlen, "%s: rank %d: a negative rank is -1 - q or -1 - (q + TOPOLOW_FIT_RANK_UPPER) with q in "
+              "0 .. 1000000", entry, k);
+      return TOPOLOW_ERR_BAD_ARGUMENT;
+    }
+  }
+  if (const int rcu = prep_check_usable(p, errbuf, errlen)) return rcu;
+  return fit_run(p, positions, ndim, picks, n_picks, errbuf, errlen, [&](const FitInputs& in) {
+    const int n = p->n;
+    DevBuf<FitSelect> sel;
+    prep_alloc(sel, 1, "the select histograms");
+    std::vector<FitSelect> hbuf(1);
+    FitSelect& h = hbuf[0];
+    FitPrefixes prefix = {};
+    unsigned long long rank[kFitMaxRanks] = {}, m = 0;
+    unsigned digit[kFitMaxRanks] = {};
+    for (int shift = 56; shift >= 0; shift -= 8) {   // exactly eight passes
+      HIP_TRY(hipMemsetAsync(sel.p, 0, sizeof(FitSelect), in.stream));
+      hipLaunchKernelGGL(fit_select_kernel, dim3(n), dim3(kFitThreads), 0, in.stream, in.pos, n, ndim, in.vals, in.codes,
+                         in.ord, in.mask, series, shift, n_ranks, prefix, sel.p);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&h, sel.p, sizeof(FitSelect), hipMemcpyDeviceToHost, in.stream));
+      HIP_TRY(hipStreamSynchronize(in.stream));
+      if (shift == 56) {
+        for (int q = 0; q < 256; ++q) m += h.hist[0][q];
+        *count_out = (int64_t)m;
+        if (m == 0) {
+          for (int k = 0; k < n_ranks; ++k) values_out[k] = NAN;
+          return;
+        }
+        for (int k = 0; k < n_ranks; ++k) {
+          if (ranks[k] >= 0) {
+            rank[k] = (unsigned long long)ranks[k];
+          } else {
+            const int64_t code = -1 - ranks[k];
+            const bool upper = code >= TOPOLOW_FIT_RANK_UPPER;
+            const unsigned __int128 h6 = (unsigned __int128)(m - 1) * (unsigned long long)(upper ? code - TOPOLOW_FIT_RANK_UPPER : code);
+            rank[k] = (unsigned long long)(h6 / 1000000u) + (upper && h6 % 1000000u != 0 ? 1ull : 0ull);
+          }
+          if (rank[k] >= m)
+            throw HipError{TOPOLOW_ERR_BAD_ARGUMENT, "rank " + std::to_string(rank[k]) + " (entry " + std::to_string(k) +
+                                                         ") is not below the series' count " + std::to_string(m)};
+        }
+      }
+      for (int k = 0; k < n_ranks; ++k) {
+        digit[k] = spec_pick_digit(h.hist[k], rank[k]);
+        prefix.key[k] |= (unsigned long long)digit[k] << shift;
+      }
+    }
+    for (int k = 0; k < n_ranks; ++k) {
+      if (h.hist[k][digit[k]] < 1 || rank[k] >= h.hist[k][digit[k]])
+        throw HipError{TOPOLOW_ERR_HIP, "the select did not find the key of rank entry " + std::to_string(k) +
+                                            " in its eighth pass: the matrix or the positions changed during the call"};
+      values_out[k] = spec_key_value(prefix.key[k]);
+    }
+  });
 }
 
 }  // extern "C"
