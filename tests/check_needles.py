@@ -199,7 +199,7 @@ def check_needle(n, dim, seed, thresholded, cells=(), row_blocks=None, margin=10
 
 
 def kernel_dim(ndim):
-    """The coordinates a session computes with (zero-padded): csrc/topolow_relax.hip, kernel_dim."""
+    """The coordinates a session computes with (zero-padded): csrc/topolow_session.h, kernel_dim."""
     return ndim if ndim <= 10 else (12 if ndim <= 12 else 16)
 
 

@@ -32,7 +32,7 @@ PATTERN = {np.dtype(np.float32): np.uint32(0xC2F0E1D2), np.dtype(np.float64): np
 
 
 def kernel_dim(ndim):
-    """The coordinates a session computes with, the rest zero-padded (csrc/topolow_relax.hip)."""
+    """The coordinates a session computes with, the rest zero-padded (csrc/topolow_session.h: kernel_dim)."""
     return ndim if ndim <= 10 else next(d for d in (12, 16, 32, 64) if ndim <= d)
 
 

@@ -232,3 +232,17 @@ def test_f64_symmetric_sweep_instances_run_without_scratch():
         assert int(re.search(r"; Occupancy: (\d+)", tail).group(1)) >= (2 if two else 1), name
         body = text[start:end]
         assert body.count("s_cbranch") <= 19, (name, body.count("s_cbranch"))     # loops and guards only (13-18): the tile has no branch
+
+
+def test_every_kernel_is_compiled_into_exactly_one_object():
+    """The library is one object per source (csrc/Makefile) and `make asm` writes the sources' device listings one
+    after the other: a kernel that two sources compile -- a kernel header included twice -- shows up twice."""
+    import collections
+    import subprocess
+    csrc = os.path.join(ROOT, "topolow_amd", "csrc")
+    subprocess.run(["make", "-C", csrc, "asm"], check=True, capture_output=True)
+    text = open(os.path.join(csrc, "topolow_relax.gfx950.s")).read()
+    names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M)
+    assert len(names) > 400          # the listing is the whole library's
+    twice = [name for name, count in collections.Counter(names).items() if count > 1]
+    assert twice == []

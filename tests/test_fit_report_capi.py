@@ -2,6 +2,7 @@
 kernels live, and every TOPOLOW_ERR_BAD_ARGUMENT case that is found before any device call -- so this runs on a box
 with or without a GPU."""
 import ctypes as C
+import glob
 import os
 import re
 
@@ -49,7 +50,8 @@ def test_ctypes_signatures_and_the_python_surface():
 
 def test_the_kernels_live_in_a_header_of_their_own():
     csrc = os.path.join(ROOT, "topolow_amd", "csrc")
-    assert '#include "relax_fit.h"' in open(os.path.join(csrc, "topolow_relax.hip")).read()
+    sources = glob.glob(os.path.join(csrc, "*.hip"))   # exactly one source compiles the kernels
+    assert sum('#include "relax_fit.h"' in open(s).read() for s in sources) == 1
     text = open(os.path.join(csrc, "relax_fit.h")).read()
     for kernel in ("fit_sums_kernel", "fit_centred_kernel", "fit_select_kernel"):
         assert re.search(r"__global__[^;{]*\b%s\(" % kernel, text), kernel
@@ -57,11 +59,14 @@ def test_the_kernels_live_in_a_header_of_their_own():
     for line in text.splitlines():                      # ... and nothing else: no floating-point atomic anywhere
         if "atomicAdd(" in line:
             assert "h[" in line or "hist[" in line, line
-    # one cell function, called by all three kernels; the distance's arithmetic is written once, in relax_post.h
+    # one cell function, called by all three kernels; the distance's arithmetic is written once, in relax_common.h,
+    # and the two post-metrics kernels call it as well
     assert len(re.findall(r"= fit_cell\(", text)) == 3
+    common = open(os.path.join(csrc, "relax_common.h")).read()
     post = open(os.path.join(csrc, "relax_post.h")).read()
     assert "sqrt" not in text and text.count("post_distance(") == 1
-    assert post.count("s += dev * dev;") == 1 and post.count("post_distance(") == 3
+    assert common.count("s += dev * dev;") == 1 and common.count("post_distance(") == 1
+    assert post.count("post_distance(") == 2
 
 
 def _err():

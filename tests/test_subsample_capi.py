@@ -3,6 +3,7 @@ surface, and every TOPOLOW_ERR_BAD_ARGUMENT case -- each found before any device
 without a GPU.  The subset rules read one thing of a handle, its n, the first field of the struct: the stand-in
 handle here is zeroed memory with n written at its start, which nothing else may read."""
 import ctypes as C
+import glob
 import os
 import re
 
@@ -38,10 +39,12 @@ def test_ctypes_signatures_and_the_python_surface():
 def test_the_kernels_live_in_a_header_of_their_own_that_the_library_depends_on():
     csrc = os.path.join(ROOT, "topolow_amd", "csrc")
     assert os.path.exists(os.path.join(csrc, "relax_prep_graph.h"))
-    assert '#include "relax_prep_graph.h"' in open(os.path.join(csrc, "topolow_relax.hip")).read()
+    sources = glob.glob(os.path.join(csrc, "*.hip"))   # exactly one source compiles the kernels
+    assert sum('#include "relax_prep_graph.h"' in open(s).read() for s in sources) == 1
     make = open(os.path.join(csrc, "Makefile")).read()
     assert re.search(r"^HDR\s*=.*\$\(wildcard \*\.h\)", make, re.M)          # every header of csrc is a dependency
-    assert re.search(r"^libtopolow_relax\.so:.*\$\(HDR\)", make, re.M)
+    assert re.search(r"^%\.o:.*\$\(HDR\)", make, re.M)                        # ... of every object
+    assert re.search(r"^libtopolow_relax\.so:.*\$\(OBJ\)", make, re.M)        # ... which the library is linked from
 
 
 class _StandIn:

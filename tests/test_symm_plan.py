@@ -1,4 +1,4 @@
-"""The host plans of the symmetric sweep (csrc/relax_symm.h: relax_symm_plan, relax_symm_plan_rows, sym_rr_row,
+"""The host plans of the symmetric sweep (csrc/relax_symm_plan.h: relax_symm_plan, relax_symm_plan_rows, sym_rr_row,
 sym_rr_above) through the host-only queries topolow_symm_plan and topolow_symm_stage_rows, which call the functions the
 session calls: every plan against a brute-force enumeration of the tiles it must cover, and the plan shapes the GPU tests
 of tests/test_gpu_symmetric_long_runs.py rely on.  No GPU."""

@@ -260,4 +260,18 @@ struct RunState {
   int pad0, pad1;
 };
 
+#if defined(__HIPCC__)
+// ||pj - pi||: pdist_kernel's own arithmetic -- a sequential s += dev * dev over the coordinates, then ::sqrt -- so the
+// result is bit-identical to topolow_est_distances.  The one copy every kernel that scores a cell calls (relax_post.h,
+// relax_fit.h).
+__device__ inline double post_distance(const double* __restrict__ pj, const double* __restrict__ pi, int dim) {
+  double s = 0.0;
+  for (int d = 0; d < dim; ++d) {
+    const double dev = pj[d] - pi[d];
+    s += dev * dev;
+  }
+  return ::sqrt(s);
+}
+#endif
+
 }  // namespace topolow

@@ -1,6 +1,7 @@
-// topolow_amd/csrc/relax_host.h -- host helpers shared by topolow_relax.hip and the host halves of its
-// headers (relax_gs.h): error type and HIP check, error text, host threads, the edge-list test.
-// Part of the library's one translation unit, so everything here has internal linkage.
+// topolow_amd/csrc/relax_host.h -- host helpers shared by the library's sources (topolow_*.hip) and the host
+// halves of their headers (relax_gs.h): error type and HIP check, error text, host threads, the edge-list test.
+// Every source includes it, so the functions here are stateless and have internal linkage; HipError alone is ONE
+// type for the whole library (hidden, not exported): what one source throws another one's guarded() catches.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,12 +21,12 @@
 
 #include "../../include/topolow_relax.h"
 
-namespace {
-
-struct HipError {
+struct __attribute__((visibility("hidden"))) HipError {
   int code;
   std::string msg;
 };
+
+namespace {
 
 void set_err(char* errbuf, size_t errlen, const char* fmt, ...) {
   if (!errbuf || errlen == 0) return;

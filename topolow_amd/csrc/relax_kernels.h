@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "relax_common.h"
+#include "relax_prep_types.h"
 
 namespace topolow {
 
@@ -1114,6 +1115,38 @@ __global__ __launch_bounds__(kThreads) void encode_dense_kernel(
   }
   out[enc_index(i - row_begin, c, ld)] = w;
   if (dout != nullptr) dout[enc_index(i - row_begin, c, ld)] = dl;
+}
+
+// ---- a session loaded from the handle (topolow_session_load_prepared) ----
+
+// The session's degree terms, upload_degrees' arithmetic on the device: gplus[q] = (float)degrees[perm[q]] + 1.0f
+// (reference src/optimization.cpp:137-140); perm (nullable): session label -> the handle's label.
+__global__ __launch_bounds__(kPrepThreads) void prep_degree_terms_kernel(const int32_t* __restrict__ degrees, int n,
+                                                                          const int* __restrict__ perm,
+                                                                          float* __restrict__ gplus) {
+  const int q = blockIdx.x * kPrepThreads + threadIdx.x;
+  if (q >= n) return;
+  gplus[q] = (float)degrees[perm != nullptr ? perm[q] : q] + 1.0f;
+}
+
+// The session's convergence edge list from the handle's compacted one, edge e to slot e (the order of the list is
+// the order of the MAE's partial sums): the ends in session labels (inv, nullable: the handle's label -> session
+// label), the code as topolow_session_set_edges maps it (0, 1, -1; anything else 2: never counts), the target as f64
+// (t64) or rounded to fp32 (t32) -- exactly one of the two is given.  Consecutive lanes on consecutive entries.
+__global__ __launch_bounds__(kPrepThreads) void prep_session_edges_kernel(
+    const int32_t* __restrict__ edge_i, const int32_t* __restrict__ edge_j, const double* __restrict__ edge_dist,
+    const int32_t* __restrict__ edge_thresh, long long n_edges, const int* __restrict__ inv, int* __restrict__ ei,
+    int* __restrict__ ej, int8_t* __restrict__ ec, double* __restrict__ t64, float* __restrict__ t32) {
+  const long long e = (long long)blockIdx.x * kPrepThreads + threadIdx.x;
+  if (e >= n_edges) return;
+  const int a = edge_i[e], b = edge_j[e];   // 0 <= a < b < n: prep_edge_write_kernel wrote them
+  ei[e] = inv != nullptr ? inv[a] : a;
+  ej[e] = inv != nullptr ? inv[b] : b;
+  const int c = edge_thresh[e];
+  ec[e] = (int8_t)(c == 0 ? 0 : (c == 1 ? 1 : (c == -1 ? -1 : 2)));
+  const double d = edge_dist[e];
+  if (t64 != nullptr) t64[e] = d;
+  else t32[e] = (float)d;
 }
 
 // Order-independent fingerprint of the measured cells the dense MAE pass would reduce, used to

@@ -8,18 +8,6 @@ namespace topolow {
 
 constexpr int kPostThreads = 256;
 
-// ||pj - pi||: pdist_kernel's own arithmetic -- a sequential s += dev * dev over the coordinates, then ::sqrt -- so the
-// result is bit-identical to topolow_est_distances.  The one copy every kernel that scores a cell calls (this file,
-// relax_fit.h).
-__device__ inline double post_distance(const double* __restrict__ pj, const double* __restrict__ pi, int dim) {
-  double s = 0.0;
-  for (int d = 0; d < dim; ++d) {
-    const double dev = pj[d] - pi[d];
-    s += dev * dev;
-  }
-  return ::sqrt(s);
-}
-
 // One workgroup per column of a tile of columns [col0, col0 + cols) of the caller's column-major n x n matrices.
 //   vals   cols x n f64: the tile of `values`, column after column (the caller's own layout)
 //   codes  cols x n i32 or nullptr

@@ -1,5 +1,5 @@
 // topolow_amd/csrc/relax_prep.h -- the pre-processing kernels: ordering sums, degrees, dense fill, edge list
-// (reference R/core.R:269-436; host pipeline: topolow_layout_prep_* in topolow_relax.hip).
+// (reference R/core.R:269-436; host pipeline: topolow_layout_prep_* in topolow_prep.hip).
 //
 // Every kernel works in BUFFER coordinates: the caller's n x n buffer is read as B[a * n + b], a the slow index and
 // b the contiguous one.  For a column-major matrix a is the column, for a row-major one (transposed != 0) the row;
@@ -9,14 +9,6 @@
 #include "relax_prep_rank.h"
 
 namespace topolow {
-
-constexpr int kPrepTile = 64;
-
-// Whole-matrix quantities.  Integer counts and a maximum: atomics do not make them depend on the grid.
-struct PrepTotals {
-  unsigned long long n_finite_nonzero, n_infinite, n_negative, n_inexact;
-  unsigned long long max_key;   // prep_order_key of the largest non-NA code-0 value; 0: there is none
-};
 
 // f64 -> u64, monotone over -Inf..+Inf; never 0 (the smallest image, that of -Inf, is 0x000f...).
 __device__ inline unsigned long long prep_order_key(double v) {
@@ -258,38 +250,6 @@ __global__ __launch_bounds__(kPrepThreads) void prep_reorder_kernel(
     if (out_vals != nullptr) out_vals[dst + b] = vals[cell];
     if (out_codes != nullptr) out_codes[dst + b] = codes[cell];
   }
-}
-
-// ---- a session loaded from the handle (topolow_session_load_prepared) ----
-
-// The session's degree terms, upload_degrees' arithmetic on the device: gplus[q] = (float)degrees[perm[q]] + 1.0f
-// (reference src/optimization.cpp:137-140); perm (nullable): session label -> the handle's label.
-__global__ __launch_bounds__(kPrepThreads) void prep_degree_terms_kernel(const int32_t* __restrict__ degrees, int n,
-                                                                          const int* __restrict__ perm,
-                                                                          float* __restrict__ gplus) {
-  const int q = blockIdx.x * kPrepThreads + threadIdx.x;
-  if (q >= n) return;
-  gplus[q] = (float)degrees[perm != nullptr ? perm[q] : q] + 1.0f;
-}
-
-// The session's convergence edge list from the handle's compacted one, edge e to slot e (the order of the list is
-// the order of the MAE's partial sums): the ends in session labels (inv, nullable: the handle's label -> session
-// label), the code as topolow_session_set_edges maps it (0, 1, -1; anything else 2: never counts), the target as f64
-// (t64) or rounded to fp32 (t32) -- exactly one of the two is given.  Consecutive lanes on consecutive entries.
-__global__ __launch_bounds__(kPrepThreads) void prep_session_edges_kernel(
-    const int32_t* __restrict__ edge_i, const int32_t* __restrict__ edge_j, const double* __restrict__ edge_dist,
-    const int32_t* __restrict__ edge_thresh, long long n_edges, const int* __restrict__ inv, int* __restrict__ ei,
-    int* __restrict__ ej, int8_t* __restrict__ ec, double* __restrict__ t64, float* __restrict__ t32) {
-  const long long e = (long long)blockIdx.x * kPrepThreads + threadIdx.x;
-  if (e >= n_edges) return;
-  const int a = edge_i[e], b = edge_j[e];   // 0 <= a < b < n: prep_edge_write_kernel wrote them
-  ei[e] = inv != nullptr ? inv[a] : a;
-  ej[e] = inv != nullptr ? inv[b] : b;
-  const int c = edge_thresh[e];
-  ec[e] = (int8_t)(c == 0 ? 0 : (c == 1 ? 1 : (c == -1 ? -1 : 2)));
-  const double d = edge_dist[e];
-  if (t64 != nullptr) t64[e] = d;
-  else t32[e] = (float)d;
 }
 
 }  // namespace topolow

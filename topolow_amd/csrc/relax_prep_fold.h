@@ -1,6 +1,6 @@
 // topolow_amd/csrc/relax_prep_fold.h -- one cross-validation fold prepared from a resident handle: the fold mask, the
 // ordering sums and degrees of the masked matrix, the held-out pairs and the scored cells (host pipeline:
-// topolow_layout_prep_fold / _cv_sweep in topolow_relax.hip; the host twin on the cell list: relax_fold.h, fold_pairs).
+// topolow_layout_prep_fold / _cv_sweep in topolow_prep.hip; the host twin on the cell list: relax_fold.h, fold_pairs).
 //
 // A fold is its picks -- linear column-major indices r + c * n -- and their mirrors (fold_dropped).  The kernels work
 // on a FOLD MASK, one bit per cell of the handle's buffer, bit a * n + b for the cell B[a * n + b]; it lives in the
@@ -18,14 +18,6 @@
 #include "relax_prep.h"
 
 namespace topolow {
-
-// Integer counts and a maximum: atomics do not make them depend on the grid.
-struct FoldTotals {
-  unsigned long long max_key;        // prep_order_key of the largest kept non-NA code-0 value; 0: there is none
-  unsigned long long n_upper;        // kept non-NA cells strictly above the diagonal (row < column)
-  unsigned long long n_bad_picks;    // picks outside [0, n * n): counted, written nowhere
-  unsigned long long n_asymmetric;   // off-diagonal cells that differ from their mirror (fold_symmetry_kernel)
-};
 
 __device__ inline bool fold_bit(const uint32_t* __restrict__ mask, size_t cell) {
   return (mask[cell >> 5] >> (cell & 31)) & 1u;

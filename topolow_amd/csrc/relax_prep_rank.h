@@ -3,12 +3,9 @@
 // (relax_prep_fold.h).  A kernel classifies its cells; these two helpers count them and rank them.
 #pragma once
 
-#include "relax_common.h"
+#include "relax_prep_types.h"
 
 namespace topolow {
-
-constexpr int kPrepThreads = 256;
-constexpr int kPrepWaves = kPrepThreads / 64;
 
 // Counting: every thread brings how many cells it found for each list; thread 0 leaves with the column's totals.
 template <int K>

@@ -2,7 +2,7 @@
 // device: the median of the numeric cells, the double-centred matrix B = -0.5 J D^2 J of the median-filled matrix, and
 // all eigenvalues of a symmetric f64 matrix by Householder tridiagonalisation and Sturm bisection
 // (host pipeline: topolow_layout_prep_spectrum / topolow_symmetric_eigenvalues / topolow_tridiagonal_eigenvalues in
-// topolow_relax.hip; NumPy model of the same algorithm: tests/models/spectrum_model.py).
+// topolow_prep.hip; NumPy model of the same algorithm: tests/models/spectrum_model.py).
 //
 // As relax_prep.h, every matrix kernel works in BUFFER coordinates, B[a * n + b] with b the contiguous index.
 // Nothing here adds floating-point numbers in an order that depends on the grid or on timing: histograms are integer
