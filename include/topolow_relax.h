@@ -1009,7 +1009,14 @@ int topolow_session_stage_fused(topolow_session* s, const void* d_pos_in, void* 
  *   topolow_session_symm_segment_sweep  reads all n positions of d_pos_in, sweeps the segment and leaves the
  *                               segment's share of every point's move in the session's moves buffer
  *                               (topolow_session_symm_moves: device float[n][ndim]); d_out2 != NULL: also the
- *                               segment's share of the MAE of d_pos_in, as topolow_session_stage_fused does
+ *                               segment's share of the MAE of d_pos_in, as topolow_session_stage_fused does.  The
+ *                               share is reduced over the block's measured cells, so d_out2 != NULL is refused
+ *                               (TOPOLOW_ERR_UNSUPPORTED, nothing launched) unless
+ *                               topolow_session_can_fuse_segment_checks: fp32, TOPOLOW_FUSE_CHECKS not 0, and the
+ *                               edge list verified to be the block's measured cells
+ *                               (topolow_session_uses_dense_mae) -- no even-rows rule, unlike
+ *                               topolow_session_can_fuse_checks.  The ranks must agree (a collective minimum of the
+ *                               query): a rank that cannot keeps topolow_session_check_partial, and then all do
  *   (the caller sums the moves buffer over the ranks in place -- ONE all-reduce of n x ndim floats, 600 KB at
  *    BASELINE config 4 -- and d_out2 as for stage_fused)
  *   topolow_session_symm_segment_apply  d_pos_out[i] = d_pos_in[i] + moves[i] for ALL n points: every rank holds
@@ -1019,6 +1026,8 @@ int32_t topolow_symm_segment_rows(int32_t n, int32_t segment, int32_t n_segments
                                   int32_t* row_end);
 /* 1 when the session can take the path cut into n_segments (fp32 slab schedule, ndim 2..10, size gate, targets loaded). */
 int32_t topolow_session_symm_segment_eligible(const topolow_session* s, int32_t n_segments);
+/* 1 when topolow_session_symm_segment_sweep may reduce a check (d_out2 != NULL) on this session. */
+int32_t topolow_session_can_fuse_segment_checks(const topolow_session* s);
 float* topolow_session_degree_terms(topolow_session* s);
 /* 1 when some target of the session's block carries a threshold code ('>' / '<'): the any_threshold of the ranks is
  * the OR of these. */

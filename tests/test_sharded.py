@@ -85,6 +85,8 @@ class ModelBackend:
 
     # ---- one-stage iterations as the symmetric sweep sharded over the ranks (sharded.HipBackend.symm_*) ----
     symm_ready = False
+    can_fuse_segment_checks = True     # (HipBackend: the session's query; ShardedRelaxation takes the ranks' minimum)
+    fused_sweeps = 0                   # symm_sweep calls that were asked for the error
 
     def symm_prepare(self, rank, world):
         """Which cells of the upper triangle are this rank's: the tiles (64 rows x 32 columns, tile-row-major from
@@ -117,6 +119,7 @@ class ModelBackend:
         return -delta * f[:, :, None]
 
     def symm_sweep(self, pos_in, it, k, with_error):
+        self.fused_sweeps += bool(with_error)
         total = self.check_partial(pos_in) if with_error else None
         if self.stopped:
             return torch.zeros(self.n * self.ndim, dtype=torch.float64), total
@@ -186,11 +189,32 @@ def _free_port():
     return p
 
 
-def _launch(world, *extra):
+def _run_fuse_guard(rank, world, port, q, n_points, no_fuse_rank):
+    """As _run with the symmetric sweep; the backend of rank `no_fuse_rank` (-1: none) says that it cannot reduce a
+    check in its segment sweep.  Also returns the check series and how many sweeps were asked for the error."""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    call = _problem(n_points)
+    n = call.initial_positions.shape[0]
+    b, e, _ = sharded.row_block(n, world, rank)
+    E = call.edge_i.shape[0]
+    backend = ModelBackend(call, b, e, slice(rank * E // world, (rank + 1) * E // world))
+    backend.symm_prepare(rank, world)
+    backend.can_fuse_segment_checks = rank != no_fuse_rank
+    res = sharded.relax_sharded(backend, sharded.Collectives(world), rank, world, n, call.initial_positions, call.n_iter,
+                                call.k0, call.cooling_rate, call.c_repulsion, call.relative_epsilon,
+                                call.convergence_window, call.convergence_check_freq, seed=31)
+    q.put((rank, res.positions, (res.converged, res.iterations, res.final_mae, res.final_k, res.iterations_run),
+           list(backend.iters), list(backend.maes), backend.fused_sweeps))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _launch(world, *extra, target=None):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_run, args=(r, world, port, q) + extra) for r in range(world)]
+    procs = [ctx.Process(target=target or _run, args=(r, world, port, q) + extra) for r in range(world)]
     for p in procs:
         p.start()
     outs = [q.get(timeout=300) for _ in range(world)]
@@ -233,6 +257,24 @@ def test_two_ranks_with_the_symmetric_sweep_equal_one_rank():
         bk.symm_prepare(r, 3)
         w += bk.cell_weight
     assert np.array_equal(w + w.T, 1.0 - np.eye(n))
+
+
+@pytest.mark.timeout(600)
+def test_a_rank_that_cannot_fuse_segment_checks_keeps_every_rank_on_the_separate_pass():
+    """ShardedRelaxation takes the collective minimum of the backends' can_fuse_segment_checks (HipBackend: fp32, fused
+    checks enabled, the MAE reduced from the block): with ONE rank's false, no rank's symm_sweep is ever asked for the
+    error -- every check is the separate pass -- and embedding, verdict and check series are those of the run in which
+    both ranks fuse (where sweeps are asked for it)."""
+    n = 300
+    both = _launch(2, n, -1, target=_run_fuse_guard)
+    one_cannot = _launch(2, n, 1, target=_run_fuse_guard)
+    assert all(o[5] > 0 for o in both)
+    assert [o[5] for o in one_cannot] == [0, 0]
+    for a, b in zip(both, one_cannot):
+        np.testing.assert_allclose(b[1], a[1], rtol=0, atol=1e-10)
+        assert b[2] == pytest.approx(a[2], rel=1e-10)
+        assert b[3] == a[3] and len(a[3]) >= 5
+        assert b[4] == pytest.approx(a[4], rel=1e-10)
 
 
 def test_row_blocks_cover_everything():

@@ -145,6 +145,28 @@ def test_the_plan_shapes_the_capped_grid_tests_are_built_on():
         assert d["longest"] == 1 and d["run_tiles"].max() == 1
 
 
+def test_segment_row_windows_are_the_tile_rows_of_the_segments_tiles():
+    """topolow_symm_segment_rows (the rows a caller brings together before topolow_session_symm_segment_build): rows
+    [64 r_first, min(n, 64 (r_last + 1))) of the tile-rows that hold the segment's tiles -- from the segment's units, and
+    from the brute-force tile list.  385 points are 7 tile-rows, 56 tiles: seven segments of eight tiles (the fewest a
+    segment may have), none for eight segments."""
+    for n in (385, 520, 1000):
+        TR, _ = _geometry(n)
+        total = TR * (TR + 1)
+        tR, _ = _triangle(n)
+        for P in (2, 3, 5, 7):
+            for b in range(P):
+                units, _ = _native.symm_plan(n, 4, segment=b, n_segments=P)
+                r_first, r_last = int(units[:, 0].min()), int(units[:, 0].max())
+                mine = tR[total * b // P:total * (b + 1) // P]
+                assert (r_first, r_last) == (mine.min(), mine.max())
+                assert _native.symm_segment_rows(n, b, P) == (64 * r_first, min(n, 64 * (r_last + 1))), (n, P, b)
+    assert [_native.symm_segment_rows(385, r, 7) for r in range(7)] == [
+        (0, 64), (0, 128), (64, 128), (64, 192), (128, 256), (192, 320), (256, 385)]
+    assert _native.symm_segment_rows(385, 0, 8) is None
+    assert _native.symm_segment_rows(385, 7, 7) is None and _native.symm_segment_rows(1, 0, 1) is None
+
+
 def test_plan_queries_refuse_what_no_session_plans_with():
     lib = _native.load()
     assert lib.topolow_symm_plan(1, 4, 0, 0, 0, 1, None, 0, None) == -1          # no pair

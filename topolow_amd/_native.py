@@ -292,6 +292,8 @@ def load() -> C.CDLL:
     lib.topolow_session_has_thresholds.argtypes = [vp]
     lib.topolow_session_symm_segment_eligible.restype = C.c_int32
     lib.topolow_session_symm_segment_eligible.argtypes = [vp, C.c_int32]
+    lib.topolow_session_can_fuse_segment_checks.restype = C.c_int32
+    lib.topolow_session_can_fuse_segment_checks.argtypes = [vp]
     lib.topolow_session_wait.restype = C.c_int
     lib.topolow_session_wait.argtypes = [vp, C.c_char_p, C.c_size_t]
     lib.topolow_session_degree_terms.restype = vp
@@ -1716,6 +1718,12 @@ class Session:
 
     def symm_segment_eligible(self, n_segments: int) -> bool:
         return bool(self.lib.topolow_session_symm_segment_eligible(self._h, int(n_segments)))
+
+    @property
+    def can_fuse_segment_checks(self) -> bool:
+        """Whether symm_segment_sweep may reduce a check (d_out2): fp32, fused checks enabled, the MAE reduced from the
+        block (topolow_session_can_fuse_segment_checks); it is refused otherwise."""
+        return bool(self.lib.topolow_session_can_fuse_segment_checks(self._h))
 
     def symm_segment_build(self, segment: int, n_segments: int, d_rows: int, row_first: int, n_rows: int,
                            any_threshold: bool):

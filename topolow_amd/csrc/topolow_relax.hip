@@ -706,6 +706,8 @@ template <int DIM>
 void sym_sweep(topolow_session* s, const SymPlanDev& plan, const void* rec, bool thr, bool err,
                unsigned long long block_cells, int col_row0, bool prio) {
   auto& y = s->sym;
+  if (err && ((size_t)plan.n_units > s->part_sum.n || (size_t)plan.n_units > s->part_cnt.n))
+    throw HipError{TOPOLOW_ERR_HIP, "symmetric sweep: the error partials are smaller than the plan's unit count"};
   sym_real<DIM>(s, [&](auto r) {
     using real = decltype(r);
     sym_sweep_instance<DIM, real>(thr, err, s->exact, [&](auto kern) {
@@ -1127,8 +1129,13 @@ void edges_begin(topolow_session* s, int64_t n_edges) {
   s->dense_grid_y = (s->rows() + kErrTileRows - 1) / kErrTileRows;
   s->dense_blocks = s->dense_grid_x * s->dense_grid_y;
   const int stage_blocks = (s->rows() + CfgProd::ROWS - 1) / CfgProd::ROWS;   // fused checks: one partial per workgroup
-  s->part_sum.alloc(std::max({s->n_parts, s->dense_blocks, stage_blocks}));
-  s->part_cnt.alloc(std::max({s->n_parts, s->dense_blocks, stage_blocks}));
+  // ... and one per unit of a sweep plan the session still holds: an fp32 session keeps its sweep buffers across a new
+  // edge list, and sym_build sizes the partials at build time only (the edge-list bookkeeping)
+  int parts = std::max({s->n_parts, s->dense_blocks, stage_blocks, s->sym.plan.n_units});
+  for (const auto& plans : s->sym.rr)
+    for (const auto& p : plans) parts = std::max(parts, p.n_units);
+  s->part_sum.alloc(parts);
+  s->part_cnt.alloc(parts);
   s->dense_mae = false;
   s->dense_parity = !(s->row_begin == 0 && s->row_end == s->n);
   s->list_is_block = false;
@@ -2200,12 +2207,23 @@ int topolow_session_symm_segment_build(topolow_session* s, int32_t segment, int3
   });
 }
 
+// The segment sweep's ERR instance reduces the block's measured cells (no even-rows rule, unlike the row-owner one): it may
+// stand for a check only where the separate pass reduces the same cells.
+int32_t topolow_session_can_fuse_segment_checks(const topolow_session* s) {
+  return s && s->fuse_checks && s->dense_mae && s->precision == TOPOLOW_PRECISION_F32 ? 1 : 0;
+}
+
 int topolow_session_symm_segment_sweep(topolow_session* s, const void* d_pos_in, int32_t iter, double k,
                                        double* d_out2, char* errbuf, size_t errlen) {
   if (!s || !d_pos_in || !s->began) return TOPOLOW_ERR_BAD_ARGUMENT;
   if (s->sym.holds != SymHolds::kCallerSegment) {
     set_err(errbuf, errlen, "no segment built (topolow_session_symm_segment_build)");
     return TOPOLOW_ERR_BAD_ARGUMENT;
+  }
+  if (d_out2 != nullptr && !topolow_session_can_fuse_segment_checks(s)) {
+    set_err(errbuf, errlen, "this session cannot reduce a check in its segment sweep (needs fp32, fused checks enabled and "
+                            "the MAE reduced from the block); use topolow_session_check_partial");
+    return TOPOLOW_ERR_UNSUPPORTED;
   }
   return guarded(errbuf, errlen, [&] {
     HIP_TRY(hipSetDevice(s->device));

@@ -276,6 +276,11 @@ class HipBackend:
         self.symm_ready = True
         return True
 
+    @property
+    def can_fuse_segment_checks(self):
+        """Whether symm_sweep may be asked with_error (the library refuses it otherwise): the ranks take the minimum."""
+        return self.session.can_fuse_segment_checks
+
     def symm_sweep(self, pos_in, it, k, with_error: bool):
         """This rank's segment of iteration `it`: returns (moves, total2) -- the session's moves buffer (the caller
         sums it over the ranks in place) and, with_error, the segment's share of the MAE of pos_in."""
@@ -336,7 +341,10 @@ class ShardedRelaxation:
         # n x ndim moves instead of the all-gather): when the backend built its segment (HipBackend.symm_prepare)
         self.symmetric = bool(getattr(backend, "symm_ready", False)) and world > 1
         if self.symmetric:
-            self.fusable = not timers     # the sweep's ERR instance has no even-rows rule
+            # the sweep's ERR instance has no even-rows rule, but it reduces the block's measured cells: every rank's
+            # separate pass must reduce the same ones (fused checks enabled, the edge list verified against the block)
+            self.fusable = coll.min_float(1.0 if getattr(backend, "can_fuse_segment_checks", False) else 0.0) > 0 \
+                and not timers
         self.pending = None   # (iter1, k_after, buffer index): a check that rides on the next iteration's single stage
 
     def _stages(self, it_, k_):
