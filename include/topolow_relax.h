@@ -361,6 +361,51 @@ int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, co
                             const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
                             int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen);
 
+/* Replaces the reference's compute_kernel_velocity (R/visualization.R:802-843): the kernel-weighted antigenic
+ * velocity of every point of a finished map, one pairwise pass on the device, all of it in f64.
+ *   positions      n x ndim f64 column-major (host), 1 <= ndim <= 16
+ *   times          n f64 (host); NaN = NA
+ *   sigma_t, sigma_x   the bandwidths of the temporal and of the spatial Gaussian kernel
+ *   excluded_bits  NULL: every earlier point is eligible.  Else n rows of ceil(n / 64) 64-bit words, row-major, in the
+ *                  caller's order: bit (j % 64) of word (j / 64) of row i set = point j does not contribute to row i.
+ *                  The reference's clade rule (:816-823) sets it when i has an entry in clade_members, j is in
+ *                  tree_present_points and j is not in i's clade; any dictionary of member lists is so represented
+ *                  exactly.  Bits of later or tied points are never read.
+ *   velocity       n x ndim f64 out, column-major;  weight_sum  n f64 out, or NULL: not wanted
+ * For row i over the points j with times[j] < times[i] (strictly: a tie contributes in neither direction; a NaN
+ * time is nobody's past and has none) whose bit is clear:
+ *   w_ij = exp(-(||x_i - x_j||^2 / (2 sigma_x^2) + (t_i - t_j)^2 / (2 sigma_t^2)))
+ *   weight_sum[i] = sum_j w_ij      velocity[i, d] = sum_j w_ij (x_id - x_jd) / (t_i - t_j) / weight_sum[i]
+ * and velocity[i, ] = NaN (R's NA) when weight_sum[i] is not > 0: no eligible past point, or every weight 0.
+ * One exp of the summed exponent replaces the reference's product of two: the two agree to a few ulp of a weight,
+ * and can differ on whether a weight is exactly 0 only where the summed exponent lies between about 700 and 760.
+ * The library sorts the points by time (stable; points of equal time by their coordinates) and permutes the bits
+ * itself; everything is taken and returned in the caller's order.  The result is reproducible: no floating-point
+ * atomic, every row's sums formed in an order that depends on n alone (columns in ascending sorted order inside
+ * chunks of columns, the chunks' partials added in chunk order; the chunk is 256 columns up to 16 384 points and
+ * n / 64 rounded up to a multiple of 256 beyond), so every call returns the same bits, and a point's row does not
+ * depend on the order the caller lists the points in -- with one exception: points that are equal in time AND in
+ * every coordinate keep the caller's order among themselves.  They add equal terms, so without bits nothing
+ * changes; with exclusion bits that differ between such twins, a row that takes one twin and not the other may add
+ * that term at another place in the order, and its last bits may then follow the caller's order.
+ * Host cost of the bits: the library permutes the bits of every row's past to the sorted order one bit at a time,
+ * about n^2 / 2 single-bit moves over up to 16 host threads (5 * 10^7 at 10 000 points, 1.25 * 10^9 at 50 000), and
+ * holds a second copy of the n^2 / 8 bytes (313 MB at 50 000).
+ * TOPOLOW_ERR_BAD_ARGUMENT, before any device call: NULL positions, times or velocity; n < 1; ndim < 1; a sigma
+ * that is not finite or not > 0.  TOPOLOW_ERR_UNSUPPORTED: ndim > 16. */
+int topolow_kernel_velocity(const double* positions, const double* times, int32_t n, int32_t ndim, double sigma_t,
+                            double sigma_x, const uint64_t* excluded_bits, double* velocity, double* weight_sum,
+                            int32_t device, char* errbuf, size_t errlen);
+
+/* The same call with the columns per chunk chosen by the caller and the device time measured (a test and study
+ * entry: tests/study/velocity_timing.py).  chunk_cols: 0 = the library's width, else a positive multiple of 64
+ * (anything else: TOPOLOW_ERR_BAD_ARGUMENT).  Two widths group a row's additions differently, so their results may
+ * differ in the last bits; one width always returns the same bits.  seconds: NULL, or 1 double out -- the two
+ * kernels from device events (the host's sort, the uploads and the downloads are not in it). */
+int topolow_kernel_velocity_ex(const double* positions, const double* times, int32_t n, int32_t ndim, double sigma_t,
+                               double sigma_x, const uint64_t* excluded_bits, double* velocity, double* weight_sum,
+                               int32_t device, int32_t chunk_cols, double* seconds, char* errbuf, size_t errlen);
+
 /* ---------------------------------------------------------------------------------------
  * Prepared layout: the reference's pre-processing (R/core.R:269-436) on the device -- ordering means, degrees,
  * the upper-triangle edge list in which() order, the symmetric dense fill, the scale of the random-walk start.

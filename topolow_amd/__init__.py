@@ -24,9 +24,11 @@ from .error_metrics import (  # noqa: F401
     error_calculator_comparison,
     fit_statistics,
 )
+from .velocity import default_bandwidths, kernel_velocity, silverman_bandwidth  # noqa: F401
 
 __all__ = ["euclidean_embedding", "create_topolow_map", "print_topolow", "summary_topolow",
            "Topolow", "RMatrix", "options", "set_seed", "NativeError", "prepare_layout_call",
            "check_matrix_connectivity", "subsample_dissimilarity_matrix", "data_characteristics",
            "adjust_ndim_range", "analyze_network_structure", "prune_sparse_matrix", "error_calculator_comparison",
-           "calculate_prediction_interval", "fit_statistics", "FitStatistics"]
+           "calculate_prediction_interval", "fit_statistics", "FitStatistics", "kernel_velocity",
+           "silverman_bandwidth", "default_bandwidths"]

@@ -265,6 +265,12 @@ def load() -> C.CDLL:
     lib.topolow_post_metrics_ex.restype = C.c_int
     lib.topolow_post_metrics_ex.argtypes = [dp, C.c_int32, C.c_int32, dp, ip, dp, dp, i64p, C.c_int32, C.c_int32, dp,
                                             C.c_char_p, C.c_size_t]
+    lib.topolow_kernel_velocity.restype = C.c_int
+    lib.topolow_kernel_velocity.argtypes = [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, u64p, dp, dp,
+                                            C.c_int32, C.c_char_p, C.c_size_t]
+    lib.topolow_kernel_velocity_ex.restype = C.c_int
+    lib.topolow_kernel_velocity_ex.argtypes = [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, u64p, dp, dp,
+                                               C.c_int32, C.c_int32, dp, C.c_char_p, C.c_size_t]
     vp = C.c_void_p
     lib.topolow_session_create.restype = C.c_int
     lib.topolow_session_create.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, C.c_int32,
@@ -937,6 +943,46 @@ def post_metrics(positions, values, codes=None, want_est: bool = True, staging: 
     if phases is not None:
         phases[:] = [ph[0], ph[1], ph[2]]
     return est, float(s.value), int(c.value)
+
+
+def kernel_velocity(positions, times, sigma_t: float, sigma_x: float, excluded_bits=None, device: Optional[int] = None,
+                    chunk_cols: Optional[int] = None, timing: Optional[list] = None):
+    """The reference's compute_kernel_velocity (R/visualization.R:802-843) on the GPU: returns (velocity n x ndim,
+    weight_sum n), rows without an eligible past point (or whose weights are all 0) NaN in velocity.
+    excluded_bits: None, or an n x ceil(n / 64) uint64 array in the caller's order -- bit (j % 64) of word
+    (j // 64) of row i set = point j does not contribute to row i (topolow_amd.velocity.pack_exclusion_bits).
+    `chunk_cols` (a multiple of 64; None = the library's width, a function of n) and `timing` (a list that
+    receives the seconds of the kernels) reach the _ex entry: for tests and tests/study/velocity_timing.py."""
+    lib = load()
+    pos = _f64F(positions)
+    if pos.ndim != 2:
+        raise ValueError("positions must be an n x ndim matrix")
+    n, dim = pos.shape
+    t = np.ascontiguousarray(times, dtype=np.float64)
+    if t.shape != (n,):
+        raise ValueError("times must hold one value per position")
+    bits = None
+    if excluded_bits is not None:
+        bits = np.ascontiguousarray(excluded_bits, dtype=np.uint64)
+        if bits.shape != (n, (n + 63) // 64):
+            raise ValueError("excluded_bits must be an n x ceil(n / 64) array of 64-bit words")
+    vel = np.empty((n, dim), dtype=np.float64, order="F")
+    w = np.empty(n, dtype=np.float64)
+    secs = C.c_double(0.0)
+    err = C.create_string_buffer(512)
+    dev = int(options.get("device", -1)) if device is None else int(device)
+    bp = bits.ctypes.data_as(C.POINTER(C.c_uint64)) if bits is not None else None
+    if chunk_cols is None and timing is None:
+        rc = lib.topolow_kernel_velocity(_dp(pos), _dp(t), n, dim, float(sigma_t), float(sigma_x), bp, _dp(vel),
+                                         _dp(w), dev, err, len(err))
+    else:
+        rc = lib.topolow_kernel_velocity_ex(_dp(pos), _dp(t), n, dim, float(sigma_t), float(sigma_x), bp, _dp(vel),
+                                            _dp(w), dev, int(chunk_cols or 0),
+                                            C.byref(secs) if timing is not None else None, err, len(err))
+    _check(rc, err)
+    if timing is not None:
+        timing[:] = [secs.value]
+    return vel, w
 
 
 ORDER_PRESERVED, ORDER_DEVICE_EXACT, ORDER_DEVICE_GAP, ORDER_DECLINED = 0, 1, 2, 3
