@@ -38,13 +38,22 @@ class NativeError(RuntimeError):
 INTERRUPT_CB = C.CFUNCTYPE(C.c_int32, C.c_void_p)
 PRINT_CB = C.CFUNCTYPE(None, C.c_char_p, C.c_void_p)
 
+# The C types of include/topolow_relax.h, as the structs and the prototype table below spell them.
+INT, I32, U32, I64, U64, F64 = C.c_int, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_double
+dp, ip, i64p, u64p = C.POINTER(F64), C.POINTER(I32), C.POINTER(I64), C.POINTER(U64)
+i8p, u8p = C.POINTER(C.c_int8), C.POINTER(C.c_uint8)
+vp = C.c_void_p            # a host pointer the binding does not look into: a session, a prepared handle, a stream
+vpp = C.POINTER(vp)
+devp = C.c_void_p          # a device address: it travels as a Python int, whatever the header's pointee type
+ERR = (C.c_char_p, C.c_size_t)   # the trailing `char* errbuf, size_t errlen` of most entries (_call supplies them)
+
 
 class TopolowOptions(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("schedule", C.c_int32), ("precision", C.c_int32),
                 ("slab_stages", C.c_int32), ("device", C.c_int32), ("gs_max_n", C.c_int32),
                 ("n_devices", C.c_int32), ("keep_labels", C.c_int32), ("reserved", C.c_int32 * 3),
                 ("interrupt_cb", INTERRUPT_CB), ("interrupt_user", C.c_void_p),
-                ("print_cb", PRINT_CB), ("print_user", C.c_void_p), ("devices", C.POINTER(C.c_int32))]
+                ("print_cb", PRINT_CB), ("print_user", C.c_void_p), ("devices", ip)]
 
 
 class TopolowRunStats(C.Structure):
@@ -63,24 +72,24 @@ class TopolowShardStats(C.Structure):
 
 
 class TopolowProblem(C.Structure):
-    _fields_ = [("initial_positions", C.POINTER(C.c_double)), ("dissimilarity_matrix", C.POINTER(C.c_double)),
-                ("threshold_matrix", C.POINTER(C.c_int32)), ("degrees", C.POINTER(C.c_int32)),
-                ("edge_i", C.POINTER(C.c_int32)), ("edge_j", C.POINTER(C.c_int32)),
-                ("edge_dist", C.POINTER(C.c_double)), ("edge_thresh", C.POINTER(C.c_int32)),
+    _fields_ = [("initial_positions", dp), ("dissimilarity_matrix", dp),
+                ("threshold_matrix", ip), ("degrees", ip),
+                ("edge_i", ip), ("edge_j", ip),
+                ("edge_dist", dp), ("edge_thresh", ip),
                 ("n_edges", C.c_int64), ("n", C.c_int32), ("ndim", C.c_int32), ("n_iter", C.c_int32),
                 ("convergence_window", C.c_int32), ("convergence_check_freq", C.c_int32),
                 ("reserved0", C.c_int32), ("k0", C.c_double), ("cooling_rate", C.c_double),
                 ("c_repulsion", C.c_double), ("relative_epsilon", C.c_double), ("seed", C.c_uint64),
-                ("holdout_i", C.POINTER(C.c_int32)), ("holdout_j", C.POINTER(C.c_int32)),
-                ("holdout_truth", C.POINTER(C.c_double)), ("n_holdout", C.c_int64)]
+                ("holdout_i", ip), ("holdout_j", ip),
+                ("holdout_truth", dp), ("n_holdout", C.c_int64)]
 
 
 class TopolowCellList(C.Structure):
     _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("n_cells", C.c_int64),
-                ("row", C.POINTER(C.c_int32)), ("col", C.POINTER(C.c_int32)),
-                ("value", C.POINTER(C.c_double)), ("code", C.POINTER(C.c_int32)),
-                ("pos_of", C.POINTER(C.c_int64)), ("by_row", C.POINTER(C.c_int64)),
-                ("row_ptr", C.POINTER(C.c_int64))]
+                ("row", ip), ("col", ip),
+                ("value", dp), ("code", ip),
+                ("pos_of", i64p), ("by_row", i64p),
+                ("row_ptr", i64p)]
 
 
 PRUNE_MAX_ATTEMPTS = 10   # TOPOLOW_PRUNE_MAX_ATTEMPTS
@@ -127,7 +136,7 @@ class TopolowPruneInfo(C.Structure):
 
 
 class TopolowResult(C.Structure):
-    _fields_ = [("positions_out", C.POINTER(C.c_double)), ("final_mae", C.c_double),
+    _fields_ = [("positions_out", dp), ("final_mae", C.c_double),
                 ("final_k", C.c_double), ("converged", C.c_int32), ("iterations", C.c_int32),
                 ("iterations_run", C.c_int32), ("n_checks", C.c_int32), ("error_code", C.c_int32),
                 ("error_iteration", C.c_int32), ("holdout_sum_abs", C.c_double),
@@ -165,6 +174,136 @@ def host_rng() -> np.random.Generator:
     return _host_rng
 
 
+optionsp, run_statsp, shard_statsp = C.POINTER(TopolowOptions), C.POINTER(TopolowRunStats), C.POINTER(TopolowShardStats)
+problemp, resultp, cellsp = C.POINTER(TopolowProblem), C.POINTER(TopolowResult), C.POINTER(TopolowCellList)
+prep_infop, prune_infop = C.POINTER(TopolowLayoutPrepInfo), C.POINTER(TopolowPruneInfo)
+spectrump, fit_reportp = C.POINTER(TopolowSpectrumInfo), C.POINTER(TopolowFitReport)
+
+# Every function include/topolow_relax.h declares, in the header's order: name -> (restype, argtypes).
+# tests/test_native_prototypes.py compares each entry with the header, type by type.
+PROTOTYPES = {
+    # ---- the `.Call` payload: one embedding, a batch of them
+    "topolow_default_options": (None, (optionsp,)),
+    "topolow_optimize_layout_exact": (INT, (dp, I32, I32, dp, ip, ip, ip, ip, dp, ip, I64, I32, F64, F64, F64, F64, I32, I32,
+                                            I32, optionsp, dp, ip, ip, dp, dp, run_statsp, *ERR)),
+    "topolow_optimize_layout_exact_batch": (INT, (problemp, resultp, I32, I32, I32, dp, *ERR)),
+    # ---- cross-validation from a cell list
+    "topolow_cell_list_index": (INT, (I32, I64, ip, ip, i64p, i64p, i64p)),
+    "topolow_cv_fold": (INT, (cellsp, i64p, I64, I32, I32, ip, ip, ip, ip, dp, ip, i64p, ip, ip, dp, i64p, dp)),
+    "topolow_cv_sweep": (INT, (cellsp, I32, I32, I32, ip, dp, dp, dp, i64p, i64p, dp, i64p, u64p, I32, F64, I32, I32, I32,
+                               I32, dp, i64p, ip, ip, ip, dp, *ERR)),
+    "topolow_batch_problem_fits": (I32, (I32, I32, I32, I64)),
+    "topolow_cv_fold_pairs": (INT, (cellsp, i64p, I64, I32, I32, ip, ip, dp, i64p, ip, ip, i64p, ip, ip, dp, i64p, *ERR)),
+    "topolow_cv_sweep_session": (INT, (cellsp, I32, I32, I32, ip, dp, dp, dp, i64p, i64p, dp, i64p, u64p, I32, F64, I32,
+                                       I32, I32, I32, I32, dp, i64p, ip, ip, ip, dp, *ERR)),
+    # ---- post-processing: distances, metrics, velocity
+    "topolow_est_distances": (INT, (dp, I32, I32, dp, I32, *ERR)),
+    "topolow_est_distances_rows": (INT, (dp, I32, I32, I32, I32, dp, I32, *ERR)),
+    "topolow_post_metrics": (INT, (dp, I32, I32, dp, ip, dp, dp, i64p, I32, *ERR)),
+    "topolow_post_metrics_ex": (INT, (dp, I32, I32, dp, ip, dp, dp, i64p, I32, I32, dp, *ERR)),
+    "topolow_kernel_velocity": (INT, (dp, dp, I32, I32, F64, F64, u64p, dp, dp, I32, *ERR)),
+    "topolow_kernel_velocity_ex": (INT, (dp, dp, I32, I32, F64, F64, u64p, dp, dp, I32, I32, dp, *ERR)),
+    # ---- prepared layout: a matrix that stays on the device
+    "topolow_layout_prep_create": (INT, (vpp, dp, i8p, I32, I32, I32, ip, I32, prep_infop, *ERR)),
+    "topolow_layout_prep_fetch": (INT, (vp, ip, ip, ip, ip, dp, ip, dp, ip, dp, i8p, *ERR)),
+    "topolow_layout_prep_destroy": (None, (vp,)),
+    "topolow_layout_prep_phase_seconds": (INT, (vp, dp)),
+    "topolow_session_load_prepared": (INT, (vp, vp, *ERR)),
+    "topolow_layout_prep_optimize": (INT, (vp, dp, I32, I32, F64, F64, F64, F64, I32, I32, I32, optionsp, dp, ip, ip, dp, dp,
+                                           run_statsp, *ERR)),
+    "topolow_layout_prep_post_metrics": (INT, (vp, dp, I32, dp, dp, i64p, *ERR)),
+    "topolow_layout_prep_order": (INT, (vp, ip, ip)),
+    "topolow_layout_prep_resident_seconds": (INT, (vp, dp)),
+    "topolow_layout_order_from_sums": (I32, (I32, dp, i64p, dp, i64p, I32, ip)),
+    "topolow_layout_prep_fold": (INT, (vp, i64p, I64, I32, I32, ip, ip, dp, i64p, ip, ip, i64p, ip, ip, dp, i64p, ip, *ERR)),
+    "topolow_layout_prep_cv_sweep": (INT, (vp, I32, I32, I32, ip, dp, dp, dp, i64p, i64p, dp, i64p, u64p, I32, F64, I32,
+                                           I32, I32, I32, dp, i64p, ip, ip, ip, ip, dp, *ERR)),
+    "topolow_layout_prep_fold_seconds": (INT, (vp, dp)),
+    "topolow_layout_prep_connectivity": (INT, (vp, ip, I32, ip, i64p, ip, *ERR)),
+    "topolow_layout_prep_subsample": (INT, (vp, ip, I32, I32, ip, vpp, prep_infop, *ERR)),
+    "topolow_layout_prep_graph_stats": (INT, (vp, ip, dp)),
+    "topolow_layout_prep_degrees": (INT, (vp, ip, I32, ip, i64p, *ERR)),
+    "topolow_layout_prep_prune": (INT, (vp, I32, F64, I32, I32, u8p, prune_infop, *ERR)),
+    "topolow_tridiagonal_eigenvalues": (INT, (dp, dp, I32, I32, dp, *ERR)),
+    "topolow_symmetric_eigenvalues": (INT, (dp, I32, I32, dp, dp, dp, *ERR)),   # its d_out is the diagonal, host memory
+    "topolow_layout_prep_spectrum": (INT, (vp, dp, dp, spectrump, *ERR)),
+    "topolow_layout_prep_fit_report": (INT, (vp, dp, I32, i64p, I64, fit_reportp, *ERR)),
+    "topolow_layout_prep_fit_order_stats": (INT, (vp, dp, I32, i64p, I64, I32, i64p, I32, dp, i64p, *ERR)),
+    # ---- session: a device-resident run
+    "topolow_session_create": (INT, (vpp, I32, I32, I32, I32, I32, I32, *ERR)),
+    "topolow_session_destroy": (None, (vp,)),
+    "topolow_session_set_relabel": (INT, (vp, U64, *ERR)),
+    "topolow_session_labels": (INT, (vp, ip)),
+    "topolow_session_load_dense": (INT, (vp, dp, ip, ip, *ERR)),
+    "topolow_session_load_coo": (INT, (vp, ip, ip, dp, ip, I64, ip, *ERR)),
+    "topolow_session_encoded_ptr": (devp, (vp,)),
+    "topolow_session_encoded_ld": (I32, (vp,)),
+    "topolow_session_commit_encoded": (INT, (vp, ip, *ERR)),
+    "topolow_session_set_edges": (INT, (vp, ip, ip, dp, ip, I64, *ERR)),
+    "topolow_session_set_positions": (INT, (vp, dp, *ERR)),
+    "topolow_session_get_positions": (INT, (vp, dp, *ERR)),
+    "topolow_session_begin": (INT, (vp, I32, F64, F64, F64, F64, I32, I32, U64, I32, *ERR)),
+    "topolow_session_enqueue": (INT, (vp, I32, ip, *ERR)),
+    "topolow_session_wait": (INT, (vp, *ERR)),
+    "topolow_session_sync": (INT, (vp, ip, ip, dp, *ERR)),
+    "topolow_session_finish": (INT, (vp, dp, ip, ip, dp, dp, *ERR)),
+    "topolow_session_check_trace": (INT, (vp, dp, I32, ip)),
+    "topolow_session_hold_out": (INT, (vp, ip, ip, I64, ip, *ERR)),
+    "topolow_session_restore_held_out": (INT, (vp, ip, *ERR)),
+    "topolow_session_score_pairs": (INT, (vp, ip, ip, dp, I64, dp, i64p, *ERR)),
+    "topolow_session_set_profiling": (INT, (vp, I32)),
+    "topolow_session_profile_fused": (INT, (vp, dp, i64p, *ERR)),
+    "topolow_session_profile_symmetric": (INT, (vp, dp, i64p, dp, i64p, *ERR)),
+    "topolow_session_profile": (INT, (vp, dp, i64p, dp, i64p, *ERR)),
+    "topolow_session_set_stream": (INT, (vp, vp, I32)),
+    "topolow_session_stream": (devp, (vp,)),
+    "topolow_session_uses_dense_mae": (I32, (vp,)),
+    "topolow_session_stage_launches": (I64, (vp,)),
+    "topolow_session_checks_in_apply": (I64, (vp,)),
+    "topolow_session_bytes_per_iteration": (I64, (vp,)),
+    "topolow_session_set_schedule": (INT, (vp, I32)),
+    "topolow_tilegs_pair_order": (I64, (I32, U64, I32, ip)),
+    "topolow_session_position_rows": (I32, (vp,)),
+    "topolow_session_position_dim": (I32, (vp,)),
+    "topolow_session_stage": (INT, (vp, devp, devp, I32, I32, I32, F64, *ERR)),
+    "topolow_session_check_partial": (INT, (vp, devp, devp, *ERR)),
+    "topolow_session_controller_step": (INT, (vp, devp, devp, I32, F64, *ERR)),
+    "topolow_session_can_fuse_checks": (I32, (vp,)),
+    "topolow_session_stage_fused": (INT, (vp, devp, devp, I32, F64, devp, *ERR)),
+    "topolow_symm_segment_rows": (I32, (I32, I32, I32, ip, ip)),
+    "topolow_session_symm_segment_eligible": (I32, (vp, I32)),
+    "topolow_session_can_fuse_segment_checks": (I32, (vp,)),
+    "topolow_session_degree_terms": (devp, (vp,)),
+    "topolow_session_has_thresholds": (I32, (vp,)),
+    "topolow_session_symm_segment_build": (INT, (vp, I32, I32, devp, I32, I32, I32, *ERR)),
+    "topolow_session_symm_moves": (devp, (vp,)),
+    "topolow_session_symm_segment_sweep": (INT, (vp, devp, I32, F64, devp, *ERR)),
+    "topolow_session_symm_segment_apply": (INT, (vp, devp, devp, I32, *ERR)),
+    "topolow_session_first_nonfinite": (INT, (vp, ip)),
+    "topolow_session_edge_error": (INT, (vp, devp, dp, i64p, *ERR)),
+    # ---- one embedding row-sharded over sessions
+    "topolow_shard_rows": (I32, (I32, I32, I32, ip, ip)),
+    "topolow_optimize_layout_exact_sharded": (INT, (dp, I32, I32, dp, ip, ip, ip, ip, dp, ip, I64, I32, F64, F64, F64, F64,
+                                                    I32, I32, I32, optionsp, dp, ip, ip, dp, dp, shard_statsp, *ERR)),
+    "topolow_sessions_run_sharded": (INT, (vpp, I32, dp, I32, F64, F64, F64, F64, I32, I32, U64, I32, INTERRUPT_CB, vp, I32,
+                                           dp, ip, ip, dp, dp, shard_statsp, *ERR)),
+    # ---- plans and host-side helpers (no device)
+    "topolow_slab_plan": (I32, (I32, I32, U64, I32, ip, I32)),
+    "topolow_slab_stages_for_k": (I32, (F64, I32)),
+    "topolow_symm_stage_bounds": (I32, (I32, I32, ip)),
+    "topolow_symm_stage_order": (I32, (U64, I32, I32, ip)),
+    "topolow_symm_stage_rows": (I32, (I32, I32, I32, ip)),
+    "topolow_symm_plan": (I32, (I32, I32, I32, I32, I32, I32, ip, I32, ip)),
+    "topolow_session_symm_grid": (I32, (vp,)),
+    "topolow_slab_stages_at": (I32, (I32, F64, I32)),
+    "topolow_gs_pair_order": (I64, (I32, U64, I32, ip)),
+    "topolow_encode_target": (U32, (F64, I32)),
+    "topolow_encoded_index": (I64, (I32, I32, I32)),
+    "topolow_decode_target": (F64, (U32, ip)),
+    "topolow_controller_script": (INT, (dp, ip, dp, I32, F64, I32, F64, ip, ip, dp, dp, ip)),
+    "topolow_relax_version": (C.c_char_p, ()),
+}
+
 _lib = None
 
 
@@ -177,275 +316,43 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C topolow_amd/csrc`. topolow_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    lib.topolow_relax_version.restype = C.c_char_p
-    lib.topolow_default_options.argtypes = [C.POINTER(TopolowOptions)]
-    lib.topolow_optimize_layout_exact.restype = C.c_int
-    lib.topolow_optimize_layout_exact.argtypes = [
-        dp, C.c_int32, C.c_int32, dp, ip, ip, ip, ip, dp, ip, C.c_int64,
-        C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
-        C.c_int32, C.POINTER(TopolowOptions), dp, ip, ip, dp, dp, C.POINTER(TopolowRunStats),
-        C.c_char_p, C.c_size_t]
-    lib.topolow_optimize_layout_exact_batch.restype = C.c_int
-    lib.topolow_optimize_layout_exact_batch.argtypes = [C.POINTER(TopolowProblem), C.POINTER(TopolowResult),
-                                                        C.c_int32, C.c_int32, C.c_int32, dp, C.c_char_p,
-                                                        C.c_size_t]
-    lib.topolow_cv_fold.restype = C.c_int
-    i64p = C.POINTER(C.c_int64)
-    lib.topolow_cv_fold.argtypes = [C.POINTER(TopolowCellList), i64p, C.c_int64, C.c_int32, C.c_int32, ip, ip,
-                                    ip, ip, dp, ip, i64p, ip, ip, dp, i64p, dp]
-    u64p = C.POINTER(C.c_uint64)
-    lib.topolow_cv_sweep.restype = C.c_int
-    lib.topolow_cv_sweep.argtypes = [C.POINTER(TopolowCellList), C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, i64p, i64p,
-                                     dp, i64p, u64p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                     dp, i64p, ip, ip, ip, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_cv_sweep_session.restype = C.c_int
-    lib.topolow_cv_sweep_session.argtypes = [C.POINTER(TopolowCellList), C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, i64p,
-                                             i64p, dp, i64p, u64p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_int32, C.c_int32, dp, i64p, ip, ip, ip, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_cv_fold_pairs.restype = C.c_int
-    lib.topolow_cv_fold_pairs.argtypes = [C.POINTER(TopolowCellList), i64p, C.c_int64, C.c_int32, C.c_int32, ip, ip, dp, i64p,
-                                          ip, ip, i64p, ip, ip, dp, i64p, C.c_char_p, C.c_size_t]
-    lib.topolow_batch_problem_fits.restype = C.c_int32
-    lib.topolow_batch_problem_fits.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64]
-    lib.topolow_session_hold_out.restype = C.c_int
-    lib.topolow_session_hold_out.argtypes = [C.c_void_p, ip, ip, C.c_int64, ip, C.c_char_p, C.c_size_t]
-    lib.topolow_session_restore_held_out.restype = C.c_int
-    lib.topolow_session_restore_held_out.argtypes = [C.c_void_p, ip, C.c_char_p, C.c_size_t]
-    lib.topolow_session_score_pairs.restype = C.c_int
-    lib.topolow_session_score_pairs.argtypes = [C.c_void_p, ip, ip, dp, C.c_int64, dp, i64p, C.c_char_p, C.c_size_t]
-    lib.topolow_session_profile_symmetric.restype = C.c_int
-    lib.topolow_session_profile_symmetric.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                                                      C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
-    lib.topolow_session_profile_fused.restype = C.c_int
-    lib.topolow_session_profile_fused.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_char_p,
-                                                  C.c_size_t]
-    lib.topolow_session_set_relabel.restype = C.c_int
-    lib.topolow_session_set_relabel.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
-    lib.topolow_session_labels.restype = C.c_int
-    lib.topolow_session_labels.argtypes = [C.c_void_p, ip]
-    lib.topolow_session_check_partial.restype = C.c_int
-    lib.topolow_session_check_partial.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
-    lib.topolow_session_can_fuse_checks.restype = C.c_int32
-    lib.topolow_session_can_fuse_checks.argtypes = [C.c_void_p]
-    lib.topolow_session_stage_fused.restype = C.c_int
-    lib.topolow_session_stage_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p,
-                                                C.c_char_p, C.c_size_t]
-    lib.topolow_session_controller_step.restype = C.c_int
-    lib.topolow_session_controller_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
-                                                    C.c_char_p, C.c_size_t]
-    lib.topolow_session_first_nonfinite.restype = C.c_int
-    lib.topolow_session_first_nonfinite.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    lib.topolow_shard_rows.restype = C.c_int32
-    lib.topolow_shard_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip]
-    lib.topolow_optimize_layout_exact_sharded.restype = C.c_int
-    lib.topolow_optimize_layout_exact_sharded.argtypes = [
-        dp, C.c_int32, C.c_int32, dp, ip, ip, ip, ip, dp, ip, C.c_int64,
-        C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
-        C.c_int32, C.POINTER(TopolowOptions), dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp,
-        C.POINTER(TopolowShardStats), C.c_char_p, C.c_size_t]
-    lib.topolow_sessions_run_sharded.restype = C.c_int
-    lib.topolow_sessions_run_sharded.argtypes = [
-        C.POINTER(C.c_void_p), C.c_int32, dp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
-        C.c_int32, C.c_int32, C.c_uint64, C.c_int32, INTERRUPT_CB, C.c_void_p, C.c_int32, dp,
-        C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, C.POINTER(TopolowShardStats), C.c_char_p, C.c_size_t]
-    lib.topolow_cell_list_index.restype = C.c_int
-    lib.topolow_cell_list_index.argtypes = [C.c_int32, C.c_int64, ip, ip, i64p, i64p, i64p]
-    lib.topolow_session_check_trace.restype = C.c_int
-    lib.topolow_session_check_trace.argtypes = [C.c_void_p, dp, C.c_int32, C.POINTER(C.c_int32)]
-    lib.topolow_est_distances.restype = C.c_int
-    lib.topolow_est_distances.argtypes = [dp, C.c_int32, C.c_int32, dp, C.c_int32, C.c_char_p,
-                                          C.c_size_t]
-    lib.topolow_est_distances_rows.restype = C.c_int
-    lib.topolow_est_distances_rows.argtypes = [dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32,
-                                               C.c_char_p, C.c_size_t]
-    lib.topolow_post_metrics.restype = C.c_int
-    lib.topolow_post_metrics.argtypes = [dp, C.c_int32, C.c_int32, dp, ip, dp, dp, i64p, C.c_int32, C.c_char_p,
-                                         C.c_size_t]
-    lib.topolow_post_metrics_ex.restype = C.c_int
-    lib.topolow_post_metrics_ex.argtypes = [dp, C.c_int32, C.c_int32, dp, ip, dp, dp, i64p, C.c_int32, C.c_int32, dp,
-                                            C.c_char_p, C.c_size_t]
-    lib.topolow_kernel_velocity.restype = C.c_int
-    lib.topolow_kernel_velocity.argtypes = [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, u64p, dp, dp,
-                                            C.c_int32, C.c_char_p, C.c_size_t]
-    lib.topolow_kernel_velocity_ex.restype = C.c_int
-    lib.topolow_kernel_velocity_ex.argtypes = [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, u64p, dp, dp,
-                                               C.c_int32, C.c_int32, dp, C.c_char_p, C.c_size_t]
-    vp = C.c_void_p
-    lib.topolow_session_create.restype = C.c_int
-    lib.topolow_session_create.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, C.c_int32,
-                                           C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]
-    lib.topolow_session_destroy.argtypes = [vp]
-    lib.topolow_session_destroy.restype = None
-    lib.topolow_session_load_dense.restype = C.c_int
-    lib.topolow_session_load_dense.argtypes = [vp, dp, ip, ip, C.c_char_p, C.c_size_t]
-    lib.topolow_session_load_coo.restype = C.c_int
-    lib.topolow_session_load_coo.argtypes = [vp, ip, ip, dp, ip, C.c_int64, ip, C.c_char_p,
-                                             C.c_size_t]
-    lib.topolow_symm_stage_bounds.restype = C.c_int32
-    lib.topolow_symm_stage_bounds.argtypes = [C.c_int32, C.c_int32, ip]
-    lib.topolow_symm_stage_order.restype = C.c_int32
-    lib.topolow_symm_stage_order.argtypes = [C.c_uint64, C.c_int32, C.c_int32, ip]
-    lib.topolow_symm_stage_rows.restype = C.c_int32
-    lib.topolow_symm_stage_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip]
-    lib.topolow_symm_plan.restype = C.c_int32
-    lib.topolow_symm_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, ip]
-    lib.topolow_session_symm_grid.restype = C.c_int32
-    lib.topolow_session_symm_grid.argtypes = [vp]
-    lib.topolow_symm_segment_rows.restype = C.c_int32
-    lib.topolow_symm_segment_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip]
-    lib.topolow_session_has_thresholds.restype = C.c_int32
-    lib.topolow_session_has_thresholds.argtypes = [vp]
-    lib.topolow_session_symm_segment_eligible.restype = C.c_int32
-    lib.topolow_session_symm_segment_eligible.argtypes = [vp, C.c_int32]
-    lib.topolow_session_can_fuse_segment_checks.restype = C.c_int32
-    lib.topolow_session_can_fuse_segment_checks.argtypes = [vp]
-    lib.topolow_session_wait.restype = C.c_int
-    lib.topolow_session_wait.argtypes = [vp, C.c_char_p, C.c_size_t]
-    lib.topolow_session_degree_terms.restype = vp
-    lib.topolow_session_degree_terms.argtypes = [vp]
-    lib.topolow_session_symm_moves.restype = vp
-    lib.topolow_session_symm_moves.argtypes = [vp]
-    lib.topolow_session_symm_segment_build.restype = C.c_int
-    lib.topolow_session_symm_segment_build.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32,
-                                                       C.c_char_p, C.c_size_t]
-    lib.topolow_session_symm_segment_sweep.restype = C.c_int
-    lib.topolow_session_symm_segment_sweep.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.c_char_p, C.c_size_t]
-    lib.topolow_session_symm_segment_apply.restype = C.c_int
-    lib.topolow_session_symm_segment_apply.argtypes = [vp, vp, vp, C.c_int32, C.c_char_p, C.c_size_t]
-    lib.topolow_session_encoded_ptr.restype = vp
-    lib.topolow_session_encoded_ptr.argtypes = [vp]
-    lib.topolow_session_encoded_ld.restype = C.c_int32
-    lib.topolow_session_encoded_ld.argtypes = [vp]
-    lib.topolow_session_commit_encoded.restype = C.c_int
-    lib.topolow_session_commit_encoded.argtypes = [vp, ip, C.c_char_p, C.c_size_t]
-    lib.topolow_session_set_edges.restype = C.c_int
-    lib.topolow_session_set_edges.argtypes = [vp, ip, ip, dp, ip, C.c_int64, C.c_char_p, C.c_size_t]
-    lib.topolow_session_set_positions.restype = C.c_int
-    lib.topolow_session_set_positions.argtypes = [vp, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_session_get_positions.restype = C.c_int
-    lib.topolow_session_get_positions.argtypes = [vp, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_session_begin.restype = C.c_int
-    lib.topolow_session_begin.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.c_double,
-                                          C.c_double, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
-                                          C.c_char_p, C.c_size_t]
-    lib.topolow_session_enqueue.restype = C.c_int
-    lib.topolow_session_enqueue.argtypes = [vp, C.c_int32, ip, C.c_char_p, C.c_size_t]
-    lib.topolow_session_sync.restype = C.c_int
-    lib.topolow_session_sync.argtypes = [vp, ip, ip, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_session_finish.restype = C.c_int
-    lib.topolow_session_finish.argtypes = [vp, dp, ip, ip, dp, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_session_set_profiling.restype = C.c_int
-    lib.topolow_session_set_profiling.argtypes = [vp, C.c_int32]
-    lib.topolow_session_profile.restype = C.c_int
-    lib.topolow_session_profile.argtypes = [vp, dp, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64),
-                                            C.c_char_p, C.c_size_t]
-    lib.topolow_session_set_stream.restype = C.c_int
-    lib.topolow_session_set_stream.argtypes = [vp, vp, C.c_int32]
-    lib.topolow_session_stream.restype = vp
-    lib.topolow_session_stream.argtypes = [vp]
-    lib.topolow_session_set_schedule.restype = C.c_int
-    lib.topolow_session_set_schedule.argtypes = [vp, C.c_int32]
-    lib.topolow_tilegs_pair_order.restype = C.c_int64
-    lib.topolow_tilegs_pair_order.argtypes = [C.c_int32, C.c_uint64, C.c_int32, ip]
-    lib.topolow_session_position_rows.restype = C.c_int32
-    lib.topolow_session_position_rows.argtypes = [vp]
-    lib.topolow_session_uses_dense_mae.restype = C.c_int32
-    lib.topolow_session_uses_dense_mae.argtypes = [vp]
-    lib.topolow_session_stage_launches.restype = C.c_int64
-    lib.topolow_session_stage_launches.argtypes = [vp]
-    lib.topolow_session_checks_in_apply.restype = C.c_int64
-    lib.topolow_session_checks_in_apply.argtypes = [vp]
-    lib.topolow_session_bytes_per_iteration.restype = C.c_int64
-    lib.topolow_session_bytes_per_iteration.argtypes = [vp]
-    lib.topolow_session_stage.restype = C.c_int
-    lib.topolow_session_stage.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double,
-                                          C.c_char_p, C.c_size_t]
-    lib.topolow_session_edge_error.restype = C.c_int
-    lib.topolow_session_edge_error.argtypes = [vp, vp, dp, C.POINTER(C.c_int64), C.c_char_p,
-                                               C.c_size_t]
-    lib.topolow_slab_plan.restype = C.c_int32
-    lib.topolow_slab_plan.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_int32, ip, C.c_int32]
-    lib.topolow_slab_stages_for_k.restype = C.c_int32
-    lib.topolow_slab_stages_for_k.argtypes = [C.c_double, C.c_int32]
-    lib.topolow_slab_stages_at.restype = C.c_int32
-    lib.topolow_slab_stages_at.argtypes = [C.c_int32, C.c_double, C.c_int32]
-    lib.topolow_gs_pair_order.restype = C.c_int64
-    lib.topolow_gs_pair_order.argtypes = [C.c_int32, C.c_uint64, C.c_int32, ip]
-    lib.topolow_encode_target.restype = C.c_uint32
-    lib.topolow_encode_target.argtypes = [C.c_double, C.c_int32]
-    lib.topolow_decode_target.restype = C.c_double
-    lib.topolow_decode_target.argtypes = [C.c_uint32, ip]
-    lib.topolow_controller_script.restype = C.c_int
-    lib.topolow_controller_script.argtypes = [dp, ip, dp, C.c_int32, C.c_double, C.c_int32,
-                                              C.c_double, ip, ip, dp, dp, ip]
-    i8p = C.POINTER(C.c_int8)
-    lib.topolow_layout_prep_create.restype = C.c_int
-    lib.topolow_layout_prep_create.argtypes = [C.POINTER(vp), dp, i8p, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32,
-                                               C.POINTER(TopolowLayoutPrepInfo), C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_fetch.restype = C.c_int
-    lib.topolow_layout_prep_fetch.argtypes = [vp, ip, ip, ip, ip, dp, ip, dp, ip, dp, i8p, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_destroy.restype = None
-    lib.topolow_layout_prep_destroy.argtypes = [vp]
-    lib.topolow_layout_prep_phase_seconds.restype = C.c_int
-    lib.topolow_layout_prep_phase_seconds.argtypes = [vp, dp]
-    lib.topolow_session_load_prepared.restype = C.c_int
-    lib.topolow_session_load_prepared.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_optimize.restype = C.c_int
-    lib.topolow_layout_prep_optimize.argtypes = [
-        vp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
-        C.POINTER(TopolowOptions), dp, ip, ip, dp, dp, C.POINTER(TopolowRunStats), C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_post_metrics.restype = C.c_int
-    lib.topolow_layout_prep_post_metrics.argtypes = [vp, dp, C.c_int32, dp, dp, i64p, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_order.restype = C.c_int
-    lib.topolow_layout_prep_order.argtypes = [vp, ip, ip]
-    lib.topolow_layout_prep_resident_seconds.restype = C.c_int
-    lib.topolow_layout_prep_resident_seconds.argtypes = [vp, dp]
-    lib.topolow_layout_prep_fold.restype = C.c_int
-    lib.topolow_layout_prep_fold.argtypes = [vp, i64p, C.c_int64, C.c_int32, C.c_int32, ip, ip, dp, i64p, ip, ip, i64p,
-                                             ip, ip, dp, i64p, ip, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_cv_sweep.restype = C.c_int
-    lib.topolow_layout_prep_cv_sweep.argtypes = [
-        vp, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, dp, i64p, i64p, dp, i64p, C.POINTER(C.c_uint64), C.c_int32,
-        C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, i64p, ip, ip, ip, ip, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_fold_seconds.restype = C.c_int
-    lib.topolow_layout_prep_fold_seconds.argtypes = [vp, dp]
-    lib.topolow_layout_prep_connectivity.restype = C.c_int
-    lib.topolow_layout_prep_connectivity.argtypes = [vp, ip, C.c_int32, ip, i64p, ip, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_subsample.restype = C.c_int
-    lib.topolow_layout_prep_subsample.argtypes = [vp, ip, C.c_int32, C.c_int32, ip, C.POINTER(vp),
-                                                  C.POINTER(TopolowLayoutPrepInfo), C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_graph_stats.restype = C.c_int
-    lib.topolow_layout_prep_graph_stats.argtypes = [vp, ip, dp]
-    lib.topolow_layout_prep_degrees.restype = C.c_int
-    lib.topolow_layout_prep_degrees.argtypes = [vp, ip, C.c_int32, ip, i64p, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_prune.restype = C.c_int
-    lib.topolow_layout_prep_prune.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
-                                              C.POINTER(TopolowPruneInfo), C.c_char_p, C.c_size_t]
-    lib.topolow_tridiagonal_eigenvalues.restype = C.c_int
-    lib.topolow_tridiagonal_eigenvalues.argtypes = [dp, dp, C.c_int32, C.c_int32, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_symmetric_eigenvalues.restype = C.c_int
-    lib.topolow_symmetric_eigenvalues.argtypes = [dp, C.c_int32, C.c_int32, dp, dp, dp, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_spectrum.restype = C.c_int
-    lib.topolow_layout_prep_spectrum.argtypes = [vp, dp, dp, C.POINTER(TopolowSpectrumInfo), C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_fit_report.restype = C.c_int
-    lib.topolow_layout_prep_fit_report.argtypes = [vp, dp, C.c_int32, i64p, C.c_int64, C.POINTER(TopolowFitReport),
-                                                   C.c_char_p, C.c_size_t]
-    lib.topolow_layout_prep_fit_order_stats.restype = C.c_int
-    lib.topolow_layout_prep_fit_order_stats.argtypes = [vp, dp, C.c_int32, i64p, C.c_int64, C.c_int32, i64p, C.c_int32, dp,
-                                                        i64p, C.c_char_p, C.c_size_t]
-    lib.topolow_layout_order_from_sums.restype = C.c_int32
-    lib.topolow_layout_order_from_sums.argtypes = [C.c_int32, dp, i64p, dp, i64p, C.c_int32, ip]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = lib
     return lib
 
 
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+_PTR = {np.dtype(t): p for t, p in ((np.float64, dp), (np.int32, ip), (np.int64, i64p), (np.uint64, u64p), (np.int8, i8p),
+                                    (np.uint8, u8p))}
 
 
-def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
+def _ptr(a):
+    """The typed pointer to an array's data, chosen by its dtype; None stays None (a NULL argument)."""
+    if a is None:
+        return None
+    if a.dtype not in _PTR:
+        raise TypeError(f"no pointer type for an array of {a.dtype}")
+    return a.ctypes.data_as(_PTR[a.dtype])
+
+
+_dp = _ip = _ptr   # thin names: tests/test_*_capi.py build their double / int32 arguments with them
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _u64(a):
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
 
 
 def _f64F(a):
@@ -456,9 +363,50 @@ def _i32F(a):
     return np.require(np.asarray(a, dtype=np.int32), requirements=["F", "A"])
 
 
-def _check(rc: int, err) -> None:
+def _check(rc: int, err=None) -> None:
     if rc != OK:
-        raise NativeError(rc, err.value.decode(errors="replace") or f"libtopolow_relax error {rc}")
+        message = err.value.decode(errors="replace") if err is not None else ""
+        raise NativeError(rc, message or f"libtopolow_relax error {rc}")
+
+
+def _call(fn, *args, err=None) -> None:
+    """Calls an entry that ends in `errbuf, errlen` (ERR in PROTOTYPES) and raises its message as a NativeError.
+    `err`: the buffer a Session / PreparedHandle owns; without one the call gets a fresh buffer."""
+    if err is None:
+        err = C.create_string_buffer(512)
+    _check(fn(*args, err, len(err)), err)
+
+
+def _fields(s) -> Dict[str, Any]:
+    """The fields of a ctypes struct as a dict, the reserved ones left out."""
+    return {k: getattr(s, k) for k, _ in s._fields_ if not k.startswith("reserved")}
+
+
+class _RunOut:
+    """The five outputs every relaxation entry ends with (positions_out, converged, iterations, final_mae, final_k):
+    `.args` go into the call, `.result(info)` reads them back.  positions=False: NULL, nothing is downloaded."""
+
+    def __init__(self, n, dim, positions=True):
+        self.out = np.zeros((n, dim), dtype=np.float64, order="F") if positions else None
+        self.conv, self.iters, self.fmae, self.fk = C.c_int32(0), C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
+        self.args = (_ptr(self.out), C.byref(self.conv), C.byref(self.iters), C.byref(self.fmae), C.byref(self.fk))
+
+    def result(self, info=None) -> "NativeResult":
+        return NativeResult(None if self.out is None else np.ascontiguousarray(self.out), bool(self.conv.value),
+                            int(self.iters.value), float(self.fmae.value), float(self.fk.value),
+                            {} if info is None else info)
+
+
+class _SumCount:
+    """k (double, int64) output pairs -- a (sum, count), a profile's (ms, launches) pairs: `.refs` go into the call,
+    `.values()` reads them back as one flat tuple."""
+
+    def __init__(self, k=1):
+        self.cells = [c for _ in range(k) for c in (C.c_double(0.0), C.c_int64(0))]
+        self.refs = [C.byref(c) for c in self.cells]
+
+    def values(self):
+        return tuple(c.value for c in self.cells)
 
 
 def make_options(**kw) -> TopolowOptions:
@@ -490,7 +438,7 @@ def make_options(**kw) -> TopolowOptions:
     devs = cfg.get("devices")
     if devs is not None:   # row-block sharded over these HIP ordinals (repeats allowed)
         o._dev_keepalive = (C.c_int32 * len(devs))(*[int(d) for d in devs])
-        o.devices = C.cast(o._dev_keepalive, C.POINTER(C.c_int32))
+        o.devices = C.cast(o._dev_keepalive, ip)
         o.n_devices = len(devs)
     return o
 
@@ -515,26 +463,15 @@ def optimize_layout_exact_arrays(initial_positions, dissimilarity_matrix, thresh
     n, dim = pos0.shape
     D = _f64F(dissimilarity_matrix)
     T = _i32F(threshold_matrix)
-    deg = np.ascontiguousarray(degrees, dtype=np.int32)
-    ei = np.ascontiguousarray(edge_i, dtype=np.int32)
-    ej = np.ascontiguousarray(edge_j, dtype=np.int32)
-    ed = np.ascontiguousarray(edge_dist, dtype=np.float64)
-    et = np.ascontiguousarray(edge_thresh, dtype=np.int32)
-    out = np.zeros((n, dim), dtype=np.float64, order="F")
-    conv, iters = C.c_int32(0), C.c_int32(0)
-    fmae, fk = C.c_double(0.0), C.c_double(0.0)
-    stats = TopolowRunStats()
-    err = C.create_string_buffer(512)
+    deg, ei, ej, ed, et = _i32(degrees), _i32(edge_i), _i32(edge_j), _f64(edge_dist), _i32(edge_thresh)
+    out, stats = _RunOut(n, dim), TopolowRunStats()
     opt = make_options(**opt_kw)
-    rc = lib.topolow_optimize_layout_exact(
-        _dp(pos0), n, dim, _dp(D), _ip(T), _ip(deg), _ip(ei), _ip(ej), _dp(ed), _ip(et),
-        int(ei.shape[0]), int(n_iter), float(k0), float(cooling_rate), float(c_repulsion),
-        float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
-        int(bool(verbose)), C.byref(opt), _dp(out), C.byref(conv), C.byref(iters), C.byref(fmae),
-        C.byref(fk), C.byref(stats), err, len(err))
-    _check(rc, err)
-    return NativeResult(np.ascontiguousarray(out), bool(conv.value), int(iters.value),
-                        float(fmae.value), float(fk.value), _run_info(stats, opt))
+    _call(lib.topolow_optimize_layout_exact,
+          _ptr(pos0), n, dim, _ptr(D), _ptr(T), _ptr(deg), _ptr(ei), _ptr(ej), _ptr(ed), _ptr(et),
+          int(ei.shape[0]), int(n_iter), float(k0), float(cooling_rate), float(c_repulsion),
+          float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
+          int(bool(verbose)), C.byref(opt), *out.args, C.byref(stats))
+    return out.result(_run_info(stats, opt))
 
 
 def _run_info(stats: TopolowRunStats, opt: TopolowOptions) -> Dict[str, Any]:
@@ -570,38 +507,29 @@ def optimize_layout_exact_batch(calls, seeds=None, precision="f64", device=-1, h
     for b, c in enumerate(calls):
         pos0 = _f64F(c.initial_positions)
         n, dim = pos0.shape
-        deg = np.ascontiguousarray(c.degrees, dtype=np.int32)
-        ei = np.ascontiguousarray(c.edge_i, dtype=np.int32)
-        ej = np.ascontiguousarray(c.edge_j, dtype=np.int32)
-        ed = np.ascontiguousarray(c.edge_dist, dtype=np.float64)
-        et = np.ascontiguousarray(c.edge_thresh, dtype=np.int32)
+        deg, ei, ej, ed, et = _i32(c.degrees), _i32(c.edge_i), _i32(c.edge_j), _f64(c.edge_dist), _i32(c.edge_thresh)
         out = np.zeros((n, dim), dtype=np.float64, order="F")
         p = probs[b]
         if c.dissimilarity_matrix is not None:
             D, T = _f64F(c.dissimilarity_matrix), _i32F(c.threshold_matrix)
-            p.dissimilarity_matrix, p.threshold_matrix = _dp(D), _ip(T)
+            p.dissimilarity_matrix, p.threshold_matrix = _ptr(D), _ptr(T)
             keep.append((D, T))
         keep.append((pos0, deg, ei, ej, ed, et))
         outs.append(out)
-        p.initial_positions = _dp(pos0)
-        p.degrees, p.edge_i, p.edge_j, p.edge_dist, p.edge_thresh = _ip(deg), _ip(ei), _ip(ej), _dp(ed), _ip(et)
+        p.initial_positions = _ptr(pos0)
+        p.degrees, p.edge_i, p.edge_j, p.edge_dist, p.edge_thresh = _ptr(deg), _ptr(ei), _ptr(ej), _ptr(ed), _ptr(et)
         p.n_edges, p.n, p.ndim, p.n_iter = int(ei.shape[0]), n, dim, int(c.n_iter)
         p.convergence_window, p.convergence_check_freq = int(c.convergence_window), int(c.convergence_check_freq)
         p.k0, p.cooling_rate, p.c_repulsion = float(c.k0), float(c.cooling_rate), float(c.c_repulsion)
         p.relative_epsilon = float(c.relative_epsilon)
         p.seed = int(seeds[b] if seeds is not None else _host_rng.integers(0, 2 ** 63 - 1)) & 0xFFFFFFFFFFFFFFFF
         if holdouts is not None and holdouts[b] is not None and len(holdouts[b][0]) > 0:
-            hi = np.ascontiguousarray(holdouts[b][0], dtype=np.int32)
-            hj = np.ascontiguousarray(holdouts[b][1], dtype=np.int32)
-            ht = np.ascontiguousarray(holdouts[b][2], dtype=np.float64)
+            hi, hj, ht = _i32(holdouts[b][0]), _i32(holdouts[b][1]), _f64(holdouts[b][2])
             keep.append((hi, hj, ht))
-            p.holdout_i, p.holdout_j, p.holdout_truth, p.n_holdout = _ip(hi), _ip(hj), _dp(ht), int(hi.shape[0])
-        ress[b].positions_out = _dp(out)
+            p.holdout_i, p.holdout_j, p.holdout_truth, p.n_holdout = _ptr(hi), _ptr(hj), _ptr(ht), int(hi.shape[0])
+        ress[b].positions_out = _ptr(out)
     secs = C.c_double(0.0)
-    err = C.create_string_buffer(512)
-    rc = lib.topolow_optimize_layout_exact_batch(probs, ress, count, _PRECISIONS[precision], int(device),
-                                                 C.byref(secs), err, len(err))
-    _check(rc, err)
+    _call(lib.topolow_optimize_layout_exact_batch, probs, ress, count, _PRECISIONS[precision], int(device), C.byref(secs))
     results = []
     for b in range(count):
         r = ress[b]
@@ -623,20 +551,15 @@ class CellList:
 
     def __init__(self, n, rows, cols, values, codes, pos_of):
         self.n = int(n)
-        self.rows = np.ascontiguousarray(rows, dtype=np.int32)
-        self.cols = np.ascontiguousarray(cols, dtype=np.int32)
-        self.values = np.ascontiguousarray(values, dtype=np.float64)
-        self.codes = np.ascontiguousarray(codes, dtype=np.int32)
-        self.pos_of = np.ascontiguousarray(pos_of, dtype=np.int64)
-        self.by_row = np.ascontiguousarray(np.lexsort((self.cols, self.rows)), dtype=np.int64)
+        self.rows, self.cols, self.values, self.codes = _i32(rows), _i32(cols), _f64(values), _i32(codes)
+        self.pos_of = _i64(pos_of)
+        self.by_row = _i64(np.lexsort((self.cols, self.rows)))
         counts = np.bincount(self.rows, minlength=self.n)
-        self.row_ptr = np.ascontiguousarray(np.concatenate([[0], np.cumsum(counts)]), dtype=np.int64)
+        self.row_ptr = _i64(np.concatenate([[0], np.cumsum(counts)]))
         c = self.c = TopolowCellList()
         c.n, c.n_cells = self.n, int(self.rows.shape[0])
-        c.row, c.col, c.value, c.code = _ip(self.rows), _ip(self.cols), _dp(self.values), _ip(self.codes)
-        i64 = C.POINTER(C.c_int64)
-        c.pos_of, c.by_row, c.row_ptr = (self.pos_of.ctypes.data_as(i64), self.by_row.ctypes.data_as(i64),
-                                         self.row_ptr.ctypes.data_as(i64))
+        c.row, c.col, c.value, c.code = _ptr(self.rows), _ptr(self.cols), _ptr(self.values), _ptr(self.codes)
+        c.pos_of, c.by_row, c.row_ptr = _ptr(self.pos_of), _ptr(self.by_row), _ptr(self.row_ptr)
 
 
 def cv_fold(cells: CellList, picks, preserve_order: bool, named: bool):
@@ -644,15 +567,15 @@ def cv_fold(cells: CellList, picks, preserve_order: bool, named: bool):
     (order or None, degrees, edge_i, edge_j, edge_dist, edge_thresh, hold_i, hold_j, hold_truth,
     numeric_max)."""
     lib = load()
-    picks = np.ascontiguousarray(picks, dtype=np.int64)
+    picks = _i64(picks)
     n, m = cells.n, int(cells.rows.shape[0])
     order, deg = np.empty(n, np.int32), np.empty(n, np.int32)
     ei, ej, ed, et = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m, np.float64), np.empty(m, np.int32)
     hi, hj, ht = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m, np.float64)
     ne, nh, vmax = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
-    rc = lib.topolow_cv_fold(C.byref(cells.c), picks.ctypes.data_as(C.POINTER(C.c_int64)), int(picks.shape[0]),
-                             int(bool(preserve_order)), int(bool(named)), _ip(order), _ip(deg), _ip(ei), _ip(ej),
-                             _dp(ed), _ip(et), C.byref(ne), _ip(hi), _ip(hj), _dp(ht), C.byref(nh), C.byref(vmax))
+    rc = lib.topolow_cv_fold(C.byref(cells.c), _ptr(picks), int(picks.shape[0]), int(bool(preserve_order)),
+                             int(bool(named)), _ptr(order), _ptr(deg), _ptr(ei), _ptr(ej), _ptr(ed), _ptr(et), C.byref(ne),
+                             _ptr(hi), _ptr(hj), _ptr(ht), C.byref(nh), C.byref(vmax))
     if rc != OK:
         raise NativeError(rc, "topolow_cv_fold failed")
     e, h = int(ne.value), int(nh.value)
@@ -665,29 +588,22 @@ def _cv_sweep_call(symbol, cells: CellList, named, preserve_order, ndims, k0s, c
     """The marshalling of cv_sweep, cv_sweep_session and PreparedHandle.cv_sweep (cells None: the callable brings its
     handle): `symbol` is the bound library entry, `extra` what it takes between `device` and the outputs."""
     nf = len(picks)
-    nd = np.ascontiguousarray(ndims, dtype=np.int32)
-    k0 = np.ascontiguousarray(k0s, dtype=np.float64)
-    cr = np.ascontiguousarray(cooling_rates, dtype=np.float64)
-    cp = np.ascontiguousarray(c_repulsions, dtype=np.float64)
+    nd, k0, cr, cp = _i32(ndims), _f64(k0s), _f64(cooling_rates), _f64(c_repulsions)
     p_off = np.zeros(nf + 1, dtype=np.int64)
     d_off = np.zeros(nf + 1, dtype=np.int64)
     if nf:
         np.cumsum([len(p) for p in picks], out=p_off[1:])
         np.cumsum([u.size for u in unit_draws], out=d_off[1:])
-    p_all = np.ascontiguousarray(np.concatenate(picks) if nf else np.zeros(0), dtype=np.int64)
-    d_all = np.ascontiguousarray(np.concatenate([np.ravel(u) for u in unit_draws]) if nf else np.zeros(0), dtype=np.float64)
-    sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+    p_all = _i64(np.concatenate(picks) if nf else np.zeros(0))
+    d_all = _f64(np.concatenate([np.ravel(u) for u in unit_draws]) if nf else np.zeros(0))
+    sd = _u64(seeds)
     hsum, hcnt = np.zeros(nf, np.float64), np.zeros(nf, np.int64)
     its, conv, ec = np.zeros(nf, np.int32), np.zeros(nf, np.int32), np.zeros(nf, np.int32)
     secs = C.c_double(0.0)
-    err = C.create_string_buffer(512)
-    i64 = C.POINTER(C.c_int64)
-    rc = symbol(C.byref(cells.c) if cells is not None else None, int(bool(named)), int(bool(preserve_order)), nf, _ip(nd), _dp(k0), _dp(cr), _dp(cp),
-                p_all.ctypes.data_as(i64), p_off.ctypes.data_as(i64), _dp(d_all), d_off.ctypes.data_as(i64),
-                sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(n_iter), float(relative_epsilon), int(convergence_window),
-                int(convergence_check_freq), _PRECISIONS[precision], int(device), *extra, _dp(hsum),
-                hcnt.ctypes.data_as(i64), _ip(its), _ip(conv), _ip(ec), C.byref(secs), err, len(err))
-    _check(rc, err)
+    _call(symbol, C.byref(cells.c) if cells is not None else None, int(bool(named)), int(bool(preserve_order)), nf,
+          _ptr(nd), _ptr(k0), _ptr(cr), _ptr(cp), _ptr(p_all), _ptr(p_off), _ptr(d_all), _ptr(d_off), _ptr(sd), int(n_iter),
+          float(relative_epsilon), int(convergence_window), int(convergence_check_freq), _PRECISIONS[precision],
+          int(device), *extra, _ptr(hsum), _ptr(hcnt), _ptr(its), _ptr(conv), _ptr(ec), C.byref(secs))
     return hsum, hcnt, its, conv, ec, float(secs.value)
 
 
@@ -705,18 +621,20 @@ def cv_sweep(cells: CellList, named: bool, preserve_order: bool, ndims, k0s, coo
 def cv_fold_pairs(cells: CellList, picks, preserve_order: bool, named: bool):
     """One fold as a resident session holds it out (topolow_cv_fold_pairs): everything in the caller's labels, no edge
     list.  Returns (order or None, degrees, numeric_max, n_edges, (pair_i, pair_j), (score_i, score_j, score_truth))."""
-    lib = load()
-    picks = np.ascontiguousarray(picks, dtype=np.int64)
-    n, k = cells.n, int(picks.shape[0])
+    return _fold_pairs_call(load().topolow_cv_fold_pairs, C.byref(cells.c), cells.n, picks, preserve_order, named)
+
+
+def _fold_pairs_call(fn, source, n, picks, preserve_order, named, *tail, err=None):
+    """The marshalling of cv_fold_pairs and PreparedHandle.fold: `source` is the cell list or the handle, `tail` what
+    the entry takes between the shared outputs and the error buffer."""
+    picks = _i64(picks)
+    k = int(picks.shape[0])
     order, deg = np.empty(n, np.int32), np.empty(n, np.int32)
     pi, pj = np.empty(max(k, 1), np.int32), np.empty(max(k, 1), np.int32)
     si, sj, st = np.empty(max(2 * k, 1), np.int32), np.empty(max(2 * k, 1), np.int32), np.empty(max(2 * k, 1), np.float64)
     ne, npair, ns, vmax = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
-    err = C.create_string_buffer(512)
-    _check(lib.topolow_cv_fold_pairs(C.byref(cells.c), picks.ctypes.data_as(C.POINTER(C.c_int64)), k,
-                                     int(bool(preserve_order)), int(bool(named)), _ip(order), _ip(deg), C.byref(vmax),
-                                     C.byref(ne), _ip(pi), _ip(pj), C.byref(npair), _ip(si), _ip(sj), _dp(st), C.byref(ns),
-                                     err, len(err)), err)
+    _call(fn, source, _ptr(picks), k, int(bool(preserve_order)), int(bool(named)), _ptr(order), _ptr(deg), C.byref(vmax),
+          C.byref(ne), _ptr(pi), _ptr(pj), C.byref(npair), _ptr(si), _ptr(sj), _ptr(st), C.byref(ns), *tail, err=err)
     p, q = int(npair.value), int(ns.value)
     return (None if order[0] < 0 else order.astype(np.int64), deg, float(vmax.value), int(ne.value),
             (pi[:p].copy(), pj[:p].copy()), (si[:q].copy(), sj[:q].copy(), st[:q].copy()))
@@ -742,13 +660,13 @@ def cv_sweep_session(cells: CellList, named: bool, preserve_order: bool, ndims, 
 def symm_stage_bounds(n: int, stages: int):
     """Slab boundaries (labels) of the symmetric form of an S-stage iteration, or None (topolow_symm_stage_bounds)."""
     out = np.zeros(stages + 1, dtype=np.int32)
-    return out.tolist() if load().topolow_symm_stage_bounds(int(n), int(stages), _ip(out)) else None
+    return out.tolist() if load().topolow_symm_stage_bounds(int(n), int(stages), _ptr(out)) else None
 
 
 def symm_stage_order(seed: int, it: int, stages: int):
     """Order of the stages of iteration `it` (topolow_symm_stage_order)."""
     out = np.zeros(stages, dtype=np.int32)
-    assert load().topolow_symm_stage_order(C.c_uint64(seed), int(it), int(stages), _ip(out))
+    assert load().topolow_symm_stage_order(C.c_uint64(seed), int(it), int(stages), _ptr(out))
     return out.tolist()
 
 
@@ -761,7 +679,7 @@ def symm_stage_rows(n: int, stages: int, stage: int):
     if tr < 0:
         return None
     out = np.zeros((tr, 4), dtype=np.int32)
-    assert lib.topolow_symm_stage_rows(int(n), int(stages), int(stage), _ip(out)) == tr
+    assert lib.topolow_symm_stage_rows(int(n), int(stages), int(stage), _ptr(out)) == tr
     return out
 
 
@@ -776,7 +694,7 @@ def symm_plan(n: int, n_waves: int, stages: int = 0, stage: int = 0, segment: in
         raise ValueError("symm_plan: no such plan for %r" % (args,))
     units = np.zeros((n_units, 4), dtype=np.int32)
     wave_first = np.zeros(int(n_waves) + 1, dtype=np.int32)
-    assert lib.topolow_symm_plan(*args, _ip(units), n_units, _ip(wave_first)) == n_units
+    assert lib.topolow_symm_plan(*args, _ptr(units), n_units, _ptr(wave_first)) == n_units
     return units, wave_first
 
 
@@ -813,30 +731,19 @@ def optimize_layout_exact_sharded(initial_positions, degrees, edge_i, edge_j, ed
     n, dim = pos0.shape
     D = _f64F(dissimilarity_matrix) if dissimilarity_matrix is not None else None
     T = _i32F(threshold_matrix) if threshold_matrix is not None else None
-    deg = np.ascontiguousarray(degrees, dtype=np.int32)
-    ei = np.ascontiguousarray(edge_i, dtype=np.int32)
-    ej = np.ascontiguousarray(edge_j, dtype=np.int32)
-    ed = np.ascontiguousarray(edge_dist, dtype=np.float64)
-    et = np.ascontiguousarray(edge_thresh, dtype=np.int32)
-    out = np.zeros((n, dim), dtype=np.float64, order="F")
-    conv, iters = C.c_int32(0), C.c_int32(0)
-    fmae, fk = C.c_double(0.0), C.c_double(0.0)
-    stats = TopolowShardStats()
-    err = C.create_string_buffer(512)
+    deg, ei, ej, ed, et = _i32(degrees), _i32(edge_i), _i32(edge_j), _f64(edge_dist), _i32(edge_thresh)
+    out, stats = _RunOut(n, dim), TopolowShardStats()
     opt = make_options(devices=list(devices), **opt_kw)
-    rc = lib.topolow_optimize_layout_exact_sharded(
-        _dp(pos0), n, dim, _dp(D) if D is not None else None, _ip(T) if T is not None else None, _ip(deg),
-        _ip(ei), _ip(ej), _dp(ed), _ip(et), int(ei.shape[0]), int(n_iter), float(k0), float(cooling_rate),
-        float(c_repulsion), float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
-        int(bool(verbose)), C.byref(opt), _dp(out), C.byref(conv), C.byref(iters), C.byref(fmae), C.byref(fk),
-        C.byref(stats), err, len(err))
-    _check(rc, err)
-    info = dict(schedule="slab", blocks=stats.blocks, groups=stats.groups, iterations_run=stats.iterations_run,
-                n_checks=stats.n_checks, loop_seconds=stats.loop_seconds, total_seconds=stats.total_seconds,
-                stage_kernel_seconds=stats.stage_kernel_seconds, check_kernel_seconds=stats.check_kernel_seconds,
-                stage_launches=stats.stage_launches, exchanges=stats.exchanges, seed=int(opt.seed))
-    return NativeResult(np.ascontiguousarray(out), bool(conv.value), int(iters.value), float(fmae.value),
-                        float(fk.value), info)
+    _call(lib.topolow_optimize_layout_exact_sharded,
+          _ptr(pos0), n, dim, _ptr(D), _ptr(T), _ptr(deg), _ptr(ei), _ptr(ej), _ptr(ed), _ptr(et), int(ei.shape[0]),
+          int(n_iter), float(k0), float(cooling_rate), float(c_repulsion), float(relative_epsilon),
+          int(convergence_window), int(convergence_check_freq), int(bool(verbose)), C.byref(opt), *out.args,
+          C.byref(stats))
+    return out.result(dict(
+        schedule="slab", blocks=stats.blocks, groups=stats.groups, iterations_run=stats.iterations_run,
+        n_checks=stats.n_checks, loop_seconds=stats.loop_seconds, total_seconds=stats.total_seconds,
+        stage_kernel_seconds=stats.stage_kernel_seconds, check_kernel_seconds=stats.check_kernel_seconds,
+        stage_launches=stats.stage_launches, exchanges=stats.exchanges, seed=int(opt.seed)))
 
 
 def run_sharded(sessions, initial_positions, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon=1e-4,
@@ -848,26 +755,17 @@ def run_sharded(sessions, initial_positions, n_iter, k0, cooling_rate, c_repulsi
     pos0 = _f64F(initial_positions)
     n, dim = pos0.shape
     hs = (C.c_void_p * len(sessions))(*[s._h for s in sessions])
-    out = np.zeros((n, dim), dtype=np.float64, order="F")
-    conv, iters = C.c_int32(0), C.c_int32(0)
-    fmae, fk = C.c_double(0.0), C.c_double(0.0)
-    stats = TopolowShardStats()
+    out, stats = _RunOut(n, dim), TopolowShardStats()
     stats.warmup_iterations = int(warmup_iterations)   # measurement aid: timed_seconds starts after these
-    err = C.create_string_buffer(512)
     cb = INTERRUPT_CB(lambda _u: 1 if interrupt() else 0) if interrupt is not None else INTERRUPT_CB()
-    rc = lib.topolow_sessions_run_sharded(hs, len(sessions), _dp(pos0), int(n_iter), float(k0), float(cooling_rate),
-                                          float(c_repulsion), float(relative_epsilon), int(convergence_window),
-                                          int(convergence_check_freq), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                          int(slab_stages), cb, None, int(bool(profile)), _dp(out), C.byref(conv),
-                                          C.byref(iters), C.byref(fmae), C.byref(fk), C.byref(stats), err, len(err))
-    _check(rc, err)
-    info = dict(schedule="slab", blocks=stats.blocks, groups=stats.groups, iterations_run=stats.iterations_run,
-                n_checks=stats.n_checks, loop_seconds=stats.loop_seconds, stage_kernel_seconds=stats.stage_kernel_seconds,
-                check_kernel_seconds=stats.check_kernel_seconds, stage_launches=stats.stage_launches,
-                exchanges=stats.exchanges, timed_seconds=stats.timed_seconds,
-                symmetric_segments=stats.symmetric_segments)
-    return NativeResult(np.ascontiguousarray(out), bool(conv.value), int(iters.value), float(fmae.value),
-                        float(fk.value), info)
+    _call(lib.topolow_sessions_run_sharded, hs, len(sessions), _ptr(pos0), int(n_iter), float(k0), float(cooling_rate),
+          float(c_repulsion), float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
+          int(seed) & 0xFFFFFFFFFFFFFFFF, int(slab_stages), cb, None, int(bool(profile)), *out.args, C.byref(stats))
+    return out.result(dict(
+        schedule="slab", blocks=stats.blocks, groups=stats.groups, iterations_run=stats.iterations_run,
+        n_checks=stats.n_checks, loop_seconds=stats.loop_seconds, stage_kernel_seconds=stats.stage_kernel_seconds,
+        check_kernel_seconds=stats.check_kernel_seconds, stage_launches=stats.stage_launches,
+        exchanges=stats.exchanges, timed_seconds=stats.timed_seconds, symmetric_segments=stats.symmetric_segments))
 
 
 def est_distances(positions) -> np.ndarray:
@@ -876,10 +774,7 @@ def est_distances(positions) -> np.ndarray:
     pos = _f64F(positions)
     n, dim = pos.shape
     out = np.empty((n, n), dtype=np.float64)
-    err = C.create_string_buffer(512)
-    rc = lib.topolow_est_distances(_dp(pos), n, dim, _dp(out), int(options.get("device", -1)),
-                                   err, len(err))
-    _check(rc, err)
+    _call(lib.topolow_est_distances, _ptr(pos), n, dim, _ptr(out), int(options.get("device", -1)))
     return out
 
 
@@ -889,10 +784,8 @@ def est_distances_rows(positions, row_begin: int, row_end: int) -> np.ndarray:
     pos = _f64F(positions)
     n, dim = pos.shape
     out = np.empty((int(row_end) - int(row_begin), n), dtype=np.float64)
-    err = C.create_string_buffer(512)
-    rc = lib.topolow_est_distances_rows(_dp(pos), n, dim, int(row_begin), int(row_end), _dp(out),
-                                        int(options.get("device", -1)), err, len(err))
-    _check(rc, err)
+    _call(lib.topolow_est_distances_rows, _ptr(pos), n, dim, int(row_begin), int(row_end), _ptr(out),
+          int(options.get("device", -1)))
     return out
 
 
@@ -932,17 +825,13 @@ def post_metrics(positions, values, codes=None, want_est: bool = True, staging: 
         if cds.shape != (n, n):
             raise ValueError("codes must have the shape of values")
     est = np.empty((n, n), dtype=np.float64) if want_est else None
-    s, c = C.c_double(0.0), C.c_int64(0)
+    sc = _SumCount()
     ph = (C.c_double * 3)()
-    err = C.create_string_buffer(512)
-    rc = lib.topolow_post_metrics_ex(_dp(pos), n, dim, _dp(vals), _ip(cds) if cds is not None else None,
-                                     _dp(est) if est is not None else None, C.byref(s), C.byref(c),
-                                     int(options.get("device", -1)), POST_STAGINGS[staging],
-                                     ph if phases is not None else None, err, len(err))
-    _check(rc, err)
+    _call(lib.topolow_post_metrics_ex, _ptr(pos), n, dim, _ptr(vals), _ptr(cds), _ptr(est), *sc.refs,
+          int(options.get("device", -1)), POST_STAGINGS[staging], ph if phases is not None else None)
     if phases is not None:
         phases[:] = [ph[0], ph[1], ph[2]]
-    return est, float(s.value), int(c.value)
+    return (est, *sc.values())
 
 
 def kernel_velocity(positions, times, sigma_t: float, sigma_x: float, excluded_bits=None, device: Optional[int] = None,
@@ -958,28 +847,23 @@ def kernel_velocity(positions, times, sigma_t: float, sigma_x: float, excluded_b
     if pos.ndim != 2:
         raise ValueError("positions must be an n x ndim matrix")
     n, dim = pos.shape
-    t = np.ascontiguousarray(times, dtype=np.float64)
+    t = _f64(times)
     if t.shape != (n,):
         raise ValueError("times must hold one value per position")
     bits = None
     if excluded_bits is not None:
-        bits = np.ascontiguousarray(excluded_bits, dtype=np.uint64)
+        bits = _u64(excluded_bits)
         if bits.shape != (n, (n + 63) // 64):
             raise ValueError("excluded_bits must be an n x ceil(n / 64) array of 64-bit words")
     vel = np.empty((n, dim), dtype=np.float64, order="F")
     w = np.empty(n, dtype=np.float64)
     secs = C.c_double(0.0)
-    err = C.create_string_buffer(512)
     dev = int(options.get("device", -1)) if device is None else int(device)
-    bp = bits.ctypes.data_as(C.POINTER(C.c_uint64)) if bits is not None else None
+    shared = (_ptr(pos), _ptr(t), n, dim, float(sigma_t), float(sigma_x), _ptr(bits), _ptr(vel), _ptr(w), dev)
     if chunk_cols is None and timing is None:
-        rc = lib.topolow_kernel_velocity(_dp(pos), _dp(t), n, dim, float(sigma_t), float(sigma_x), bp, _dp(vel),
-                                         _dp(w), dev, err, len(err))
+        _call(lib.topolow_kernel_velocity, *shared)
     else:
-        rc = lib.topolow_kernel_velocity_ex(_dp(pos), _dp(t), n, dim, float(sigma_t), float(sigma_x), bp, _dp(vel),
-                                            _dp(w), dev, int(chunk_cols or 0),
-                                            C.byref(secs) if timing is not None else None, err, len(err))
-    _check(rc, err)
+        _call(lib.topolow_kernel_velocity_ex, *shared, int(chunk_cols or 0), C.byref(secs) if timing is not None else None)
     if timing is not None:
         timing[:] = [secs.value]
     return vel, w
@@ -1010,13 +894,10 @@ class PreparedLayout:
 def order_from_sums(row_sum, row_cnt, col_sum, col_cnt, exact_sums: int):
     """topolow_layout_order_from_sums: (route, order or None).  Host only."""
     lib = load()
-    rs, cs = np.ascontiguousarray(row_sum, dtype=np.float64), np.ascontiguousarray(col_sum, dtype=np.float64)
-    rc_, cc = np.ascontiguousarray(row_cnt, dtype=np.int64), np.ascontiguousarray(col_cnt, dtype=np.int64)
+    rs, cs, rc_, cc = _f64(row_sum), _f64(col_sum), _i64(row_cnt), _i64(col_cnt)
     n = rs.shape[0]
     order = np.empty(max(n, 1), dtype=np.int32)
-    i64p = C.POINTER(C.c_int64)
-    route = lib.topolow_layout_order_from_sums(n, _dp(rs), rc_.ctypes.data_as(i64p), _dp(cs), cc.ctypes.data_as(i64p),
-                                               int(exact_sums), _ip(order))
+    route = lib.topolow_layout_order_from_sums(n, _ptr(rs), _ptr(rc_), _ptr(cs), _ptr(cc), int(exact_sums), _ptr(order))
     return int(route), (None if order[0] == -1 else order[:n])
 
 
@@ -1037,8 +918,7 @@ class PreparedHandle:
 
     def __init__(self, values, codes=None, preserve_order: bool = False, order=None, layout: Optional[str] = None,
                  device: Optional[int] = None):
-        self.lib = load()
-        self._h = C.c_void_p(None)
+        self._blank()
         vals = np.asarray(values)
         if vals.ndim != 2 or vals.shape[0] != vals.shape[1]:
             raise ValueError("values must be an n x n matrix")
@@ -1054,20 +934,19 @@ class PreparedHandle:
                 raise ValueError("codes must have the shape of values")
         oin = None
         if order is not None:
-            oin = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+            oin = _i32(order).reshape(-1)
             if oin.shape[0] != n and not (oin.shape[0] >= 1 and oin[0] == -1):
                 raise ValueError("order must have n entries")
         self.n, self.layout, self.has_codes = int(n), layout, cds is not None
-        i8p = C.POINTER(C.c_int8)
         info = TopolowLayoutPrepInfo()
-        self._err = C.create_string_buffer(512)
-        rc = self.lib.topolow_layout_prep_create(
-            C.byref(self._h), _dp(vals), cds.ctypes.data_as(i8p) if cds is not None else None, n,
-            1 if layout == "C" else 0, 1 if preserve_order else 0, _ip(oin) if oin is not None else None,
-            int(options.get("device", -1)) if device is None else int(device), C.byref(info), self._err, len(self._err))
-        _check(rc, self._err)
-        self.info = {k: getattr(info, k) for k, _ in TopolowLayoutPrepInfo._fields_ if k != "reserved"}
-        self._order = None
+        _call(self.lib.topolow_layout_prep_create, C.byref(self._h), _ptr(vals), _ptr(cds), n, 1 if layout == "C" else 0,
+              1 if preserve_order else 0, _ptr(oin), int(options.get("device", -1)) if device is None else int(device),
+              C.byref(info), err=self._err)
+        self.info = _fields(info)
+
+    def _blank(self):
+        """A handle before the library has filled it: the constructor and .subsample start from it."""
+        self.lib, self._h, self._err, self._order = load(), C.c_void_p(None), C.create_string_buffer(512), None
 
     @property
     def declined(self) -> bool:
@@ -1081,7 +960,7 @@ class PreparedHandle:
             return None
         if self._order is None:
             o = np.empty(self.n, dtype=np.int32)
-            if self.lib.topolow_layout_prep_order(self._h, _ip(o), None) != OK:
+            if self.lib.topolow_layout_prep_order(self._h, _ptr(o), None) != OK:
                 raise NativeError(ERR_BAD_ARGUMENT, "topolow_layout_prep_order refused the handle")
             self._order = o
         return self._order
@@ -1092,7 +971,6 @@ class PreparedHandle:
         if self.declined:
             return out
         n, layout = self.n, self.layout
-        i8p = C.POINTER(C.c_int8)
         E = int(self.info["n_edges"])
         o = np.empty(n, dtype=np.int32)
         out.degrees = np.empty(n, dtype=np.int32)
@@ -1105,12 +983,9 @@ class PreparedHandle:
         if want_reordered:
             out.values_reordered = np.empty((n, n), dtype=np.float64, order=layout)
             out.codes_reordered = np.empty((n, n), dtype=np.int8, order=layout)
-        rc = self.lib.topolow_layout_prep_fetch(
-            self._h, _ip(o), _ip(out.degrees), _ip(out.edge_i), _ip(out.edge_j), _dp(out.edge_dist), _ip(out.edge_thresh),
-            _dp(out.dense) if want_dense else None, _ip(out.tdense) if want_dense else None,
-            _dp(out.values_reordered) if want_reordered else None,
-            out.codes_reordered.ctypes.data_as(i8p) if want_reordered else None, self._err, len(self._err))
-        _check(rc, self._err)
+        _call(self.lib.topolow_layout_prep_fetch, self._h, _ptr(o), _ptr(out.degrees), _ptr(out.edge_i), _ptr(out.edge_j),
+              _ptr(out.edge_dist), _ptr(out.edge_thresh), _ptr(out.dense), _ptr(out.tdense), _ptr(out.values_reordered),
+              _ptr(out.codes_reordered), err=self._err)
         out.order = None if o[0] == -1 else o
         out.phase_seconds = self.phase_seconds()
         return out
@@ -1125,19 +1000,12 @@ class PreparedHandle:
         n, dim = pos0.shape
         if n != self.n or (ndim is not None and int(ndim) != dim):
             raise ValueError("initial_positions must be n x ndim")
-        out = np.zeros((n, dim), dtype=np.float64, order="F")
-        conv, iters = C.c_int32(0), C.c_int32(0)
-        fmae, fk = C.c_double(0.0), C.c_double(0.0)
-        stats = TopolowRunStats()
+        out, stats = _RunOut(n, dim), TopolowRunStats()
         opt = make_options(**opt_kw)
-        rc = self.lib.topolow_layout_prep_optimize(
-            self._h, _dp(pos0), dim, int(n_iter), float(k0), float(cooling_rate), float(c_repulsion),
-            float(relative_epsilon), int(convergence_window), int(convergence_check_freq), int(bool(verbose)),
-            C.byref(opt), _dp(out), C.byref(conv), C.byref(iters), C.byref(fmae), C.byref(fk), C.byref(stats),
-            self._err, len(self._err))
-        _check(rc, self._err)
-        return NativeResult(np.ascontiguousarray(out), bool(conv.value), int(iters.value), float(fmae.value),
-                            float(fk.value), _run_info(stats, opt))
+        _call(self.lib.topolow_layout_prep_optimize, self._h, _ptr(pos0), dim, int(n_iter), float(k0), float(cooling_rate),
+              float(c_repulsion), float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
+              int(bool(verbose)), C.byref(opt), *out.args, C.byref(stats), err=self._err)
+        return out.result(_run_info(stats, opt))
 
     def post_metrics(self, positions, want_est: bool = True):
         """topolow_layout_prep_post_metrics: (est_distances or None, sum_abs, count) of the handle's resident matrix,
@@ -1147,31 +1015,19 @@ class PreparedHandle:
         if n != self.n:
             raise ValueError("positions must have one row per point")
         est = np.empty((n, n), dtype=np.float64) if want_est else None
-        s, c = C.c_double(0.0), C.c_int64(0)
-        rc = self.lib.topolow_layout_prep_post_metrics(self._h, _dp(pos), dim, _dp(est) if est is not None else None,
-                                                       C.byref(s), C.byref(c), self._err, len(self._err))
-        _check(rc, self._err)
-        return est, float(s.value), int(c.value)
+        sc = _SumCount()
+        _call(self.lib.topolow_layout_prep_post_metrics, self._h, _ptr(pos), dim, _ptr(est), *sc.refs, err=self._err)
+        return (est, *sc.values())
 
     def fold(self, picks, preserve_order: bool, named: bool):
         """One cross-validation fold prepared on the device (topolow_layout_prep_fold): what cv_fold_pairs computes from
         the cell list, from the resident matrix.  Returns (order or None, degrees, numeric_max, n_edges, (pair_i, pair_j),
         (score_i, score_j, score_truth), order_route); the pairs are cv_fold_pairs' as a set (sorted by (j, i)), everything
         else is equal to it.  order_route == ORDER_DECLINED: the order is the caller's to compute (None is returned)."""
-        picks = np.ascontiguousarray(picks, dtype=np.int64)
-        n, k = self.n, int(picks.shape[0])
-        order, deg = np.empty(n, np.int32), np.empty(n, np.int32)
-        pi, pj = np.empty(max(k, 1), np.int32), np.empty(max(k, 1), np.int32)
-        si, sj, st = np.empty(max(2 * k, 1), np.int32), np.empty(max(2 * k, 1), np.int32), np.empty(max(2 * k, 1), np.float64)
-        ne, npair, ns, vmax, route = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0.0), C.c_int32(0)
-        rc = self.lib.topolow_layout_prep_fold(
-            self._h, picks.ctypes.data_as(C.POINTER(C.c_int64)), k, int(bool(preserve_order)), int(bool(named)), _ip(order),
-            _ip(deg), C.byref(vmax), C.byref(ne), _ip(pi), _ip(pj), C.byref(npair), _ip(si), _ip(sj), _dp(st), C.byref(ns),
-            C.byref(route), self._err, len(self._err))
-        _check(rc, self._err)
-        p, q = int(npair.value), int(ns.value)
-        return (None if order[0] < 0 else order.astype(np.int64), deg, float(vmax.value), int(ne.value),
-                (pi[:p].copy(), pj[:p].copy()), (si[:q].copy(), sj[:q].copy(), st[:q].copy()), int(route.value))
+        route = C.c_int32(0)
+        out = _fold_pairs_call(self.lib.topolow_layout_prep_fold, self._h, self.n, picks, preserve_order, named,
+                               C.byref(route), err=self._err)
+        return out + (int(route.value),)
 
     def cv_sweep(self, named: bool, preserve_order: bool, ndims, k0s, cooling_rates, c_repulsions, picks, unit_draws, seeds,
                  n_iter: int, relative_epsilon: float, convergence_window: int = 5, convergence_check_freq: int = 3,
@@ -1188,7 +1044,7 @@ class PreparedHandle:
                    prec, device, sched, *outs):
             return self.lib.topolow_layout_prep_cv_sweep(self._h, named_, preserve_, nf_, nd, k0, cr, cp, p_all, p_off, d_all,
                                                          d_off, sd, n_iter_, eps, window, freq, prec, sched, *outs[:5],
-                                                         _ip(route), *outs[5:])
+                                                         _ptr(route), *outs[5:])
         out = _cv_sweep_call(symbol, None, named, preserve_order, ndims, k0s, cooling_rates, c_repulsions, picks, unit_draws,
                              seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq, precision, -1,
                              _SCHEDULES[schedule])
@@ -1198,7 +1054,7 @@ class PreparedHandle:
         """`indices` as the C entries take a subset: (int32 array or None, m).  None: all n points."""
         if indices is None:
             return None, self.n
-        sub = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        sub = _i32(indices).reshape(-1)
         return sub, int(sub.shape[0])
 
     def connectivity(self, subset=None):
@@ -1209,9 +1065,8 @@ class PreparedHandle:
         sub, m = self._subset(subset)
         labels = np.empty(m, dtype=np.int32)
         nc, cells = C.c_int32(0), C.c_int64(0)
-        rc = self.lib.topolow_layout_prep_connectivity(self._h, _ip(sub) if sub is not None else None, m, C.byref(nc),
-                                                       C.byref(cells), _ip(labels), self._err, len(self._err))
-        _check(rc, self._err)
+        _call(self.lib.topolow_layout_prep_connectivity, self._h, _ptr(sub), m, C.byref(nc), C.byref(cells), _ptr(labels),
+              err=self._err)
         return int(nc.value), int(cells.value), labels
 
     def subsample(self, indices, preserve_order: bool = False, order_in=None) -> "PreparedHandle":
@@ -1222,18 +1077,16 @@ class PreparedHandle:
         sub, m = self._subset(indices)
         oin = None
         if order_in is not None:
-            oin = np.ascontiguousarray(order_in, dtype=np.int32).reshape(-1)
+            oin = _i32(order_in).reshape(-1)
             if oin.shape[0] != m and not (oin.shape[0] >= 1 and oin[0] == -1):
                 raise ValueError("order must have one entry per selected point")
         child = PreparedHandle.__new__(PreparedHandle)
-        child.lib, child._h, child._err, child._order = self.lib, C.c_void_p(None), C.create_string_buffer(512), None
+        child._blank()
         child.n, child.layout, child.has_codes = m, self.layout, self.has_codes
         info = TopolowLayoutPrepInfo()
-        rc = self.lib.topolow_layout_prep_subsample(
-            self._h, _ip(sub) if sub is not None else None, m, 1 if preserve_order else 0,
-            _ip(oin) if oin is not None else None, C.byref(child._h), C.byref(info), child._err, len(child._err))
-        _check(rc, child._err)
-        child.info = {k: getattr(info, k) for k, _ in TopolowLayoutPrepInfo._fields_ if k != "reserved"}
+        _call(self.lib.topolow_layout_prep_subsample, self._h, _ptr(sub), m, 1 if preserve_order else 0, _ptr(oin),
+              C.byref(child._h), C.byref(info), err=child._err)
+        child.info = _fields(info)
         return child
 
     def degrees(self, subset=None):
@@ -1243,9 +1096,7 @@ class PreparedHandle:
         sub, m = self._subset(subset)
         deg = np.empty(m, dtype=np.int32)
         cells = C.c_int64(0)
-        rc = self.lib.topolow_layout_prep_degrees(self._h, _ip(sub) if sub is not None else None, m, _ip(deg),
-                                                  C.byref(cells), self._err, len(self._err))
-        _check(rc, self._err)
+        _call(self.lib.topolow_layout_prep_degrees, self._h, _ptr(sub), m, _ptr(deg), C.byref(cells), err=self._err)
         return deg, int(cells.value)
 
     def prune(self, min_connections=4, target_completeness=None, max_iterations=100, min_points=10):
@@ -1258,11 +1109,9 @@ class PreparedHandle:
 
         kept = np.zeros(self.n, dtype=np.uint8)
         info = TopolowPruneInfo()
-        rc = self.lib.topolow_layout_prep_prune(
-            self._h, as_i32(min_connections), float("nan") if target_completeness is None else float(target_completeness),
-            as_i32(max_iterations), as_i32(min_points), kept.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info),
-            self._err, len(self._err))
-        _check(rc, self._err)
+        _call(self.lib.topolow_layout_prep_prune, self._h, as_i32(min_connections),
+              float("nan") if target_completeness is None else float(target_completeness), as_i32(max_iterations),
+              as_i32(min_points), _ptr(kept), C.byref(info), err=self._err)
         out = {}
         for k, _ in TopolowPruneInfo._fields_:
             v = getattr(info, k)
@@ -1281,11 +1130,8 @@ class PreparedHandle:
         eig = np.empty(n, dtype=np.float64) if want_eigenvalues else None
         cen = np.empty((n, n), dtype=np.float64, order=self.layout) if want_centered else None
         info = TopolowSpectrumInfo()
-        rc = self.lib.topolow_layout_prep_spectrum(self._h, _dp(eig) if eig is not None else None,
-                                                   _dp(cen) if cen is not None else None, C.byref(info), self._err,
-                                                   len(self._err))
-        _check(rc, self._err)
-        out = {k: getattr(info, k) for k, _ in TopolowSpectrumInfo._fields_ if not k.startswith("reserved")}
+        _call(self.lib.topolow_layout_prep_spectrum, self._h, _ptr(eig), _ptr(cen), C.byref(info), err=self._err)
+        out = _fields(info)
         out["seconds"] = list(info.seconds)
         return out, eig, cen
 
@@ -1293,8 +1139,8 @@ class PreparedHandle:
         pos = _f64F(positions)
         if pos.ndim != 2 or pos.shape[0] != self.n:
             raise ValueError("positions must have one row per point")
-        pk = np.ascontiguousarray(picks if picks is not None else [], dtype=np.int64).reshape(-1)
-        return pos, pk, (pk.ctypes.data_as(C.POINTER(C.c_int64)) if pk.size else None)
+        pk = _i64(picks if picks is not None else []).reshape(-1)
+        return pos, pk, (_ptr(pk) if pk.size else None)
 
     def fit_report(self, positions, picks=None):
         """topolow_layout_prep_fit_report: the moments of the signed errors value - distance of the handle's resident
@@ -1305,11 +1151,9 @@ class PreparedHandle:
         total]}, each series with the fields of topolow_fit_series."""
         pos, pk, pkp = self._fit_inputs(positions, picks)
         rep = TopolowFitReport()
-        rc = self.lib.topolow_layout_prep_fit_report(self._h, _dp(pos), pos.shape[1], pkp, int(pk.size), C.byref(rep),
-                                                     self._err, len(self._err))
-        _check(rc, self._err)
-        out = {name: {k: getattr(rep.series[s], k) for k, _ in TopolowFitSeries._fields_}
-               for name, s in (("in", FIT_IN), ("out", FIT_OUT), ("all", FIT_ALL))}
+        _call(self.lib.topolow_layout_prep_fit_report, self._h, _ptr(pos), pos.shape[1], pkp, int(pk.size), C.byref(rep),
+              err=self._err)
+        out = {name: _fields(rep.series[s]) for name, s in (("in", FIT_IN), ("out", FIT_OUT), ("all", FIT_ALL))}
         out["seconds"] = list(rep.seconds)
         return out
 
@@ -1321,13 +1165,11 @@ class PreparedHandle:
         if series not in _FIT_SERIES:
             raise ValueError('series must be "in", "out" or "all"')
         pos, pk, pkp = self._fit_inputs(positions, picks)
-        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        rk = _i64(ranks).reshape(-1)
         vals = np.full(max(int(rk.size), 1), np.nan)
         m = C.c_int64(0)
-        rc = self.lib.topolow_layout_prep_fit_order_stats(
-            self._h, _dp(pos), pos.shape[1], pkp, int(pk.size), _FIT_SERIES[series],
-            rk.ctypes.data_as(C.POINTER(C.c_int64)), int(rk.size), _dp(vals), C.byref(m), self._err, len(self._err))
-        _check(rc, self._err)
+        _call(self.lib.topolow_layout_prep_fit_order_stats, self._h, _ptr(pos), pos.shape[1], pkp, int(pk.size),
+              _FIT_SERIES[series], _ptr(rk), int(rk.size), _ptr(vals), C.byref(m), err=self._err)
         return vals[:rk.size].copy(), int(m.value)
 
     def graph_stats(self):
@@ -1338,19 +1180,18 @@ class PreparedHandle:
 
     def fold_seconds(self) -> list:
         """Seconds of the last .cv_sweep on this handle, summed over its folds: preparation, hold-out, score, restore."""
-        ph = (C.c_double * 4)()
-        self.lib.topolow_layout_prep_fold_seconds(self._h, ph)
-        return list(ph)
+        return self._seconds(self.lib.topolow_layout_prep_fold_seconds, 4)
 
     def phase_seconds(self) -> list:
-        ph = (C.c_double * 5)()
-        self.lib.topolow_layout_prep_phase_seconds(self._h, ph)
-        return list(ph)
+        return self._seconds(self.lib.topolow_layout_prep_phase_seconds, 5)
 
     def resident_seconds(self) -> list:
         """Seconds of the last Session.load_prepared, .optimize and .post_metrics on this handle."""
-        ph = (C.c_double * 3)()
-        self.lib.topolow_layout_prep_resident_seconds(self._h, ph)
+        return self._seconds(self.lib.topolow_layout_prep_resident_seconds, 3)
+
+    def _seconds(self, fn, k: int) -> list:
+        ph = (C.c_double * k)()
+        fn(self._h, ph)
         return list(ph)
 
     def close(self):
@@ -1376,17 +1217,13 @@ def tridiagonal_eigenvalues(d, e, device: Optional[int] = None) -> np.ndarray:
     """topolow_tridiagonal_eigenvalues: all eigenvalues of the symmetric tridiagonal matrix (diagonal d, off-diagonal
     e), descending, by Sturm bisection on the device."""
     lib = load()
-    d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
-    e = np.ascontiguousarray(e, dtype=np.float64).reshape(-1)
+    d, e = _f64(d).reshape(-1), _f64(e).reshape(-1)
     n = int(d.shape[0])
     if e.shape[0] != max(n - 1, 0):
         raise ValueError("e must have n - 1 entries")
     out = np.empty(max(n, 1), dtype=np.float64)
-    err = C.create_string_buffer(512)
-    rc = lib.topolow_tridiagonal_eigenvalues(_dp(d), _dp(e) if n >= 2 else None, n,
-                                             int(options.get("device", -1)) if device is None else int(device), _dp(out),
-                                             err, len(err))
-    _check(rc, err)
+    _call(lib.topolow_tridiagonal_eigenvalues, _ptr(d), _ptr(e) if n >= 2 else None, n,
+          int(options.get("device", -1)) if device is None else int(device), _ptr(out))
     return out[:n]
 
 
@@ -1403,11 +1240,8 @@ def symmetric_eigenvalues(a, want_tridiagonal: bool = False, want_eigenvalues: b
     eig = np.empty(max(n, 1), dtype=np.float64) if want_eigenvalues else None
     d = np.empty(max(n, 1), dtype=np.float64) if want_tridiagonal else None
     e = np.empty(max(n, 1), dtype=np.float64) if want_tridiagonal else None
-    err = C.create_string_buffer(512)
-    rc = lib.topolow_symmetric_eigenvalues(_dp(a), n, int(options.get("device", -1)) if device is None else int(device),
-                                           _dp(d) if d is not None else None, _dp(e) if e is not None else None,
-                                           _dp(eig) if eig is not None else None, err, len(err))
-    _check(rc, err)
+    _call(lib.topolow_symmetric_eigenvalues, _ptr(a), n, int(options.get("device", -1)) if device is None else int(device),
+          _ptr(d), _ptr(e), _ptr(eig))
     eig = eig[:n] if eig is not None else None
     return (eig, d[:n], e[:max(n - 1, 0)]) if want_tridiagonal else eig
 
@@ -1429,7 +1263,7 @@ def prepare_layout(values, codes=None, preserve_order: bool = False, order=None,
 def slab_plan(n: int, slab_stages: int, seed: int, it: int) -> np.ndarray:
     lib = load()
     buf = np.zeros((64, 4), dtype=np.int32)
-    ns = lib.topolow_slab_plan(int(n), int(slab_stages), int(seed), int(it), _ip(buf), 64)
+    ns = lib.topolow_slab_plan(int(n), int(slab_stages), int(seed), int(it), _ptr(buf), 64)
     return buf[:ns].copy()
 
 
@@ -1449,7 +1283,7 @@ def slab_stages_at(it: int, k: float, ndim: int = 5) -> int:
 def gs_pair_order(n: int, seed: int, it: int) -> np.ndarray:
     lib = load()
     buf = np.zeros((n * (n - 1) // 2, 2), dtype=np.int32)
-    cnt = lib.topolow_gs_pair_order(int(n), int(seed), int(it), _ip(buf))
+    cnt = lib.topolow_gs_pair_order(int(n), int(seed), int(it), _ptr(buf))
     assert cnt == buf.shape[0]
     return buf
 
@@ -1457,7 +1291,7 @@ def gs_pair_order(n: int, seed: int, it: int) -> np.ndarray:
 def tilegs_pair_order(n: int, seed: int, it: int) -> np.ndarray:
     lib = load()
     buf = np.zeros((n * (n - 1) // 2, 2), dtype=np.int32)
-    cnt = lib.topolow_tilegs_pair_order(int(n), int(seed), int(it), _ip(buf))
+    cnt = lib.topolow_tilegs_pair_order(int(n), int(seed), int(it), _ptr(buf))
     assert cnt == buf.shape[0], (cnt, buf.shape)
     return buf
 
@@ -1474,15 +1308,13 @@ def decode_target(bits: int):
 
 def controller_script(mae_seq, iter_seq, k_seq, k0, window, eps):
     lib = load()
-    m = np.ascontiguousarray(mae_seq, dtype=np.float64)
-    it = np.ascontiguousarray(iter_seq, dtype=np.int32)
-    ks = np.ascontiguousarray(k_seq, dtype=np.float64)
+    m, it, ks = _f64(mae_seq), _i32(iter_seq), _f64(k_seq)
     n = int(m.shape[0])
     stopped = C.c_int32(-1)
     snaps = np.zeros(n, dtype=np.int32)
     bm, bk, bi = C.c_double(0), C.c_double(0), C.c_int32(0)
-    lib.topolow_controller_script(_dp(m), _ip(it), _dp(ks), n, float(k0), int(window), float(eps),
-                                  C.byref(stopped), _ip(snaps), C.byref(bm), C.byref(bk),
+    lib.topolow_controller_script(_ptr(m), _ptr(it), _ptr(ks), n, float(k0), int(window), float(eps),
+                                  C.byref(stopped), _ptr(snaps), C.byref(bm), C.byref(bk),
                                   C.byref(bi))
     return dict(stopped_at=int(stopped.value), snapshots=snaps.astype(bool),
                 best_mae=float(bm.value), best_k=float(bk.value), best_iter=int(bi.value))
@@ -1499,10 +1331,8 @@ class Session:
         self.precision = precision
         self._h = C.c_void_p(None)
         self._err = C.create_string_buffer(512)
-        rc = self.lib.topolow_session_create(C.byref(self._h), self.n, self.ndim, self.row_begin,
-                                             self.row_end, _PRECISIONS[precision], int(device),
-                                             self._err, len(self._err))
-        _check(rc, self._err)
+        _call(self.lib.topolow_session_create, C.byref(self._h), self.n, self.ndim, self.row_begin, self.row_end,
+              _PRECISIONS[precision], int(device), err=self._err)
 
     def close(self):
         if self._h:
@@ -1517,25 +1347,18 @@ class Session:
 
     def load_dense(self, D, T, degrees):
         D, T = _f64F(D), _i32F(T)
-        deg = np.ascontiguousarray(degrees, dtype=np.int32)
-        _check(self.lib.topolow_session_load_dense(self._h, _dp(D), _ip(T), _ip(deg), self._err,
-                                                   len(self._err)), self._err)
+        deg = _i32(degrees)
+        _call(self.lib.topolow_session_load_dense, self._h, _ptr(D), _ptr(T), _ptr(deg), err=self._err)
 
     def load_coo(self, ei, ej, ed, et, degrees):
-        ei = np.ascontiguousarray(ei, dtype=np.int32)
-        ej = np.ascontiguousarray(ej, dtype=np.int32)
-        ed = np.ascontiguousarray(ed, dtype=np.float64)
-        et = np.ascontiguousarray(et, dtype=np.int32)
-        deg = np.ascontiguousarray(degrees, dtype=np.int32)
-        _check(self.lib.topolow_session_load_coo(self._h, _ip(ei), _ip(ej), _dp(ed), _ip(et),
-                                                 int(ei.shape[0]), _ip(deg), self._err,
-                                                 len(self._err)), self._err)
+        ei, ej, ed, et, deg = _i32(ei), _i32(ej), _f64(ed), _i32(et), _i32(degrees)
+        _call(self.lib.topolow_session_load_coo, self._h, _ptr(ei), _ptr(ej), _ptr(ed), _ptr(et), int(ei.shape[0]),
+              _ptr(deg), err=self._err)
 
     def load_prepared(self, handle: "PreparedHandle"):
         """topolow_session_load_prepared: targets, degrees and the convergence edge list from a PreparedHandle, device
         to device -- what load_dense + set_edges do with the arrays handle.fetch() returns."""
-        _check(self.lib.topolow_session_load_prepared(self._h, handle._h if handle is not None else None, self._err,
-                                                      len(self._err)), self._err)
+        _call(self.lib.topolow_session_load_prepared, self._h, handle._h if handle is not None else None, err=self._err)
 
     @property
     def encoded_ptr(self) -> int:
@@ -1546,92 +1369,72 @@ class Session:
         return int(self.lib.topolow_session_encoded_ld(self._h))
 
     def commit_encoded(self, degrees):
-        deg = np.ascontiguousarray(degrees, dtype=np.int32)
+        deg = _i32(degrees)
         assert deg.shape[0] == self.n
-        _check(self.lib.topolow_session_commit_encoded(self._h, _ip(deg), self._err,
-                                                       len(self._err)), self._err)
+        _call(self.lib.topolow_session_commit_encoded, self._h, _ptr(deg), err=self._err)
 
     def set_edges(self, ei, ej, ed, et):
-        ei = np.ascontiguousarray(ei, dtype=np.int32)
-        ej = np.ascontiguousarray(ej, dtype=np.int32)
-        ed = np.ascontiguousarray(ed, dtype=np.float64)
-        et = np.ascontiguousarray(et, dtype=np.int32)
-        _check(self.lib.topolow_session_set_edges(self._h, _ip(ei), _ip(ej), _dp(ed), _ip(et),
-                                                  int(ei.shape[0]), self._err, len(self._err)),
-               self._err)
+        ei, ej, ed, et = _i32(ei), _i32(ej), _f64(ed), _i32(et)
+        _call(self.lib.topolow_session_set_edges, self._h, _ptr(ei), _ptr(ej), _ptr(ed), _ptr(et), int(ei.shape[0]),
+              err=self._err)
 
     def set_positions(self, pos):
         pos = _f64F(pos)
         assert pos.shape == (self.n, self.ndim)
-        _check(self.lib.topolow_session_set_positions(self._h, _dp(pos), self._err,
-                                                      len(self._err)), self._err)
+        _call(self.lib.topolow_session_set_positions, self._h, _ptr(pos), err=self._err)
 
     def get_positions(self):
         out = np.zeros((self.n, self.ndim), dtype=np.float64, order="F")
-        _check(self.lib.topolow_session_get_positions(self._h, _dp(out), self._err,
-                                                      len(self._err)), self._err)
+        _call(self.lib.topolow_session_get_positions, self._h, _ptr(out), err=self._err)
         return np.ascontiguousarray(out)
 
     def begin(self, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon=1e-4,
               convergence_window=5, convergence_check_freq=3, seed=0, slab_stages=0):
-        _check(self.lib.topolow_session_begin(
-            self._h, int(n_iter), float(k0), float(cooling_rate), float(c_repulsion),
-            float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(slab_stages), self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_begin, self._h, int(n_iter), float(k0), float(cooling_rate), float(c_repulsion),
+              float(relative_epsilon), int(convergence_window), int(convergence_check_freq),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(slab_stages), err=self._err)
 
     def enqueue(self, max_iters) -> int:
         enq = C.c_int32(0)
-        _check(self.lib.topolow_session_enqueue(self._h, int(max_iters), C.byref(enq), self._err,
-                                                len(self._err)), self._err)
+        _call(self.lib.topolow_session_enqueue, self._h, int(max_iters), C.byref(enq), err=self._err)
         return int(enq.value)
 
     def wait(self):
         """Waits for the launches enqueued so far; a check waiting to ride on the next sweep stays pending."""
-        _check(self.lib.topolow_session_wait(self._h, self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_wait, self._h, err=self._err)
 
     def sync(self):
         it, st, mae = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
-        _check(self.lib.topolow_session_sync(self._h, C.byref(it), C.byref(st), C.byref(mae),
-                                             self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_sync, self._h, C.byref(it), C.byref(st), C.byref(mae), err=self._err)
         return int(it.value), bool(st.value), float(mae.value)
 
     def finish(self, download: bool = True) -> NativeResult:
         """download = False: the positions stay on the device (score_pairs reads them there); `positions` is None."""
-        out = np.zeros((self.n, self.ndim), dtype=np.float64, order="F") if download else None
-        conv, iters = C.c_int32(0), C.c_int32(0)
-        fmae, fk = C.c_double(0.0), C.c_double(0.0)
-        _check(self.lib.topolow_session_finish(self._h, _dp(out) if download else None, C.byref(conv), C.byref(iters),
-                                               C.byref(fmae), C.byref(fk), self._err,
-                                               len(self._err)), self._err)
-        return NativeResult(np.ascontiguousarray(out) if download else None, bool(conv.value), int(iters.value),
-                            float(fmae.value), float(fk.value))
+        out = _RunOut(self.n, self.ndim, positions=download)
+        _call(self.lib.topolow_session_finish, self._h, *out.args, err=self._err)
+        return out.result()
 
     def hold_out(self, pair_i, pair_j, degrees):
         """The listed pairs (caller's labels) become unmeasured for the coming runs, `degrees` the fold's degrees
         (topolow_session_hold_out); outside a run only."""
-        pi = np.ascontiguousarray(pair_i, dtype=np.int32)
-        pj = np.ascontiguousarray(pair_j, dtype=np.int32)
-        deg = np.ascontiguousarray(degrees, dtype=np.int32)
+        pi, pj, deg = _i32(pair_i), _i32(pair_j), _i32(degrees)
         assert pi.shape == pj.shape and deg.shape[0] == self.n
-        _check(self.lib.topolow_session_hold_out(self._h, _ip(pi), _ip(pj), int(pi.shape[0]), _ip(deg), self._err,
-                                                 len(self._err)), self._err)
+        _call(self.lib.topolow_session_hold_out, self._h, _ptr(pi), _ptr(pj), int(pi.shape[0]), _ptr(deg), err=self._err)
 
     def restore_held_out(self, degrees):
         """Puts the held-out cells back, with the full matrix's degrees."""
-        deg = np.ascontiguousarray(degrees, dtype=np.int32)
+        deg = _i32(degrees)
         assert deg.shape[0] == self.n
-        _check(self.lib.topolow_session_restore_held_out(self._h, _ip(deg), self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_restore_held_out, self._h, _ptr(deg), err=self._err)
 
     def score_pairs(self, pair_i, pair_j, truth):
         """(sum |truth - distance|, count) over the pairs on the positions finish() restores, on the device."""
-        pi = np.ascontiguousarray(pair_i, dtype=np.int32)
-        pj = np.ascontiguousarray(pair_j, dtype=np.int32)
-        t = np.ascontiguousarray(truth, dtype=np.float64)
+        pi, pj, t = _i32(pair_i), _i32(pair_j), _f64(truth)
         assert pi.shape == pj.shape == t.shape
-        total, cnt = C.c_double(0.0), C.c_int64(0)
-        _check(self.lib.topolow_session_score_pairs(self._h, _ip(pi), _ip(pj), _dp(t), int(pi.shape[0]), C.byref(total),
-                                                    C.byref(cnt), self._err, len(self._err)), self._err)
-        return float(total.value), int(cnt.value)
+        sc = _SumCount()
+        _call(self.lib.topolow_session_score_pairs, self._h, _ptr(pi), _ptr(pj), _ptr(t), int(pi.shape[0]), *sc.refs,
+              err=self._err)
+        return sc.values()
 
     def run(self, chunk=64):
         while self.enqueue(chunk) > 0:
@@ -1641,21 +1444,19 @@ class Session:
     def check_trace(self) -> np.ndarray:
         """(iteration, MAE, k) of every convergence check of the current run, shape (checks, 3)."""
         n = C.c_int32(0)
-        err = C.create_string_buffer(8)
-        _check(self.lib.topolow_session_check_trace(self._h, None, 0, C.byref(n)), err)
+        _check(self.lib.topolow_session_check_trace(self._h, None, 0, C.byref(n)))
         out = np.zeros((max(int(n.value), 1), 3), dtype=np.float64)
-        _check(self.lib.topolow_session_check_trace(self._h, _dp(out), int(n.value), C.byref(n)), err)
+        _check(self.lib.topolow_session_check_trace(self._h, _ptr(out), int(n.value), C.byref(n)))
         return out[: int(n.value)]
 
     def set_relabel(self, seed: int):
         """Store the points in a random order drawn from `seed` (0 = the caller's order); before loading."""
-        _check(self.lib.topolow_session_set_relabel(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                                    self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_set_relabel, self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), err=self._err)
 
     def labels(self) -> np.ndarray:
         """session label -> caller's label."""
         out = np.empty(self.n, dtype=np.int32)
-        self.lib.topolow_session_labels(self._h, _ip(out))
+        self.lib.topolow_session_labels(self._h, _ptr(out))
         return out
 
     def set_schedule(self, schedule: str):
@@ -1668,27 +1469,21 @@ class Session:
 
     def profile(self):
         """(stage_ms, stage_launches, check_ms, checks) since profiling was enabled."""
-        sm, cm = C.c_double(0.0), C.c_double(0.0)
-        sl, cl = C.c_int64(0), C.c_int64(0)
-        _check(self.lib.topolow_session_profile(self._h, C.byref(sm), C.byref(sl), C.byref(cm),
-                                                C.byref(cl), self._err, len(self._err)), self._err)
-        return float(sm.value), int(sl.value), float(cm.value), int(cl.value)
+        return self._profile(self.lib.topolow_session_profile, 2)
+
+    def _profile(self, fn, k: int):
+        out = _SumCount(k)
+        _call(fn, self._h, *out.refs, err=self._err)
+        return out.values()
 
     def profile_symmetric(self):
         """(plain_ms, plain_iterations, fused_ms, fused_iterations) of the iterations that ran as a symmetric sweep +
         apply since profiling was enabled (not part of profile() / profile_fused())."""
-        a, b = C.c_double(0.0), C.c_double(0.0)
-        na, nb = C.c_int64(0), C.c_int64(0)
-        _check(self.lib.topolow_session_profile_symmetric(self._h, C.byref(a), C.byref(na), C.byref(b), C.byref(nb),
-                                                          self._err, len(self._err)), self._err)
-        return float(a.value), int(na.value), float(b.value), int(nb.value)
+        return self._profile(self.lib.topolow_session_profile_symmetric, 2)
 
     def profile_fused(self):
         """(ms, launches) of the stage launches that also reduced a check's MAE; ask before profile()."""
-        ms, n = C.c_double(0.0), C.c_int64(0)
-        _check(self.lib.topolow_session_profile_fused(self._h, C.byref(ms), C.byref(n), self._err, len(self._err)),
-               self._err)
-        return float(ms.value), int(n.value)
+        return self._profile(self.lib.topolow_session_profile_fused, 1)
 
     def set_stream(self, hip_stream, external: bool = True):
         """hip_stream: integer hipStream_t (0/None = the device's default stream)."""
@@ -1726,21 +1521,18 @@ class Session:
         return int(self.lib.topolow_session_bytes_per_iteration(self._h))
 
     def stage(self, d_pos_in: int, d_pos_out: int, it: int, stage: int, n_stages: int, k: float):
-        _check(self.lib.topolow_session_stage(self._h, C.c_void_p(d_pos_in), C.c_void_p(d_pos_out),
-                                              int(it), int(stage), int(n_stages), float(k),
-                                              self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_stage, self._h, C.c_void_p(d_pos_in), C.c_void_p(d_pos_out), int(it), int(stage),
+              int(n_stages), float(k), err=self._err)
 
     def check_partial(self, d_pos: int, d_out2: int):
         """Enqueue this block's share of the convergence MAE on the positions at d_pos: two doubles
         (sum, count) at the device address d_out2."""
-        _check(self.lib.topolow_session_check_partial(self._h, C.c_void_p(d_pos), C.c_void_p(d_out2),
-                                                      self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_check_partial, self._h, C.c_void_p(d_pos), C.c_void_p(d_out2), err=self._err)
 
     def controller_step(self, d_total2: int, d_pos: int, iter1: int, k_after: float):
         """Enqueue the controller (reference :303-357) on the all-reduced (sum, count) at d_total2."""
-        _check(self.lib.topolow_session_controller_step(self._h, C.c_void_p(d_total2), C.c_void_p(d_pos),
-                                                        int(iter1), float(k_after), self._err,
-                                                        len(self._err)), self._err)
+        _call(self.lib.topolow_session_controller_step, self._h, C.c_void_p(d_total2), C.c_void_p(d_pos), int(iter1),
+              float(k_after), err=self._err)
 
     @property
     def can_fuse_checks(self) -> bool:
@@ -1748,9 +1540,8 @@ class Session:
 
     def stage_fused(self, d_pos_in: int, d_pos_out: int, it: int, k: float, d_out2: int):
         """The single stage of iteration `it`, also reducing this block's share of the MAE of d_pos_in."""
-        _check(self.lib.topolow_session_stage_fused(self._h, C.c_void_p(d_pos_in), C.c_void_p(d_pos_out), int(it),
-                                                    float(k), C.c_void_p(d_out2), self._err, len(self._err)),
-               self._err)
+        _call(self.lib.topolow_session_stage_fused, self._h, C.c_void_p(d_pos_in), C.c_void_p(d_pos_out), int(it), float(k),
+              C.c_void_p(d_out2), err=self._err)
 
     # ---- one-stage iterations as the symmetric sweep sharded over the processes (include/topolow_relax.h) ----
     @property
@@ -1773,9 +1564,8 @@ class Session:
 
     def symm_segment_build(self, segment: int, n_segments: int, d_rows: int, row_first: int, n_rows: int,
                            any_threshold: bool):
-        _check(self.lib.topolow_session_symm_segment_build(self._h, int(segment), int(n_segments), C.c_void_p(d_rows),
-                                                           int(row_first), int(n_rows), int(bool(any_threshold)),
-                                                           self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_symm_segment_build, self._h, int(segment), int(n_segments), C.c_void_p(d_rows),
+              int(row_first), int(n_rows), int(bool(any_threshold)), err=self._err)
 
     @property
     def symm_moves_ptr(self) -> int:
@@ -1783,13 +1573,12 @@ class Session:
         return int(self.lib.topolow_session_symm_moves(self._h) or 0)
 
     def symm_segment_sweep(self, d_pos_in: int, it: int, k: float, d_out2: int = 0):
-        _check(self.lib.topolow_session_symm_segment_sweep(self._h, C.c_void_p(d_pos_in), int(it), float(k),
-                                                           C.c_void_p(d_out2) if d_out2 else None, self._err,
-                                                           len(self._err)), self._err)
+        _call(self.lib.topolow_session_symm_segment_sweep, self._h, C.c_void_p(d_pos_in), int(it), float(k),
+              C.c_void_p(d_out2) if d_out2 else None, err=self._err)
 
     def symm_segment_apply(self, d_pos_in: int, d_pos_out: int, it: int):
-        _check(self.lib.topolow_session_symm_segment_apply(self._h, C.c_void_p(d_pos_in), C.c_void_p(d_pos_out),
-                                                           int(it), self._err, len(self._err)), self._err)
+        _call(self.lib.topolow_session_symm_segment_apply, self._h, C.c_void_p(d_pos_in), C.c_void_p(d_pos_out), int(it),
+              err=self._err)
 
     def first_nonfinite(self) -> int:
         it = C.c_int32(0)
@@ -1797,7 +1586,6 @@ class Session:
         return int(it.value)
 
     def edge_error(self, d_pos: int):
-        s, c = C.c_double(0.0), C.c_int64(0)
-        _check(self.lib.topolow_session_edge_error(self._h, C.c_void_p(d_pos), C.byref(s),
-                                                   C.byref(c), self._err, len(self._err)), self._err)
-        return float(s.value), int(c.value)
+        sc = _SumCount()
+        _call(self.lib.topolow_session_edge_error, self._h, C.c_void_p(d_pos), *sc.refs, err=self._err)
+        return sc.values()
