@@ -246,3 +246,54 @@ def test_every_kernel_is_compiled_into_exactly_one_object():
     assert len(names) > 400          # the listing is the whole library's
     twice = [name for name, count in collections.Counter(names).items() if count > 1]
     assert twice == []
+
+
+def test_makefile_builds_every_source():
+    """SRC of csrc/Makefile names exactly the *.hip files of csrc: a source left out of the list would be left out of
+    the library without a word (its entries missing, or -- worse -- an older object of it linked)."""
+    csrc = os.path.join(ROOT, "topolow_amd", "csrc")
+    make = open(os.path.join(csrc, "Makefile")).read()
+    src = re.search(r"^SRC\s*=\s*(.*)$", make, re.M).group(1).split()
+    assert len(src) == len(set(src))
+    assert sorted(src) == sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert src[0] == "topolow_relax.hip"     # the longest compile starts first: the link waits for it
+
+
+def test_drivers_compile_no_kernel_and_one_source_holds_the_gs_kernels():
+    """topolow_drivers.hip is host code: its device listing holds no kernel, so an edit of a driver recompiles none.
+    The one-workgroup Gauss-Seidel kernel is instantiated by topolow_gs.hip alone: 48 instances (12 coordinate counts
+    x {f32, f64} x {dense, sparse})."""
+    import subprocess
+    csrc = os.path.join(ROOT, "topolow_amd", "csrc")
+    subprocess.run(["make", "-C", csrc, "asm"], check=True, capture_output=True)
+    kernels = {}
+    for part in os.listdir(csrc):
+        if part.endswith(".part.gfx950.s"):
+            kernels[part] = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", open(os.path.join(csrc, part)).read(), re.M)
+    assert kernels["topolow_drivers.part.gfx950.s"] == []
+    gs = {part: [k for k in names if "gs_embed_kernel" in k] for part, names in kernels.items()}
+    assert len(gs["topolow_gs.part.gfx950.s"]) == 48
+    assert [part for part, names in gs.items() if names] == ["topolow_gs.part.gfx950.s"]
+
+
+def test_library_exports_the_c_abi_and_nothing_else_of_its_own():
+    """The defined dynamic symbols of the built library: every function of _native.PROTOTYPES (the C ABI, checked
+    against the header elsewhere), and beyond them only what the compiler and the HIP runtime put there -- mangled names
+    (the kernels' host stubs and handles), the fat binary's and the C runtime's.  A helper that crosses a source
+    boundary has hidden visibility (csrc/topolow_session.h, topolow_prep.h, topolow_drivers.h): no topolow_* name
+    outside the table may show, and no unmangled helper name but the ones the library has always had -- helpers of
+    topolow_prep.hip, whose anonymous namespaces stand inside its extern "C" block (a list that may shrink, never
+    grow)."""
+    import subprocess
+    if not os.path.exists(_native.LIB_PATH):
+        pytest.skip("libtopolow_relax.so is not built")
+    out = subprocess.run(["nm", "-D", "--defined-only", _native.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    symbols = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    own = {s for s in symbols if not s.startswith(("_Z", "__hip_", "_init", "_fini"))}
+    prep_helpers = set("""fit_check_arguments fit_run fold_grid prep_check_subset prep_fold_alloc prep_fold_check_handle
+                          prep_fold_prepare prep_fold_symmetry prep_is_permutation prep_order_in_ok prep_passes
+                          prune_all_alive prune_launch_count prune_row_bits spec_all_finite spec_bisect
+                          spec_characteristics spec_key_value spec_pick_digit spec_tridiagonalize""".split())
+    assert set(_native.PROTOTYPES) <= own
+    assert own - set(_native.PROTOTYPES) <= prep_helpers
+    assert not [s for s in symbols - own if re.match(r"_?_?topolow_", s)]

@@ -1,5 +1,6 @@
-// topolow_amd/csrc/relax_post.h -- the post-metrics kernel: est_distances and the terms of mae in one pass
-// (reference R/core.R:474-481; host pipeline: topolow_post_metrics in topolow_relax.hip).
+// topolow_amd/csrc/relax_post.h -- the post-metrics kernels: est_distances alone, and est_distances with the terms of
+// mae in one pass (reference R/core.R:474-481; host pipelines: topolow_est_distances_rows, topolow_post_metrics in
+// topolow_post.hip).  Plain __global__ functions: topolow_post.hip alone includes this header.
 #pragma once
 
 #include "relax_common.h"
@@ -7,6 +8,23 @@
 namespace topolow {
 
 constexpr int kPostThreads = 256;
+
+// est_distances = as.matrix(dist(positions)) (reference R/core.R:474), f64, rows [row0, row0 + rows).
+// positions: n x dim row-major f64; out: rows x n f64, row-major (the full matrix is symmetric, so
+// R's column-major reading of an n x n result is the same matrix).
+__global__ __launch_bounds__(kPostThreads) void pdist_kernel(const double* __restrict__ pos, int n, int dim, int row0,
+                                                             int rows, double* __restrict__ out) {
+  const int j = blockIdx.y * kPostThreads + threadIdx.x;   // grid: x = row of the block, y = 256-column group
+  const int r = blockIdx.x;
+  if (j >= n || r >= rows) return;
+  const int i = row0 + r;
+  double s = 0.0;
+  for (int d = 0; d < dim; ++d) {
+    const double dev = pos[(size_t)i * dim + d] - pos[(size_t)j * dim + d];
+    s += dev * dev;
+  }
+  out[(size_t)r * n + j] = ::sqrt(s);
+}
 
 // One workgroup per column of a tile of columns [col0, col0 + cols) of the caller's column-major n x n matrices.
 //   vals   cols x n f64: the tile of `values`, column after column (the caller's own layout)

@@ -601,7 +601,7 @@ __global__ __launch_bounds__(256) void symm_tiles_kernel(const uint32_t* const* 
   }
 }
 
-// ---- the sweep sharded over P row-block sessions (relax_sharded_engine.h) --------------------------------------
+// ---- the sweep sharded over P row-block sessions (topolow_relax.hip: sharded_worker) -------------------------
 // Session b sweeps segment b of the tile list (equal tile counts, so equal work) into its own partials; a point's
 // move needs the partials of every segment, so each session folds ITS partials per point (symm_partial_kernel: what
 // symm_apply_kernel sums, restricted to one segment) and stores the result into slot b of the inbox of the session

@@ -1,6 +1,7 @@
-// topolow_amd/csrc/topolow_drivers.h -- what the drivers in topolow_relax.hip share with the entries of a prepared
+// topolow_amd/csrc/topolow_drivers.h -- what the drivers in topolow_drivers.hip share with the entries of a prepared
 // handle (topolow_prep.hip): opening and running a whole-problem session, the route of an embedding, and the sweep
-// over resident folds.  Types, declarations and the one template; no kernels.
+// over resident folds; and the one door to the one-workgroup Gauss-Seidel kernels (topolow_gs.hip).  Types,
+// declarations and the one template; no kernels.
 #pragma once
 
 #include "topolow_session.h"
@@ -10,7 +11,7 @@
 // Targets, degrees and the convergence edge list into a fresh whole-problem session (relabelled already).
 using SessionLoader = std::function<int(topolow_session*, char*, size_t)>;
 
-// ---- defined in topolow_relax.hip ----
+// ---- defined in topolow_drivers.hip ----
 bool cv_sweep_args_ok(const void* cells, int32_t n_folds, const int32_t* ndim, const double* k0,
                       const double* cooling_rate, const double* c_repulsion, const int64_t* picks_offset,
                       const double* unit_draws, const int64_t* draws_offset, const uint64_t* seeds,
@@ -142,5 +143,10 @@ int run_session_layout(int32_t n, int32_t ndim, bool tile_gs, const topolow_opti
                        int32_t convergence_check_freq, int32_t verbose, double* positions_out, int32_t* converged,
                        int32_t* iterations, double* final_mae, double* final_k, topolow_run_stats* stats,
                        double t_start, char* errbuf, size_t errlen);
+
+// ---- defined in topolow_gs.hip: gs_relax (relax_gs.h) in the precision asked for; see there ----
+void gs_relax_by_precision(int32_t precision, const topolow_problem* problems, topolow_result* results, int32_t count,
+                           double* device_seconds, int32_t (*interrupt_cb)(void*), void* interrupt_user,
+                           std::vector<double>* trace_out);
 
 #pragma GCC visibility pop

@@ -1,6 +1,6 @@
 // topolow_amd/csrc/topolow_prep.h -- the prepared handle as the library's sources see it: struct topolow_layout_prep
 // and what it is made of, the pinned staging and the stream pipe the post-metrics share with the handle's entries, and
-// the functions that cross a source boundary (topolow_prep.hip <-> topolow_relax.hip).  Types and
+// the functions that cross a source boundary (topolow_prep.hip <-> topolow_relax.hip, topolow_post.hip).  Types and
 // declarations only; the kernels live in the sources.
 #pragma once
 
@@ -92,7 +92,7 @@ struct PostResident {
   const int32_t* ord;    // nullable: the input order is kept
 };
 
-// topolow_relax.hip: the pipeline of topolow_post_metrics_ex, and of topolow_layout_prep_post_metrics when `resident` is given.
+// topolow_post.hip: the pipeline of topolow_post_metrics_ex, and of topolow_layout_prep_post_metrics when `resident` is given.
 int post_metrics_run(const double* positions, int32_t n, int32_t ndim, const double* values, const int32_t* codes,
                      const PostResident* resident, double* est_distances, double* sum_abs, int64_t* count,
                      int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen);

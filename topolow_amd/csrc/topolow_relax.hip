@@ -1,66 +1,22 @@
-// topolow_amd/csrc/topolow_relax.hip -- host side of libtopolow_relax.so: the C ABI of
-// include/topolow_relax.h over the HIP kernels in relax_kernels.h / relax_gs.h -- the session, the drivers and the
-// post-metrics.  The prepared handle and its entries are a source of their own, topolow_prep.hip.
+// topolow_amd/csrc/topolow_relax.hip -- the session of libtopolow_relax.so: everything that touches a session's
+// buffers or launches a relaxation kernel (relax_kernels.h, relax_exact.h, relax_tilegs.h, relax_symm*.h, relax_cv.h)
+// -- the launch helpers, the symmetric sweep's host code, the row-sharded engine and the topolow_session_* C ABI of
+// include/topolow_relax.h.  The drivers that run whole embeddings on sessions are topolow_drivers.hip, the
+// one-workgroup Gauss-Seidel entries topolow_gs.hip, the post-metrics topolow_post.hip, the prepared handle
+// topolow_prep.hip.
 //
-// Replaces the native half of the reference's euclidean_embedding():
-//   .Call(`_topolow_optimize_layout_exact_cpp`, ...)  (reference R/RcppExports.R:4-6)
-//   -> optimize_layout_exact_cpp                       (reference src/optimization.cpp:109-382)
 // There is no CPU fallback in this library: without a HIP device every entry point that
 // computes returns TOPOLOW_ERR_NO_DEVICE.
 
 #include "topolow_session.h"
 #include "topolow_prep.h"
-#include "topolow_drivers.h"
 #include "relax_kernels.h"
 #include "relax_exact.h"
-#include "relax_fold.h"
-#include "relax_gs.h"
 #include "relax_tilegs.h"
 #include "relax_symm.h"
 #include "relax_symm64.h"
 #include "relax_symm_wide.h"
 #include "relax_cv.h"
-#include "relax_post.h"
-
-namespace {
-
-constexpr int kDefaultGsMaxN = 1024;
-
-// verbose lines go to the caller's sink (topolow_options.print_cb) or stdout
-void emit(const topolow_options& opt, const char* fmt, ...) {
-  char line[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(line, sizeof line, fmt, ap);
-  va_end(ap);
-  if (opt.print_cb) opt.print_cb(line, opt.print_user);
-  else { std::fputs(line, stdout); std::fflush(stdout); }
-}
-
-// The reference's opening lines (src/optimization.cpp:183-188) plus which device path runs.
-void emit_header(const topolow_options& opt, const char* path, int n, double k0, double cooling, double c_rep) {
-  emit(opt, "=== Exact Algorithm (O(N^2) Full Pairwise) on HIP: %s ===\n", path);
-  emit(opt, "Points: %d, Pairs per iteration: %lld\n", n, (long long)n * (n - 1) / 2);
-  emit(opt, "Parameters: k0=%g, cooling=%g, c_rep=%g\n", k0, cooling, c_rep);
-}
-
-// Progress lines of the checks [from, to) of a trace (3 doubles per check), with the reference's
-// cadence: checks that fall on a multiple of 10 iterations or on the last one (:298-301).
-void emit_checks(const topolow_options& opt, const double* trace, int from, int to, int n_iter) {
-  for (int c = from; c < to; ++c) {
-    const int it = (int)trace[3 * c];
-    if (it % 10 == 0 || it == n_iter)
-      emit(opt, "Iter %d/%d, MAE=%g, k=%g\n", it, n_iter, trace[3 * c + 1], trace[3 * c + 2]);
-  }
-}
-
-// Closing line of a converged run (:334-336, :351-353): the controller's counters tell which rule fired.
-void emit_converged(const topolow_options& opt, bool plateau, int best_iter, double best_mae) {
-  if (plateau) emit(opt, "Converged (plateau) at iter %d, MAE=%g\n", best_iter, best_mae);
-  else emit(opt, "Converged (MAE worsening, best restored) at iter %d, MAE=%g\n", best_iter, best_mae);
-}
-
-}  // namespace
 
 // =========================================================================================
 // Session (slab path)
@@ -895,7 +851,7 @@ bool check_fusable(topolow_session* s, int n_stages) {
   return n_stages == 1 && (s->rows() % 2 == 0 || sym_form(s, 1) == SymForm::kSweep);
 }
 
-// ---- the symmetric sweep sharded over the row-block sessions of one run (relax_symm.h, relax_sharded_engine.h) ----
+// ---- the symmetric sweep sharded over the row-block sessions of one run (relax_symm.h; the engine below) ----
 // Segment b of P of the sweep over n points: tiles [t0, t1), equal runs of the tile-row-major list of the upper
 // triangle (`total` tiles); tile-rows [r_first, r_last] hold its tiles (-1: none).
 struct SymSegment {
@@ -1328,9 +1284,275 @@ void cv_score_device(topolow_session* s, const int* d_i, const int* d_j, const d
   if (count) *count = n_pairs;
 }
 
+// =========================================================================================
+// Row-sharded engine: ONE embedding relaxed over several row-block sessions, driven from one process (an R session
+// is one process: reference src/RcppExports.cpp:16-39)
+// =========================================================================================
+// Layout: block b owns rows [row_begin_b, row_end_b) of the encoded target
+// matrix and moves only its own points; every block keeps ALL n positions (they are tiny).  Per slab
+// stage:
+//   * block b's stage kernel writes its updated rows into its own next-position buffer AND, from the
+//     same epilogue, into the next-position buffer of every other block (peer stores -- over xGMI when
+//     the blocks sit on different GPUs): the all-gather of the position slices is fused into the
+//     kernel, there is no separate collective and no staging copy;
+//   * a barrier between the GPUs out of HIP events: every GPU's thread records an event behind its
+//     stage kernels and makes its stream wait for the events of the others (blocks that share a GPU share
+//     a stream: stream order is their barrier).  Peer-written data is consumed only by
+//     kernels that START after that wait -- kernel-boundary visibility, the guarantee HIP gives for
+//     ordinary (coarse-grained) device memory; nothing spins inside a kernel on a remote flag.
+// Per convergence check each block reduces its parity share of the measured pairs, folds the
+// partials into one (sum, count) and peer-stores it into a slot of every block's rank table; after
+// one more barrier every block runs the SAME controller on the SAME numbers in the same order, so
+// the decisions (stop / snapshot) are replicated without any host round trip.
+// One host thread per GPU enqueues that GPU's work (the event waits are per pair of GPUs, a single
+// thread would issue G^2 of them per stage); threads meet in a spin barrier between "record" and
+// "wait" so an event is always recorded before anyone waits on it.  The calling thread is the first
+// GPU's thread: only it polls the caller's interrupt callback (R's API is main-thread only).
+// Measured on one MI355X (tests/study/shard_exchange_latency.py): with every block forced into its own
+// thread and stream the barrier costs 27 / 62 / 198 us per stage at 2 / 4 / 8 blocks -- eight threads
+// issuing 72 event calls per stage into ONE device's runtime lock; that is why same-GPU blocks share a
+// stream, and it is the upper bound of what 8 GPUs (one lock each, 9 calls per thread) can cost.
 namespace {
 
-#include "relax_sharded_engine.h"
+struct ShardedAbortableBarrier {
+  std::atomic<int> count{0};
+  std::atomic<int> sense{0};
+  std::atomic<bool> failed{false};
+  int n;
+  explicit ShardedAbortableBarrier(int n_) : n(n_) {}
+  // false: some thread failed (it never arrives); the caller must unwind
+  bool wait() {
+    const int s = sense.load(std::memory_order_acquire);
+    if (count.fetch_add(1, std::memory_order_acq_rel) == n - 1) {
+      count.store(0, std::memory_order_relaxed);
+      sense.store(s ^ 1, std::memory_order_release);
+      return !failed.load(std::memory_order_acquire);
+    }
+    int spins = 0;
+    while (sense.load(std::memory_order_acquire) == s) {
+      if (failed.load(std::memory_order_acquire)) return false;
+      if (++spins > 4000) std::this_thread::yield();
+    }
+    return !failed.load(std::memory_order_acquire);
+  }
+  void fail() { failed.store(true, std::memory_order_release); }
+};
+
+// Blocks that share a GPU form a GROUP: one host thread enqueues all of them on ONE stream, stage by
+// stage, so stream order is their barrier (their kernels each fill the chip anyway).  Groups -- i.e.
+// different GPUs, one block each in production -- meet at the event barrier.  TOPOLOW_SHARD_THREAD_PER_BLOCK=1
+// makes every block its own group (tests drive the cross-group path on one GPU with it).
+struct ShardedGroup {
+  std::vector<int> blocks;     // indices into ShardedRun::ss, ascending
+  hipStream_t stream = nullptr;
+  int device = 0;
+};
+
+struct ShardedRun {
+  std::vector<topolow_session*> ss;
+  std::vector<ShardedGroup> groups;
+  std::vector<std::array<hipEvent_t, 2>> ev;      // per group
+  ShardedAbortableBarrier* bar = nullptr;
+  std::atomic<int> flag[2];      // published by group 0's thread before barrier g (slot g & 1): bit 0 stop, bit 1 interrupt
+  int32_t (*interrupt_cb)(void*) = nullptr;
+  void* interrupt_user = nullptr;
+  std::mutex err_mu;
+  HipError first_error{TOPOLOW_OK, ""};
+  int warmup_iters = 0;          // > 0: the clock of `timed_seconds` starts when these iterations have drained
+  double t_timed0 = 0.0;
+  bool pair_sharded = false;     // one-stage iterations run as the symmetric sweep sharded over the sessions (relax_symm.h)
+  // results of the loop
+  int iters_enqueued = 0;
+  bool interrupted = false;
+  long long exchanges = 0;
+};
+
+// One group's enqueue loop (thread r).  Throws HipError; the caller marks the barrier failed.
+void sharded_worker(ShardedRun& R, int r) {
+  const ShardedGroup& G = R.groups[r];
+  const int n_groups = (int)R.groups.size();
+  topolow_session* lead = R.ss[G.blocks[0]];
+  HIP_TRY(hipSetDevice(G.device));
+  long long g = 0;          // exchange counter, identical in every thread
+  int seen = 0;             // flag value read at the last exchange, identical in every thread
+  auto exchange = [&]() -> bool {
+    int f = 0;
+    if (r == 0) {
+      f = R.ss[0]->mailbox->stopped ? 1 : 0;
+      if (R.interrupted) f |= 2;
+    }
+    if (n_groups == 1) { seen = f; ++g; return true; }   // stream order is the barrier
+    HIP_TRY(hipEventRecord(R.ev[r][g & 1], G.stream));
+    if (r == 0) R.flag[g & 1].store(f, std::memory_order_release);
+    if (!R.bar->wait()) return false;
+    for (int p = 0; p < n_groups; ++p)
+      if (p != r) HIP_TRY(hipStreamWaitEvent(G.stream, R.ev[p][g & 1], 0));
+    seen = R.flag[g & 1].load(std::memory_order_acquire);
+    ++g;
+    return true;
+  };
+  // The run's parameters are every session's (topolow_session_begin); the schedule is the lead block's.
+  const int P = (int)R.ss.size();
+  int cur = 0;
+  double k = lead->k0;
+  int iter = 0;
+  // Position buffers rotate through three: a stage reads `cur` and writes (own rows, and the other blocks' copies)
+  // the next one, so the buffer a check measured is not written for two more stages.
+  // A check whose error pass is deferred into the next iteration's single sweep (slab_stage_pipe_kernel<ERR>):
+  // the sweep's barrier then also carries the blocks' (sum, count) slots, so the check costs no pass over the
+  // block and no barrier of its own.  Its controller runs behind that barrier and snapshots the buffer the sweep
+  // READ; other blocks may already be writing their next stage -- into the third buffer.  Decided from the
+  // schedule alone, hence identically in every thread.
+  PendingCheck pend;
+  // Rank tables alternate between successive checks: with fused checks a block may already be pushing the NEXT
+  // check's (sum, count) -- it rides on the sweep that follows the barrier -- while another block's controller
+  // still reads this check's table behind the same barrier.  Two tables are enough: the push of check q + 2 is
+  // issued behind the barrier that follows controller(q) in every stream.  (With one table and one stream per
+  // block, controllers of different blocks saw different MAEs for the same check and stopped at different
+  // iterations: tests/test_gpu_sharded_native.py::test_sharded_fuzz_equals_single_session.)
+  long long n_check = 0;
+  auto can_fuse = [&](const topolow_session* s) {
+    return s->fuse_checks && s->dense_mae && s->precision == TOPOLOW_PRECISION_F32 && s->rows() % 2 == 0;
+  };
+  bool fusable = true;
+  for (topolow_session* s : R.ss) fusable = fusable && can_fuse(s);
+  // one-stage iterations as the sharded symmetric sweep: its ERR instance has no even-rows rule
+  bool fusable_pair = R.pair_sharded;
+  for (topolow_session* s : R.ss)
+    fusable_pair = fusable_pair && s->fuse_checks && s->dense_mae && s->precision == TOPOLOW_PRECISION_F32;
+  // a check's `parts` partials -> this block's slot of every rank table `tab` (inside the caller's check ProfScope)
+  auto push_partials = [&](topolow_session* s, int parts, int tab) {
+    hipLaunchKernelGGL(reduce_push_kernel, dim3(1), dim3(1024), 0, s->stream, s->part_sum.p, s->part_cnt.p, parts,
+                       s->rsum_tab.p, s->rcnt_tab.p, s->n_ranks, tab + s->rank, s->state.p);
+    HIP_TRY(hipGetLastError());
+  };
+  // behind the barrier: every block's controller on rank table `tab`, for check pc
+  auto controllers = [&](const PendingCheck& pc, int tab) {
+    for (int b : G.blocks) {
+      topolow_session* s = R.ss[b];
+      ProfScope prof(s, &s->prof_check);
+      launch_controller(s, s->pos[pc.buf].p, pc.iter1, pc.k_after, s->rank_sum.p + tab, s->rank_cnt.p + tab, s->n_ranks);
+    }
+  };
+  auto separate_check = [&](const PendingCheck& pc) -> bool {
+    const int tab = (int)(n_check & 1) * P;
+    ++n_check;
+    for (int b : G.blocks) {
+      topolow_session* s = R.ss[b];
+      ProfScope prof(s, &s->prof_check);
+      TL_DISPATCH_DIM(s->dim, launch_edge_error, s, s->pos[pc.buf].p, s->state.p);
+      push_partials(s, error_parts(s), tab);
+    }
+    if (!exchange()) return false;
+    controllers(pc, tab);
+    return true;
+  };
+  for (; iter < lead->n_iter; ++iter) {
+    if (seen != 0) break;
+    if (R.warmup_iters > 0 && iter == R.warmup_iters) {   // measurement only: drain, meet, start the clock
+      HIP_TRY(hipStreamSynchronize(G.stream));
+      if (n_groups > 1 && !R.bar->wait()) return;
+      if (r == 0) R.t_timed0 = now_s();
+      if (n_groups > 1 && !R.bar->wait()) return;
+    }
+    if (r == 0 && R.interrupt_cb != nullptr && iter > 0 && iter % 50 == 0 && !R.interrupted)   // reference :364
+      R.interrupted = R.interrupt_cb(R.interrupt_user) != 0;   // published at the next exchange
+    // the session loop's plan: ONE block (the whole matrix) takes its symmetric forms, a block of several is row-owner
+    const IterPlan plan = plan_iteration(lead, iter, k);
+    const bool fuse_now = pend.active && plan.geo.n_stages == 1;
+    if (pend.active && !fuse_now) { if (!separate_check(pend)) return; pend.active = false; }
+    const int tab = (int)(n_check & 1) * P;   // the table of the check this sweep carries, if any
+    if (fuse_now) ++n_check;
+    if (R.pair_sharded && plan.geo.n_stages == 1) {
+      // every session sweeps its segment of the tile list and folds its partials into the owners' inboxes; barrier;
+      // the owners move their points and store them into every session's next buffer; barrier
+      const int nxt = (cur + 1) % 3;
+      for (int b : G.blocks) {
+        topolow_session* s = R.ss[b];
+        TL_DISPATCH_SYM(s->dim, sym_sharded_sweep, s, s->pos[cur].p, iter, k, fuse_now);
+        if (fuse_now) { ProfScope prof(s, &s->prof_check); push_partials(s, s->sym.plan.n_units, tab); }
+      }
+      if (!exchange()) return;
+      if (fuse_now) { controllers(pend, tab); pend.active = false; }
+      for (int b : G.blocks) {
+        topolow_session* s = R.ss[b];
+        TL_DISPATCH_SYM(s->dim, sym_owner_apply, s, s->pos[cur].p, s->pos[nxt].p, s->row_begin, s->row_end, s->push_tab[nxt].p,
+                        s->n_push, iter);
+      }
+      if (!exchange()) return;
+      cur = nxt;
+    } else
+    for (int t = 0; t < plan.geo.n_stages; ++t) {
+      const int nxt = (cur + 1) % 3;
+      for (int b : G.blocks) {
+        topolow_session* s = R.ss[b];
+        const int parts = enqueue_stage(s, plan, t, s->pos[cur].p, s->pos[nxt].p, iter, k, s->push_tab[nxt].p, s->n_push,
+                                        fuse_now);
+        if (fuse_now) { ProfScope prof(s, &s->prof_check); push_partials(s, parts, tab); }
+      }
+      if (!exchange()) return;
+      if (fuse_now) { controllers(pend, tab); pend.active = false; }
+      cur = nxt;
+    }
+    k *= (1.0 - lead->cooling);   // reference :289
+    if (check_after(lead, iter)) {
+      const PendingCheck pc{true, iter + 1, k, cur};
+      const bool fuse = (fusable || fusable_pair) && iter + 1 < lead->n_iter && iteration_stages(lead, iter + 1, k) == 1;
+      if (fuse) pend = pc;
+      else if (!separate_check(pc)) return;
+    }
+  }
+  if (pend.active && !separate_check(pend)) return;   // the loop ended early
+  for (int b : G.blocks) R.ss[b]->cur = cur;
+  if (r == 0) { R.iters_enqueued = iter; R.exchanges = g; }
+  HIP_TRY(hipStreamSynchronize(G.stream));
+}
+
+// Wires `count` loaded sessions (row blocks tiling [0, n) in order, same n / ndim / precision) into one
+// another: peer access between their devices, push tables, rank tables.
+void sharded_wire(std::vector<topolow_session*>& ss) {
+  const int P = (int)ss.size();
+  for (int a = 0; a < P; ++a)
+    for (int b = 0; b < P; ++b) {
+      if (ss[a]->device == ss[b]->device) continue;
+      int can = 0;
+      HIP_TRY(hipDeviceCanAccessPeer(&can, ss[a]->device, ss[b]->device));
+      if (!can) throw HipError{TOPOLOW_ERR_UNSUPPORTED, "row-sharded run: the GPUs cannot access each other's memory"};
+      HIP_TRY(hipSetDevice(ss[a]->device));
+      const hipError_t e = hipDeviceEnablePeerAccess(ss[b]->device, 0);
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_TRY(e);
+      (void)hipGetLastError();
+    }
+  for (int a = 0; a < P; ++a) {
+    topolow_session* s = ss[a];
+    HIP_TRY(hipSetDevice(s->device));
+    s->n_ranks = P;
+    s->rank = a;
+    s->n_push = P - 1;
+    for (int b2 = 0; b2 < 3; ++b2) {
+      std::vector<void*> tab;
+      for (int q = 0; q < P; ++q) if (q != a) tab.push_back((void*)ss[q]->pos[b2].p);
+      s->push_tab[b2].alloc(tab.size());
+      if (!tab.empty())
+        HIP_TRY(hipMemcpy(s->push_tab[b2].p, tab.data(), tab.size() * sizeof(void*), hipMemcpyHostToDevice));
+    }
+    s->rank_sum.alloc(2 * P);   // two tables, alternating between successive checks (see sharded_worker)
+    s->rank_cnt.alloc(2 * P);
+    HIP_TRY(hipMemset(s->rank_sum.p, 0, sizeof(double) * 2 * P));
+    HIP_TRY(hipMemset(s->rank_cnt.p, 0, sizeof(unsigned long long) * 2 * P));
+  }
+  for (int a = 0; a < P; ++a) {
+    topolow_session* s = ss[a];
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<double*> ts;
+    std::vector<unsigned long long*> tc;
+    for (int q = 0; q < P; ++q) { ts.push_back(ss[q]->rank_sum.p); tc.push_back(ss[q]->rank_cnt.p); }
+    s->rsum_tab.alloc(P);
+    s->rcnt_tab.alloc(P);
+    HIP_TRY(hipMemcpy(s->rsum_tab.p, ts.data(), P * sizeof(double*), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->rcnt_tab.p, tc.data(), P * sizeof(unsigned long long*), hipMemcpyHostToDevice));
+  }
+}
 
 }  // namespace
 
@@ -1340,20 +1562,6 @@ namespace {
 extern "C" {
 
 const char* topolow_relax_version(void) { return "topolow_relax 0.1 (gfx950)"; }
-
-void topolow_default_options(topolow_options* opt) {
-  if (!opt) return;
-  std::memset(opt, 0, sizeof(*opt));
-  opt->seed = 0;
-  opt->schedule = TOPOLOW_SCHEDULE_AUTO;
-  opt->precision = TOPOLOW_PRECISION_AUTO;
-  opt->slab_stages = 0;
-  opt->device = -1;
-  opt->gs_max_n = 0;
-  opt->keep_labels = 0;
-  opt->interrupt_cb = nullptr;
-  opt->interrupt_user = nullptr;
-}
 
 int64_t topolow_encoded_index(int32_t row_in_block, int32_t column, int32_t ld) {
   return (int64_t)enc_index(row_in_block, column, ld);
@@ -1384,10 +1592,6 @@ int32_t topolow_slab_plan(int32_t n, int32_t slab_stages, uint64_t seed, int32_t
     ranges_out[4 * slot + 3] = r.e1;
   }
   return g.n_stages;
-}
-
-int64_t topolow_gs_pair_order(int32_t n, uint64_t seed, int32_t iter, int32_t* pairs_out) {
-  return gs_pair_order(n, seed, iter, pairs_out);
 }
 
 int topolow_controller_script(const double* mae_seq, const int32_t* iter_seq,
@@ -2277,157 +2481,6 @@ int topolow_session_edge_error(topolow_session* s, const void* d_pos, double* su
   });
 }
 
-// ---- batch of independent embeddings (GS kernel, one workgroup each) --------------------
-int topolow_optimize_layout_exact_batch(const topolow_problem* problems, topolow_result* results,
-                                        int32_t count, int32_t precision, int32_t device,
-                                        double* device_seconds, char* errbuf, size_t errlen) {
-  if (count < 0 || (count > 0 && (!problems || !results))) return TOPOLOW_ERR_BAD_ARGUMENT;
-  if (device_seconds) *device_seconds = 0.0;
-  if (count == 0) return TOPOLOW_OK;
-  return guarded(errbuf, errlen, [&] {
-    select_device(device);
-    for (int b = 0; b < count; ++b)
-      if (problems[b].n < 2) throw HipError{TOPOLOW_ERR_TOO_FEW_POINTS, "Need at least 2 points for embedding"};
-    if (precision == TOPOLOW_PRECISION_F32) gs_relax<float>(problems, results, count, device_seconds);
-    else gs_relax<double>(problems, results, count, device_seconds);
-  });
-}
-
-// ---- post metric -----------------------------------------------------------------------
-int topolow_cell_list_index(int32_t n, int64_t n_cells, const int32_t* row, const int32_t* col,
-                            int64_t* pos_of, int64_t* by_row, int64_t* row_ptr) {
-  if (n < 1 || n_cells < 0 || !pos_of || !by_row || !row_ptr || (n_cells > 0 && (!row || !col)))
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  for (int64_t q = 0; q < (int64_t)n * n; ++q) pos_of[q] = -1;
-  for (int i = 0; i <= n; ++i) row_ptr[i] = 0;
-  for (int64_t c = 0; c < n_cells; ++c) {
-    if (row[c] < 0 || row[c] >= n || col[c] < 0 || col[c] >= n) return TOPOLOW_ERR_BAD_ARGUMENT;
-    pos_of[(int64_t)row[c] + (int64_t)col[c] * n] = c;   // linear column-major index, as R's which()
-    row_ptr[row[c] + 1] += 1;
-  }
-  for (int i = 0; i < n; ++i) row_ptr[i + 1] += row_ptr[i];
-  try {
-    // counting sort by row; the listing is column-major, so columns ascend inside every row
-    std::vector<int64_t> at(row_ptr, row_ptr + n);
-    for (int64_t c = 0; c < n_cells; ++c) by_row[at[row[c]]++] = c;
-  } catch (const std::bad_alloc&) {
-    return TOPOLOW_ERR_HIP;
-  }
-  return TOPOLOW_OK;
-}
-
-int topolow_cv_fold(const topolow_cell_list* cells, const int64_t* picks, int64_t n_picks,
-                    int32_t preserve_order, int32_t named, int32_t* order, int32_t* degrees,
-                    int32_t* edge_i, int32_t* edge_j, double* edge_dist, int32_t* edge_thresh,
-                    int64_t* n_edges, int32_t* holdout_i, int32_t* holdout_j, double* holdout_truth,
-                    int64_t* n_holdout, double* numeric_max) {
-  if (!cells || (!picks && n_picks > 0) || !order || !degrees || !edge_i || !edge_j || !edge_dist ||
-      !edge_thresh || !n_edges || !holdout_i || !holdout_j || !holdout_truth || !n_holdout || !numeric_max)
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  try {
-    return fold_problem(cells, picks, n_picks, preserve_order, named, order, degrees, edge_i, edge_j,
-                        edge_dist, edge_thresh, n_edges, holdout_i, holdout_j, holdout_truth, n_holdout,
-                        numeric_max);
-  } catch (const std::bad_alloc&) {
-    return TOPOLOW_ERR_HIP;
-  }
-}
-
-}  // extern "C"
-
-// The arguments the sweeps share: the cell list (or the prepared handle) always, the per-fold arrays wherever there is a fold.
-bool cv_sweep_args_ok(const void* cells, int32_t n_folds, const int32_t* ndim, const double* k0,
-                      const double* cooling_rate, const double* c_repulsion, const int64_t* picks_offset,
-                      const double* unit_draws, const int64_t* draws_offset, const uint64_t* seeds,
-                      const double* holdout_sum_abs, const int64_t* holdout_count, const int32_t* iterations,
-                      const int32_t* converged, const int32_t* error_code) {
-  if (!cells || n_folds < 0) return false;
-  return n_folds == 0 || (ndim && k0 && cooling_rate && c_repulsion && picks_offset && unit_draws && draws_offset && seeds &&
-                          holdout_sum_abs && holdout_count && iterations && converged && error_code);
-}
-
-extern "C" {
-
-// All folds of a cross-validation sweep in ONE call: the folds' problems are built side by side on host threads
-// (fold_problem; start positions from the caller's unit draws with NumPy's / R's arithmetic: a random walk whose
-// steps are uniform(0, 2 max / n), R/core.R:407-415) and relaxed as one batch; only the per-fold scores come back.
-int topolow_cv_sweep(const topolow_cell_list* cells, int32_t named, int32_t preserve_order, int32_t n_folds,
-                     const int32_t* ndim, const double* k0, const double* cooling_rate, const double* c_repulsion,
-                     const int64_t* picks, const int64_t* picks_offset, const double* unit_draws,
-                     const int64_t* draws_offset, const uint64_t* seeds, int32_t n_iter, double relative_epsilon,
-                     int32_t convergence_window, int32_t convergence_check_freq, int32_t precision, int32_t device,
-                     double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations, int32_t* converged,
-                     int32_t* error_code, double* device_seconds, char* errbuf, size_t errlen) {
-  if (!cv_sweep_args_ok(cells, n_folds, ndim, k0, cooling_rate, c_repulsion, picks_offset, unit_draws, draws_offset, seeds,
-                        holdout_sum_abs, holdout_count, iterations, converged, error_code))
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  if (device_seconds) *device_seconds = 0.0;
-  if (n_folds == 0) return TOPOLOW_OK;
-  const int n = cells->n;
-  const size_t m = (size_t)cells->n_cells;
-  struct Fold {
-    std::vector<int32_t> order, deg, ei, ej, et, hi, hj;
-    std::vector<double> ed, ht, pos, out;
-    int64_t ne = 0, nh = 0;
-    int rc = TOPOLOW_OK;
-  };
-  std::vector<Fold> F;
-  const int rc_folds = guarded(errbuf, errlen, [&] {
-    F.resize((size_t)n_folds);
-    host_parallel(n_folds, 16, [&](size_t lo, size_t hi) {
-      for (size_t f = lo; f < hi; ++f) {
-        Fold& x = F[f];
-        x.order.resize(n); x.deg.resize(n);
-        x.ei.resize(m); x.ej.resize(m); x.et.resize(m); x.ed.resize(m);
-        x.hi.resize(m); x.hj.resize(m); x.ht.resize(m);
-        double vmax = 0.0;
-        x.rc = fold_problem(cells, picks + picks_offset[f], picks_offset[f + 1] - picks_offset[f], preserve_order, named,
-                            x.order.data(), x.deg.data(), x.ei.data(), x.ej.data(), x.ed.data(), x.et.data(), &x.ne,
-                            x.hi.data(), x.hj.data(), x.ht.data(), &x.nh, &vmax);
-        x.rc = fold_check(x.rc, x.ne, vmax, ndim[f], draws_offset[f + 1] - draws_offset[f], n);
-        if (x.rc != TOPOLOW_OK) continue;
-        start_walk(unit_draws + draws_offset[f], vmax, n, ndim[f], nullptr, x.pos);
-        x.out.assign((size_t)n * ndim[f], 0.0);
-      }
-    });
-  });
-  if (rc_folds != TOPOLOW_OK) return rc_folds;
-  std::vector<topolow_problem> P;
-  std::vector<topolow_result> R;
-  std::vector<int> idx;
-  for (int f = 0; f < n_folds; ++f) {
-    Fold& x = F[(size_t)f];
-    holdout_sum_abs[f] = 0.0; holdout_count[f] = 0; iterations[f] = 0; converged[f] = 0;
-    error_code[f] = x.rc;
-    if (x.rc != TOPOLOW_OK) continue;
-    topolow_problem p;
-    std::memset(&p, 0, sizeof p);
-    p.initial_positions = x.pos.data();
-    p.degrees = x.deg.data();
-    p.edge_i = x.ei.data(); p.edge_j = x.ej.data(); p.edge_dist = x.ed.data(); p.edge_thresh = x.et.data();
-    p.n_edges = x.ne; p.n = n; p.ndim = ndim[f]; p.n_iter = n_iter;
-    p.convergence_window = convergence_window; p.convergence_check_freq = convergence_check_freq;
-    p.k0 = k0[f]; p.cooling_rate = cooling_rate[f]; p.c_repulsion = c_repulsion[f]; p.relative_epsilon = relative_epsilon;
-    p.seed = seeds[f];
-    if (x.nh > 0) { p.holdout_i = x.hi.data(); p.holdout_j = x.hj.data(); p.holdout_truth = x.ht.data(); p.n_holdout = x.nh; }
-    topolow_result r;
-    std::memset(&r, 0, sizeof r);
-    r.positions_out = x.out.data();
-    P.push_back(p); R.push_back(r); idx.push_back(f);
-  }
-  if (P.empty()) return TOPOLOW_OK;
-  const int rc = topolow_optimize_layout_exact_batch(P.data(), R.data(), (int32_t)P.size(), precision, device, device_seconds,
-                                                     errbuf, errlen);
-  if (rc != TOPOLOW_OK) return rc;
-  for (size_t q = 0; q < idx.size(); ++q) {
-    const int f = idx[q];
-    error_code[f] = R[q].error_code;
-    holdout_sum_abs[f] = R[q].holdout_sum_abs; holdout_count[f] = R[q].holdout_count;
-    iterations[f] = R[q].iterations; converged[f] = R[q].converged;
-  }
-  return TOPOLOW_OK;
-}
-
 // ---- a cross-validation fold on a resident session (relax_cv.h) ---------------------------
 int topolow_session_hold_out(topolow_session* s, const int32_t* pair_i, const int32_t* pair_j, int64_t n_pairs,
                              const int32_t* degrees, char* errbuf, size_t errlen) {
@@ -2536,379 +2589,6 @@ int topolow_session_score_pairs(topolow_session* s, const int32_t* pair_i, const
     HIP_TRY(hipMemcpyAsync(h.sc_t.p, truth, np * 8, hipMemcpyHostToDevice, s->stream));
     cv_score_device(s, h.sc_i.p, h.sc_j.p, h.sc_t.p, (long long)n_pairs, sum_abs, count);
   });
-}
-
-int32_t topolow_batch_problem_fits(int32_t n, int32_t ndim, int32_t precision, int64_t n_edges) {
-  if (n < 2 || ndim < 1 || ndim > kMaxTunedDim) return 0;
-  const int dim = kernel_dim(ndim);
-  const size_t rs = precision == TOPOLOW_PRECISION_F32 ? 4 : 8;   // AUTO: f64, as the batch call
-  // GsBatch::stage: the LDS-resident edge table when it fits its budget, the dense form otherwise
-  const bool sparse = n <= 2048 && n_edges > 0 && n_edges < 65535 && gs_lds_bytes(n, dim, rs, n_edges) <= kGsSparseLdsBudget;
-  return gs_lds_bytes(n, dim, rs, sparse ? n_edges : 0) <= kGsLdsLimit ? 1 : 0;
-}
-
-int topolow_cv_fold_pairs(const topolow_cell_list* cells, const int64_t* picks, int64_t n_picks, int32_t preserve_order,
-                          int32_t named, int32_t* order, int32_t* degrees, double* numeric_max, int64_t* n_edges,
-                          int32_t* pair_i, int32_t* pair_j, int64_t* n_pairs, int32_t* score_i, int32_t* score_j,
-                          double* score_truth, int64_t* n_scored, char* errbuf, size_t errlen) {
-  if (!cells || (!picks && n_picks > 0) || !order || !degrees || !numeric_max || !n_edges || !pair_i || !pair_j ||
-      !n_pairs || !score_i || !score_j || !score_truth || !n_scored)
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  int rc = TOPOLOW_OK;
-  const int rcg = guarded(errbuf, errlen, [&] {
-    if (!fold_cells_symmetric(cells))
-      throw HipError{TOPOLOW_ERR_UNSUPPORTED, kAsymmetricCells};
-    FoldPairs fp;
-    rc = fold_pairs(cells, picks, n_picks, preserve_order, named, fp);
-    if (rc != TOPOLOW_OK) return;
-    std::copy(fp.order.begin(), fp.order.end(), order);
-    std::copy(fp.degrees.begin(), fp.degrees.end(), degrees);
-    *numeric_max = fp.numeric_max;
-    *n_edges = fp.n_edges;
-    std::copy(fp.pair_i.begin(), fp.pair_i.end(), pair_i);
-    std::copy(fp.pair_j.begin(), fp.pair_j.end(), pair_j);
-    *n_pairs = (int64_t)fp.pair_i.size();
-    std::copy(fp.score_i.begin(), fp.score_i.end(), score_i);
-    std::copy(fp.score_j.begin(), fp.score_j.end(), score_j);
-    std::copy(fp.score_truth.begin(), fp.score_truth.end(), score_truth);
-    *n_scored = (int64_t)fp.score_i.size();
-  });
-  return rcg != TOPOLOW_OK ? rcg : rc;
-}
-
-namespace {
-
-// Schedule gs is tuned up to kMaxTunedDim dimensions: the one place that says so to a caller.
-int check_gs_dim(int ndim, char* errbuf, size_t errlen) {
-  if (ndim <= kMaxTunedDim) return TOPOLOW_OK;
-  set_err(errbuf, errlen, "schedule gs: ndim must be between 1 and %d (wider embeddings run the slab schedule)", kMaxTunedDim);
-  return TOPOLOW_ERR_UNSUPPORTED;
-}
-
-}  // namespace
-
-}  // extern "C"
-
-// A whole-problem session, opened: session_create, tile Gauss-Seidel where asked for, the labels shuffled by
-// relabel_seed (slabs / tiles of random points instead of index-contiguous ones; NULL: the caller's labels), then the
-// loader.  Where a step fails nothing stays open and *out is NULL.
-int open_session(topolow_session** out, int32_t n, int32_t ndim, bool tile_gs, int32_t precision, int32_t device,
-                 const uint64_t* relabel_seed, const SessionLoader& load, char* errbuf, size_t errlen) {
-  *out = nullptr;
-  topolow_session* s = nullptr;
-  int rc = topolow_session_create(&s, n, ndim, 0, n, precision, device, errbuf, errlen);
-  if (rc != TOPOLOW_OK) return rc;
-  if (tile_gs) {
-    rc = check_gs_dim(ndim, errbuf, errlen);
-    if (rc == TOPOLOW_OK) rc = topolow_session_set_schedule(s, TOPOLOW_SCHEDULE_GS);
-  }
-  if (rc == TOPOLOW_OK && relabel_seed)
-    rc = topolow_session_set_relabel(s, mix64(*relabel_seed ^ 0x1abe15eedull) | 1ull, errbuf, errlen);
-  if (rc == TOPOLOW_OK) rc = load(s, errbuf, errlen);
-  if (rc != TOPOLOW_OK) {
-    topolow_session_destroy(s);
-    return rc;
-  }
-  *out = s;
-  return TOPOLOW_OK;
-}
-
-// Every iteration of a begun run, enqueued 50 at a time: the reference's interrupt cadence (src/optimization.cpp:364).
-// after_chunk, where there is one, runs after each chunk that enqueued work; anything but TOPOLOW_OK from it ends the
-// run with that code.
-int enqueue_run(topolow_session* s, const std::function<int()>& after_chunk, char* errbuf, size_t errlen) {
-  for (;;) {
-    int enq = 0;
-    int rc = topolow_session_enqueue(s, 50, &enq, errbuf, errlen);
-    if (rc || enq == 0) return rc;
-    if (after_chunk && (rc = after_chunk()) != TOPOLOW_OK) return rc;
-  }
-}
-
-extern "C" {
-
-namespace {
-
-// Folds from the host's cell list (fold_pairs), each prepared on a host thread while the fold before it runs.
-struct CellFolds {
-  const topolow_cell_list* cells;
-  const SweepArgs& a;
-  int32_t device, n = 0;
-  struct Fold { int code = TOPOLOW_OK; FoldPairs fp; std::vector<double> pos; };
-  std::vector<int32_t> fi, fj, ft, fdeg;   // what the sessions load: the (symmetric) list's upper triangle, degrees
-  std::vector<double> fd;
-  const int32_t* degrees = nullptr;
-  double untold[4], *seconds = untold;
-  std::future<std::unique_ptr<Fold>> next;
-  bool next_valid = false;
-  int begin(char* errbuf, size_t errlen) {
-    n = cells->n;
-    return guarded(errbuf, errlen, [&] {
-      if (n < 2) throw HipError{TOPOLOW_ERR_TOO_FEW_POINTS, "Need at least 2 points for embedding"};
-      if (!fold_cells_symmetric(cells)) throw HipError{TOPOLOW_ERR_UNSUPPORTED, kAsymmetricCells};
-      fdeg.resize((size_t)n); degrees = fdeg.data();
-      for (int i = 0; i < n; ++i) fdeg[(size_t)i] = (int32_t)(cells->row_ptr[i + 1] - cells->row_ptr[i]);
-      for (int64_t q = 0; q < cells->n_cells; ++q)
-        if (cells->row[q] < cells->col[q]) {
-          fi.push_back(cells->row[q]); fj.push_back(cells->col[q]); fd.push_back(cells->value[q]); ft.push_back(cells->code[q]);
-        }
-    });
-  }
-  int load(topolow_session* t, char* eb, size_t el) const {
-    const int rcl = topolow_session_load_coo(t, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), fdeg.data(), eb, el);
-    return rcl ? rcl : topolow_session_set_edges(t, fi.data(), fj.data(), fd.data(), ft.data(), (int64_t)fi.size(), eb, el);
-  }
-  std::unique_ptr<Fold> build(int f) const {
-    auto p = std::make_unique<Fold>();
-    try {
-      p->code = fold_pairs(cells, a.picks + a.picks_offset[f], a.picks_offset[f + 1] - a.picks_offset[f], a.preserve_order, a.named, p->fp);
-      p->code = fold_check(p->code, p->fp.n_edges, p->fp.numeric_max, a.ndim[f], a.draws_offset[f + 1] - a.draws_offset[f], n);
-      if (p->code != TOPOLOW_OK) return p;
-      // the random walk of topolow_cv_sweep in the caller's labels
-      start_walk(a.unit_draws + a.draws_offset[f], p->fp.numeric_max, n, a.ndim[f],
-                 p->fp.order[0] >= 0 ? p->fp.order.data() : nullptr, p->pos);
-    } catch (const std::bad_alloc&) {
-      p->code = TOPOLOW_ERR_HIP;
-    }
-    return p;
-  }
-  void prefetch(int f) { next = std::async(std::launch::async, [this, f] { return build(f); }); next_valid = true; }
-  std::unique_ptr<Fold> prepare(topolow_session*, int, int*, char*, size_t) { next_valid = false; return next.get(); }
-  void drain() { if (next_valid) (void)next.get(); next_valid = false; }
-  int hold_out(topolow_session* s, const Fold& p, char* errbuf, size_t errlen) const {
-    return topolow_session_hold_out(s, p.fp.pair_i.data(), p.fp.pair_j.data(), (int64_t)p.fp.pair_i.size(),
-                                    p.fp.degrees.data(), errbuf, errlen);
-  }
-  int score(topolow_session* s, const Fold& p, double* sum_abs, int64_t* count, char* errbuf, size_t errlen) const {
-    return topolow_session_score_pairs(s, p.fp.score_i.data(), p.fp.score_j.data(), p.fp.score_truth.data(),
-                                       (int64_t)p.fp.score_i.size(), sum_abs, count, errbuf, errlen);
-  }
-};
-
-}  // namespace
-
-int topolow_cv_sweep_session(const topolow_cell_list* cells, int32_t named, int32_t preserve_order, int32_t n_folds,
-                             const int32_t* ndim, const double* k0, const double* cooling_rate, const double* c_repulsion,
-                             const int64_t* picks, const int64_t* picks_offset, const double* unit_draws,
-                             const int64_t* draws_offset, const uint64_t* seeds, int32_t n_iter, double relative_epsilon,
-                             int32_t convergence_window, int32_t convergence_check_freq, int32_t precision, int32_t device,
-                             int32_t schedule, double* holdout_sum_abs, int64_t* holdout_count, int32_t* iterations,
-                             int32_t* converged, int32_t* error_code, double* device_seconds, char* errbuf, size_t errlen) {
-  const SweepArgs a{named, preserve_order, n_folds, ndim, k0, cooling_rate, c_repulsion, picks, picks_offset, unit_draws,
-                    draws_offset, seeds, n_iter, relative_epsilon, convergence_window, convergence_check_freq, precision,
-                    schedule, holdout_sum_abs, holdout_count, iterations, converged, error_code, device_seconds};
-  CellFolds src{cells, a, device};
-  return cv_sweep_resident(cells, src, a, errbuf, errlen);
-}
-
-// rows [row_begin, row_end) of as.matrix(dist(positions)): out is (row_end - row_begin) x n, row-major.
-// Device memory is bounded: the rows are produced in tiles of at most 256 MB.
-int topolow_est_distances_rows(const double* positions, int32_t n, int32_t ndim, int32_t row_begin,
-                               int32_t row_end, double* out, int32_t device, char* errbuf, size_t errlen) {
-  if (!positions || !out || n < 1 || ndim < 1 || row_begin < 0 || row_end > n || row_begin > row_end)
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  return guarded(errbuf, errlen, [&] {
-    select_device(device);
-    std::vector<double> rowmajor((size_t)n * ndim);
-    for (int i = 0; i < n; ++i)
-      for (int d = 0; d < ndim; ++d) rowmajor[(size_t)i * ndim + d] = positions[i + (size_t)d * n];
-    DevBuf<double> dp, dout;
-    dp.alloc(rowmajor.size());
-    HIP_TRY(hipMemcpy(dp.p, rowmajor.data(), rowmajor.size() * 8, hipMemcpyHostToDevice));
-    const int tile = std::max(1, std::min(row_end - row_begin, (int)((256ll << 20) / (8ll * n))));
-    dout.alloc((size_t)tile * n);
-    for (int r0 = row_begin; r0 < row_end; r0 += tile) {
-      const int rows = std::min(tile, row_end - r0);
-      dim3 grid(rows, (n + kThreads - 1) / kThreads);
-      hipLaunchKernelGGL(pdist_kernel, grid, dim3(kThreads), 0, 0, dp.p, n, ndim, r0, rows, dout.p);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpy(out + (size_t)(r0 - row_begin) * n, dout.p, (size_t)rows * n * 8, hipMemcpyDeviceToHost));
-    }
-  });
-}
-
-int topolow_est_distances(const double* positions, int32_t n, int32_t ndim,
-                          double* est_distances, int32_t device, char* errbuf, size_t errlen) {
-  return topolow_est_distances_rows(positions, n, ndim, 0, n, est_distances, device, errbuf, errlen);
-}
-
-// ---- post-metrics: est_distances and the terms of mae in one pass (R/core.R:474-481) ----
-// The caller's matrices travel in tiles of whole columns (contiguous in column-major storage).  A tile's upload, the
-// kernel of the tile before it and the download of the est tile before that run on three streams and overlap; kPostSlots
-// sets of buffers go round, ordered by events.  What is allocated is bounded whatever n is: per slot one tile of values,
-// of codes and of est on the device (<= kPostTileBytes each while a column fits in that), and as much pinned memory when
-// the staging is PINNED.
-namespace {
-
-constexpr size_t kPostTileBytes = (size_t)32 << 20;   // of `values` per tile
-
-// hipHostRegister on a range of the caller's memory for as long as this object lives
-struct HostRegistration {
-  void* p = nullptr;
-  void pin(const void* q, size_t bytes) {
-    HIP_TRY(hipHostRegister(const_cast<void*>(q), bytes, hipHostRegisterDefault));
-    p = const_cast<void*>(q);
-  }
-  ~HostRegistration() { if (p) (void)hipHostUnregister(p); }
-  HostRegistration() = default;
-  HostRegistration(const HostRegistration&) = delete;
-  HostRegistration& operator=(const HostRegistration&) = delete;
-};
-
-}  // namespace
-
-}  // extern "C"
-
-// The pipeline of topolow_post_metrics_ex, and of topolow_layout_prep_post_metrics when `resident` is given (values
-// and codes are then NULL and the device is the current one).  The arguments are checked by the callers.
-int post_metrics_run(const double* positions, int32_t n, int32_t ndim, const double* values, const int32_t* codes,
-                     const PostResident* resident, double* est_distances, double* sum_abs, int64_t* count,
-                     int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen) {
-  return guarded(errbuf, errlen, [&] {
-    if (!resident) select_device(device);
-    const bool pinned = staging == TOPOLOW_POST_STAGING_PINNED, want_est = est_distances != nullptr;
-    int tile = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, kPostTileBytes / ((size_t)n * 8)));
-    if (const char* e = getenv("TOPOLOW_POST_TILE_COLS")) {
-      const int cap = atoi(e);
-      if (cap >= 1) tile = std::min(tile, cap);
-    }
-    const int n_tiles = (n + tile - 1) / tile, slots = std::min(kPostSlots, n_tiles);
-    const size_t tile_cells = (size_t)tile * n;
-
-    std::vector<double> rowmajor((size_t)n * ndim);
-    for (int i = 0; i < n; ++i)
-      for (int d = 0; d < ndim; ++d) rowmajor[(size_t)i * ndim + d] = positions[i + (size_t)d * n];
-    DevBuf<double> dp, dsum, dvals[kPostSlots], dest[kPostSlots];
-    DevBuf<uint32_t> dcnt;
-    DevBuf<int32_t> dcodes[kPostSlots];
-    PinBuf pvals[kPostSlots], pcodes[kPostSlots], pest[kPostSlots];
-    HostRegistration reg_values, reg_codes, reg_est;
-    PostPipe P;
-    dp.alloc(rowmajor.size());
-    HIP_TRY(hipMemcpy(dp.p, rowmajor.data(), rowmajor.size() * 8, hipMemcpyHostToDevice));
-    dsum.alloc((size_t)n);
-    dcnt.alloc((size_t)n);
-    for (int b = 0; b < slots; ++b) {
-      if (!resident) dvals[b].alloc(tile_cells);
-      if (codes) dcodes[b].alloc(tile_cells);
-      if (want_est) dest[b].alloc(tile_cells);
-      if (pinned) {
-        if (!resident) pvals[b].alloc(tile_cells * 8);
-        if (codes) pcodes[b].alloc(tile_cells * 4);
-        if (want_est) pest[b].alloc(tile_cells * 8);
-      }
-    }
-    if (staging == TOPOLOW_POST_STAGING_REGISTER && !resident) {
-      const size_t cells = (size_t)n * n;
-      reg_values.pin(values, cells * 8);
-      if (codes) reg_codes.pin(codes, cells * 4);
-      if (want_est) reg_est.pin(est_distances, cells * 8);
-    }
-    P.create(slots, phase_seconds ? n_tiles : 0);
-
-    // est tile `t` has arrived in its pinned buffer: hand it to the caller
-    auto drain = [&](int t) {
-      const int b = t % slots, c0 = t * tile, cols = std::min(tile, n - c0);
-      HIP_TRY(hipEventSynchronize(P.down_done[b]));
-      post_host_copy(est_distances + (size_t)c0 * n, pest[b].p, (size_t)cols * n * 8);
-    };
-    for (int t = 0; t < n_tiles; ++t) {
-      const int b = t % slots, c0 = t * tile, cols = std::min(tile, n - c0);
-      const size_t off = (size_t)c0 * n, cells = (size_t)cols * n;
-      const bool reused = t >= slots;   // tile t - slots went through this slot
-      if (resident) {   // nothing to upload: the kernel reads the handle's buffers
-        if (want_est && reused) HIP_TRY(hipStreamWaitEvent(P.run, P.down_done[b], 0));   // its est tile has left the device
-        P.mark(t, 0, P.run);
-        P.mark(t, 1, P.run);
-        P.mark(t, 2, P.run);
-        hipLaunchKernelGGL(post_metrics_resident_kernel, dim3(cols), dim3(kPostThreads), 0, P.run, dp.p, n, ndim, c0, cols,
-                           resident->vals, resident->codes, resident->ord, want_est ? dest[b].p : nullptr, dsum.p, dcnt.p);
-        HIP_TRY(hipGetLastError());
-        P.mark(t, 3, P.run);
-        HIP_TRY(hipEventRecord(P.run_done[b], P.run));
-      } else {
-        const double* src_v = values + off;
-        const int32_t* src_c = codes ? codes + off : nullptr;
-        if (pinned) {
-          if (reused) HIP_TRY(hipEventSynchronize(P.up_done[b]));   // its upload has left the staging buffers
-          post_host_copy(pvals[b].p, src_v, cells * 8);
-          src_v = static_cast<const double*>(pvals[b].p);
-          if (codes) {
-            post_host_copy(pcodes[b].p, src_c, cells * 4);
-            src_c = static_cast<const int32_t*>(pcodes[b].p);
-          }
-        }
-        if (reused) HIP_TRY(hipStreamWaitEvent(P.up, P.run_done[b], 0));   // its kernel has read the device tile
-        P.mark(t, 0, P.up);
-        HIP_TRY(hipMemcpyAsync(dvals[b].p, src_v, cells * 8, hipMemcpyHostToDevice, P.up));
-        if (codes) HIP_TRY(hipMemcpyAsync(dcodes[b].p, src_c, cells * 4, hipMemcpyHostToDevice, P.up));
-        P.mark(t, 1, P.up);
-        HIP_TRY(hipEventRecord(P.up_done[b], P.up));
-
-        HIP_TRY(hipStreamWaitEvent(P.run, P.up_done[b], 0));
-        if (want_est && reused) HIP_TRY(hipStreamWaitEvent(P.run, P.down_done[b], 0));   // its est tile has left the device
-        P.mark(t, 2, P.run);
-        hipLaunchKernelGGL(post_metrics_kernel, dim3(cols), dim3(kPostThreads), 0, P.run, dp.p, n, ndim, c0, cols,
-                           dvals[b].p, codes ? dcodes[b].p : nullptr, want_est ? dest[b].p : nullptr, dsum.p, dcnt.p);
-        HIP_TRY(hipGetLastError());
-        P.mark(t, 3, P.run);
-        HIP_TRY(hipEventRecord(P.run_done[b], P.run));
-      }
-
-      if (want_est) {
-        HIP_TRY(hipStreamWaitEvent(P.down, P.run_done[b], 0));
-        P.mark(t, 4, P.down);
-        HIP_TRY(hipMemcpyAsync(pinned ? pest[b].p : (void*)(est_distances + off), dest[b].p, cells * 8,
-                               hipMemcpyDeviceToHost, P.down));
-        P.mark(t, 5, P.down);
-        HIP_TRY(hipEventRecord(P.down_done[b], P.down));
-        // the tile before this one is drained while this one is on its way: with two slots or more its pinned
-        // buffer is not the one just handed to the download above
-        if (pinned && t >= 1) drain(t - 1);
-      }
-    }
-    if (pinned && want_est) drain(n_tiles - 1);
-    P.sync();
-
-    std::vector<double> col_sum((size_t)n);
-    std::vector<uint32_t> col_cnt((size_t)n);
-    HIP_TRY(hipMemcpy(col_sum.data(), dsum.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(col_cnt.data(), dcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    double total = 0.0;
-    int64_t cells = 0;
-    for (int j = 0; j < n; ++j) { total += col_sum[(size_t)j]; cells += col_cnt[(size_t)j]; }   // columns in index order
-    *sum_abs = total;
-    *count = cells;
-    if (phase_seconds) {
-      for (int q = 0; q < 3; ++q) phase_seconds[q] = 0.0;
-      for (int t = 0; t < n_tiles; ++t)
-        for (int q = 0; q < (want_est ? 3 : 2); ++q) {
-          float ms = 0.0f;
-          HIP_TRY(hipEventElapsedTime(&ms, P.timing[(size_t)t * 6 + 2 * q], P.timing[(size_t)t * 6 + 2 * q + 1]));
-          phase_seconds[q] += 1e-3 * ms;
-        }
-    }
-  });
-}
-
-extern "C" {
-
-int topolow_post_metrics_ex(const double* positions, int32_t n, int32_t ndim, const double* values,
-                            const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
-                            int32_t device, int32_t staging, double* phase_seconds, char* errbuf, size_t errlen) {
-  if (!positions || !values || !sum_abs || !count || n < 1 || ndim < 1 || staging < TOPOLOW_POST_STAGING_DEFAULT ||
-      staging > TOPOLOW_POST_STAGING_PAGEABLE)
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  if (staging == TOPOLOW_POST_STAGING_DEFAULT) staging = kPostDefaultStaging;
-  return post_metrics_run(positions, n, ndim, values, codes, nullptr, est_distances, sum_abs, count, device, staging,
-                          phase_seconds, errbuf, errlen);
-}
-
-int topolow_post_metrics(const double* positions, int32_t n, int32_t ndim, const double* values,
-                         const int32_t* codes, double* est_distances, double* sum_abs, int64_t* count,
-                         int32_t device, char* errbuf, size_t errlen) {
-  return topolow_post_metrics_ex(positions, n, ndim, values, codes, est_distances, sum_abs, count, device,
-                                 TOPOLOW_POST_STAGING_DEFAULT, nullptr, errbuf, errlen);
 }
 
 // ---- ONE embedding row-sharded over several sessions (one process, one host thread per block) ----
@@ -3097,326 +2777,6 @@ int32_t topolow_shard_rows(int32_t n, int32_t blocks, int32_t block, int32_t* ro
     if (row_end) *row_end = n;
   }
   return used;
-}
-
-int topolow_optimize_layout_exact_sharded(
-    const double* initial_positions, int32_t n, int32_t ndim, const double* dissimilarity_matrix,
-    const int32_t* threshold_matrix, const int32_t* degrees, const int32_t* edge_i, const int32_t* edge_j,
-    const double* edge_dist, const int32_t* edge_thresh, int64_t n_edges, int32_t n_iter, double k0,
-    double cooling_rate, double c_repulsion, double relative_epsilon, int32_t convergence_window,
-    int32_t convergence_check_freq, int32_t verbose, const topolow_options* opt_in, double* positions_out,
-    int32_t* converged, int32_t* iterations, double* final_mae, double* final_k, topolow_shard_stats* stats,
-    char* errbuf, size_t errlen) {
-  if (n < 2) {  // reference :131
-    set_err(errbuf, errlen, "Need at least 2 points for embedding");
-    return TOPOLOW_ERR_TOO_FEW_POINTS;
-  }
-  if (!initial_positions || !degrees || !positions_out || !converged || !iterations || !final_mae || !final_k ||
-      ((dissimilarity_matrix == nullptr) != (threshold_matrix == nullptr)) || n_edges < 0 ||
-      (n_edges > 0 && (!edge_i || !edge_j || !edge_dist || !edge_thresh))) {
-    set_err(errbuf, errlen, "null argument");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
-  topolow_options opt;
-  if (opt_in) opt = *opt_in; else topolow_default_options(&opt);
-  if (opt.schedule == TOPOLOW_SCHEDULE_GS) {
-    set_err(errbuf, errlen, "the row-sharded path runs the slab schedule; exact Gauss-Seidel is a one-GPU schedule");
-    return TOPOLOW_ERR_UNSUPPORTED;
-  }
-  if (opt.precision == TOPOLOW_PRECISION_F64_EXACT) {
-    set_err(errbuf, errlen, "precision f64_exact: one GPU only (the row-sharded engine has no exact kernels)");
-    return TOPOLOW_ERR_UNSUPPORTED;
-  }
-  const int want = opt.n_devices > 0 ? opt.n_devices : 1;
-  const int blocks = topolow_shard_rows(n, want, -1, nullptr, nullptr);
-  const int precision = opt.precision == TOPOLOW_PRECISION_F64 ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32;
-  const double t_start = now_s();
-  std::vector<topolow_session*> ss(blocks, nullptr);
-  int rc = TOPOLOW_OK;
-  for (int b = 0; b < blocks && rc == TOPOLOW_OK; ++b) {
-    int rb = 0, re = 0;
-    topolow_shard_rows(n, want, b, &rb, &re);
-    const int dev = opt.devices ? opt.devices[b % want] : (opt.n_devices > 1 ? b : opt.device);
-    rc = topolow_session_create(&ss[b], n, ndim, rb, re, precision, dev, errbuf, errlen);
-    if (rc) break;
-    if (!opt.keep_labels) {   // every block draws the same permutation (same n, same seed)
-      rc = topolow_session_set_relabel(ss[b], mix64(opt.seed ^ 0x1abe15eedull) | 1ull, errbuf, errlen);
-      if (rc) break;
-    }
-    if (dissimilarity_matrix)
-      rc = topolow_session_load_dense(ss[b], dissimilarity_matrix, threshold_matrix, degrees, errbuf, errlen);
-    else
-      rc = topolow_session_load_coo(ss[b], edge_i, edge_j, edge_dist, edge_thresh, n_edges, degrees, errbuf, errlen);
-    if (rc) break;
-    // this block's share of the convergence MAE: pair {lo, hi} belongs to the owner of lo when lo + hi
-    // is even, of hi when it is odd (every block then reduces about half of its row block's pairs)
-    try {
-      std::vector<int32_t> bi, bj, bt;
-      std::vector<double> bd;
-      const int* inv = ss[b]->inv.empty() ? nullptr : ss[b]->inv.data();   // ownership is by session label
-      for (int64_t e = 0; e < n_edges; ++e) {
-        const int a = edge_i[e], c = edge_j[e];
-        if (a < 0 || c < 0 || a >= n || c >= n) continue;
-        const int sa = inv ? inv[a] : a, sc = inv ? inv[c] : c;
-        const int lo = sa < sc ? sa : sc, hi = sa < sc ? sc : sa;
-        const int owner = blocks == 1 ? lo : ((((lo + hi) & 1) == 0) ? lo : hi);
-        if (owner >= rb && owner < re) { bi.push_back(a); bj.push_back(c); bd.push_back(edge_dist[e]); bt.push_back(edge_thresh[e]); }
-      }
-      rc = topolow_session_set_edges(ss[b], bi.data(), bj.data(), bd.data(), bt.data(), (int64_t)bi.size(), errbuf, errlen);
-    } catch (const std::bad_alloc&) {
-      set_err(errbuf, errlen, "out of host memory");
-      rc = TOPOLOW_ERR_HIP;
-    }
-  }
-  if (rc == TOPOLOW_OK) {
-    if (verbose) {
-      char what[64];
-      snprintf(what, sizeof what, "row-owner slabs, %d row blocks", blocks);
-      emit_header(opt, what, n, k0, cooling_rate, c_repulsion);
-    }
-    rc = topolow_sessions_run_sharded(ss.data(), blocks, initial_positions, n_iter, k0, cooling_rate, c_repulsion,
-                                      relative_epsilon, convergence_window, convergence_check_freq, opt.seed,
-                                      opt.slab_stages, opt.interrupt_cb, opt.interrupt_user, stats != nullptr,
-                                      positions_out, converged, iterations, final_mae, final_k, stats, errbuf, errlen);
-    if (rc == TOPOLOW_OK && verbose) {
-      int nc = 0;
-      if (topolow_session_check_trace(ss[0], nullptr, 0, &nc) == TOPOLOW_OK && nc > 0) {
-        std::vector<double> trace(3 * (size_t)nc);
-        if (topolow_session_check_trace(ss[0], trace.data(), nc, &nc) == TOPOLOW_OK)
-          emit_checks(opt, trace.data(), 0, nc, n_iter);
-      }
-      if (*converged)
-        emit_converged(opt, ss[0]->mailbox->ctl.plateau >= ss[0]->mailbox->ctl.window, *iterations, *final_mae);
-    }
-  }
-  for (topolow_session* s : ss) topolow_session_destroy(s);
-  if (rc == TOPOLOW_OK && stats) stats->total_seconds = now_s() - t_start;
-  return rc;
-}
-
-}  // extern "C"
-
-int layout_route(int n, int ndim, const topolow_options& opt, LayoutRoute* r, char* errbuf, size_t errlen) {
-  int schedule = opt.schedule;
-  const int gs_max_n = opt.gs_max_n > 0 ? opt.gs_max_n : kDefaultGsMaxN;
-  if (schedule == TOPOLOW_SCHEDULE_AUTO)
-    schedule = (n <= gs_max_n && ndim <= kMaxTunedDim) ? TOPOLOW_SCHEDULE_GS : TOPOLOW_SCHEDULE_SLAB;
-  if (schedule == TOPOLOW_SCHEDULE_GS) {
-    if (const int rc = check_gs_dim(ndim, errbuf, errlen)) return rc;
-  }
-
-  // exact GS: one workgroup while the problem fits its LDS, the tile schedule beyond that
-  const bool gs_fits_lds =
-      gs_lds_bytes(n, kernel_dim(ndim), (opt.precision == TOPOLOW_PRECISION_F32) ? 4 : 8) <= 150 * 1024 && n <= 2048;
-  r->schedule = schedule;
-  r->tile_gs = schedule == TOPOLOW_SCHEDULE_GS && !gs_fits_lds;
-  return TOPOLOW_OK;
-}
-
-// One embedding on a session, from session_create to session_finish: the slab schedule or tile Gauss-Seidel.  The
-// body of topolow_optimize_layout_exact (its loader: the 16 arguments) and of topolow_layout_prep_optimize (its
-// loader: the handle).  t_start: when the caller's entry began (stats->total_seconds, ->setup_seconds).
-int run_session_layout(int32_t n, int32_t ndim, bool tile_gs, const topolow_options& opt, const SessionLoader& load,
-                       const double* initial_positions, int32_t n_iter, double k0, double cooling_rate,
-                       double c_repulsion, double relative_epsilon, int32_t convergence_window,
-                       int32_t convergence_check_freq, int32_t verbose, double* positions_out, int32_t* converged,
-                       int32_t* iterations, double* final_mae, double* final_k, topolow_run_stats* stats,
-                       double t_start, char* errbuf, size_t errlen) {
-  const int precision = opt.precision == TOPOLOW_PRECISION_AUTO
-                            ? (tile_gs ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32)
-                            : opt.precision;
-  topolow_session* s = nullptr;
-  int rc = open_session(&s, n, ndim, tile_gs, precision, opt.device, opt.keep_labels ? nullptr : &opt.seed, load, errbuf, errlen);
-  if (rc != TOPOLOW_OK) return rc;
-  double t_dev0 = 0.0, t_dev1 = 0.0;
-  int iters_run = 0, stopped = 0;
-  double t_setup = 0.0;
-  do {
-    rc = topolow_session_set_positions(s, initial_positions, errbuf, errlen);
-    if (rc) break;
-    rc = topolow_session_begin(s, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon,
-                               convergence_window, convergence_check_freq, opt.seed,
-                               opt.slab_stages, errbuf, errlen);
-    if (rc) break;
-    t_dev0 = now_s();
-    t_setup = t_dev0 - t_start;
-    if (verbose)
-      emit_header(opt, tile_gs ? "tile Gauss-Seidel" : "row-owner slabs", n, k0, cooling_rate, c_repulsion);
-    int reported = 0;
-    std::vector<double> trace;
-    auto report = [&] {   // verbose: the checks since the last report (waits for the enqueued work)
-      int nc = 0;
-      if (topolow_session_check_trace(s, nullptr, 0, &nc) != TOPOLOW_OK || nc <= reported) return;
-      trace.resize(3 * (size_t)nc);
-      if (topolow_session_check_trace(s, trace.data(), nc, &nc) != TOPOLOW_OK) return;
-      emit_checks(opt, trace.data(), reported, nc, n_iter);
-      reported = nc;
-    };
-    rc = enqueue_run(s, [&]() -> int {
-      if (opt.interrupt_cb && opt.interrupt_cb(opt.interrupt_user)) {
-        set_err(errbuf, errlen, "interrupted by the caller");
-        return TOPOLOW_ERR_INTERRUPTED;
-      }
-      if (verbose) report();
-      return TOPOLOW_OK;
-    }, errbuf, errlen);
-    if (rc == TOPOLOW_OK && verbose) report();
-    if (rc) break;
-    double last = 0.0;
-    rc = topolow_session_sync(s, &iters_run, &stopped, &last, errbuf, errlen);
-    if (rc) break;
-    t_dev1 = now_s();
-    rc = topolow_session_finish(s, positions_out, converged, iterations, final_mae, final_k,
-                                errbuf, errlen);
-  } while (0);
-  if (rc == TOPOLOW_OK && stats) {
-    std::memset(stats, 0, sizeof *stats);
-    stats->schedule_used = tile_gs ? TOPOLOW_SCHEDULE_GS : TOPOLOW_SCHEDULE_SLAB;
-    stats->precision_used = precision;
-    stats->iterations_run = iters_run;
-    stats->n_checks = s->mailbox->n_checks;
-    stats->device_seconds = t_dev1 - t_dev0;
-    stats->setup_seconds = t_setup;
-    stats->stage_launches = s->stage_launches;
-  }
-  if (rc == TOPOLOW_OK && verbose && *converged)
-    emit_converged(opt, s->mailbox->ctl.plateau >= s->mailbox->ctl.window, *iterations, *final_mae);
-  topolow_session_destroy(s);
-  if (rc == TOPOLOW_OK && stats) stats->total_seconds = now_s() - t_start;
-  return rc;
-}
-
-extern "C" {
-
-// ---- the .Call payload -------------------------------------------------------------------
-int topolow_optimize_layout_exact(
-    const double* initial_positions, int32_t n, int32_t ndim,
-    const double* dissimilarity_matrix, const int32_t* threshold_matrix,
-    const int32_t* degrees, const int32_t* edge_i, const int32_t* edge_j,
-    const double* edge_dist, const int32_t* edge_thresh, int64_t n_edges, int32_t n_iter,
-    double k0, double cooling_rate, double c_repulsion, double relative_epsilon,
-    int32_t convergence_window, int32_t convergence_check_freq, int32_t verbose,
-    const topolow_options* opt_in, double* positions_out, int32_t* converged,
-    int32_t* iterations, double* final_mae, double* final_k, topolow_run_stats* stats,
-    char* errbuf, size_t errlen) {
-  if (n < 2) {  // reference :131
-    set_err(errbuf, errlen, "Need at least 2 points for embedding");
-    return TOPOLOW_ERR_TOO_FEW_POINTS;
-  }
-  if (!initial_positions || !dissimilarity_matrix || !threshold_matrix || !degrees ||
-      !positions_out || !converged || !iterations || !final_mae || !final_k ||
-      (n_edges > 0 && (!edge_i || !edge_j || !edge_dist || !edge_thresh)) || n_edges < 0) {
-    set_err(errbuf, errlen, "null argument");
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
-  topolow_options opt;
-  if (opt_in) opt = *opt_in; else topolow_default_options(&opt);
-  const double t_start = now_s();
-  if (opt.n_devices > 1 || opt.devices != nullptr) {   // ONE embedding over several GPUs / row blocks
-    topolow_shard_stats sh;
-    const int rcs = topolow_optimize_layout_exact_sharded(
-        initial_positions, n, ndim, dissimilarity_matrix, threshold_matrix, degrees, edge_i, edge_j, edge_dist,
-        edge_thresh, n_edges, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon, convergence_window,
-        convergence_check_freq, verbose, &opt, positions_out, converged, iterations, final_mae, final_k,
-        stats ? &sh : nullptr, errbuf, errlen);
-    if (rcs == TOPOLOW_OK && stats) {
-      std::memset(stats, 0, sizeof *stats);
-      stats->schedule_used = TOPOLOW_SCHEDULE_SLAB;
-      stats->precision_used = opt.precision == TOPOLOW_PRECISION_F64 ? TOPOLOW_PRECISION_F64 : TOPOLOW_PRECISION_F32;
-      stats->iterations_run = sh.iterations_run;
-      stats->n_checks = sh.n_checks;
-      stats->device_seconds = sh.loop_seconds;
-      stats->total_seconds = sh.total_seconds;
-      stats->stage_launches = sh.stage_launches;
-    }
-    return rcs;
-  }
-
-  LayoutRoute route;
-  if (const int rcr = layout_route(n, ndim, opt, &route, errbuf, errlen)) return rcr;
-  const int schedule = route.schedule;
-  const bool tile_gs = route.tile_gs;
-  if (schedule == TOPOLOW_SCHEDULE_GS && !tile_gs) {
-    const int precision = opt.precision == TOPOLOW_PRECISION_AUTO ? TOPOLOW_PRECISION_F64 : opt.precision;
-    topolow_problem pb;
-    std::memset(&pb, 0, sizeof pb);
-    pb.initial_positions = initial_positions; pb.n = n; pb.ndim = ndim;
-    pb.dissimilarity_matrix = dissimilarity_matrix; pb.threshold_matrix = threshold_matrix; pb.degrees = degrees;
-    pb.edge_i = edge_i; pb.edge_j = edge_j; pb.edge_dist = edge_dist; pb.edge_thresh = edge_thresh;
-    pb.n_edges = n_edges; pb.n_iter = n_iter; pb.k0 = k0; pb.cooling_rate = cooling_rate;
-    pb.c_repulsion = c_repulsion; pb.relative_epsilon = relative_epsilon; pb.convergence_window = convergence_window;
-    pb.convergence_check_freq = convergence_check_freq; pb.seed = opt.seed;
-    topolow_result res;
-    std::memset(&res, 0, sizeof res);
-    res.positions_out = positions_out;
-    double dev_s = 0.0;
-    std::vector<double> trace;
-    if (verbose) emit_header(opt, "one-workgroup Gauss-Seidel", n, k0, cooling_rate, c_repulsion);
-    const int rc = guarded(errbuf, errlen, [&] {
-      select_device(opt.device);
-      std::vector<double>* trace_out = verbose ? &trace : nullptr;
-      if (precision == TOPOLOW_PRECISION_F32)
-        gs_relax<float>(&pb, &res, 1, &dev_s, opt.interrupt_cb, opt.interrupt_user, trace_out);
-      else
-        gs_relax<double>(&pb, &res, 1, &dev_s, opt.interrupt_cb, opt.interrupt_user, trace_out);
-    });
-    if (rc != TOPOLOW_OK) return rc;
-    if (res.error_code == TOPOLOW_ERR_NONFINITE)
-      set_err(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.", res.error_iteration);
-    if (res.error_code == TOPOLOW_ERR_INTERRUPTED) set_err(errbuf, errlen, "interrupted by the caller");
-    if (res.error_code != TOPOLOW_OK) return res.error_code;
-    *converged = res.converged; *iterations = res.iterations; *final_mae = res.final_mae;
-    *final_k = res.final_k;
-    if (stats) {
-      std::memset(stats, 0, sizeof *stats);
-      stats->schedule_used = TOPOLOW_SCHEDULE_GS;
-      stats->precision_used = precision;
-      stats->iterations_run = res.iterations_run;
-      stats->n_checks = res.n_checks;
-      stats->device_seconds = dev_s;
-      stats->total_seconds = now_s() - t_start;
-    }
-    if (verbose) {
-      const int nc = (int)(trace.size() / 3);
-      emit_checks(opt, trace.data(), 0, nc, n_iter);
-      if (res.converged) {
-        // the rule that stopped the run: the last `window` checks all lie inside the plateau band
-        // (plateau) or above it (worsening); the last check decides
-        const bool plateau = nc > 0 && trace[3 * (nc - 1) + 1] <= res.final_mae * (1.0 + relative_epsilon);
-        emit_converged(opt, plateau, res.iterations, res.final_mae);
-      }
-    }
-    return TOPOLOW_OK;
-  }
-
-  // ---- slab schedule, or exact tile Gauss-Seidel (same session, different iteration body) ----
-  return run_session_layout(n, ndim, tile_gs, opt, [&](topolow_session* s, char* eb, size_t el) -> int {
-    int rc = TOPOLOW_OK;
-    // The 16 arguments carry the matrix twice: dense (800 + 400 MB at config 3) and as the list of its
-    // measured upper-triangle cells (R/core.R:383-402 and :429-436 build both from one matrix).  When
-    // the list is verified to BE the matrix, the encoded block is built from the list -- a quarter of
-    // the bytes over PCIe -- and the dense arrays are only read on the host, once, to verify it.
-    bool from_edges = false;
-    if (s->precision == TOPOLOW_PRECISION_F32 && getenv("TOPOLOW_DENSE_UPLOAD") == nullptr &&
-        edges_are_the_matrix(dissimilarity_matrix, threshold_matrix, n, edge_i, edge_j, edge_dist, edge_thresh, n_edges,
-                             true)) {
-      rc = topolow_session_load_coo(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, degrees, eb, el);
-      if (rc) return rc;
-      rc = topolow_session_set_edges(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, eb, el);
-      if (rc) return rc;
-      // the device-side fingerprint (count and hash of the block's measured cells == the list) rules
-      // out what the host pass cannot see cheaply: a pair listed twice
-      from_edges = topolow_session_uses_dense_mae(s) != 0;
-    }
-    if (!from_edges) {
-      rc = topolow_session_load_dense(s, dissimilarity_matrix, threshold_matrix, degrees, eb, el);
-      if (rc) return rc;
-      rc = topolow_session_set_edges(s, edge_i, edge_j, edge_dist, edge_thresh, n_edges, eb, el);
-      if (rc) return rc;
-    }
-    return rc;
-  }, initial_positions, n_iter, k0, cooling_rate, c_repulsion, relative_epsilon, convergence_window,
-  convergence_check_freq, verbose, positions_out, converged, iterations, final_mae, final_k, stats, t_start, errbuf, errlen);
 }
 
 // ---- the resident embedding: a session, the whole relaxation and the post-metrics from a prepared handle ----

@@ -228,7 +228,7 @@ struct topolow_session {
     int grid_cap = 0;              // > 0: at most this many workgroups (TOPOLOW_SYMMETRIC_GRID; tests: long runs on small problems)
     DevBuf<const uint32_t*> src_tab;   // the row blocks the tile-major copy is gathered from (one: the session's own)
     DevBuf<int> src_row0;
-    // the sweep sharded over the row-block sessions of a run (relax_sharded_engine.h): this session's segment
+    // the sweep sharded over the row-block sessions of a run (topolow_relax.hip: sharded_worker): this session's segment
     bool seg_thr = false;          // some session of the run holds threshold targets: the classifying instance
     int seg_first = 0, seg_last = -1;   // tile-rows that hold a tile of the segment
     int seg_slots = 0;             // sessions of the run (slots of an inbox)
