@@ -406,6 +406,54 @@ int topolow_kernel_velocity_ex(const double* positions, const double* times, int
                                double sigma_x, const uint64_t* excluded_bits, double* velocity, double* weight_sum,
                                int32_t device, int32_t chunk_cols, double* seconds, char* errbuf, size_t errlen);
 
+/* Replaces the two n x n distance matrices and the objective of the reference's scale_to_original_distances
+ * (R/visualization.R:624-640), the scale = TRUE step of reduce_dimensions: one pairwise pass on the device over the
+ * coordinates themselves, all of it in f64.
+ *   positions   n x ndim f64 column-major (host), 1 <= ndim <= 16: the map
+ *   reduced     n x k f64 column-major (host), 1 <= k <= ndim: its plot coordinates (the PCA scores)
+ *   scales      m f64, 1 <= m <= 8: all m are evaluated in the one pass (they share the square roots)
+ *   objective   m f64 out;  sum_orig, sum_reduced  1 f64 out each, or NULL: not wanted
+ * With d_ij = ||x_i - x_j|| and r_ij = ||y_i - y_j||:
+ *   objective[q] = sum_{i != j} |d_ij - scales[q] r_ij|     sum_orig = sum_{i != j} d_ij     sum_reduced = sum_{i != j} r_ij
+ * -- the reference's sums over the full matrices (the diagonal adds 0).  Only the pairs j < i are visited and the
+ * sums doubled, which is exact; a pair's term is |fma(-s, r, d)|.  The result is reproducible: no floating-point
+ * atomic; a row's terms are added in ascending column order inside units of 256 rows by chunk_cols columns, the rows
+ * of a unit by a fixed tree, the units in a fixed order -- an order that depends on n and the chunk alone (256
+ * columns up to 16 384 points, n / 64 rounded up to a multiple of 256 beyond), so every call returns the same bits,
+ * and a call with m scales returns the bits of m calls with one.
+ * TOPOLOW_ERR_BAD_ARGUMENT, before any device call: NULL positions, reduced, scales or objective; n < 2; k < 1 or
+ * k > ndim; m outside 1..8; a scale or a coordinate that is not finite (the reference's optimize fails on one).
+ * TOPOLOW_ERR_UNSUPPORTED: ndim > 16. */
+int topolow_scale_objective(const double* positions, const double* reduced, int32_t n, int32_t ndim, int32_t k,
+                            const double* scales, int32_t m, double* objective, double* sum_orig, double* sum_reduced,
+                            int32_t device, char* errbuf, size_t errlen);
+
+/* The same call with the columns per unit chosen by the caller and the device time measured (a test and study
+ * entry: tests/study/reduce_timing.py).  chunk_cols: 0 = the library's width, else 64, 128, 256 or 512 (anything
+ * else: TOPOLOW_ERR_BAD_ARGUMENT).  Two widths group the additions differently, so their results may differ in the
+ * last bits; one width always returns the same bits.  seconds: NULL, or 1 double out -- the two kernels from device
+ * events (the uploads and the download are not in it). */
+int topolow_scale_objective_ex(const double* positions, const double* reduced, int32_t n, int32_t ndim, int32_t k,
+                               const double* scales, int32_t m, double* objective, double* sum_orig, double* sum_reduced,
+                               int32_t device, int32_t chunk_cols, double* seconds, char* errbuf, size_t errlen);
+
+/* The reference's scale_to_original_distances: the scale s in [lower, upper] that minimises objective(s) above.
+ * positions and reduced are uploaded once; Brent's fmin -- the algorithm behind R's optimize: golden section with
+ * parabolic steps, eps = sqrt(DBL_EPSILON), tol1 = eps |x| + tol / 3 -- runs on the host inside the library, every
+ * evaluation one launch pair with one scale.  (The reference calls optimize on [0.01, 40] with R's default tol,
+ * DBL_EPSILON^0.25.)
+ *   scale        1 f64 out: the minimiser;  objective  1 f64 out, or NULL: its objective, the smallest one evaluated
+ *   evaluations  1 i32 out, or NULL: how often the objective was evaluated
+ *   trace_scale, trace_objective   NULL, or trace_len f64 each: the first trace_len evaluated (s, objective) pairs
+ *                in the order of evaluation (both or neither)
+ * TOPOLOW_ERR_BAD_ARGUMENT, before any device call: NULL positions, reduced or scale; n < 2; k < 1 or k > ndim; a
+ * bound or tol that is not finite; lower >= upper; tol <= 0; trace_len < 0 or one trace array without the other; a
+ * coordinate that is not finite.  TOPOLOW_ERR_UNSUPPORTED: ndim > 16. */
+int topolow_scale_to_original_distances(const double* positions, const double* reduced, int32_t n, int32_t ndim, int32_t k,
+                                        double lower, double upper, double tol, double* scale, double* objective,
+                                        int32_t* evaluations, double* trace_scale, double* trace_objective,
+                                        int32_t trace_len, int32_t device, char* errbuf, size_t errlen);
+
 /* ---------------------------------------------------------------------------------------
  * Prepared layout: the reference's pre-processing (R/core.R:269-436) on the device -- ordering means, degrees,
  * the upper-triangle edge list in which() order, the symmetric dense fill, the scale of the random-walk start.

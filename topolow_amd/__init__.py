@@ -25,10 +25,18 @@ from .error_metrics import (  # noqa: F401
     fit_statistics,
 )
 from .velocity import default_bandwidths, kernel_velocity, silverman_bandwidth  # noqa: F401
+from .reduce import (  # noqa: F401
+    DimReductionConfig,
+    pca_scores,
+    reduce_dimensions,
+    scale_to_original_distances,
+    temporal_map_data,
+)
 
 __all__ = ["euclidean_embedding", "create_topolow_map", "print_topolow", "summary_topolow",
            "Topolow", "RMatrix", "options", "set_seed", "NativeError", "prepare_layout_call",
            "check_matrix_connectivity", "subsample_dissimilarity_matrix", "data_characteristics",
            "adjust_ndim_range", "analyze_network_structure", "prune_sparse_matrix", "error_calculator_comparison",
            "calculate_prediction_interval", "fit_statistics", "FitStatistics", "kernel_velocity",
-           "silverman_bandwidth", "default_bandwidths"]
+           "silverman_bandwidth", "default_bandwidths", "DimReductionConfig", "pca_scores", "reduce_dimensions",
+           "scale_to_original_distances", "temporal_map_data"]

@@ -203,6 +203,9 @@ PROTOTYPES = {
     "topolow_post_metrics_ex": (INT, (dp, I32, I32, dp, ip, dp, dp, i64p, I32, I32, dp, *ERR)),
     "topolow_kernel_velocity": (INT, (dp, dp, I32, I32, F64, F64, u64p, dp, dp, I32, *ERR)),
     "topolow_kernel_velocity_ex": (INT, (dp, dp, I32, I32, F64, F64, u64p, dp, dp, I32, I32, dp, *ERR)),
+    "topolow_scale_objective": (INT, (dp, dp, I32, I32, I32, dp, I32, dp, dp, dp, I32, *ERR)),
+    "topolow_scale_objective_ex": (INT, (dp, dp, I32, I32, I32, dp, I32, dp, dp, dp, I32, I32, dp, *ERR)),
+    "topolow_scale_to_original_distances": (INT, (dp, dp, I32, I32, I32, F64, F64, F64, dp, dp, ip, dp, dp, I32, I32, *ERR)),
     # ---- prepared layout: a matrix that stays on the device
     "topolow_layout_prep_create": (INT, (vpp, dp, i8p, I32, I32, I32, ip, I32, prep_infop, *ERR)),
     "topolow_layout_prep_fetch": (INT, (vp, ip, ip, ip, ip, dp, ip, dp, ip, dp, i8p, *ERR)),
@@ -867,6 +870,61 @@ def kernel_velocity(positions, times, sigma_t: float, sigma_x: float, excluded_b
     if timing is not None:
         timing[:] = [secs.value]
     return vel, w
+
+
+def _map_and_reduced(positions, reduced):
+    pos, red = _f64F(positions), _f64F(reduced)
+    if pos.ndim != 2 or red.ndim != 2:
+        raise ValueError("positions and reduced must be matrices, n x ndim and n x k")
+    if red.shape[0] != pos.shape[0]:
+        raise ValueError("reduced must hold one row per position")
+    return pos, red
+
+
+def scale_objective(positions, reduced, scales, device: Optional[int] = None, chunk_cols: Optional[int] = None,
+                    timing: Optional[list] = None):
+    """The objective of the reference's scale_to_original_distances (R/visualization.R:629-632) on the GPU, with no
+    n x n matrix: returns (F, G, H) with F[q] = sum_{i != j} |d_ij - scales[q] r_ij| (up to 8 scales in one pass),
+    G = sum d_ij and H = sum r_ij, d and r the pairwise distances of positions (n x ndim) and reduced (n x k).
+    `chunk_cols` (64, 128, 256 or 512; None = the library's width, a function of n) and `timing` (a list that
+    receives the seconds of the kernels) reach the _ex entry: for tests and tests/study/reduce_timing.py."""
+    lib = load()
+    pos, red = _map_and_reduced(positions, reduced)
+    s = _f64(np.atleast_1d(scales))
+    if s.ndim != 1:
+        raise ValueError("scales must be a vector")
+    F = np.empty(s.size, dtype=np.float64)
+    G, H, secs = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    dev = int(options.get("device", -1)) if device is None else int(device)
+    shared = (_ptr(pos), _ptr(red), pos.shape[0], pos.shape[1], red.shape[1], _ptr(s), s.size, _ptr(F), C.byref(G),
+              C.byref(H), dev)
+    if chunk_cols is None and timing is None:
+        _call(lib.topolow_scale_objective, *shared)
+    else:
+        _call(lib.topolow_scale_objective_ex, *shared, int(chunk_cols or 0), C.byref(secs) if timing is not None else None)
+    if timing is not None:
+        timing[:] = [secs.value]
+    return F, G.value, H.value
+
+
+def scale_to_original_distances(positions, reduced, lower: float = 0.01, upper: float = 40.0,
+                                tol: float = float(np.finfo(np.float64).eps) ** 0.25, device: Optional[int] = None,
+                                trace_len: int = 0):
+    """The scale in [lower, upper] that minimises scale_objective, by Brent's fmin inside the library (the reference's
+    optimize call, R/visualization.R:635-636): returns (scale, objective, evaluations, trace) with trace the first
+    trace_len evaluated (s, F) pairs as a k x 2 array."""
+    lib = load()
+    pos, red = _map_and_reduced(positions, reduced)
+    scale, objective, evals = C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+    trace_len = int(trace_len)
+    ts = np.full(max(trace_len, 0), np.nan)
+    tf = np.full(max(trace_len, 0), np.nan)
+    dev = int(options.get("device", -1)) if device is None else int(device)
+    _call(lib.topolow_scale_to_original_distances, _ptr(pos), _ptr(red), pos.shape[0], pos.shape[1], red.shape[1],
+          float(lower), float(upper), float(tol), C.byref(scale), C.byref(objective), C.byref(evals),
+          _ptr(ts) if trace_len > 0 else None, _ptr(tf) if trace_len > 0 else None, trace_len, dev)
+    kept = min(trace_len, evals.value)
+    return scale.value, objective.value, evals.value, np.column_stack([ts[:kept], tf[:kept]])
 
 
 ORDER_PRESERVED, ORDER_DEVICE_EXACT, ORDER_DEVICE_GAP, ORDER_DECLINED = 0, 1, 2, 3
