@@ -276,24 +276,47 @@ def test_drivers_compile_no_kernel_and_one_source_holds_the_gs_kernels():
     assert [part for part, names in gs.items() if names] == ["topolow_gs.part.gfx950.s"]
 
 
+def test_each_source_of_the_prepared_handle_holds_its_own_kernels():
+    """The prepared handle is four sources, divided by the kernel headers they own: the spectrum kernels are in
+    topolow_spectrum.hip's listing alone, the graph and prune kernels in topolow_prep_graph.hip's, the fold and fit
+    kernels in topolow_prep_fold.hip's, and topolow_prep.hip keeps the six kernels of relax_prep.h -- so an edit of
+    the prune loop recompiles no fold, fit, spectrum or prep kernel."""
+    import subprocess
+    csrc = os.path.join(ROOT, "topolow_amd", "csrc")
+    subprocess.run(["make", "-C", csrc, "asm"], check=True, capture_output=True)
+    kernels = {}
+    for part in os.listdir(csrc):
+        if part.endswith(".part.gfx950.s"):
+            names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", open(os.path.join(csrc, part)).read(), re.M)
+            kernels[part[:-len(".part.gfx950.s")]] = names
+    # a kernel's family: how its function name begins inside the mangled one (_ZN7topolow<length><name>...).  The six
+    # of relax_prep.h by name: the two kernels a session loads from a handle with (relax_kernels.h) are prep_* as well.
+    six = ("prep_sums_kernel", "prep_finish_sums_kernel", "prep_dense_kernel", "prep_edge_count_kernel",
+           "prep_edge_write_kernel", "prep_reorder_kernel")
+    families = {"topolow_spectrum": ("spec_",), "topolow_prep_graph": ("graph_", "prune_"),
+                "topolow_prep_fold": ("fold_", "fit_"), "topolow_prep": tuple(k + "E" for k in six)}
+    for source, begins in families.items():
+        pattern = re.compile(r"_ZN7topolow\d+(%s)" % "|".join(begins))
+        held = {s: [k for k in names if pattern.match(k)] for s, names in kernels.items()}
+        assert [s for s, names in held.items() if names] == [source], (begins, held)
+        assert sorted(kernels[source]) == sorted(held[source]), source     # and it holds no kernel of another family
+    assert len(kernels["topolow_prep"]) == len(six)
+    assert len(kernels["topolow_spectrum"]) == 10 and len(kernels["topolow_prep_graph"]) == 7
+    assert len(kernels["topolow_prep_fold"]) == 10
+
+
 def test_library_exports_the_c_abi_and_nothing_else_of_its_own():
     """The defined dynamic symbols of the built library: every function of _native.PROTOTYPES (the C ABI, checked
     against the header elsewhere), and beyond them only what the compiler and the HIP runtime put there -- mangled names
     (the kernels' host stubs and handles), the fat binary's and the C runtime's.  A helper that crosses a source
-    boundary has hidden visibility (csrc/topolow_session.h, topolow_prep.h, topolow_drivers.h): no topolow_* name
-    outside the table may show, and no unmangled helper name but the ones the library has always had -- helpers of
-    topolow_prep.hip, whose anonymous namespaces stand inside its extern "C" block (a list that may shrink, never
-    grow)."""
+    boundary has hidden visibility (csrc/topolow_session.h, topolow_prep.h, topolow_drivers.h), one that does not
+    stands in an anonymous namespace outside extern "C": no topolow_* name outside the table may show, and no
+    unmangled helper name at all."""
     import subprocess
     if not os.path.exists(_native.LIB_PATH):
         pytest.skip("libtopolow_relax.so is not built")
     out = subprocess.run(["nm", "-D", "--defined-only", _native.LIB_PATH], check=True, capture_output=True, text=True).stdout
     symbols = {line.split()[-1] for line in out.splitlines() if line.strip()}
     own = {s for s in symbols if not s.startswith(("_Z", "__hip_", "_init", "_fini"))}
-    prep_helpers = set("""fit_check_arguments fit_run fold_grid prep_check_subset prep_fold_alloc prep_fold_check_handle
-                          prep_fold_prepare prep_fold_symmetry prep_is_permutation prep_order_in_ok prep_passes
-                          prune_all_alive prune_launch_count prune_row_bits spec_all_finite spec_bisect
-                          spec_characteristics spec_key_value spec_pick_digit spec_tridiagonalize""".split())
-    assert set(_native.PROTOTYPES) <= own
-    assert own - set(_native.PROTOTYPES) <= prep_helpers
+    assert own == set(_native.PROTOTYPES)
     assert not [s for s in symbols - own if re.match(r"_?_?topolow_", s)]

@@ -1,7 +1,7 @@
 // topolow_amd/csrc/relax_fit.h -- the fit report of a resident embedding: the signed errors truth - distance of the
 // handle's matrix against a set of positions, their moments per series and their exact order statistics (reference
 // R/error_metrics.R:55-202, R/visualization.R:2626-2648; host pipeline: topolow_layout_prep_fit_report /
-// _fit_order_stats in topolow_prep.hip; the NumPy specification: topolow_amd/error_metrics.py, fit_statistics).
+// _fit_order_stats in topolow_prep_fold.hip; the NumPy specification: topolow_amd/error_metrics.py, fit_statistics).
 //
 // As relax_post.h's resident kernel: BUFFER coordinates, one workgroup per LINE a of the handle's buffer, the matrix
 // gathered through ord (nullable) -- cell (a, b) is B[ord[a] * n + ord[b]] -- so the source line is contiguous and the

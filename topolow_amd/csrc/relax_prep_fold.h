@@ -1,6 +1,6 @@
 // topolow_amd/csrc/relax_prep_fold.h -- one cross-validation fold prepared from a resident handle: the fold mask, the
 // ordering sums and degrees of the masked matrix, the held-out pairs and the scored cells (host pipeline:
-// topolow_layout_prep_fold / _cv_sweep in topolow_prep.hip; the host twin on the cell list: relax_fold.h, fold_pairs).
+// topolow_layout_prep_fold / _cv_sweep in topolow_prep_fold.hip; the host twin on the cell list: relax_fold.h, fold_pairs).
 //
 // A fold is its picks -- linear column-major indices r + c * n -- and their mirrors (fold_dropped).  The kernels work
 // on a FOLD MASK, one bit per cell of the handle's buffer, bit a * n + b for the cell B[a * n + b]; it lives in the
@@ -11,11 +11,11 @@
 // handle's buffer as COLUMN-major whatever `transposed` says: the slow index a is the column, the contiguous index b
 // the row, and a pick IS its bit index.  Nothing here writes vals or codes.
 //
-// The masked sums are prep_tile_sums of relax_prep.h with this file's policy, the compaction prep_column_counts and
+// The masked sums are prep_tile_sums of relax_prep_device.h with this file's policy, the compaction prep_column_counts and
 // prep_rank_trip of relax_prep_rank.h with this file's cell test: only what a fold adds to them is written here.
 #pragma once
 
-#include "relax_prep.h"
+#include "relax_prep_device.h"
 
 namespace topolow {
 

@@ -1,6 +1,6 @@
 // topolow_amd/csrc/relax_prep_graph.h -- the measurement graph of a resident matrix and its sub-handles
 // (reference R/utils.R:199-253 check_matrix_connectivity over R/diagnostics.R:442-468, R/utils.R:321-463
-// subsample_dissimilarity_matrix; host pipeline: topolow_layout_prep_connectivity / _subsample in topolow_prep.hip).
+// subsample_dissimilarity_matrix; host pipeline: topolow_layout_prep_connectivity / _subsample in topolow_prep_graph.hip).
 //
 // Two kernel groups.  Both work in BUFFER coordinates, as relax_prep.h does: B[a * n + b], a the slow index.  The graph
 // takes either cell of a pair, so it is the same graph in either layout and no transposed read is made.
@@ -19,7 +19,7 @@
 // (2) graph_gather_kernel: lines [a0, a0 + lines) of child = parent[sub, sub], values and codes, device to device.
 #pragma once
 
-#include "relax_prep.h"
+#include "relax_common.h"
 
 namespace topolow {
 

@@ -1,6 +1,6 @@
 // topolow_amd/csrc/relax_prep_prune.h -- degrees of a resident matrix and the pruning of its poorly connected points
 // (reference R/diagnostics.R:434-475 analyze_network_structure, R/data_preprocessing.R:1225-1503 prune_sparse_matrix;
-// host pipeline: topolow_layout_prep_degrees / _prune in topolow_prep.hip).
+// host pipeline: topolow_layout_prep_degrees / _prune in topolow_prep_graph.hip).
 //
 // Everything here works on the packed bits graph_bits_kernel (relax_prep_graph.h) leaves: the n x n doubles are read
 // once per call.  The counts are along MATRIX ROWS and the matrix need not be symmetric, so the bits must be

@@ -2,14 +2,14 @@
 // device: the median of the numeric cells, the double-centred matrix B = -0.5 J D^2 J of the median-filled matrix, and
 // all eigenvalues of a symmetric f64 matrix by Householder tridiagonalisation and Sturm bisection
 // (host pipeline: topolow_layout_prep_spectrum / topolow_symmetric_eigenvalues / topolow_tridiagonal_eigenvalues in
-// topolow_prep.hip; NumPy model of the same algorithm: tests/models/spectrum_model.py).
+// topolow_spectrum.hip; NumPy model of the same algorithm: tests/models/spectrum_model.py).
 //
 // As relax_prep.h, every matrix kernel works in BUFFER coordinates, B[a * n + b] with b the contiguous index.
 // Nothing here adds floating-point numbers in an order that depends on the grid or on timing: histograms are integer
 // atomics, every floating-point reduction has fixed partitions added in a fixed order.
 #pragma once
 
-#include "relax_prep.h"
+#include "relax_prep_device.h"
 
 namespace topolow {
 
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kSpecThreads) void spec_select_kernel(
 
 // ---- 2. the centred matrix -----------------------------------------------------------------------------------------
 // x = the cell where it is numeric, otherwise the median; D2 = x * x.  The sums of D2 along both directions by the
-// first pass's rule (relax_prep.h: prep_tile_sums): one partial per (point, block of 64 cells), the cells added in
+// first pass's rule (relax_prep_device.h: prep_tile_sums): one partial per (point, block of 64 cells), the cells added in
 // index order from 0.0 -- here every cell counts, the diagonal too.
 __global__ __launch_bounds__(kPrepThreads) void spec_square_sums_kernel(
     const double* __restrict__ vals, const int8_t* __restrict__ codes, int n, double median,

@@ -1,5 +1,5 @@
 // topolow_amd/csrc/topolow_drivers.h -- what the drivers in topolow_drivers.hip share with the entries of a prepared
-// handle (topolow_prep.hip): opening and running a whole-problem session, the route of an embedding, and the sweep
+// handle (topolow_prep.hip, topolow_prep_fold.hip): opening and running a whole-problem session, the route of an embedding, and the sweep
 // over resident folds; and the one door to the one-workgroup Gauss-Seidel kernels (topolow_gs.hip).  Types,
 // declarations and the one template; no kernels.
 #pragma once

@@ -1,6 +1,6 @@
 // topolow_amd/csrc/topolow_drivers.hip -- the drivers of libtopolow_relax.so: whole embeddings and cross-validation
 // sweeps run on sessions, the host's fold entries and the verbose report.  Host code only: it reaches a session through
-// the C ABI and the fields of topolow_session.h, as topolow_prep.hip does, and this source compiles no kernel -- it
+// the C ABI and the fields of topolow_session.h, as the handle's sources do, and this source compiles no kernel -- it
 // includes no header that defines a plain __global__ function (relax_gs.h is here for gs_lds_bytes).
 //
 // Replaces the native half of the reference's euclidean_embedding():

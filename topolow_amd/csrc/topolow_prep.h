@@ -1,7 +1,9 @@
 // topolow_amd/csrc/topolow_prep.h -- the prepared handle as the library's sources see it: struct topolow_layout_prep
 // and what it is made of, the pinned staging and the stream pipe the post-metrics share with the handle's entries, and
-// the functions that cross a source boundary (topolow_prep.hip <-> topolow_relax.hip, topolow_post.hip).  Types and
-// declarations only; the kernels live in the sources.
+// the functions that cross a source boundary: between the handle's four sources (topolow_prep.hip: create, fetch and
+// the entries that run from a handle; topolow_prep_graph.hip: connectivity, sub-handles, degrees, pruning;
+// topolow_spectrum.hip; topolow_prep_fold.hip: folds, CV sweep, fit report) and to topolow_relax.hip and
+// topolow_post.hip.  Types, declarations and a few host helpers; the kernels live in the sources.
 #pragma once
 
 #include "topolow_session.h"
@@ -20,6 +22,31 @@ void prep_alloc(DevBuf<T>& buf, size_t count, const char* what) {
                                                 std::to_string(count * sizeof(T)) + " bytes): " + e.msg};
   }
 }
+
+// Counts per column -> exclusive offsets, off[0 .. n]; returns the total.
+int64_t prep_offsets(const int32_t* per_col, size_t n, int64_t* off) {
+  off[0] = 0;
+  for (size_t j = 0; j < n; ++j) off[j + 1] = off[j] + per_col[j];
+  return off[n];
+}
+
+// The host's side of a radix select over prep_order_key (the median of the spectrum, the fit report's order statistics).
+// Rank `rank` (0-based) among the keys counted in hist: its digit; rank becomes the rank within that digit.
+unsigned spec_pick_digit(const unsigned long long* hist, unsigned long long& rank) {
+  unsigned digit = 0;
+  while (digit < 255 && rank >= hist[digit]) rank -= hist[digit++];
+  return digit;
+}
+
+double spec_key_value(unsigned long long key) {
+  const unsigned long long bits = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
+  double v;
+  std::memcpy(&v, &bits, 8);
+  return v;
+}
+
+constexpr size_t kPrepChunkBytes = (size_t)32 << 20;
+constexpr int kPrepSlots = 3;
 
 constexpr int kPostSlots = 3;
 constexpr int kPostDefaultStaging = TOPOLOW_POST_STAGING_PINNED;
@@ -119,7 +146,8 @@ struct PrepSums {
     prep_alloc(totals, 1, "the totals");
   }
   // Behind the tile kernels on `stream`: the partials added per point, all of it sent down; the caller synchronises.
-  void fetch(int n, hipStream_t stream);   // (defined in topolow_prep.hip: it launches a kernel of relax_prep.h)
+  // Defined in topolow_prep.hip, for PrepTotals and FoldTotals: it launches a kernel of relax_prep.h.
+  void fetch(int n, hipStream_t stream);
   // topolow_layout_order_from_sums on the fetched sums, the counts less the diagonal; rows at row_at, columns at col_at.
   int32_t order(int n, size_t row_at, size_t col_at, bool exact_sums, bool negative_or_infinite, int32_t* order_out) const {
     std::vector<int64_t> row_cnt((size_t)n), col_cnt((size_t)n);
@@ -188,8 +216,28 @@ struct topolow_layout_prep {
   }
 };
 
-// ---- defined in topolow_prep.hip, called by topolow_session_load_prepared (topolow_relax.hip) ----
+// ---- defined in topolow_prep.hip, called by topolow_session_load_prepared (topolow_relax.hip) and the fit report ----
 void prep_compact_edges(topolow_layout_prep* p, hipStream_t stream);
 int prep_check_usable(const topolow_layout_prep* p, char* errbuf, size_t errlen);
+
+// How the lines of an n x n matrix arrive on the device: in chunks of whole 64-line blocks of about kPrepChunkBytes.
+struct PrepChunks {
+  int chunk_lines, n_chunks, slots;
+  size_t chunk_cells;
+  explicit PrepChunks(int n) {
+    const size_t N = (size_t)n;
+    const int nb = (n + kPrepTile - 1) / kPrepTile;
+    chunk_lines = (int)std::min<size_t>(
+        (size_t)nb * kPrepTile, std::max<size_t>(kPrepTile, kPrepChunkBytes / (N * 8) / kPrepTile * kPrepTile));
+    n_chunks = (n + chunk_lines - 1) / chunk_lines;
+    slots = std::min(kPrepSlots, n_chunks);
+    chunk_cells = (size_t)std::min(chunk_lines, n) * N;
+  }
+};
+
+// ---- defined in topolow_prep.hip, called by topolow_layout_prep_subsample (topolow_prep_graph.hip) as well ----
+bool prep_order_in_ok(int32_t preserve_order, const int32_t* order_in, int n, char* errbuf, size_t errlen);
+void prep_passes(topolow_layout_prep* p, int32_t preserve_order, const int32_t* order_in, topolow_layout_prep_info* info,
+                 double t0, const PrepChunks& g, const std::function<void(PostPipe&, int, int, int)>& arrive);
 
 #pragma GCC visibility pop

@@ -3,7 +3,7 @@
 // -- the launch helpers, the symmetric sweep's host code, the row-sharded engine and the topolow_session_* C ABI of
 // include/topolow_relax.h.  The drivers that run whole embeddings on sessions are topolow_drivers.hip, the
 // one-workgroup Gauss-Seidel entries topolow_gs.hip, the post-metrics topolow_post.hip, the prepared handle
-// topolow_prep.hip.
+// topolow_prep.hip with topolow_prep_graph.hip, topolow_spectrum.hip and topolow_prep_fold.hip.
 //
 // There is no CPU fallback in this library: without a HIP device every entry point that
 // computes returns TOPOLOW_ERR_NO_DEVICE.
@@ -1200,7 +1200,7 @@ int cv_check_session(const topolow_session* s, char* errbuf, size_t errlen) {
 
 }  // namespace
 
-// ---- the three functions topolow_prep.hip calls as well (declared in topolow_session.h) ----
+// ---- the three functions topolow_prep_fold.hip calls as well (declared in topolow_session.h) ----
 
 // The device half of a hold-out, shared by topolow_session_hold_out and the folds prepared on the device
 // (topolow_layout_prep_cv_sweep).  fill(lo, hi) enqueues on s->stream whatever writes the n_pairs held-out pairs into

@@ -308,7 +308,7 @@ struct topolow_session {
   }
 };
 
-// ---- defined in topolow_relax.hip, called by the folds of a prepared handle (topolow_prep.hip: HandleFolds) ----
+// ---- defined in topolow_relax.hip, called by the folds of a prepared handle (topolow_prep_fold.hip: HandleFolds) ----
 int cv_check_hold_out(const topolow_session* s, char* errbuf, size_t errlen);
 void cv_hold_out_pairs(topolow_session* s, long long np, const int32_t* degrees, const std::function<void(int*, int*)>& fill);
 void cv_score_device(topolow_session* s, const int* d_i, const int* d_j, const double* d_truth, long long n_pairs,
