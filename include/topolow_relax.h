@@ -905,6 +905,58 @@ int topolow_layout_prep_fit_order_stats(topolow_layout_prep* p, const double* po
                                         char* errbuf, size_t errlen);
 
 /* ---------------------------------------------------------------------------------------
+ * The fit's diagnostic plots without their points (reference R/visualization.R:2616-2701 scatterplot_fitted_vs_true,
+ * R/diagnostics.R:128-183 plot_embedding_quality): the extent of a series, exact 2-D bin counts and the mass
+ * distribution of density()'s linear binning, one pass each over the resident matrix, integer atomics only -- the same
+ * numbers on every call.  p, positions, ndim, picks, n_picks and series mean exactly what they mean for
+ * topolow_layout_prep_fit_report: the same three series (the diagonal counts; +-Inf cells are left out of every series),
+ * the same marking and clearing of the fold mask, the same handles served, the handle left as it was on every return,
+ * and TOPOLOW_ERR_BAD_ARGUMENT with a message before any device call for a NULL handle, positions or output, ndim < 1,
+ * n_picks < 0, picks NULL with n_picks > 0, an unknown series or axis and the limits stated below.
+ * DEVIATION from plot_embedding_quality, which masks the diagonal: here the diagonal counts, as in the fit report.
+ * A cell offers four quantities, v its value and r the distance with the bits of topolow_est_distances.  RESIDUAL is
+ * there so that neither plot's sign convention needs reversed edges, which would move the closed side of a bin.
+ * ------------------------------------------------------------------------------------- */
+#define TOPOLOW_FIT_AXIS_TRUE 0      /* v */
+#define TOPOLOW_FIT_AXIS_PREDICTED 1 /* r */
+#define TOPOLOW_FIT_AXIS_ERROR 2     /* v - r */
+#define TOPOLOW_FIT_AXIS_RESIDUAL 3  /* r - v */
+#define TOPOLOW_FIT_MAX_BINS 8192    /* nx * ny of topolow_layout_prep_fit_hist2d */
+#define TOPOLOW_FIT_MAX_GRID 4096    /* m of topolow_layout_prep_fit_linear_bins */
+
+/* out[2 a], out[2 a + 1]: the bits of the smallest and the largest value of axis a (TOPOLOW_FIT_AXIS_*) over the
+ * series; NaN when the series is empty.  count_out: the series' count. */
+int topolow_layout_prep_fit_extent(topolow_layout_prep* p, const double* positions, int32_t ndim, const int64_t* picks,
+                                   int64_t n_picks, int32_t series, double* out /* 8 */, int64_t* count_out,
+                                   char* errbuf, size_t errlen);
+
+/* Exact 2-D bin counts of (x_axis, y_axis) over the series.
+ *   x_edges, y_edges   nx + 1 and ny + 1 finite, strictly increasing f64 (host); nx, ny >= 1, nx ny <= TOPOLOW_FIT_MAX_BINS
+ *   counts_out         nx * ny, y fastest: counts_out[kx * ny + ky]
+ * A value x lies in bin k iff edges[k] <= x < edges[k + 1]; the last bin also takes x == edges[nx] (NumPy's histogram2d
+ * with explicit edges).  The bin is found by comparing against the edges themselves, never from a formula, so any
+ * strictly increasing edges work and a host that compares the same doubles gets the same counts.  A cell of the series
+ * outside either axis goes to outside_out: the sum of counts_out plus outside_out equals count_out. */
+int topolow_layout_prep_fit_hist2d(topolow_layout_prep* p, const double* positions, int32_t ndim, const int64_t* picks,
+                                   int64_t n_picks, int32_t series, int32_t x_axis, const double* x_edges, int32_t nx,
+                                   int32_t y_axis, const double* y_edges, int32_t ny, int64_t* counts_out,
+                                   int64_t* outside_out, int64_t* count_out, char* errbuf, size_t errlen);
+
+/* The mass distribution of density()'s linear binning (R's BinDist) of one axis over the series, in integers:
+ *   delta = (up - lo) / (m - 1); xpos = (x - lo) / delta; ix = floor(xpos); fx = xpos - ix
+ * For 0 <= ix <= m - 2 the cell adds 1 to count_out[ix] and (uint64)(fx 2^32) to frac_out[ix]; every other cell of the
+ * series goes to outside_out; total_out is the series' count.  The host forms mass[g] = (count[g] - S[g]) + S[g - 1]
+ * with S = frac 2^-32.  Every operation is a plain IEEE f64 one, so a host doing the same gets the same integers.
+ * DEVIATION from BinDist: the quantisation of fx moves a cell's mass by at most 2^-32 of itself.
+ *   m        2 <= m <= TOPOLOW_FIT_MAX_GRID;  lo < up, both finite
+ * TOPOLOW_ERR_UNSUPPORTED when n n >= 2^32: a bin's fraction sum must fit 64 bits. */
+int topolow_layout_prep_fit_linear_bins(topolow_layout_prep* p, const double* positions, int32_t ndim,
+                                        const int64_t* picks, int64_t n_picks, int32_t series, int32_t axis, double lo,
+                                        double up, int32_t m, int64_t* count_out /* m */,
+                                        uint64_t* frac_out /* m, units of 2^-32 */, int64_t* outside_out,
+                                        int64_t* total_out, char* errbuf, size_t errlen);
+
+/* ---------------------------------------------------------------------------------------
  * Device-resident session: the same relaxation with inputs kept in HBM, for callers that
  * run many iterations / many embeddings on data they already hold on the GPU (bench.py, the
  * row-sharded multi-GPU driver).  Pointers named d_* are DEVICE pointers.

@@ -19,8 +19,14 @@ from .subsample import check_matrix_connectivity, subsample_dissimilarity_matrix
 from .prune import analyze_network_structure, prune_sparse_matrix  # noqa: F401
 from .spectrum import adjust_ndim_range, data_characteristics  # noqa: F401
 from .error_metrics import (  # noqa: F401
+    BinnedCloud,
+    Density,
+    EmbeddingQualityData,
     FitStatistics,
+    bw_nrd0,
     calculate_prediction_interval,
+    density_default,
+    embedding_quality_data,
     error_calculator_comparison,
     fit_statistics,
 )
@@ -39,4 +45,5 @@ __all__ = ["euclidean_embedding", "create_topolow_map", "print_topolow", "summar
            "adjust_ndim_range", "analyze_network_structure", "prune_sparse_matrix", "error_calculator_comparison",
            "calculate_prediction_interval", "fit_statistics", "FitStatistics", "kernel_velocity",
            "silverman_bandwidth", "default_bandwidths", "DimReductionConfig", "pca_scores", "reduce_dimensions",
-           "scale_to_original_distances", "temporal_map_data"]
+           "scale_to_original_distances", "temporal_map_data", "embedding_quality_data", "EmbeddingQualityData",
+           "BinnedCloud", "Density", "density_default", "bw_nrd0"]

@@ -112,6 +112,11 @@ FIT_IN, FIT_OUT, FIT_ALL = 0, 1, 2   # TOPOLOW_FIT_*
 FIT_MAX_RANKS = 8                     # TOPOLOW_FIT_MAX_RANKS
 FIT_RANK_UPPER = 1 << 32              # TOPOLOW_FIT_RANK_UPPER
 _FIT_SERIES = {"in": FIT_IN, "out": FIT_OUT, "all": FIT_ALL, FIT_IN: FIT_IN, FIT_OUT: FIT_OUT, FIT_ALL: FIT_ALL}
+FIT_AXIS_TRUE, FIT_AXIS_PREDICTED, FIT_AXIS_ERROR, FIT_AXIS_RESIDUAL = 0, 1, 2, 3   # TOPOLOW_FIT_AXIS_*
+FIT_AXES = ("true", "predicted", "error", "residual")   # v, r, v - r, r - v
+FIT_MAX_BINS = 8192                   # TOPOLOW_FIT_MAX_BINS
+FIT_MAX_GRID = 4096                   # TOPOLOW_FIT_MAX_GRID
+_FIT_AXIS = {**{name: k for k, name in enumerate(FIT_AXES)}, **{k: k for k in range(4)}}
 
 
 class TopolowFitSeries(C.Structure):
@@ -232,6 +237,10 @@ PROTOTYPES = {
     "topolow_layout_prep_spectrum": (INT, (vp, dp, dp, spectrump, *ERR)),
     "topolow_layout_prep_fit_report": (INT, (vp, dp, I32, i64p, I64, fit_reportp, *ERR)),
     "topolow_layout_prep_fit_order_stats": (INT, (vp, dp, I32, i64p, I64, I32, i64p, I32, dp, i64p, *ERR)),
+    "topolow_layout_prep_fit_extent": (INT, (vp, dp, I32, i64p, I64, I32, dp, i64p, *ERR)),
+    "topolow_layout_prep_fit_hist2d": (INT, (vp, dp, I32, i64p, I64, I32, I32, dp, I32, I32, dp, I32, i64p, i64p, i64p, *ERR)),
+    "topolow_layout_prep_fit_linear_bins": (INT, (vp, dp, I32, i64p, I64, I32, I32, F64, F64, I32, i64p, u64p, i64p, i64p,
+                                                  *ERR)),
     # ---- session: a device-resident run
     "topolow_session_create": (INT, (vpp, I32, I32, I32, I32, I32, I32, *ERR)),
     "topolow_session_destroy": (None, (vp,)),
@@ -1229,6 +1238,57 @@ class PreparedHandle:
         _call(self.lib.topolow_layout_prep_fit_order_stats, self._h, _ptr(pos), pos.shape[1], pkp, int(pk.size),
               _FIT_SERIES[series], _ptr(rk), int(rk.size), _ptr(vals), C.byref(m), err=self._err)
         return vals[:rk.size].copy(), int(m.value)
+
+    def _fit_series_axes(self, series, *axes):
+        if series not in _FIT_SERIES:
+            raise ValueError('series must be "in", "out" or "all"')
+        for axis in axes:
+            if axis not in _FIT_AXIS:
+                raise ValueError('an axis must be "true", "predicted", "error" or "residual"')
+        return (_FIT_SERIES[series],) + tuple(_FIT_AXIS[axis] for axis in axes)
+
+    def fit_extent(self, positions, series, picks=None):
+        """topolow_layout_prep_fit_extent: ({"true": (min, max), "predicted": ..., "error": ..., "residual": ...}, m) of
+        `series` -- the bits of the extremes of v, r, v - r and r - v; NaN when the series is empty (m = 0).  positions,
+        picks and the series as fit_report; the diagonal counts."""
+        (s,) = self._fit_series_axes(series)
+        pos, pk, pkp = self._fit_inputs(positions, picks)
+        out, m = np.full(8, np.nan), C.c_int64(0)
+        _call(self.lib.topolow_layout_prep_fit_extent, self._h, _ptr(pos), pos.shape[1], pkp, int(pk.size), s, _ptr(out),
+              C.byref(m), err=self._err)
+        return {name: (float(out[2 * k]), float(out[2 * k + 1])) for k, name in enumerate(FIT_AXES)}, int(m.value)
+
+    def fit_hist2d(self, positions, series, x_axis, x_edges, y_axis, y_edges, picks=None):
+        """topolow_layout_prep_fit_hist2d: (counts, outside, m) -- counts[kx, ky] (int64, len(x_edges) - 1 by
+        len(y_edges) - 1) the cells of `series` with x_edges[kx] <= x < x_edges[kx + 1] and the same for y, the last
+        bin of either axis closed above: np.histogram2d's rule with explicit edges, and its counts.  outside: the cells
+        of the series outside either axis; counts.sum() + outside == m.  Axes: "true", "predicted", "error" (v - r),
+        "residual" (r - v).  At most FIT_MAX_BINS bins; the edges finite and strictly increasing."""
+        s, ax, ay = self._fit_series_axes(series, x_axis, y_axis)
+        pos, pk, pkp = self._fit_inputs(positions, picks)
+        xe, ye = _f64(x_edges).reshape(-1), _f64(y_edges).reshape(-1)
+        nx, ny = int(xe.size) - 1, int(ye.size) - 1
+        fits = nx >= 1 and ny >= 1 and nx * ny <= FIT_MAX_BINS      # (otherwise the library refuses, and says why)
+        counts = np.zeros((nx, ny) if fits else (1, 1), dtype=np.int64)
+        outside, m = C.c_int64(0), C.c_int64(0)
+        _call(self.lib.topolow_layout_prep_fit_hist2d, self._h, _ptr(pos), pos.shape[1], pkp, int(pk.size), s, ax, _ptr(xe),
+              nx, ay, _ptr(ye), ny, _ptr(counts), C.byref(outside), C.byref(m), err=self._err)
+        return counts, int(outside.value), int(m.value)
+
+    def fit_linear_bins(self, positions, series, axis, lo, up, m=512, picks=None):
+        """topolow_layout_prep_fit_linear_bins: (count, frac, outside, total) -- density()'s linear binning of `axis`
+        over `series` on the m-point grid over [lo, up], in integers: count[ix] the cells with floor((x - lo) / delta)
+        = ix, frac[ix] (uint64) the sum of their (uint64)(fx * 2^32); ix in 0 .. m - 2, every other cell in `outside`.
+        error_metrics.linear_bin_masses forms the masses."""
+        s, ax = self._fit_series_axes(series, axis)
+        pos, pk, pkp = self._fit_inputs(positions, picks)
+        m = int(m)
+        size = min(max(m, 1), FIT_MAX_GRID)
+        count, frac = np.zeros(size, dtype=np.int64), np.zeros(size, dtype=np.uint64)
+        outside, total = C.c_int64(0), C.c_int64(0)
+        _call(self.lib.topolow_layout_prep_fit_linear_bins, self._h, _ptr(pos), pos.shape[1], pkp, int(pk.size), s, ax,
+              float(lo), float(up), m, _ptr(count), _ptr(frac), C.byref(outside), C.byref(total), err=self._err)
+        return count, frac, int(outside.value), int(total.value)
 
     def graph_stats(self):
         """(rounds, [seconds of the bit pass, seconds of the rounds]) of the last .connectivity on this handle."""

@@ -17,10 +17,13 @@
 // No floating-point atomics: every sum is reduced in post_metrics_kernel's fixed order -- each lane over its indices in
 // ascending order, the 64 lanes of a wave by a shuffle tree, the four waves in wave order -- into one partial per line;
 // the host adds the lines in index order.  The histograms of the select are integer atomics.
+//
+// The cell function and the block reduction serve relax_fit_bins.h as well, whose kernels are another source's: that
+// source defines TOPOLOW_FIT_CELL_ONLY and gets everything above the first kernel, and no kernel.
 #pragma once
 
 #include "relax_common.h"
-#include "relax_prep_fold.h"
+#include "relax_prep_device.h"
 
 namespace topolow {
 
@@ -77,6 +80,8 @@ __device__ inline void fit_block_reduce(T (&x)[K], T (*part)[K], Op op) {
       x[k] = t;
     }
 }
+
+#ifndef TOPOLOW_FIT_CELL_ONLY
 
 // ---- pass 1: counts, sums, extremes -------------------------------------------------------------------------------
 struct FitLineSums {   // one per line
@@ -204,5 +209,7 @@ __global__ __launch_bounds__(kFitThreads) void fit_select_kernel(
   for (int r = 0; r < n_ranks; ++r)
     if (h[r][threadIdx.x]) atomicAdd(&out->hist[r][threadIdx.x], (unsigned long long)h[r][threadIdx.x]);
 }
+
+#endif  // TOPOLOW_FIT_CELL_ONLY
 
 }  // namespace topolow

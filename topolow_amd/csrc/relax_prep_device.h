@@ -1,6 +1,6 @@
 // topolow_amd/csrc/relax_prep_device.h -- the device functions the pre-processing kernels share: the order key, the
-// wave reductions of the totals, the sums pass of one tile and the full matrix's cell policy; through
-// relax_prep_rank.h the ranked compaction.  Included by relax_prep.h, relax_prep_fold.h, relax_fit.h and
+// fold mask's bit test, the wave reductions of the totals, the sums pass of one tile and the full matrix's cell policy;
+// through relax_prep_rank.h the ranked compaction.  Included by relax_prep.h, relax_prep_fold.h, relax_fit.h and
 // relax_spectrum.h.  No kernels here: any source may include it.
 //
 // Everything works in BUFFER coordinates: the caller's n x n buffer is read as B[a * n + b], a the slow index and
@@ -16,6 +16,11 @@ namespace topolow {
 __device__ inline unsigned long long prep_order_key(double v) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// One bit per cell of the handle's buffer (the fold mask of relax_prep_fold.h): bit a * n + b for the cell B[a * n + b].
+__device__ inline bool fold_bit(const uint32_t* __restrict__ mask, size_t cell) {
+  return (mask[cell >> 5] >> (cell & 31)) & 1u;
 }
 
 __device__ inline unsigned long long prep_wave_sum(unsigned long long x) {

@@ -19,9 +19,7 @@
 
 namespace topolow {
 
-__device__ inline bool fold_bit(const uint32_t* __restrict__ mask, size_t cell) {
-  return (mask[cell >> 5] >> (cell & 31)) & 1u;
-}
+// (fold_bit, the mask's bit test, is in relax_prep_device.h: the fit kernels of other sources read the mask too.)
 
 // mark: one thread per pick sets the bits of (r, c) and (c, r).  A pick listed twice, or together with its mirror,
 // sets a bit twice, which is setting it once: no sort, no de-duplication.

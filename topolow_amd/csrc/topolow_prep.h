@@ -1,8 +1,9 @@
 // topolow_amd/csrc/topolow_prep.h -- the prepared handle as the library's sources see it: struct topolow_layout_prep
 // and what it is made of, the pinned staging and the stream pipe the post-metrics share with the handle's entries, and
-// the functions that cross a source boundary: between the handle's four sources (topolow_prep.hip: create, fetch and
+// the functions that cross a source boundary: between the handle's five sources (topolow_prep.hip: create, fetch and
 // the entries that run from a handle; topolow_prep_graph.hip: connectivity, sub-handles, degrees, pruning;
-// topolow_spectrum.hip; topolow_prep_fold.hip: folds, CV sweep, fit report) and to topolow_relax.hip and
+// topolow_spectrum.hip; topolow_prep_fold.hip: folds, CV sweep, fit report; topolow_fit_bins.hip: the fit's binned
+// diagnostics) and to topolow_relax.hip and
 // topolow_post.hip.  Types, declarations and a few host helpers; the kernels live in the sources.
 #pragma once
 
@@ -239,5 +240,23 @@ struct PrepChunks {
 bool prep_order_in_ok(int32_t preserve_order, const int32_t* order_in, int n, char* errbuf, size_t errlen);
 void prep_passes(topolow_layout_prep* p, int32_t preserve_order, const int32_t* order_in, topolow_layout_prep_info* info,
                  double t0, const PrepChunks& g, const std::function<void(PostPipe&, int, int, int)>& arrive);
+
+// ---- defined in topolow_prep_fold.hip with the fit report, called by the binned diagnostics (topolow_fit_bins.hip) as well ----
+// What the fit kernels read: the handle's buffers, the positions one row per point, the fold mask where picks were given.
+struct FitInputs {
+  const double* pos;
+  const double* vals;
+  const int8_t* codes;
+  const int32_t* ord;
+  const uint32_t* mask;
+  hipStream_t stream;
+};
+int fit_check_arguments(const char* entry, const topolow_layout_prep* p, const double* positions, int32_t ndim,
+                        const int64_t* picks, int64_t n_picks, const void* out, char* errbuf, size_t errlen);
+int fit_check_series(const char* entry, int32_t series, char* errbuf, size_t errlen);
+// The positions go up, the picks are marked in the handle's fold mask, body(inputs) runs, and the mask is empty again
+// when this returns, whatever body threw.
+int fit_run(topolow_layout_prep* p, const double* positions, int32_t ndim, const int64_t* picks, int64_t n_picks,
+            char* errbuf, size_t errlen, const std::function<void(const FitInputs&)>& body);
 
 #pragma GCC visibility pop

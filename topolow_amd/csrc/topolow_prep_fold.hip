@@ -215,19 +215,13 @@ struct HandleFolds {
   }
 };
 
+}  // namespace
+
 // ---- the fit report of a resident embedding (relax_fit.h) ---------------------------------------------------------------
+// fit_check_arguments, fit_check_series and fit_run are declared in topolow_prep.h: the binned diagnostics
+// (topolow_fit_bins.hip) check their arguments and mark their picks through them.
 
 static_assert(kFitMaxRanks == TOPOLOW_FIT_MAX_RANKS, "relax_fit.h and the header disagree");
-
-// What the fit kernels read: the handle's buffers, the positions one row per point, the fold mask where picks were given.
-struct FitInputs {
-  const double* pos;
-  const double* vals;
-  const int8_t* codes;
-  const int32_t* ord;
-  const uint32_t* mask;
-  hipStream_t stream;
-};
 
 int fit_check_arguments(const char* entry, const topolow_layout_prep* p, const double* positions, int32_t ndim,
                         const int64_t* picks, int64_t n_picks, const void* out, char* errbuf, size_t errlen) {
@@ -244,6 +238,12 @@ int fit_check_arguments(const char* entry, const topolow_layout_prep* p, const d
     return TOPOLOW_ERR_BAD_ARGUMENT;
   }
   return TOPOLOW_OK;
+}
+
+int fit_check_series(const char* entry, int32_t series, char* errbuf, size_t errlen) {
+  if (series == TOPOLOW_FIT_IN || series == TOPOLOW_FIT_OUT || series == TOPOLOW_FIT_ALL) return TOPOLOW_OK;
+  set_err(errbuf, errlen, "%s: unknown series %d (TOPOLOW_FIT_IN, _OUT or _ALL)", entry, series);
+  return TOPOLOW_ERR_BAD_ARGUMENT;
 }
 
 // The positions go up, the picks are marked in the handle's fold mask, body(inputs) runs, and the mask is empty again
@@ -285,8 +285,6 @@ int fit_run(topolow_layout_prep* p, const double* positions, int32_t ndim, const
     body(in);
   });
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -443,10 +441,7 @@ int topolow_layout_prep_fit_order_stats(topolow_layout_prep* p, const double* po
                                           ranks && values_out && count_out ? (const void*)values_out : nullptr, errbuf,
                                           errlen))
     return rca;
-  if (series != TOPOLOW_FIT_IN && series != TOPOLOW_FIT_OUT && series != TOPOLOW_FIT_ALL) {
-    set_err(errbuf, errlen, "%s: unknown series %d (TOPOLOW_FIT_IN, _OUT or _ALL)", entry, series);
-    return TOPOLOW_ERR_BAD_ARGUMENT;
-  }
+  if (const int rcs = fit_check_series(entry, series, errbuf, errlen)) return rcs;
   if (n_ranks < 1 || n_ranks > TOPOLOW_FIT_MAX_RANKS) {
     set_err(errbuf, errlen, "%s: 1 <= n_ranks <= %d is required (got %d)", entry, TOPOLOW_FIT_MAX_RANKS, n_ranks);
     return TOPOLOW_ERR_BAD_ARGUMENT;

@@ -13,7 +13,14 @@ A cell belongs to zero or more of three series: IN (finite, no threshold prefix,
 prefix, held out) and ALL (finite, with or without a prefix, held out or not: `extract_numeric_values`).  The diagonal
 counts.  DEVIATION from the reference: cells that are +-Inf are left out of every series, as `post_metrics` leaves them
 out; in the reference they would turn every statistic into Inf or NaN.  This holds for `fit_statistics` in both forms;
-`error_calculator_comparison` and `calculate_prediction_interval` are the reference's functions as they are."""
+`error_calculator_comparison` and `calculate_prediction_interval` are the reference's functions as they are.
+
+`embedding_quality_data` returns the data behind the reference's diagnostic plots of a fit
+(`scatterplot_fitted_vs_true`, R/visualization.R:2616-2701; `plot_embedding_quality`, R/diagnostics.R:128-183) without
+their point clouds: exact 2-D bin counts (`BinnedCloud`, whose conditional quantiles replace the plots' loess), the
+residual density as `density.default` computes it (`density_default`, `bw_nrd0`) and the FitStatistics.  It has the same
+two forms; the device form reads the resident matrix through topolow_layout_prep_fit_extent / _fit_hist2d /
+_fit_linear_bins."""
 import math
 from dataclasses import dataclass
 from typing import Callable, Dict, Optional, Sequence
@@ -24,7 +31,9 @@ from . import _native, cv
 from .core import _as_rmatrix, coded_matrix
 
 __all__ = ["error_calculator_comparison", "calculate_prediction_interval", "fit_statistics", "FitStatistics",
-           "SeriesStatistics", "student_t_quantile", "type7_quantiles"]
+           "SeriesStatistics", "student_t_quantile", "type7_quantiles", "bw_nrd0", "density_grid", "linear_bin_counts",
+           "linear_bin_masses", "density_default", "Density", "BinnedCloud", "bin_counts_2d", "embedding_quality_data",
+           "EmbeddingQualityData"]
 
 
 # --------------------------------------------------------------------------------------
@@ -368,3 +377,297 @@ def fit_statistics(dissimilarity_matrix, predicted=None, *, input_dissimilaritie
     n_validation = int((finite & (codes == 0) & held).sum())
     return _assemble(moments, probs, lambda name: (lambda ranks: sorted_errors[name][list(ranks)]), n_validation,
                      int(has_pred.sum()), int((finite & (codes == 0)).sum()), confidence_level)
+
+
+# --------------------------------------------------------------------------------------
+# density.default
+# --------------------------------------------------------------------------------------
+def bw_nrd0(sd: float, iqr: float, n: int, first: float = 0.0) -> float:
+    """stats::bw.nrd0 from the sample's sd (n - 1), interquartile range (type 7) and size:
+    0.9 * min(sd, IQR / 1.34) * n^(-1/5).  R's fall-backs where that minimum is 0: sd, then |x[1]| (`first`: with sd = 0
+    every value equals the first one), then 1."""
+    if n < 2:
+        raise ValueError("need at least 2 data points")
+    lo = min(float(sd), float(iqr) / 1.34)
+    if not lo:
+        lo = float(sd) or abs(float(first)) or 1.0
+    return 0.9 * lo * float(n) ** (-0.2)
+
+
+def density_grid(xmin: float, xmax: float, bw: float, cut: float = 3.0):
+    """density.default's ranges: (from, to, lo, up) = (min - cut bw, max + cut bw, from - 4 bw, to + 4 bw).  The density
+    is returned on [from, to]; the masses are binned on [lo, up]."""
+    from_, to = xmin - cut * bw, xmax + cut * bw
+    return from_, to, from_ - 4.0 * bw, to + 4.0 * bw
+
+
+def linear_bin_counts(x, lo: float, up: float, m: int):
+    """The host twin of topolow_layout_prep_fit_linear_bins: (count int64[m], frac uint64[m], outside) of the values x.
+    delta = (up - lo) / (m - 1), xpos = (x - lo) / delta, ix = floor(xpos), fx = xpos - ix; for 0 <= ix <= m - 2 a value
+    adds 1 to count[ix] and (uint64)(fx * 2^32) to frac[ix]; every other value is outside.  IEEE f64 throughout, as on
+    the device: the integers are the same."""
+    x = np.asarray(x, dtype=np.float64).ravel()
+    m = int(m)
+    if not (2 <= m <= _native.FIT_MAX_GRID) or not (math.isfinite(lo) and math.isfinite(up) and lo < up):
+        raise ValueError("2 <= m <= %d and finite lo < up are required" % _native.FIT_MAX_GRID)
+    delta = (float(up) - float(lo)) / float(m - 1)
+    xpos = (x - float(lo)) / delta
+    fl = np.floor(xpos)
+    ok = (fl >= 0.0) & (fl <= float(m - 2))
+    ix = fl[ok].astype(np.int64)
+    q = ((xpos[ok] - fl[ok]) * 4294967296.0).astype(np.uint64)
+    count = np.bincount(ix, minlength=m).astype(np.int64)
+    # exact in f64: each half is below 2^16 and there are fewer than 2^32 values
+    hi = np.bincount(ix, weights=(q >> np.uint64(16)).astype(np.float64), minlength=m).astype(np.uint64)
+    low = np.bincount(ix, weights=(q & np.uint64(0xFFFF)).astype(np.float64), minlength=m).astype(np.uint64)
+    return count, (hi << np.uint64(16)) + low, int(x.size - ix.size)
+
+
+def linear_bin_masses(count, frac) -> np.ndarray:
+    """mass[g] = (count[g] - S[g]) + S[g - 1] with S = frac * 2^-32: what R's BinDist puts on grid point g (times N).
+    DEVIATION from BinDist: fx is quantised to 2^-32, which moves a value's mass by at most 2^-32 of itself."""
+    count = np.asarray(count, dtype=np.float64)
+    s = np.asarray(frac, dtype=np.uint64).astype(np.float64) * 2.0 ** -32
+    mass = count - s
+    mass[1:] += s[:-1]
+    return mass
+
+
+@dataclass
+class Density:
+    """density.default's result: y at the n points x over [from, to], and the bandwidth."""
+    x: np.ndarray
+    y: np.ndarray
+    bw: float
+    n: int               # the values behind it
+
+
+def density_default(x=None, *, binned=None, bw: Optional[float] = None, xmin: Optional[float] = None,
+                    xmax: Optional[float] = None, n: int = 512, cut: float = 3.0) -> Density:
+    """stats::density.default with its defaults (bw = "nrd0", n = 512, cut = 3, Gaussian kernel), restated.
+
+    Either the raw values `x` (bw, xmin, xmax taken from them where not given), or `binned=(count, frac, lo, up, total)`
+    as topolow_layout_prep_fit_linear_bins returns them, with `bw`, `xmin` and `xmax` of the values -- lo and up must be
+    density_grid(xmin, xmax, bw, cut)'s.  Both go through the same quantised masses (linear_bin_counts,
+    linear_bin_masses): the raw form is the specification of the binned one.
+
+    The steps: from = min - cut bw, to = max + cut bw, lo = from - 4 bw, up = to + 4 bw; the masses / total on the
+    n-point grid over [lo, up], zero-padded to 2 n; kords = seq(0, 2 (up - lo), length 2 n) with its upper half
+    mirrored negative; dnorm(kords, sd = bw); pmax(0, Re(ifft(fft(y) conj(fft(kords))))[1:n]); linear interpolation
+    from the grid onto seq(from, to, length n).  n above 512 is rounded up to a power of two for the grid, as R does.
+    DEVIATION: the 2^-32 quantisation of linear_bin_masses."""
+    n_out = int(n)
+    grid = max(n_out, 512)
+    if grid > 512:
+        grid = 1 << int(math.ceil(math.log2(grid)))
+    if binned is None:
+        xs = np.asarray(x, dtype=np.float64).ravel()
+        if xs.size < 2 or not np.isfinite(xs).all():
+            raise ValueError("need at least 2 finite data points")
+        if bw is None:
+            srt = np.sort(xs)
+            q = type7_quantiles(xs.size, (0.25, 0.75), lambda ranks: srt[list(ranks)])
+            bw = bw_nrd0(float(np.std(xs, ddof=1)), float(q[1] - q[0]), xs.size, float(xs[0]))
+        xmin = float(xs.min()) if xmin is None else xmin
+        xmax = float(xs.max()) if xmax is None else xmax
+    elif bw is None or xmin is None or xmax is None:
+        raise ValueError("the binned form needs bw, xmin and xmax")
+    bw = float(bw)
+    if not (bw > 0.0 and math.isfinite(bw)):
+        raise ValueError("'bw' is not positive.")
+    from_, to, lo, up = density_grid(float(xmin), float(xmax), bw, cut)
+    if binned is None:
+        count, frac, _ = linear_bin_counts(xs, lo, up, grid)
+        total = xs.size
+    else:
+        count, frac, blo, bup, total = binned
+        if float(blo) != lo or float(bup) != up or len(count) != grid or len(frac) != grid:
+            raise ValueError("the bins were not made on density_grid(xmin, xmax, bw, cut)'s lo and up with the grid's size")
+    y = np.zeros(2 * grid)
+    y[:grid] = linear_bin_masses(count, frac) / float(total)
+    kords = np.linspace(0.0, 2.0 * (up - lo), 2 * grid)
+    kords[grid + 1:] = -kords[grid - 1:0:-1]
+    kords = np.exp(-0.5 * (kords / bw) ** 2) / (bw * math.sqrt(2.0 * math.pi))
+    conv = np.maximum(0.0, np.fft.ifft(np.fft.fft(y) * np.conj(np.fft.fft(kords))).real[:grid])
+    xout = np.linspace(from_, to, n_out)
+    return Density(x=xout, y=np.interp(xout, np.linspace(lo, up, grid), conv), bw=bw, n=int(total))
+
+
+# --------------------------------------------------------------------------------------
+# the diagnostic plots' clouds, binned
+# --------------------------------------------------------------------------------------
+def _bin_of(x: np.ndarray, edges: np.ndarray) -> np.ndarray:
+    """np.histogram's rule with explicit edges: k with edges[k] <= x < edges[k + 1], the last bin closed above; -1
+    outside.  Found by comparing against the edges, as on the device."""
+    nb = edges.size - 1
+    k = np.searchsorted(edges, x, side="right") - 1
+    k[x == edges[-1]] = nb - 1
+    k[(k < 0) | (k >= nb)] = -1
+    return k
+
+
+def bin_counts_2d(x, y, x_edges, y_edges):
+    """The host twin of topolow_layout_prep_fit_hist2d: (counts int64[nx, ny], outside)."""
+    xe, ye = np.asarray(x_edges, dtype=np.float64), np.asarray(y_edges, dtype=np.float64)
+    for e in (xe, ye):
+        if e.ndim != 1 or e.size < 2 or not np.isfinite(e).all() or not (np.diff(e) > 0).all():
+            raise ValueError("edges must be finite and strictly increasing")
+    nx, ny = xe.size - 1, ye.size - 1
+    if nx * ny > _native.FIT_MAX_BINS:
+        raise ValueError("at most %d bins" % _native.FIT_MAX_BINS)
+    kx = _bin_of(np.asarray(x, dtype=np.float64).ravel(), xe)
+    ky = _bin_of(np.asarray(y, dtype=np.float64).ravel(), ye)
+    inside = (kx >= 0) & (ky >= 0)
+    counts = np.bincount(kx[inside] * ny + ky[inside], minlength=nx * ny).astype(np.int64).reshape(nx, ny)
+    return counts, int(kx.size - inside.sum())
+
+
+@dataclass
+class BinnedCloud:
+    """A point cloud as exact 2-D bin counts: counts[kx, ky] over x_edges x y_edges (np.histogram2d's rule), the points
+    outside the edges, and the cloud's size n = counts.sum() + outside."""
+    x_axis: str
+    y_axis: str
+    x_edges: np.ndarray
+    y_edges: np.ndarray
+    counts: np.ndarray
+    outside: int
+    n: int
+
+    def conditional_quantiles(self, probs=(0.5,)) -> np.ndarray:
+        """[len(probs), nx]: per x-bin the y at which the cumulative count over the y-bins reaches p * c (c the x-bin's
+        count), linear inside the y-bin that reaches it; NaN for an empty x-bin.  p = 0 gives the lower edge of the
+        first y-bin that holds a point, p = 1 the upper edge of the last.
+        This is the trend line of the plots.  DEVIATION: it replaces the reference's `loess` and `geom_smooth` curves
+        deliberately -- a loess over the 3 * 10^7 points of a large map is not something R finishes either, and the
+        points do not exist here; a conditional median read off the exact counts does the plot's job."""
+        probs = [float(p) for p in probs]
+        if any(not (0.0 <= p <= 1.0) for p in probs):
+            raise ValueError("probs must lie in [0, 1]")
+        nx = self.counts.shape[0]
+        out = np.full((len(probs), nx), np.nan)
+        for kx in range(nx):
+            row = self.counts[kx]
+            c = int(row.sum())
+            if c == 0:
+                continue
+            cum = np.cumsum(row)
+            filled = np.flatnonzero(row)
+            for q, p in enumerate(probs):
+                t = p * c
+                ky = int(filled[np.searchsorted(cum[filled], t, side="left")]) if t <= cum[filled[-1]] else int(filled[-1])
+                before = float(cum[ky] - row[ky])
+                out[q, kx] = self.y_edges[ky] + (t - before) / float(row[ky]) * (self.y_edges[ky + 1] - self.y_edges[ky])
+        return out
+
+
+@dataclass
+class EmbeddingQualityData:
+    series: str
+    n: int                              # the series' cells
+    scatter: BinnedCloud                # true x predicted
+    residual_vs_true: BinnedCloud       # true x (predicted - true)
+    residual_vs_fitted: BinnedCloud     # predicted x (true - predicted)
+    residual_density: Optional[Density]   # of predicted - true; None for fewer than 2 cells
+    statistics: FitStatistics
+
+
+def _plot_edges(lo: float, hi: float, bins: int) -> np.ndarray:
+    """bins + 1 edges from lo to hi; a range without width (or none: an empty series) gets one of width 1 around it."""
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        lo, hi = 0.0, 1.0
+    if not hi > lo:
+        lo, hi = lo - 0.5, hi + 0.5
+    return np.linspace(lo, hi, int(bins) + 1)
+
+
+def embedding_quality_data(dissimilarity_matrix=None, predicted=None, *, positions=None,
+                           handle: Optional["_native.PreparedHandle"] = None, holdout=None, series="all", bins=(64, 64),
+                           confidence_level=0.95) -> EmbeddingQualityData:
+    """The data behind the reference's three diagnostic plots of a fit -- `scatterplot_fitted_vs_true`
+    (R/visualization.R:2616-2701: predicted against true, residual against fitted) and `plot_embedding_quality`
+    (R/diagnostics.R:128-183: estimated against input, residual against input, the density of the residuals) -- without
+    the point clouds: exact 2-D bin counts (BinnedCloud; its conditional_quantiles are the trend line, which replaces
+    the plots' loess / geom_smooth, see there), the residual density as density.default computes it (density_default),
+    and the FitStatistics the plots' titles and lines come from (fit_statistics, unchanged).
+
+    `series`: "in", "out" or "all", as fit_statistics (see the module's text).  The diagonal counts, as in the fit
+    report.  DEVIATION: `plot_embedding_quality` masks the diagonal; here it is a cell like any other (a diagonal of
+    zeros adds n points at the origin of the scatter).  +-Inf cells are in no series.
+    `bins`: (x bins, y bins) of every cloud, at most 8192 together.  Default edges: np.linspace from 0 (or the minimum,
+    where that is negative) to the series' maximum on the true and predicted axes, as the plots' limits; from the
+    minimum to the maximum on the residual axes.
+
+    Host form (no `handle`): `predicted` is the n x n matrix of predicted dissimilarities, `holdout` picks as in
+    fit_statistics.  NumPy on n x n temporaries; this form is the specification.
+    Device form (`handle=` and `positions=`, as fit_statistics): fit_statistics as it is, one fit_extent, one
+    fit_order_stats (the quartiles of the bandwidth), three fit_hist2d and one fit_linear_bins on the resident matrix;
+    nothing of size n x n reaches the host.  All counts equal the host form's; so does the density wherever the
+    bandwidth does: the sd behind it comes from FitStatistics, whose sums differ between the forms in their last bits,
+    and enters the bandwidth rounded to float32 so that those bits do not move the grid."""
+    if series not in ("in", "out", "all"):
+        raise ValueError('series must be "in", "out" or "all"')
+    bx, by = (int(b) for b in bins)
+    if bx < 1 or by < 1 or bx * by > _native.FIT_MAX_BINS:
+        raise ValueError("bins must be at least 1 x 1 and at most %d together" % _native.FIT_MAX_BINS)
+    if handle is not None:
+        stats = fit_statistics(None, handle=handle, positions=positions, holdout=holdout, confidence_level=confidence_level)
+        pos = np.asarray(positions, dtype=np.float64)
+        picks = None if holdout is None else np.asarray(holdout, dtype=np.int64).reshape(-1)
+        extent, m = handle.fit_extent(pos, series, picks)
+
+        def hist2d(xa, xe, ya, ye):
+            counts, outside, _ = handle.fit_hist2d(pos, series, xa, xe, ya, ye, picks)
+            return counts, outside
+
+        def order_stats(ranks):
+            return handle.fit_order_stats(pos, series, ranks, picks)[0]
+
+        def linear_bins(lo, up, grid):
+            count, frac, _, total = handle.fit_linear_bins(pos, series, "residual", lo, up, grid, picks)
+            return count, frac, lo, up, total
+    else:
+        stats = fit_statistics(dissimilarity_matrix, predicted, holdout=holdout, confidence_level=confidence_level)
+        truth_m = coded_matrix(dissimilarity_matrix)
+        pred = np.asarray(predicted.to_numpy() if hasattr(predicted, "to_numpy") else predicted, dtype=np.float64)
+        n = truth_m.values.shape[0]
+        held = _holdout_mask(n, None, holdout)
+        finite, plain = np.isfinite(truth_m.values) & ~np.isnan(pred), truth_m.codes == 0
+        mask = {"in": finite & plain & ~held, "out": finite & plain & held, "all": finite}[series]
+        v, r = truth_m.values[mask], pred[mask]
+        axes = {"true": v, "predicted": r, "error": v - r, "residual": r - v}
+        m = int(v.size)
+        extent = {k: (float(a.min()), float(a.max())) if m else (math.nan, math.nan) for k, a in axes.items()}
+        sorted_e = np.sort(axes["error"])
+
+        def hist2d(xa, xe, ya, ye):
+            return bin_counts_2d(axes[xa], axes[ya], xe, ye)
+
+        def order_stats(ranks):
+            return sorted_e[list(ranks)]
+
+        def linear_bins(lo, up, grid):
+            count, frac, _ = linear_bin_counts(axes["residual"], lo, up, grid)
+            return count, frac, lo, up, m
+
+    def edges_from_zero(axis, k):
+        return _plot_edges(min(0.0, extent[axis][0]) if m else math.nan, extent[axis][1], k)
+
+    def cloud(xa, xe, ya, ye):
+        counts, outside = hist2d(xa, xe, ya, ye)
+        return BinnedCloud(xa, ya, xe, ye, counts, outside, m)
+
+    true_x, fitted_x = edges_from_zero("true", bx), edges_from_zero("predicted", bx)
+    scatter = cloud("true", true_x, "predicted", edges_from_zero("predicted", by))
+    res_true = cloud("true", true_x, "residual", _plot_edges(*extent["residual"], by))
+    res_fitted = cloud("predicted", fitted_x, "error", _plot_edges(*extent["error"], by))
+    density = None
+    if m >= 2:
+        sd = {"in": stats.in_sample.sd, "out": stats.out_sample.sd, "all": stats.residual_sd}[series]
+        q = type7_quantiles(m, (0.25, 0.75), order_stats)      # of v - r; r - v has the same interquartile range
+        rmin, rmax = extent["residual"]
+        bw = bw_nrd0(float(np.float32(sd)), float(q[1] - q[0]), m, rmin)
+        _, _, lo, up = density_grid(rmin, rmax, bw)
+        density = density_default(binned=linear_bins(lo, up, 512), bw=bw, xmin=rmin, xmax=rmax)
+    return EmbeddingQualityData(series=series, n=m, scatter=scatter, residual_vs_true=res_true,
+                                residual_vs_fitted=res_fitted, residual_density=density, statistics=stats)
