@@ -258,6 +258,15 @@ struct RunState {
   int n_checks;
   int first_nonfinite;  // first iteration (1-based) that produced a non-finite position
   int pad0, pad1;
+  // The best snapshot lives in one of the session's two snapshot buffers (0, 1).  best_buf[best_entry] names it.  Two
+  // entries, so that a check that rides in an apply's launch never reads what its own launch writes: the launch of
+  // check number c reads entry c & 1 (every column block copies its points into the OTHER buffer) and its controller
+  // writes entry (c + 1) & 1 and best_entry; controller_kernel copies by itself and leaves both entries equal.
+  int best_buf[2];
+  int best_entry;
+  // 0 while the run goes on; after a stop, check number + 1 of the in-apply check that stopped it, or -1 (a stop by
+  // controller_kernel).  One word, so the apply kernel learns from one load whether the stop is its own launch's.
+  int stop_mark;
 };
 
 #if defined(__HIPCC__)

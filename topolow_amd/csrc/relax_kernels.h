@@ -1002,14 +1002,21 @@ __global__ __launch_bounds__(1024) void reduce_total_kernel(
 // of THREADS < kCtlThreads threads gives thread t the virtual threads t, t + THREADS, ... and
 // folds them exactly as the tree's first levels do (v with v + 512, then with v + 256, ...)
 // before it runs the remaining levels: the same additions on the same operands.
+//
+// The snapshot (RunState::best_buf).  check_no < 0, a launch of its own: the step copies the positions by itself into
+// the buffer the current entry names, kCtlCopyBatch 16-byte loads of a thread in flight together, and leaves both
+// entries equal.  check_no >= 0, check number check_no riding in an apply's launch: the launch's column blocks have
+// copied the positions into the buffer entry check_no & 1 does NOT name (relax_symm.h); the step copies nothing and
+// writes entry (check_no + 1) & 1 -- that other buffer when the error improved, the same buffer otherwise.
 constexpr int kCtlThreads = 1024;
+constexpr int kCtlCopyBatch = 4;
 
 template <int THREADS, typename real>
 __device__ __forceinline__ void controller_step(
     RunState* st, RunState* mailbox, const double* __restrict__ part_sum,
     const unsigned long long* __restrict__ part_cnt, int n_parts, const real* __restrict__ pos,
-    real* __restrict__ best_pos, long long n_values, int iter1, double k_after,
-    double* __restrict__ trace, int trace_cap, const double* __restrict__ total2) {
+    real* __restrict__ best0, real* __restrict__ best1, long long n_values, int iter1, double k_after,
+    double* __restrict__ trace, int trace_cap, const double* __restrict__ total2, int check_no) {
   static_assert(THREADS >= 64 && THREADS <= kCtlThreads && kCtlThreads % THREADS == 0 && (THREADS & (THREADS - 1)) == 0,
                 "controller_step: a power-of-two workgroup of at most kCtlThreads threads");
   constexpr int V = kCtlThreads / THREADS;   // virtual threads per thread
@@ -1018,7 +1025,7 @@ __device__ __forceinline__ void controller_step(
   if (st->stopped) return;
   __shared__ double sh_s[THREADS];
   __shared__ unsigned long long sh_c[THREADS];
-  __shared__ int sh_action;
+  __shared__ int sh_action, sh_cur;
   double s[V];
   unsigned long long c[V];
 #pragma unroll
@@ -1056,17 +1063,42 @@ __device__ __forceinline__ void controller_step(
     st->n_checks += 1;
     st->iter_base = iter1;
     st->k_base = k_after;
-    if (action & 1) { st->stopped = 1; st->converged = 1; }
+    if (check_no >= 0) {
+      const int cur = st->best_buf[check_no & 1];
+      st->best_buf[(check_no + 1) & 1] = (action & 2) ? cur ^ 1 : cur;
+      st->best_entry = (check_no + 1) & 1;
+      sh_cur = -1;                                   // (nothing to copy here)
+    } else {
+      const int cur = st->best_buf[st->best_entry & 1];
+      st->best_buf[0] = cur;
+      st->best_buf[1] = cur;
+      sh_cur = cur;
+    }
+    if (action & 1) { st->stop_mark = check_no >= 0 ? check_no + 1 : -1; st->stopped = 1; st->converged = 1; }
     sh_action = action;
   }
   __syncthreads();
-  if (sh_action & 2) {
-    // snapshot: 16-byte copies (both buffers come from hipMalloc, so they are 256-B aligned)
+  if ((sh_action & 2) && sh_cur >= 0) {
+    // snapshot: 16-byte copies (both buffers come from hipMalloc, so they are 256-B aligned), a thread's kCtlCopyBatch
+    // loads issued before its first store (a chunk past the end repeats the last one: the same bytes to the same place)
+    real* __restrict__ best_pos = sh_cur ? best1 : best0;
     const long long bytes = n_values * (long long)sizeof(real);
     const long long n16 = bytes / 16;
     const uint4* src = reinterpret_cast<const uint4*>(pos);
     uint4* dst = reinterpret_cast<uint4*>(best_pos);
-    for (long long q = threadIdx.x; q < n16; q += THREADS) dst[q] = src[q];
+    for (long long q = threadIdx.x; q < n16; q += (long long)THREADS * kCtlCopyBatch) {
+      uint4 v[kCtlCopyBatch];
+#pragma unroll
+      for (int j = 0; j < kCtlCopyBatch; ++j) {
+        const long long at = q + (long long)j * THREADS;
+        v[j] = src[at < n16 ? at : n16 - 1];
+      }
+#pragma unroll
+      for (int j = 0; j < kCtlCopyBatch; ++j) {
+        const long long at = q + (long long)j * THREADS;
+        dst[at < n16 ? at : n16 - 1] = v[j];   // (unconditional: a store under a branch pulls its load in behind it)
+      }
+    }
     for (long long q = n16 * 16 / (long long)sizeof(real) + threadIdx.x; q < n_values; q += THREADS)
       best_pos[q] = pos[q];
   }
@@ -1085,10 +1117,10 @@ template <typename real>
 __global__ __launch_bounds__(kCtlThreads) void controller_kernel(
     RunState* st, RunState* mailbox, const double* __restrict__ part_sum,
     const unsigned long long* __restrict__ part_cnt, int n_parts, const real* __restrict__ pos,
-    real* __restrict__ best_pos, long long n_values, int iter1, double k_after,
+    real* __restrict__ best0, real* __restrict__ best1, long long n_values, int iter1, double k_after,
     double* __restrict__ trace, int trace_cap, const double* __restrict__ total2) {
-  controller_step<kCtlThreads, real>(st, mailbox, part_sum, part_cnt, n_parts, pos, best_pos, n_values, iter1, k_after,
-                                     trace, trace_cap, total2);
+  controller_step<kCtlThreads, real>(st, mailbox, part_sum, part_cnt, n_parts, pos, best0, best1, n_values, iter1, k_after,
+                                     trace, trace_cap, total2, /*check_no=*/-1);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -424,9 +424,11 @@ struct SymApplyCheck {
   const double* part_sum = nullptr;
   const unsigned long long* part_cnt = nullptr;
   int n_parts = 0;
-  const void* pos = nullptr;   // the check's positions and the snapshot's buffer (the session's precision), n_values of them
-  void* best = nullptr;
+  const void* pos = nullptr;   // the check's positions and the two snapshot buffers (the session's precision), n_values of them
+  void* best0 = nullptr;
+  void* best1 = nullptr;
   long long n_values = 0;
+  int check_no = 0;            // the check's number in the run: RunState::best_buf[check_no & 1] is the entry this launch reads
   int iter1 = 0;
   double k_after = 0.0;
   double* trace = nullptr;
@@ -446,14 +448,28 @@ struct SymApplyCheck {
 // 1 024): it needs nothing from its siblings -- the partials are the sweep's, a launch earlier -- and they nothing from
 // it, so there is no synchronisation between workgroups.  The branch is on blockIdx.x and npad alone, wave-uniform, and sits
 // behind the opening all workgroups share (the check's workgroup reads row_units[0] for nothing: row_units ends at the
-// last tile-row).  The controller may set st->stopped
-// while its siblings are starting: one that sees the flag returns without storing, the others store, and pos_out and
-// rec_next come out mixed.  That is the race a controller beside running stage kernels has always had: after a stop every
-// later kernel is a no-op and the caller receives the snapshot (`best`), the run state and the trace, never pos_out.
+// last tile-row).
+//
+// The snapshot of a check's positions is the column blocks' work, not the controller's: every column block copies its
+// 32 points of chk.pos into the snapshot buffer that entry check_no & 1 of RunState::best_buf does NOT name, whatever
+// the controller will decide, and the controller only writes entry (check_no + 1) & 1: that buffer when the error
+// improved, the old one otherwise.  No workgroup reads what another writes in the same launch.
+//
+// The controller may stop the run while its siblings are starting.  A stop must leave the snapshot complete, and a
+// launch behind a stopped run must leave it alone (its entry may be the stale one, so "the other buffer" may be the
+// best one).  The choice made here: a sibling ALWAYS makes its copy when the stop it sees is its own launch's, and
+// never otherwise -- the flag the kernel reads is RunState::stop_mark, one word that says which check stopped the run
+// (check_no + 1; -1: a controller launch of its own), so one load tells "not stopped" (copy and move the points), "stopped
+// by this launch's controller" (copy, then return) and "stopped before" (return).  The copy's value is requested in
+// front of that branch and stored behind it.  As for the positions: a sibling that sees the stop returns without storing,
+// the others store, and pos_out and rec_next come out mixed.  That is the race a controller beside running stage kernels
+// has always had: after a stop every later kernel is a no-op and the caller receives the snapshot, the run state and
+// the trace, never pos_out.
 #ifndef TL_APPLY_PARTS
 #define TL_APPLY_PARTS 16
 #endif
 constexpr int kSymApplyParts = TL_APPLY_PARTS;   // threads of the apply kernel: 16 parts x 32 points (a column block); a wave = 2 parts
+
 template <int DIM, typename real>
 __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
     const real* __restrict__ rec, real* __restrict__ rec_next, real* __restrict__ pos_out, const float* __restrict__ gplus,
@@ -467,16 +483,32 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
   // itself waits for the flag's pointer, the flag, the other arguments and row_units[R] one after the other
   // (st is never null here).  Both loads stand in front of the check's branch: behind it, on a path the controller
   // step's stores to *st might reach as far as the optimiser can tell, the flag would no longer be a scalar load.
+  // The snapshot entry of a launch with a check travels in the same batch (without a check: entry 0, unused).
   const int2 ru = row_units[R];
-  int stopped = st->stopped;
-  asm("" : "+s"(stopped) : "s"(ru.x), "s"(ru.y), "s"(rec), "s"(rowpart), "s"(colpart), "s"(n), "s"(npad), "s"(rr_stages), "s"(rr_stage),
+  int stopped = st->stop_mark;
+  // (Both entries, from fixed addresses, and the choice between them afterwards: an address that depends on check_no
+  // would wait for that argument first, one scalar round trip in front of the batch.)
+  int best_e0 = st->best_buf[0], best_e1 = st->best_buf[1];
+  asm("" : "+s"(stopped), "+s"(best_e0), "+s"(best_e1) : "s"(ru.x), "s"(ru.y), "s"(rec), "s"(rowpart), "s"(colpart), "s"(n), "s"(npad), "s"(rr_stages), "s"(rr_stage),
       "s"(rec_next), "s"(pos_out), "s"(gplus), "s"(k_next), "s"(c_rep));
-  if (stopped) return;
   if (check_wg) {                                  // (wave-uniform: blockIdx.x and a kernel argument)
-    if (chk.part_sum != nullptr)
+    if (stopped == 0 && chk.part_sum != nullptr)
       controller_step<32 * kSymApplyParts, real>(st, chk.mailbox, chk.part_sum, chk.part_cnt, chk.n_parts,
-                                                 (const real*)chk.pos, (real*)chk.best, chk.n_values, chk.iter1,
-                                                 chk.k_after, chk.trace, chk.trace_cap, nullptr);
+                                                 (const real*)chk.pos, (real*)chk.best0, (real*)chk.best1, chk.n_values,
+                                                 chk.iter1, chk.k_after, chk.trace, chk.trace_cap, nullptr, chk.check_no);
+    return;
+  }
+  // this column block's share of the check's snapshot: 32 x DIM values, one per thread, into the buffer the entry does not name
+  static_assert(kSymCols * DIM <= 32 * kSymApplyParts, "symm_apply_kernel: one snapshot value per thread");
+  const long long snap_at = (long long)blockIdx.x * (kSymCols * DIM) + threadIdx.x;
+  const bool snaps = chk.part_sum != nullptr && (stopped == 0 || stopped == chk.check_no + 1) &&
+                     (int)threadIdx.x < kSymCols * DIM && snap_at < chk.n_values;
+  const int best_cur = (chk.check_no & 1) ? best_e1 : best_e0;
+  real* const snap_to = (real*)(best_cur ? chk.best0 : chk.best1);
+  real snap = 0;
+  if (snaps) snap = ((const real*)chk.pos)[snap_at];
+  if (stopped) {
+    if (snaps) snap_to[snap_at] = snap;
     return;
   }
   using T = SymReal<DIM, real>;
@@ -488,8 +520,13 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
   real acc[DIM];
 #pragma unroll
   for (int d = 0; d < DIM; ++d) acc[d] = 0;
-  // column sums of the tile-rows above (added), this thread's share: R' = part, part + 16, ... (independent loads: all
-  // of a thread's strips are in flight together).  rr_stages > 0: the sweep was ONE STAGE of a multi-stage iteration
+  // column sums of the tile-rows above (added), this thread's share: R' = part, part + 16, ..., one strip after the
+  // other: the trip counts are run-time values, the loops are not unrolled, and every trip is load, wait, add (a thread
+  // of the last column blocks of config 3: ten column strips and up to two row strips, each a memory round trip).  That
+  // chain does not set the launch's length: with the strips in batches of four raw buffer loads per thread, issued in
+  // front of the first add, the launch was as long as this one (7.87 us either way at config 3), and in batches of
+  // eight it was a microsecond longer (profiles/r19_apply.txt); so the plain loops stay.
+  // rr_stages > 0: the sweep was ONE STAGE of a multi-stage iteration
   // (sym_rr_*: the tiles that pair this point's slab with its partner slab of the stage): only those tile-rows' sums are
   // this sweep's, the other slots hold an older sweep's
   int rp0 = 0, rp1 = R;
@@ -505,6 +542,7 @@ __global__ __launch_bounds__(32 * kSymApplyParts) void symm_apply_kernel(
 #pragma unroll
     for (int d = 0; d < DIM; ++d) acc[d] -= src[d];
   }
+  if (snaps) snap_to[snap_at] = snap;
   // fixed order: the two parts of a wave (lanes l, l + 32), then the waves, then onto the point
 #pragma unroll
   for (int d = 0; d < DIM; ++d) {   // (each type keeps its own spelling of the exchange: a wrapped fp32 shuffle allocates differently)

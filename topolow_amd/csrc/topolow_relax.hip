@@ -286,11 +286,11 @@ void launch_controller(topolow_session* s, const void* pos, int iter1, double k_
   if (s->precision == TOPOLOW_PRECISION_F64) {
     hipLaunchKernelGGL((controller_kernel<double>), dim3(1), dim3(kCtlThreads), 0, s->stream,
                        s->state.p, s->mailbox_dev, psum, pcnt, nparts,
-                       (const double*)pos, (double*)s->best.p, nv, iter1, k_after, s->trace_dev, s->trace_cap, total2);
+                       (const double*)pos, (double*)s->best[0].p, (double*)s->best[1].p, nv, iter1, k_after, s->trace_dev, s->trace_cap, total2);
   } else {
     hipLaunchKernelGGL((controller_kernel<float>), dim3(1), dim3(kCtlThreads), 0, s->stream,
                        s->state.p, s->mailbox_dev, psum, pcnt, nparts,
-                       (const float*)pos, (float*)s->best.p, nv, iter1, k_after, s->trace_dev, s->trace_cap, total2);
+                       (const float*)pos, (float*)s->best[0].p, (float*)s->best[1].p, nv, iter1, k_after, s->trace_dev, s->trace_cap, total2);
   }
   HIP_TRY(hipGetLastError());
 }
@@ -701,7 +701,9 @@ void sym_apply(topolow_session* s, const SymPlanDev& plan, const void* rec, void
     ac.part_cnt = s->part_cnt.p;
     ac.n_parts = n_parts;
     ac.pos = pin;
-    ac.best = s->best.p;
+    ac.best0 = s->best[0].p;
+    ac.best1 = s->best[1].p;
+    ac.check_no = s->checks_launched;   // (check_went_in_apply counts this one afterwards)
     ac.n_values = (long long)s->n * s->dim;
     ac.iter1 = chk->iter1;
     ac.k_after = chk->k_after;
@@ -1269,10 +1271,10 @@ void cv_score_device(topolow_session* s, const int* d_i, const int* d_j, const d
   const int blocks = (int)std::min<long long>(1024, (n_pairs + kThreads - 1) / kThreads);   // fixed by n_pairs alone
   grow_buf(h.sc_part, 1024);
   if (s->precision == TOPOLOW_PRECISION_F64)
-    hipLaunchKernelGGL((cv_score_kernel<double>), dim3(blocks), dim3(kThreads), 0, s->stream, (const double*)s->best.p,
+    hipLaunchKernelGGL((cv_score_kernel<double>), dim3(blocks), dim3(kThreads), 0, s->stream, (const double*)s->best_now(),
                        s->dim, d_i, d_j, d_truth, n_pairs, h.sc_part.p);
   else
-    hipLaunchKernelGGL((cv_score_kernel<float>), dim3(blocks), dim3(kThreads), 0, s->stream, (const float*)s->best.p,
+    hipLaunchKernelGGL((cv_score_kernel<float>), dim3(blocks), dim3(kThreads), 0, s->stream, (const float*)s->best_now(),
                        s->dim, d_i, d_j, d_truth, n_pairs, h.sc_part.p);
   HIP_TRY(hipGetLastError());
   std::vector<double> part((size_t)blocks);
@@ -1682,7 +1684,7 @@ int topolow_session_create(topolow_session** out, int32_t n, int32_t ndim, int32
     if (s->exact) s->denc.alloc(s->enc.n);
     const size_t pos_bytes = (size_t)s->pos_rows() * s->dim * s->real_size();
     for (auto& b : s->pos) b.alloc(pos_bytes);
-    s->best.alloc(pos_bytes);
+    for (auto& b : s->best) b.alloc(pos_bytes);
     s->state.alloc(1);
     HIP_TRY(hipHostMalloc((void**)&s->mailbox, sizeof(RunState), hipHostMallocMapped));
     std::memset(s->mailbox, 0, sizeof(RunState));
@@ -1968,8 +1970,9 @@ int topolow_session_begin(topolow_session* s, int32_t n_iter, double k0, double 
     st.first_nonfinite = 0x7fffffff;
     *s->mailbox = st;
     HIP_TRY(hipMemcpyAsync(s->state.p, &st, sizeof st, hipMemcpyHostToDevice, s->stream));
-    // best snapshot starts as the initial positions (reference :171)
-    HIP_TRY(hipMemcpyAsync(s->best.p, s->pos[s->cur].p,
+    // best snapshot starts as the initial positions (reference :171): in buffer 0, which both entries of the cleared
+    // state name
+    HIP_TRY(hipMemcpyAsync(s->best[0].p, s->pos[s->cur].p,
                            (size_t)s->pos_rows() * s->dim * s->real_size(), hipMemcpyDeviceToDevice,
                            s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -2095,7 +2098,7 @@ int topolow_session_finish(topolow_session* s, double* positions_out, int32_t* c
       rc_nonfinite = TOPOLOW_ERR_NONFINITE;
       return;
     }
-    if (positions_out) download_positions(s, s->best.p, positions_out);
+    if (positions_out) download_positions(s, s->best[topolow_session::best_index(st)].p, positions_out);
     if (converged) *converged = st.converged;
     if (iterations) *iterations = st.ctl.best_iter;
     if (final_mae) *final_mae = st.ctl.best_mae;
@@ -2749,7 +2752,7 @@ int topolow_sessions_run_sharded(topolow_session** sessions, int32_t count, cons
         set_err(errbuf, errlen, "Numerical instability at iteration %d. Reduce k0 or c_repulsion.", t);
         rc_extra = TOPOLOW_ERR_NONFINITE;
       } else {
-        if (positions_out) download_positions(s0, s0->best.p, positions_out);
+        if (positions_out) download_positions(s0, s0->best[topolow_session::best_index(st)].p, positions_out);
         if (converged) *converged = st.converged;
         if (iterations) *iterations = st.ctl.best_iter;
         if (final_mae) *final_mae = st.ctl.best_mae;

@@ -135,7 +135,13 @@ struct topolow_session {
   int schedule = TOPOLOW_SCHEDULE_SLAB;   // SLAB, or GS = exact tile Gauss-Seidel (relax_tilegs.h)
   DevBuf<int> bperm;
   DevBuf<unsigned char> pos[3];   // stage ping-pong + the buffer a running check reads
-  DevBuf<unsigned char> best;
+  // The two snapshot buffers: the run state names the one that holds the best positions (RunState::best_buf).  A check
+  // that rides in an apply's launch has the column blocks copy its positions into the other one (relax_symm.h).
+  DevBuf<unsigned char> best[2];
+  static int best_index(const RunState& st) { return st.best_buf[st.best_entry & 1] & 1; }
+  // ... as the pinned mailbox has it, which every controller step mirrors the run state to: for a caller that has
+  // waited for the session's streams
+  void* best_now() const { return best[mailbox != nullptr ? best_index(*mailbox) : 0].p; }
   DevBuf<int> ei, ej;
   DevBuf<unsigned char> et;
   DevBuf<int8_t> ec;
