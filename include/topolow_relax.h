@@ -1197,7 +1197,7 @@ int topolow_session_edge_error(topolow_session* s, const void* d_pos, double* su
  * encoded matrix and moves its own points; a stage kernel stores its updated rows straight into the
  * position buffers of all blocks (peer stores over xGMI), blocks meet at HIP-event barriers, and the
  * convergence controller is replicated from per-block (sum, count) partials -- no host round trip
- * per stage or per check (csrc/topolow_relax.hip).  Results equal the one-session run of the
+ * per stage or per check (the engine: csrc/topolow_relax.hip; its sharded sweep: csrc/topolow_symm.hip).  Results equal the one-session run of the
  * same seed: positions bit for bit, the MAE to rounding (its partial sums are grouped by block) -- on
  * the multi-stage iterations and wherever the row-owner kernel runs.  ONE-stage iterations of fp32 runs with
  * ndim 2..10 and >= 7168 points run as the symmetric sweep sharded over the sessions (csrc/relax_symm.h): session b

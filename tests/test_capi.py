@@ -305,6 +305,32 @@ def test_each_source_of_the_prepared_handle_holds_its_own_kernels():
     assert len(kernels["topolow_prep_fold"]) == 10
 
 
+def test_each_source_of_the_session_holds_its_own_kernels():
+    """The session is four sources, divided by the kernel headers they own: the symmetric sweep's kernels (symm_*,
+    symm64_*, symm64x_*) are in topolow_symm.hip's listing alone, the tile Gauss-Seidel kernels in topolow_tilegs.hip's,
+    the hold-out and scoring kernels in topolow_cv.hip's, each of the three holds nothing else, and topolow_relax.hip
+    keeps the stage, check, controller and loader kernels -- so an edit of the session's loop or of the sweep's host
+    side recompiles no kernel of the other."""
+    import subprocess
+    csrc = os.path.join(ROOT, "topolow_amd", "csrc")
+    subprocess.run(["make", "-C", csrc, "asm"], check=True, capture_output=True)
+    kernels = {}
+    for part in os.listdir(csrc):
+        if part.endswith(".part.gfx950.s"):
+            names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", open(os.path.join(csrc, part)).read(), re.M)
+            kernels[part[:-len(".part.gfx950.s")]] = names
+    families = {"topolow_symm": ("symm",), "topolow_tilegs": ("tilegs_",), "topolow_cv": ("cv_",)}
+    for source, begins in families.items():
+        pattern = re.compile(r"_ZN7topolow\d+(%s)" % "|".join(begins))
+        held = {s: [k for k in names if pattern.match(k)] for s, names in kernels.items()}
+        assert [s for s, names in held.items() if names] == [source], (begins, held)
+        assert sorted(kernels[source]) == sorted(held[source]), source     # and it holds no kernel of another family
+    assert len(kernels["topolow_symm"]) == 124
+    assert len(kernels["topolow_tilegs"]) == 75
+    assert len(kernels["topolow_cv"]) == 9
+    assert len(kernels["topolow_relax"]) == 187
+
+
 def test_library_exports_the_c_abi_and_nothing_else_of_its_own():
     """The defined dynamic symbols of the built library: every function of _native.PROTOTYPES (the C ABI, checked
     against the header elsewhere), and beyond them only what the compiler and the HIP runtime put there -- mangled names

@@ -9,8 +9,8 @@
 #pragma once
 
 #include "relax_common.h"
-#include "relax_kernels.h"
-#include "relax_symm.h"
+#include "relax_device.h"
+#include "relax_symm_plan.h"
 
 namespace topolow {
 

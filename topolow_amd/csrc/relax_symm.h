@@ -26,7 +26,7 @@
 #include <type_traits>
 #include <vector>
 #include "relax_common.h"
-#include "relax_kernels.h"
+#include "relax_device.h"
 #include "relax_symm_plan.h"
 
 namespace topolow {
@@ -444,7 +444,7 @@ struct SymApplyCheck {
 // iteration (k_next).
 //
 // With a check (chk.part_sum != nullptr) the grid is npad / 32 + 1 workgroups and the last one is the controller
-// (relax_kernels.h: controller_step on this kernel's 512 threads, the same sums in the same order as controller_kernel's
+// (relax_device.h: controller_step on this kernel's 512 threads, the same sums in the same order as controller_kernel's
 // 1 024): it needs nothing from its siblings -- the partials are the sweep's, a launch earlier -- and they nothing from
 // it, so there is no synchronisation between workgroups.  The branch is on blockIdx.x and npad alone, wave-uniform, and sits
 // behind the opening all workgroups share (the check's workgroup reads row_units[0] for nothing: row_units ends at the
@@ -639,7 +639,7 @@ __global__ __launch_bounds__(256) void symm_tiles_kernel(const uint32_t* const* 
   }
 }
 
-// ---- the sweep sharded over P row-block sessions (topolow_relax.hip: sharded_worker) -------------------------
+// ---- the sweep sharded over P row-block sessions (topolow_symm.hip: sym_sharded_sweep; the engine: topolow_relax.hip, sharded_worker) -------------------------
 // Session b sweeps segment b of the tile list (equal tile counts, so equal work) into its own partials; a point's
 // move needs the partials of every segment, so each session folds ITS partials per point (symm_partial_kernel: what
 // symm_apply_kernel sums, restricted to one segment) and stores the result into slot b of the inbox of the session

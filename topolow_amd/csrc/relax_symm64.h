@@ -24,7 +24,7 @@
 // threshold comparisons and the check alike -- the caller's f64 targets to 2e-14 relative throughout.
 #pragma once
 
-#include "relax_kernels.h"
+#include "relax_device.h"
 #include "relax_symm.h"
 
 namespace topolow {
@@ -57,7 +57,7 @@ __device__ __forceinline__ void sym64_pair(const double (&pc)[DIM], double ksc, 
     dx[d] = pc[d] - pi[d];
     s = fma(dx[d], dx[d], s);
   }
-  const double r = Math<double>::sqrt(s);             // 1 ulp (relax_kernels.h): estimate + two Newton steps
+  const double r = Math<double>::sqrt(s);             // 1 ulp (relax_device.h): estimate + two Newton steps
   const double inv = Math<double>::rcp(r + 0.01);
   double t = (double)bits_f32(THR ? (w & ~kCodeMask) : w);
   if constexpr (EXACT) {

@@ -147,7 +147,7 @@ TL_HD inline void sym_rr_order(uint64_t seed, int iter, int S, int* perm) {
 
 // The plan of an arbitrary set of tiles given per tile-row as ONE interval of column blocks: rows_j(R, j0, j1) sets the
 // interval [j0, j1) of tile-row R (j0 >= 2 R; empty when j0 >= j1).  Equal runs per wave as above; row_units covers all
-// tile-rows.  Used for the two halves of a two-stage iteration (topolow_relax.hip: sym_half_stage).
+// tile-rows.  Used for the stages of a multi-stage iteration (topolow_symm.hip: sym_rr_plan).
 template <typename RowsJ>
 inline SymPlan relax_symm_plan_rows(int npad, int n_waves, RowsJ rows_j) {
   SymPlan P;

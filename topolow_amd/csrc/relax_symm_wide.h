@@ -28,7 +28,7 @@
 // (tests/test_symm_wide_isa.py).  At ndim 10 the row sums are 80 of them, the prefetched words and records 40, a
 // column's packed sums, a row pair and the column itself 56.
 //
-// Which sessions run it is the host's decision (topolow_relax.hip: sym_shape_ok, sym_dim_default): a dimension is on
+// Which sessions run it is the host's decision (topolow_symm.hip: sym_shape_ok, sym_dim_default): a dimension is on
 // by default where the sweep measured faster than the row-owner kernel -- all four: at N = 10 000 an iteration takes
 // 69 .. 82 us (87 with thresholds) against 96 .. 116 (145) us (profiles/r05_symm_wide.txt).  Also measured there and
 // not kept: reading a column's record one column and a row pair one pair ahead of their use (+29 VGPRs, spills from

@@ -1,7 +1,9 @@
 // topolow_amd/csrc/topolow_session.h -- the session as the library's sources see it: struct topolow_session, the
-// device buffer it is made of, and the few session functions another source calls.  Types and declarations only: the
-// kernels and everything that launches them live in topolow_relax.hip.  What is defined once and called from another
-// source has hidden visibility, so the library exports the C ABI of include/topolow_relax.h and nothing else.
+// device buffer it is made of, and the few session functions another source calls.  Types, declarations and small
+// stateless helpers only; the kernels and what launches them live in the session's four sources: topolow_relax.hip (the
+// session, its loop, the stage and check kernels, the row-sharded engine), topolow_symm.hip (the symmetric sweep),
+// topolow_tilegs.hip (tile Gauss-Seidel) and topolow_cv.hip (hold-out and scoring).  What is defined once and called
+// from another source has hidden visibility, so the library exports the C ABI of include/topolow_relax.h and nothing else.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -62,6 +64,9 @@ constexpr int kMaxTunedDim = 16;
 // 33..63 as 64 with the extra coordinates held at exactly zero (a zero coordinate adds 0 to every distance and
 // receives 0 of every move)
 constexpr int kernel_dim(int ndim) { return ndim <= 10 ? ndim : (ndim <= 12 ? 12 : (ndim <= 16 ? 16 : (ndim <= 32 ? 32 : 64))); }
+
+// The symmetric sweep's size gate (topolow_symm.hip: sym_shape_ok; a session reads TOPOLOW_SYMMETRIC_MIN_N over it at creation).
+constexpr int kSymMinPoints = 7168;   // below ~7000 points a resident wave gets fewer than 8 tiles and the row-owner sweep is faster (tests/study/symm_crossover.py; at ndim 10 the two meet near 4 100 points and the sweep leads by 1.11 at 6 144, 1.27 at 7 168: the gate stays, profiles/r05_symm_wide.txt)
 
 int select_device(int device) {
   int count = 0;
@@ -234,7 +239,7 @@ struct topolow_session {
     int grid_cap = 0;              // > 0: at most this many workgroups (TOPOLOW_SYMMETRIC_GRID; tests: long runs on small problems)
     DevBuf<const uint32_t*> src_tab;   // the row blocks the tile-major copy is gathered from (one: the session's own)
     DevBuf<int> src_row0;
-    // the sweep sharded over the row-block sessions of a run (topolow_relax.hip: sharded_worker): this session's segment
+    // the sweep sharded over the row-block sessions of a run (topolow_symm.hip: sym_sharded_*; the engine: topolow_relax.hip): this session's segment
     bool seg_thr = false;          // some session of the run holds threshold targets: the classifying instance
     int seg_first = 0, seg_last = -1;   // tile-rows that hold a tile of the segment
     int seg_slots = 0;             // sessions of the run (slots of an inbox)
@@ -314,7 +319,78 @@ struct topolow_session {
   }
 };
 
-// ---- defined in topolow_relax.hip, called by the folds of a prepared handle (topolow_prep_fold.hip: HandleFolds) ----
+// ---- FN<DIM>(...) at the coordinates a session's kernels carry (kernel_dim): the launch helpers of topolow_relax.hip
+// and topolow_tilegs.hip.  The symmetric sweep has a switch of its own, over its dims (topolow_symm.hip) ----
+#define TL_DISPATCH_DIM(dim, FN, ...)                 \
+  switch (dim) {                                      \
+    case 1: FN<1>(__VA_ARGS__); break;                \
+    case 2: FN<2>(__VA_ARGS__); break;                \
+    case 3: FN<3>(__VA_ARGS__); break;                \
+    case 4: FN<4>(__VA_ARGS__); break;                \
+    case 5: FN<5>(__VA_ARGS__); break;                \
+    case 6: FN<6>(__VA_ARGS__); break;                \
+    case 7: FN<7>(__VA_ARGS__); break;                \
+    case 8: FN<8>(__VA_ARGS__); break;                \
+    case 9: FN<9>(__VA_ARGS__); break;                \
+    case 10: FN<10>(__VA_ARGS__); break;              \
+    case 12: FN<12>(__VA_ARGS__); break;              \
+    case 16: FN<16>(__VA_ARGS__); break;              \
+    case 32: FN<32>(__VA_ARGS__); break;              \
+    case 64: FN<64>(__VA_ARGS__); break;              \
+    default: throw HipError{TOPOLOW_ERR_UNSUPPORTED, "ndim must be between 1 and 64"}; \
+  }
+
+using SymHolds = topolow_session::SymState::Holds;
+
+namespace {
+
+// Profiling sessions: a pair of timing events around what is enqueued on the session's stream while the scope lives.
+struct ProfScope {
+  topolow_session* s;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>>* dst;
+  hipEvent_t a = nullptr, b = nullptr;
+  ProfScope(topolow_session* s_, std::vector<std::pair<hipEvent_t, hipEvent_t>>* d) : s(s_), dst(d) {
+    if (!s->profiling) return;
+    HIP_TRY(hipEventCreate(&a));
+    HIP_TRY(hipEventCreate(&b));
+    HIP_TRY(hipEventRecord(a, s->stream));
+  }
+  ~ProfScope() {
+    if (!a) return;
+    (void)hipEventRecord(b, s->stream);
+    dst->emplace_back(a, b);
+  }
+};
+
+}  // namespace
+
+// ---- defined in topolow_relax.hip ----
+int edge_error_blocks(long long n_edges);
+void scan_row_flags(topolow_session* s);
+void upload_degrees(topolow_session* s, const int32_t* degrees);
+// part_sum / part_cnt [0, n_parts) folded into d_out2 (sum, count), on the session's stream (reduce_total_kernel)
+void reduce_total(topolow_session* s, int n_parts, double* d_out2);
+
+// ---- defined in topolow_symm.hip: the symmetric sweep as the session's loop and the row-sharded engine see it ----
+enum class SymForm { kRowOwner, kSweep, kStages };
+bool sym_eligible(const topolow_session* s);
+bool sym_available(topolow_session* s);
+bool sym_fused_ok(const topolow_session* s);
+SymForm sym_form(topolow_session* s, int n_stages);
+// sym_iteration<DIM>, sym_sharded_sweep<DIM> and sym_owner_apply<DIM> at the session's ndim
+void sym_run_iteration(topolow_session* s, const void* pin, void* pout, int iter, double k, bool err, int S, int st, bool last,
+                       const PendingCheck* in_apply);
+bool sym_sharded_eligible(const std::vector<topolow_session*>& ss);
+void sym_sharded_prepare(std::vector<topolow_session*>& ss);
+void sym_run_sharded_sweep(topolow_session* s, const void* pin, int iter, double k, bool err);
+void sym_run_owner_apply(topolow_session* s, const void* pin, void* pout, int row_begin, int row_end, const void* push,
+                         int n_push, int iter);
+
+// ---- defined in topolow_tilegs.hip ----
+void tilegs_run_iteration(topolow_session* s, void* pos, int iter, double k);   // launch_tilegs_iteration<DIM> at the session's ndim
+void launch_tilegs_finite(topolow_session* s, const void* pos, int iter1);
+
+// ---- defined in topolow_cv.hip, called by the folds of a prepared handle too (topolow_prep_fold.hip: HandleFolds) ----
 int cv_check_hold_out(const topolow_session* s, char* errbuf, size_t errlen);
 void cv_hold_out_pairs(topolow_session* s, long long np, const int32_t* degrees, const std::function<void(int*, int*)>& fill);
 void cv_score_device(topolow_session* s, const int* d_i, const int* d_j, const double* d_truth, long long n_pairs,

@@ -298,7 +298,7 @@ class HipBackend:
 
 class ShardedRelaxation:
     """The slab relaxation of one embedding over `world` processes (one per GPU).  Mirrors the
-    single-GPU session loop (topolow_relax.hip: topolow_session_enqueue) and the reference's iteration
+    single-GPU session loop (topolow_relax.hip: topolow_session_enqueue; the segment sweep: topolow_symm.hip) and the reference's iteration
     structure (src/optimization.cpp:193-374 of the reference).
 
     Per stage: one kernel launch + one all-gather of the position slices; per check: the block's error
